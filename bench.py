@@ -7,10 +7,16 @@
 
 Rank 0 prints ONE JSON line.  A "step" is one training iteration of ModeDisparity over one synthetic batch that is already
 resident in HBM: zero-grad, forward (3 heads), masked smooth-L1 loss 0.5/0.7/1.0, backward, gradient all-reduce (N > 1),
-Adam step.  By default zero-grad + forward + loss + backward are replayed as one hipGraph (--launch graph).  `roofline`
-describes the dominant hand-written kernel, timed with HIP events on its launch stream (inside the timed region with
---launch eager; over --profile-steps eager steps right after it with --launch graph, where events cannot sit inside the
-replayed graph); `cpu_baseline` times the CPU oracle (a port, not the product) on this host's cores.
+Adam step.  By default zero-grad + forward + loss + backward are replayed as one hipGraph (--launch graph).
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, ...); nothing else.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (float32; inputs are seeded, so two builds can
+be compared output for output).  --full adds everything else the line can carry, each after the timed region: `roofline` /
+`targets` / `kernels` (the dominant hand-written kernel, timed with HIP events on its launch stream -- inside the timed region with
+--launch eager, over --profile-steps eager steps right after it with --launch graph, where events cannot sit inside the replayed
+graph), `clocks`, `eval_b1`, the world-size-1 `collective` self-test, the vendor-library guard on the first step, and
+`cpu_baseline` (the CPU oracle, a port and not the product, on this host's cores).  The --no-* options below drop single parts of
+--full.
 """
 import argparse
 import json
@@ -23,6 +29,7 @@ for p in (ROOT, os.path.join(ROOT, 'mode-2022_amd'), os.path.join(ROOT, 'tests',
   if p not in sys.path:
     sys.path.insert(0, p)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
@@ -124,7 +131,17 @@ def parse():
   ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                   help="'nccl' is RCCL on ROCm (xGMI inside the node); 'gloo' lets several ranks share ONE GPU in the tests "
                   '(RCCL refuses two ranks on the same device)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run every measurement and check beyond the headline figure (per-kernel roofline, clocks, eval_b1, collective '
+                       'self-test, vendor-library guard, finite-parameter check, CPU baseline); without it none of them runs')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; a fixed seeded sample of '
+                       'an array where the whole would not fit)')
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
+  if not args.full:
+    args.no_cpu_baseline = args.no_kernel_timing = args.no_collective_self_test = args.no_clock_sample = args.no_eval_b1 = True
   if args.batch is None:
     args.batch = 1 if args.mode == 'fusion' else 2
   global TIMED_BATCH
@@ -379,6 +396,48 @@ def synthetic_batch(B, H, W, maxdisp, device, seed):
   gt = torch.rand(B, 1, H, W, generator=g) * (maxdisp / 2.0)
   gt[torch.rand(B, 1, H, W, generator=g) < 0.05] = float('nan')
   return left.to(device), right.to(device), gt.to(device)
+
+
+DUMP_BUDGET_BYTES = 60 * 2**20  # (under the 64 MB that --dump-outputs promises, .npy headers included)
+
+
+def host_copies(named):
+  """{name: tensor} -> {name: float32 numpy array} on the host, taken at once (a later replay overwrites a graph's static outputs)."""
+  return {k: v.detach().float().cpu().numpy() for k, v in named.items()}
+
+
+def step_outputs(net, reducer, out, mode):
+  """What a caller of the timed step receives.  Training: the loss, the three disparity predictions, the flat gradient buffer
+  (all-reduced when N > 1) and, after the optimizer step, every floating-point tensor of the state_dict in key order (parameters and
+  BatchNorm running statistics).  Inference: the disparity map (and the confidence map where the model returns one)."""
+  if mode == 'train':
+    loss, preds = out
+    named = {'loss': loss, 'grad': reducer.flat}
+    named.update(('disp%d' % (i + 1), p) for i, p in enumerate(preds))
+    named['state'] = torch.cat([t.detach().reshape(-1).float() for t in net.state_dict().values() if t.is_floating_point()])
+    return named
+  if isinstance(out, (tuple, list)):
+    return dict(zip(('disp', 'conf'), out))
+  return {'disp': out}
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+  """Write {name: float32 array} as directory/<name>.npy.  Arrays that fit the budget together are written whole; otherwise the budget
+  is shared out smallest first, and an array larger than its share is written as a fixed sample of its flattened elements (sorted
+  indices from numpy.random.RandomState(0): the same elements in every run with the same arguments)."""
+  os.makedirs(directory, exist_ok=True)
+  left = budget
+  names = sorted(arrays, key=lambda k: arrays[k].nbytes)
+  for i, name in enumerate(names):
+    a = arrays[name]
+    share = left // (len(names) - i)
+    if a.nbytes > share:
+      n = share // a.itemsize
+      idx = np.unique(np.random.RandomState(0).randint(0, a.size, size=n))
+      a = a.reshape(-1)[idx]
+    np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a))
+    left -= a.nbytes
+  return sorted(names)
 
 
 def usable_cores():
@@ -698,9 +757,13 @@ def fusion_main(args):
     with torch.no_grad():
       return net(depthes, confs, rgbs)
 
-  with no_vendor.no_vendor_arithmetic() as guard:
-    out0 = fwd()
-  assert bool(torch.isfinite(out0).all())
+  guard = None
+  if args.full:
+    with no_vendor.no_vendor_arithmetic() as guard:
+      out0 = fwd()
+    assert bool(torch.isfinite(out0).all())
+  else:
+    fwd()
   for _ in range(args.warmup):
     fwd()
   torch.cuda.synchronize()
@@ -715,9 +778,11 @@ def fusion_main(args):
   torch.cuda.synchronize()
   t0 = time.time()
   for _ in range(args.steps):
-    run()
+    last = run()
   torch.cuda.synchronize()
   elapsed = time.time() - t0
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, host_copies({'depth': last}))
   kern = None
   if not args.no_kernel_timing:
     profiling.enable(True)
@@ -736,9 +801,10 @@ def fusion_main(args):
       'config': {'workload': 'ModeFusion(1000,[32,64,128,256],depth 12,rgb 12) eval forward, %d frame(s)/call, %dx%d (BASELINE configs[4], '
                              'fusion half; train_fusion.py:64)' % (B, H, W),
                  'global_batch': B, 'conv_arith': args.conv_arith, 'launch': launch, 'init': 'torch.manual_seed(0) constructor init, BatchNorm '
-                 'running statistics from two training-mode forwards',
-                 'vendor_guard': 'first forward ran under mode_hip.no_vendor (%d aten ops seen, none of them vendor arithmetic)' % guard.seen},
+                 'running statistics from two training-mode forwards'},
   }
+  if guard is not None:
+    out['config']['vendor_guard'] = 'first forward ran under mode_hip.no_vendor (%d aten ops seen, none of them vendor arithmetic)' % guard.seen
   if kern:
     out['roofline'] = roofline_block(kern, args.conv_arith, B, args.profile_steps, '%d eager forwards after the timed region' % args.profile_steps)
     out['kernels'] = {k: {'calls': v['calls'], 'avg_ms': round(v['avg_ms'], 4), 'GBps': round(v['GBps'], 1), 'TFLOPs': round(v['TFLOPs'], 2)}
@@ -818,7 +884,7 @@ def main():
   def fwd_bwd():
     reducer.zero_grad()
     if not args.no_fused_loss:  # the same loss, formed next to the heads (ModeDisparity.forward_loss; tests/test_gpu_steps.py pins both forms)
-      loss, _ = net.forward_loss(left, right, gt, count=count)
+      loss, preds = net.forward_loss(left, right, gt, count=count)
     else:
       mask = ~torch.isnan(gt)
       gt0 = torch.nan_to_num(gt)
@@ -826,8 +892,11 @@ def main():
       loss = 0
       for wgt, o in ((0.5, o1), (0.7, o2), (1.0, o3)):
         loss = loss + wgt * data_parallel.global_masked_mean(F.smooth_l1_loss(o, gt0, reduction='none'), mask, count=count)
+      preds = (o1, o2, o3)
     loss.backward()
-    return loss
+    # detached aliases (no launch): a returned tensor that kept this step's autograd graph alive into the next one would pin its
+    # AccumulateGrad nodes to this step's stream, and the side-stream warm-up / capture of GraphedStep would then sync against it
+    return loss.detach(), tuple(p.detach() for p in preds)
 
   def eval_fwd():
     with torch.no_grad():
@@ -853,8 +922,9 @@ def main():
       opt.step()
 
   def eager_step():
-    body()
+    out = body()
     finish()
+    return out
 
   def fence():
     torch.cuda.synchronize()
@@ -866,7 +936,11 @@ def main():
   # interpolation) reached from the step: the host-side helpers keep silent exits to the torch module for shapes the kernels do not
   # take (models/stage3d.conv3 -> conv(x), bn_act_torch), and a timed step must not be one of those.
   from mode_hip import no_vendor
-  with no_vendor.no_vendor_arithmetic() as guard:
+  guard = None
+  if args.full:
+    with no_vendor.no_vendor_arithmetic() as guard:
+      eager_step()
+  else:
     eager_step()
   fence()
   for _ in range(args.warmup):
@@ -879,8 +953,9 @@ def main():
       graphed = GraphedStep(body, (left, right, gt, count), warmup=1)
 
       def step():
-        graphed.replay()
+        out = graphed.replay()
         finish()
+        return out
 
       step()  # first replay uploads the graph; not timed
       fence()
@@ -899,9 +974,11 @@ def main():
   del ar_events[:]
   t0 = time.time()
   for _ in range(args.steps):
-    step()
+    last = step()
   fence()
   elapsed = time.time() - t0
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, host_copies(step_outputs(net, reducer, last, args.mode)))
   allreduce_ms = sum(a.elapsed_time(b) for a, b in ar_events) / max(len(ar_events), 1) if ar_events else None
   clocks = None
   if world == 1 and not args.no_clock_sample:
@@ -931,7 +1008,7 @@ def main():
       fence()
       del fr, ft
   kern = profiling.summary()
-  if args.mode == 'train':
+  if args.mode == 'train' and args.full:
     # sanity of the steps just timed: every parameter still finite after the optimizer updates (one reduction, after the timing)
     flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
     if not bool(torch.isfinite(flat).all()):
@@ -992,6 +1069,8 @@ def main():
                                else 'per-kernel HIP events inside the timed region',
         },
     }
+    if args.no_kernel_timing:
+      del out['config']['roofline_timing']
     if clocks:
       out['clocks'] = clocks
     if kern:
@@ -1026,7 +1105,8 @@ def main():
         # the same fraction against the matrix peak at the clock the chip SUSTAINS under this step (peak scales with the engine clock)
         out['roofline']['sclk_mhz_under_step'] = clocks['sclk_mhz_under_step']
         out['roofline']['frac_at_sustained_clock'] = round(out['roofline']['frac'] * NOMINAL_SCLK_MHZ / clocks['sclk_mhz_under_step'], 4)
-      out['config']['vendor_guard'] = 'first eager step ran under mode_hip.no_vendor (%d aten ops seen, none of them vendor arithmetic)' % guard.seen
+      if guard is not None:
+        out['config']['vendor_guard'] = 'first eager step ran under mode_hip.no_vendor (%d aten ops seen, none of them vendor arithmetic)' % guard.seen
       out['kernels'] = {k: {'calls': v['calls'], 'avg_ms': round(v['avg_ms'], 4), 'GBps': round(v['GBps'], 1),
                             'TFLOPs': round(v['TFLOPs'], 2)} for k, v in kern.items()}
     else:

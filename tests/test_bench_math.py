@@ -193,3 +193,25 @@ def test_clock_sampling_parses_rocm_smi_and_never_raises(monkeypatch):
   assert c['sclk_mhz_under_step'] == 2165 and c['socket_power_w_under_step'] == 1208.0 and c['sclk_mhz_idle_after'] == 2165 and len(steps) == c['extra_steps']
   assert bench.sample_clocks(lambda: None, lambda: None, 1, seconds=0.05)['sclk_mhz_under_step'] == 95
   assert bench.sample_clocks(lambda: None, lambda: None, 3, seconds=0.05) is None  # no such device in the listing
+
+
+def test_dump_outputs_whole_under_the_budget_and_a_fixed_sample_above(tmp_path):
+  """bench.py --dump-outputs: arrays that fit the budget together are written whole; a larger one is written as the same seeded sample
+  of its elements in every run, and the files stay within the budget (the option promises at most 64 MB in all)."""
+  import os
+
+  import numpy as np
+  rng = np.random.RandomState(5)
+  small = rng.rand(3, 7).astype(np.float32)
+  big = rng.rand(2, 1000, 1000).astype(np.float32)
+  assert bench.dump_outputs(str(tmp_path / 'a'), {'small': small, 'big': big}, budget=16 * 2**20) == ['big', 'small']
+  assert np.array_equal(np.load(str(tmp_path / 'a' / 'big.npy')), big) and np.array_equal(np.load(str(tmp_path / 'a' / 'small.npy')), small)
+  for run in ('b', 'c'):
+    bench.dump_outputs(str(tmp_path / run), {'small': small, 'big': big}, budget=2**20)
+  got, again = np.load(str(tmp_path / 'b' / 'big.npy')), np.load(str(tmp_path / 'c' / 'big.npy'))
+  assert got.dtype == np.float32 and np.array_equal(got, again)
+  assert 0.9 * (2**20 - small.nbytes) / 4 < got.size <= (2**20 - small.nbytes) / 4
+  assert np.isin(got, big).all() and np.array_equal(np.load(str(tmp_path / 'b' / 'small.npy')), small)
+  total = sum(os.path.getsize(str(p)) for p in (tmp_path / 'b').iterdir())
+  assert total <= 2**20 + 1024
+  assert bench.DUMP_BUDGET_BYTES + 64 * 1024 <= 64 * 10**6

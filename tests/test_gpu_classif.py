@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import cpu_threads
 import mode_hip
 from mode_hip import functional as HF
 
@@ -125,7 +126,7 @@ def test_fused_classifier_head_with_a_large_mean():
 def test_fused_classifier_head_at_the_benchmark_volume():
   """2 x 32 x 48 x 256 x 128 (BASELINE configs[2]) against float64 and against the library's unfused operators on the same inputs."""
   B, C, D, H, W = 2, 32, 48, 256, 128
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   y = _rand((B, C, D, H, W), 6) * 1.3 + 0.2
   add = _rand((B, 1, D, H, W), 7)
   go = _rand((B, 1, D, H, W), 8)

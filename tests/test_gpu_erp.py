@@ -15,6 +15,7 @@ import recipe
 from oracle import mode_ref, sphere_conv_ref
 
 import models
+import cpu_threads
 import mode_hip
 from mode_hip import functional as HF
 
@@ -53,7 +54,7 @@ def test_erp_operator_at_the_benchmark_shape_against_the_float64_oracle(arith):
   assert HF.sphere_t_supported(post, torch.empty(C, C, 3, 3), B, 1), 'and the windowed forward is taken at this size'
   x, w, gy = _rand((B, C, H, W), 1), _rand((C, C, 3, 3), 2, (2.0 / (9 * C))**0.5), _rand((B, C, H, W), 3)
   cfg = ((1, 1), (1, 1), (1, 1), 1)
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   y_ref = sphere_conv_ref.forward(x.double(), pos, w.double(), *cfg)
   gx_ref, gw_ref = sphere_conv_ref.backward(x.double(), pos, w.double(), gy.double(), *cfg)
   xd, wd, gyd = x.to(DEV), w.to(DEV), gy.to(DEV)

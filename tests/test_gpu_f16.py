@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import cpu_threads
 import mode_hip
 from mode_hip import functional as HF
 
@@ -451,7 +452,7 @@ def test_sphere_input_gradient_on_two_fp16_pieces_against_float64(ih, iw, B, ci,
     gy = gy * 1e-7
   if case == 'one outlier':
     gy[0, 0, H // 2, W // 2] = 1e4
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   want, _ = sphere_conv_ref.backward(torch.zeros((B, ci, H, W), dtype=torch.float64), pos, w.cpu().double(), gy.cpu().double(), (1, 1), (1, 1),
                                      (1, 1), groups)
   pd = pos.to(DEV)
@@ -503,7 +504,7 @@ def test_sphere_weight_gradient_on_two_fp16_pieces_against_float64(case, f16_swi
   if case == 'one outlier':
     gy[0, 3, H // 2, W // 2] = 1e4
     x[1, 5, H // 3, W // 3] = -3e3
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   _, want = sphere_conv_ref.backward(x.cpu().double(), pos, torch.zeros((co, ci // groups, 3, 3), dtype=torch.float64), gy.cpu().double(),
                                      (1, 1), (1, 1), (1, 1), groups)
   pd = pos.to(DEV)

@@ -15,6 +15,7 @@ import torch
 
 from oracle import conv_ref
 
+import cpu_threads
 import mode_hip
 from mode_hip import functional as HF
 
@@ -30,7 +31,7 @@ QUARTER = (12, 64, 32)
 def _need_gpu():
   assert torch.cuda.is_available(), 'GPU tests need a GPU'
   mode_hip.lib()
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
 
 
 def _rand(shape, seed, scale=1.0):

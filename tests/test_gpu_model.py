@@ -153,7 +153,7 @@ def test_bench_two_ranks_share_one_gpu():
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
   cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--height', '256',
-         '--width', '128', '--maxdisp', '64', '--batch', '1', '--no-cpu-baseline', '--dist-backend', 'gloo', '--value-1gpu', '10.0']
+         '--width', '128', '--maxdisp', '64', '--batch', '1', '--full', '--no-cpu-baseline', '--dist-backend', 'gloo', '--value-1gpu', '10.0']
   r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
   lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
   assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
@@ -167,6 +167,36 @@ def test_bench_two_ranks_share_one_gpu():
   assert d['collective']['avg_ms_rank0'] is not None and d['collective']['avg_ms_rank0'] > 0
   assert d['scaling_vs_1gpu']['value_1gpu'] == 10.0 and abs(d['scaling_vs_1gpu']['efficiency'] - d['value'] / 20.0) < 1e-12
   assert 0 < d['targets']['regulariser3d_mfma_frac'] < 1 and 0 < d['roofline']['frac'] < 1 and 0 < d['roofline']['by_label']['frac'] < 1
+
+
+@pytest.mark.parametrize('mode', ['train', 'eval'])
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path, mode):
+  """A plain `bench.py` run (no --full) times exactly --steps steps and prints the headline line without the extras; --dump-outputs
+  writes what the last timed step computed -- loss, predictions, gradient buffer and state after the optimizer step for training, the
+  disparity map for inference -- as float32 .npy files."""
+  import json
+  import os
+  import subprocess
+  import sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+  cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--height', '256', '--width', '128',
+         '--maxdisp', '64', '--batch', '1', '--mode', mode, '--dump-outputs', str(tmp_path)]
+  r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+  lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+  assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
+  d = json.loads(lines[0])
+  assert d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'pairs/s' and d['higher_is_better'] is True and d['dtype']
+  assert d['metric'].startswith('ERP stereo pairs/sec') and abs(d['value'] * d['ms_per_step'] - 1e3) < 1e-6 * 1e3
+  assert d['config']['launch'].startswith('hipGraph')
+  assert d['roofline'] is None and d['collective'] is None and not {'cpu_baseline', 'eval_b1', 'clocks', 'kernels', 'targets'} & set(d)
+  got = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+  want = {'loss', 'grad', 'disp1', 'disp2', 'disp3', 'state'} if mode == 'train' else {'disp'}
+  assert set(got) == want and all(a.dtype == np.float32 for a in got.values())
+  assert got['disp1' if mode == 'train' else 'disp'].size == 256 * 128
+  if mode == 'train':
+    assert all(np.isfinite(a).all() for a in got.values())
+    assert got['loss'].size == 1 and got['grad'].size == 5489280 and got['state'].size > got['grad'].size and np.abs(got['grad']).max() > 0
 
 
 def test_smoke_entry():

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from oracle import conv_ref
 
+import cpu_threads
 import mode_hip
 from mode_hip import functional as HF
 
@@ -217,7 +218,7 @@ def test_split_at_the_benchmark_size_against_the_float64_oracle(split_arith):
   """32 -> 32 at 48 x 256 x 128 (one sample): forward and input gradient against oracle/conv_ref.py, same bound as the fp32 kernels'
   full-size test; the fp32 MFMA kernel's error on the same inputs is printed beside it."""
   D, H, W = 48, 256, 128
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   x = _rand((1, 32, D, H, W), 1)
   w = _rand((32, 32, 3, 3, 3), 2, (2.0 / (27 * 32))**0.5)
   gy = _rand((1, 32, D, H, W), 3)
@@ -311,7 +312,7 @@ def test_split_conv2d_with_the_folded_batchnorm_epilogue(relu, with_add, split_a
 
 def test_split_conv2d_at_the_extractor_sizes_against_float64(split_arith):
   """64 -> 64 at 256 x 128 and 512 x 256, four images (the step's shapes): forward against torch's float64 conv2d on the CPU."""
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   for H, W in ((256, 128), (512, 256)):
     x = _rand((4, 64, H, W), 201)
     w = _rand((64, 64, 3, 3), 202, (2.0 / (9 * 64))**0.5)
@@ -400,7 +401,7 @@ def test_split_sphere_input_gradient_against_float64(ih, iw, B, ci, co, groups, 
   w = _rand((co, ci // groups, 3, 3), 401, (2.0 / (9 * ci // groups))**0.5)
   gy = _rand((B, co, H, W), 402)
   x0 = torch.zeros((B, ci, H, W), dtype=torch.float64)
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   want, _ = sphere_conv_ref.backward(x0, pos, w.double(), gy.double(), (1, 1), (1, 1), (1, 1), groups)
   pd, wd = pos.to(DEV), w.to(DEV)
   ap = HF.sphere_adjplan(pd, 3, 3)
@@ -445,7 +446,7 @@ def test_split_sphere_weight_gradient_against_float64(ih, iw, B, ci, co, groups,
   x = _rand((B, ci, H, W), 411)
   gy = _rand((B, co, H, W), 412)
   w0 = torch.zeros((co, ci // groups, 3, 3), dtype=torch.float64)
-  torch.set_num_threads(max(1, len(__import__('os').sched_getaffinity(0))))
+  torch.set_num_threads(cpu_threads.usable_cores())
   _, want = sphere_conv_ref.backward(x.double(), pos, w0, gy.double(), (1, 1), (1, 1), (1, 1), groups)
   pd = pos.to(DEV)
   plan = HF.sphere_plan(pd, 3, 3)

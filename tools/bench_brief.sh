@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 PAT=${1:-'^$'}; shift
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-eval-b1 --no-collective-self-test "$@" 2>/dev/null | grep "^{" > /tmp/bench_brief_$$.json
+python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-eval-b1 --no-collective-self-test "$@" 2>/dev/null | grep "^{" > /tmp/bench_brief_$$.json
 python - "$PAT" /tmp/bench_brief_$$.json <<'PY'
 import json, re, sys
 pat, path = sys.argv[1], sys.argv[2]

@@ -5,9 +5,9 @@ python -m pytest tests/test_gpu_f16.py -m gpu -q -x --timeout 900 -s -k "eval" 2
 python -m pytest tests/test_gpu_split.py tests/test_gpu_kernels.py tests/test_gpu_model.py tests/test_gpu_parity.py tests/test_fusion.py -m gpu -q -x --timeout 900 -k "folded or eval or golden or reference or fixture or captured or fusion or conv2d" 2>&1 | grep -E "passed|failed|^FAILED|^ERROR|Error" | tail -5
 for r in 1 2; do for v in "" "--no-eval-f16"; do
   echo "== eval $v (round $r)"
-  python bench.py --mode eval --batch 1 --steps 30 --warmup 5 --no-cpu-baseline $v 2>/dev/null | grep "^{" > gpurun_out/eval_ab.json; python - <<'P'
+  python bench.py --mode eval --batch 1 --steps 30 --warmup 5 --full --no-cpu-baseline $v 2>/dev/null | grep "^{" > /tmp/eval_ab.json; python - <<'P'
 import json
-d=json.load(open('gpurun_out/eval_ab.json'))
+d=json.load(open('/tmp/eval_ab.json'))
 k=d.get('kernels',{})
 c3=sum(v['calls']*v['avg_ms']/2 for n,v in k.items() if n.startswith('conv3d_bn_eval') and ' s1 ' in n)
 c2=sum(v['calls']*v['avg_ms']/2 for n,v in k.items() if n.startswith('conv2d_bn_eval'))

@@ -4,7 +4,7 @@ FLAG=$1; PFX=$2
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 for f in "" "$FLAG"; do
-  python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-eval-b1 --no-collective-self-test --profile-steps 3 $f 2>/dev/null | grep '^{' | python -c "
+  python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-eval-b1 --no-collective-self-test --profile-steps 3 $f 2>/dev/null | grep '^{' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels']; pf='$PFX'.split(',')
 print('== flag [$f]: %.2f ms/step' % d['ms_per_step'])

@@ -8,7 +8,7 @@ cd $R
 export TMPDIR=/tmp
 timeout 1700 python -m pytest tests/test_gpu_repeat.py tests/test_gpu_classif.py tests/test_gpu_kernels.py tests/test_gpu_fullsize.py tests/test_gpu_split.py -m gpu -q --timeout 1500 -s -k "repeat or second_process or classif or stride2 or deconv or hourglass or transposed or s2" 2>&1 | grep -v 'MIOpen\|^add \|^MODE\|^using' > $OUT/pytest.log
 grep -E 'differ|^(FAILED|ERROR)|passed|failed' $OUT/pytest.log | tail -30
-python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-eval-b1 2>/dev/null | grep "^{" > $OUT/bench.json
+python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-eval-b1 2>/dev/null | grep "^{" > $OUT/bench.json
 python - <<PY
 import json
 d=json.loads(open("$OUT/bench.json").read())

@@ -21,7 +21,7 @@ RUNS = [
 def main():
   import json
   for name, extra in RUNS:
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2', '--no-cpu-baseline'] + extra
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2', '--full', '--no-cpu-baseline'] + extra
     r = subprocess.run(cmd, capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith('{')]
     if not line:
