@@ -729,6 +729,67 @@ size_t mode_conv1x1_sigmoid_bwd_workspace_bytes(int B, long long S);
 int mode_conv1x1_sigmoid_bwd(const float* x, const float* w, const float* s, const float* gs, float* gx, float* gw, float* gbias,
                              int accumulate, float* workspace, int B, int C, long long S, mode_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Metrics and losses (csrc/metrics.hip): the reductions of the reference's utils/evaluation.py (mae, max_ae, rmse, absrel, sqrel,
+ * silog, pixel_error_pct, D1, delta_acc, threshold_acc: :4-55) and the SILog training loss of the fusion stage (train_fusion.py:82-87,
+ * applied at :99-111).  All deterministic (two launches, a fixed summation order that depends on n only, no atomics).
+ *
+ * mode_masked_metrics: ONE pass over pred, gt (fp32, n elements) and mask (n bytes, nonzero = selected; NULL = every element) that
+ *   writes out[MODE_METRICS_COUNT] (fp64, device) with the statistics below over the selected elements -- the reference's functions on
+ *   pred[mask], gt[mask], without the compaction.  Per-element terms are formed in fp32 as torch forms them: d = p - g, |d|, d * d,
+ *   |d| / g, (d * d) / (g * g), p / g and g / p as IEEE fp32 operations, thresholds rounded to fp32 (torch casts a Python scalar to
+ *   the tensor's dtype), t_pct * g as an fp32 product; l = log p - log g in fp64.  Sums accumulate in fp64.
+ *     out[MODE_METRICS_N]          selected elements              (numel)
+ *     out[MODE_METRICS_N_GT]       ... with gt > 0                (absrel, sqrel)
+ *     out[MODE_METRICS_N_BOTH]     ... with gt > 0 and pred > 0   (silog)
+ *     out[MODE_METRICS_SUM_ABS]    sum |d|                         out[MODE_METRICS_SUM_SQ]      sum d * d
+ *     out[MODE_METRICS_SUM_ABSREL] sum |d| / g over gt > 0         out[MODE_METRICS_SUM_SQREL]   sum d*d / (g*g) over gt > 0
+ *     out[MODE_METRICS_SUM_LOG]    sum l over gt, pred > 0         out[MODE_METRICS_SUM_LOG2]    sum l * l over gt, pred > 0
+ *     out[MODE_METRICS_MAX_ABS]    max |d|, NaN if any |d| is NaN (torch.max); 0 for no element
+ *     out[MODE_METRICS_PX + k]     count of |d| >= px[k]                                   (pixel_error_pct), k < n_px
+ *     out[MODE_METRICS_D1 + k]     count of |d| >= d1_px[k] and |d| >= d1_pct[k] * g      (D1), k < n_d1
+ *     out[MODE_METRICS_RATIO + k]  count of max(p / g, g / p) < ratio[k], NaN-propagating  (delta_acc, threshold_acc), k < n_ratio
+ *   (NaN fails every comparison and still counts in N.)  `params` lives in host memory and is read during the call.
+ *   workspace: device, 8-byte aligned, workspace_bytes >= mode_masked_metrics_workspace_bytes(n).
+ * mode_silog_loss_fwd: the same pass restricted to l (mask, gt > 0, pred > 0): stats[MODE_METRICS_COUNT] (fp64, device; the l entries
+ *   and N_BOTH filled, the others 0) and loss[0] = sum l^2 / N_BOTH - lamda (sum l / N_BOTH)^2 as a device fp32 scalar (NaN when
+ *   N_BOTH = 0, as torch's mean of nothing).  No host synchronisation: capturable into a graph.  Workspace as mode_masked_metrics.
+ * mode_silog_loss_bwd: gpred (n) = gloss[0] * (2 / N_BOTH) (l - lamda sum l / N_BOTH) / p on the selected elements, exactly 0 elsewhere
+ *   (all zeros when N_BOTH = 0); `stats` as written by mode_silog_loss_fwd for the same inputs, gloss a device fp32 scalar.
+ * pred, gt and gpred may be NULL when n = 0 (an empty tensor).  Bad arguments (NULL pointers, n < 0, more than MODE_METRICS_MAX_THRESHOLDS of a kind) return MODE_ERR_BAD_ARG, a missing or small
+ * workspace MODE_ERR_WORKSPACE, before any launch. */
+#define MODE_METRICS_MAX_THRESHOLDS 4
+#define MODE_METRICS_N 0
+#define MODE_METRICS_N_GT 1
+#define MODE_METRICS_N_BOTH 2
+#define MODE_METRICS_SUM_ABS 3
+#define MODE_METRICS_SUM_SQ 4
+#define MODE_METRICS_SUM_ABSREL 5
+#define MODE_METRICS_SUM_SQREL 6
+#define MODE_METRICS_SUM_LOG 7
+#define MODE_METRICS_SUM_LOG2 8
+#define MODE_METRICS_MAX_ABS 9
+#define MODE_METRICS_PX 10
+#define MODE_METRICS_D1 (MODE_METRICS_PX + MODE_METRICS_MAX_THRESHOLDS)
+#define MODE_METRICS_RATIO (MODE_METRICS_D1 + MODE_METRICS_MAX_THRESHOLDS)
+#define MODE_METRICS_COUNT (MODE_METRICS_RATIO + MODE_METRICS_MAX_THRESHOLDS)
+typedef struct mode_metrics_params {
+  int n_px; /* pixel_error_pct thresholds used */
+  float px[MODE_METRICS_MAX_THRESHOLDS];
+  int n_d1; /* D1 (th_pixel, th_pct) pairs used */
+  float d1_px[MODE_METRICS_MAX_THRESHOLDS];
+  float d1_pct[MODE_METRICS_MAX_THRESHOLDS];
+  int n_ratio; /* ratio bounds used (delta_acc: 1.25^exp, threshold_acc: 1 + err_pct) */
+  float ratio[MODE_METRICS_MAX_THRESHOLDS];
+} mode_metrics_params;
+size_t mode_masked_metrics_workspace_bytes(long long n);
+int mode_masked_metrics(const float* pred, const float* gt, const uint8_t* mask, long long n, const mode_metrics_params* params,
+                        void* workspace, size_t workspace_bytes, double* out, mode_stream_t stream);
+int mode_silog_loss_fwd(const float* pred, const float* gt, const uint8_t* mask, long long n, float lamda, void* workspace,
+                        size_t workspace_bytes, double* stats, float* loss, mode_stream_t stream);
+int mode_silog_loss_bwd(const float* pred, const float* gt, const uint8_t* mask, long long n, float lamda, const double* stats,
+                        const float* gloss, float* gpred, mode_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,11 @@ SIGNATURES = {
     'mode_conv1x1_sigmoid_fwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 2 + [ctypes.c_longlong, _c_ptr]),
     'mode_conv1x1_sigmoid_bwd_workspace_bytes': (_c_size, [_c_int, ctypes.c_longlong]),
     'mode_conv1x1_sigmoid_bwd': (_c_int, [_c_ptr] * 7 + [_c_int] + [_c_ptr] + [_c_int] * 2 + [ctypes.c_longlong, _c_ptr]),
+    # metrics and losses (csrc/metrics.hip; reference utils/evaluation.py, train_fusion.py:82-87)
+    'mode_masked_metrics_workspace_bytes': (_c_size, [ctypes.c_longlong]),
+    'mode_masked_metrics': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong] + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 2),
+    'mode_silog_loss_fwd': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong, ctypes.c_float, _c_ptr, _c_size] + [_c_ptr] * 3),
+    'mode_silog_loss_bwd': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong, ctypes.c_float] + [_c_ptr] * 4),
 }
 
 ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against
@@ -196,6 +201,21 @@ class BnEpilogue(ctypes.Structure):
   """struct mode_bn_epilogue of include/mode_hip.h (host-side struct of device pointers)."""
   _fields_ = [('gamma', _c_ptr), ('beta', _c_ptr), ('mean', _c_ptr), ('var', _c_ptr), ('eps', ctypes.c_float), ('add', _c_ptr),
               ('relu', _c_int)]
+
+
+METRICS_MAX_THRESHOLDS = 4  # MODE_METRICS_MAX_THRESHOLDS
+# MODE_METRICS_* of include/mode_hip.h: indices into the statistic vector of mode_masked_metrics / mode_silog_loss_fwd
+(M_N, M_N_GT, M_N_BOTH, M_SUM_ABS, M_SUM_SQ, M_SUM_ABSREL, M_SUM_SQREL, M_SUM_LOG, M_SUM_LOG2, M_MAX_ABS) = range(10)
+M_PX = 10
+M_D1 = M_PX + METRICS_MAX_THRESHOLDS
+M_RATIO = M_D1 + METRICS_MAX_THRESHOLDS
+METRICS_COUNT = M_RATIO + METRICS_MAX_THRESHOLDS
+
+
+class MetricsParams(ctypes.Structure):
+  """struct mode_metrics_params of include/mode_hip.h (host memory, read during the call)."""
+  _T = ctypes.c_float * METRICS_MAX_THRESHOLDS
+  _fields_ = [('n_px', _c_int), ('px', _T), ('n_d1', _c_int), ('d1_px', _T), ('d1_pct', _T), ('n_ratio', _c_int), ('ratio', _T)]
 
 
 def check(rc, what):

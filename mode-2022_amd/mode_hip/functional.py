@@ -6,7 +6,7 @@ import threading
 
 import torch
 
-from . import BnEpilogue, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of
+from . import METRICS_COUNT, METRICS_MAX_THRESHOLDS, BnEpilogue, MetricsParams, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of
 
 
 def _stream_capturing():
@@ -1788,6 +1788,90 @@ def head_loss(costs, size, gt, scale, weights=(0.5, 0.7, 1.0)):
   """costs = (cost1, cost2, cost3) (B, 1, D/4, H/4, W/4) each -> (loss, (pred1, pred2, pred3)); head_loss_supported(costs[0], size)."""
   out = HeadLossFunction.apply(costs[0], costs[1], costs[2], gt, scale, tuple(weights), tuple(size))
   return out[0], tuple(out[1:])
+
+
+# ------------------------------------------------------------------------------------ evaluation metrics and the SILog loss
+# utils/evaluation.py of the reference compacts pred[mask], gt[mask] twice per metric and syncs once per metric; here a whole list of
+# metrics is one pass of mode_masked_metrics over the uncompacted maps (the mask applied in the kernel) and one 8-byte-per-statistic
+# copy back.  The SILog loss of train_fusion.py:82-87 is the same pass finalised on the device.
+def _metrics_operands(pred, gt, mask, who):
+  require_gpu(pred, gt, mask)
+  for t in (pred, gt):
+    if t.dtype != torch.float32:
+      raise TypeError('%s: pred and gt must be float32 (got %s)' % (who, t.dtype))
+  if pred.numel() != gt.numel() or (mask is not None and mask.numel() != gt.numel()):
+    raise ValueError('%s: pred %s, gt %s and mask %s differ in element count' %
+                     (who, tuple(pred.shape), tuple(gt.shape), None if mask is None else tuple(mask.shape)))
+  if mask is not None:
+    if mask.dtype != torch.bool:
+      raise TypeError('%s: the mask must be torch.bool (got %s)' % (who, mask.dtype))
+    mask = mask.contiguous().view(torch.uint8)
+  return pred.contiguous(), gt.contiguous(), mask
+
+
+def _metrics_workspace(n, device):
+  return torch.empty(max(lib().mode_masked_metrics_workspace_bytes(n) // 8, 1), dtype=torch.float64, device=device)
+
+
+def masked_metrics(pred, gt, mask=None, px=(), d1=(), ratio=()):
+  """The statistic vector of mode_masked_metrics (include/mode_hip.h) over the elements `mask` selects (None: all) as a float64 numpy
+  array of METRICS_COUNT entries (indices mode_hip.M_*): one launch pair and one small device-to-host copy.  px: thresholds of
+  pixel_error_pct; d1: (th_pixel, th_pct) pairs of D1; ratio: bounds of delta_acc / threshold_acc (each rounded to fp32 as torch does)."""
+  pred, gt, mask = _metrics_operands(pred, gt, mask, 'masked_metrics')
+  if max(len(px), len(d1), len(ratio)) > METRICS_MAX_THRESHOLDS:
+    raise ValueError('masked_metrics: at most %d thresholds of each kind' % METRICS_MAX_THRESHOLDS)
+  prm = MetricsParams()
+  prm.n_px, prm.n_d1, prm.n_ratio = len(px), len(d1), len(ratio)
+  for k, t in enumerate(px):
+    prm.px[k] = float(t)
+  for k, (tp, tc) in enumerate(d1):
+    prm.d1_px[k], prm.d1_pct[k] = float(tp), float(tc)
+  for k, r in enumerate(ratio):
+    prm.ratio[k] = float(r)
+  n = gt.numel()
+  out = torch.empty(METRICS_COUNT, dtype=torch.float64, device=gt.device)
+  with torch.cuda.device_of(gt), profiling.region('masked_metrics', (8 + (1 if mask is not None else 0)) * n, 0, gt.device):
+    ws = _metrics_workspace(n, gt.device)
+    check(lib().mode_masked_metrics(ptr(pred), ptr(gt), None if mask is None else ptr(mask), n, ctypes.byref(prm), ptr(ws),
+                                    ws.numel() * 8, ptr(out), stream_of(gt)), 'mode_masked_metrics')
+  return out.cpu().numpy()
+
+
+class SilogLossFunction(torch.autograd.Function):
+  """loss = mean(l^2) - lamda mean(l)^2, l = log pred - log gt over the elements with mask, gt > 0 and pred > 0 (train_fusion.py:82-87
+  on pred[mask], gt[mask]): a device scalar, NaN with a zero gradient when nothing is selected, as torch's."""
+
+  @staticmethod
+  def forward(ctx, pred, gt, mask, lamda):
+    p, g, m = _metrics_operands(pred, gt, mask, 'silog_loss')
+    n = g.numel()
+    stats = torch.empty(METRICS_COUNT, dtype=torch.float64, device=g.device)
+    loss = torch.empty(1, dtype=torch.float32, device=g.device)
+    with torch.cuda.device_of(g), profiling.region('silog_loss_fwd', (8 + (1 if m is not None else 0)) * n, 0, g.device):
+      ws = _metrics_workspace(n, g.device)
+      check(lib().mode_silog_loss_fwd(ptr(p), ptr(g), None if m is None else ptr(m), n, float(lamda), ptr(ws), ws.numel() * 8, ptr(stats),
+                                      ptr(loss), stream_of(g)), 'mode_silog_loss_fwd')
+    ctx.save_for_backward(p, g, m if m is not None else torch.empty(0, dtype=torch.uint8, device=g.device), stats)
+    ctx.has_mask, ctx.lamda, ctx.shape = m is not None, float(lamda), pred.shape
+    return loss.reshape(())
+
+  @staticmethod
+  def backward(ctx, gloss):
+    p, g, m, stats = ctx.saved_tensors
+    n = g.numel()
+    gl = gloss.reshape(1).to(torch.float32).contiguous()
+    gp = torch.empty_like(p)
+    with torch.cuda.device_of(g), profiling.region('silog_loss_bwd', (12 + (1 if ctx.has_mask else 0)) * n, 0, g.device):
+      check(lib().mode_silog_loss_bwd(ptr(p), ptr(g), ptr(m) if ctx.has_mask else None, n, ctx.lamda, ptr(stats), ptr(gl), ptr(gp),
+                                      stream_of(g)), 'mode_silog_loss_bwd')
+    return gp.view(ctx.shape), None, None, None
+
+
+def silog_loss(pred, gt, mask=None, lamda=0.5):
+  """The fusion stage's training loss (train_fusion.py:82-87 applied at :100-111 as silog_loss(0.5, output[mask], gt[mask])) without
+  the compaction: `mask` is the outer selection (gt <= maxdepth; None: every element), gt > 0 and pred > 0 are applied inside.  pred
+  may be (B, 1, H, W) with gt and mask (B, H, W).  Returns a 0-d device tensor; no host synchronisation (graph-capturable)."""
+  return SilogLossFunction.apply(pred, gt, mask, lamda)
 
 
 # ------------------------------------------------------------------------------------ BatchNorm (+ add) (+ ReLU)
