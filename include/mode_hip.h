@@ -680,6 +680,26 @@ int mode_depth_view_project(const float* view1, const float* trig, const double*
 int mode_zbuffer(const double* r2, const int32_t* target, const float* conf1, float* view2, float* conf2, void* workspace,
                  long long n, mode_stream_t stream);
 
+/* Multi-view hand-off (csrc/multiview.hip): the six camera pairs (order 12, 13, 14, 23, 24, 34) of F Deep360 frames from the
+ * disparity network to the fusion network in three launches.  disp, conf (F, 6, H, W) -> out (F, 12, H, W) with
+ *   out[f, 2p] = depth, out[f, 2p + 1] = confidence   of what the single-map entries compute for pair p: mode_disp2depth (12);
+ *                                                     + mode_grid_sample_border on [depth; conf] (13, 14); + mode_depth_view_trans (23, 24, 34)
+ * bit for bit, or out (F, 6, H, W) with out[f, p] = depth under MODE_MV_DEPTH_ONLY.  MODE_MV_CONF_PNG rounds every confidence
+ * as the reference's 8-bit PNG round trip does: q(c) = (float)((double)min(255, max(0, rint(c * 255.0f))) / 255.0) (half to even).
+ *   baselines6  host, the baseline of every pair
+ *   rot_grids   device (2, H, W, 2), 8-byte aligned: the rotateCassini grids of pitch pi/2 (13) and pi/4 (14)
+ *   trig        device, as mode_depth_view_trans
+ *   xforms      host, 3 x (R[9] row-major, t[3]) for pairs 23, 24, 34, as mode_depth_view_trans
+ *   workspace   device, 8-byte aligned, >= mode_multiview_handoff_workspace_bytes(F, H, W) = 3 F H W 8 bytes (the key planes)
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, unknown flags and sizes with H, W <= 0, F < 0
+ * or 3 F H W >= 2^31; MODE_ERR_WORKSPACE for a missing or unaligned workspace.  F = 0 is a no-op. */
+#define MODE_MV_CONF_PNG 1
+#define MODE_MV_DEPTH_ONLY 2
+size_t mode_multiview_handoff_workspace_bytes(int F, int H, int W);
+
+int mode_multiview_handoff(const float* disp, const float* conf, int F, int H, int W, const float* baselines6, const float* rot_grids,
+                           const float* trig, const double* xforms, int flags, float* out, void* workspace, mode_stream_t stream);
+
 /* Training forward of convbn_3d (models/submodule.py:20-22) without the statistics pass: the stride-1 split-bf16 convolution kernel
  * takes the BatchNorm batch statistics of its output from the accumulators (per channel: sum(y - K), sum((y - K)^2), K = the layer's own
  * first output value) and leaves them in `stats` = the BatchNorm workspace (>= mode_bn_workspace_bytes(Co) bytes) as

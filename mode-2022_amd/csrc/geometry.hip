@@ -11,33 +11,23 @@
 // caller); everything per pixel runs on the GPU with no host round trip.  All three kernels are HBM-bound elementwise /
 // gather / scatter work: 4-16 bytes per pixel and direction.
 #include "common.h"
+#include "geometry_internal.h"
 
 namespace {
 
+namespace geom = mode::geom;
 constexpr int NT = 256;
 
-// ---------------------------------------------------------------------------------------------------------------------
-// disparity -> depth by the sine rule (save_output_disparity_stage.py:118-135), float32 arithmetic like numpy's:
-//   phi_l = float(start + j * (-step))   (np.arange in float64, then .astype(float32))
-//   phi_r = disp * pi / W + phi_l        depth = baseline * sin(pi/2 - phi_r) / sin(phi_r - phi_l)
-//   disp == 0 -> 1000 (masked, filled);  depth > 1000 -> 1000;  depth < 0 -> 0
+// The per-pixel arithmetic lives in geometry_internal.h (shared with the multi-view hand-off, multiview.hip).
+using geom::Bilinear;
+using geom::ViewXform;
+
+// disparity -> depth by the sine rule (geom::sine_rule_depth)
 __global__ __launch_bounds__(NT) void disp2depth_kernel(const float* __restrict__ disp, float* __restrict__ depth, long long n, int W,
                                                         float baseline) {
-  const float pi_f = 3.14159265358979323846f, half_pi_f = 1.57079632679489661923f;
-  const double start = 0.5 * 3.14159265358979323846 - (0.5 * 3.14159265358979323846 / W);
-  const double step = 3.14159265358979323846 / W;
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
     const int j = (int)(i % W);
-    const float d = disp[i];
-    float out = 1000.f;
-    if (d != 0.f) {
-      const float phi_l = (float)(start + (double)j * (-step));
-      const float phi_r = d * pi_f / (float)W + phi_l;
-      out = baseline * sinf(half_pi_f - phi_r) / sinf(phi_r - phi_l);
-      if (out > 1000.f) out = 1000.f;
-      if (out < 0.f) out = 0.f;  // NaN stays NaN, as in numpy
-    }
-    depth[i] = out;
+    depth[i] = geom::sine_rule_depth(disp[i], j, W, baseline);
   }
 }
 
@@ -53,86 +43,19 @@ __global__ __launch_bounds__(NT) void grid_sample_border_kernel(const float* __r
     const int n = (int)(i / npix);
     const long long p = i - (long long)n * npix;
     const float2 g = reinterpret_cast<const float2*>(grid)[(Ng == 1 ? 0 : (long long)n * npix) + p];
-    // unnormalise (align_corners=True), clip to the border
-    float x = (g.x + 1.f) * 0.5f * (float)(Ws - 1);
-    float y = (g.y + 1.f) * 0.5f * (float)(Hs - 1);
-    x = fminf(fmaxf(x, 0.f), (float)(Ws - 1));
-    y = fminf(fmaxf(y, 0.f), (float)(Hs - 1));
-    const float xf = floorf(x), yf = floorf(y);
-    const int x0 = (int)xf, y0 = (int)yf;
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const float wx1 = x - xf, wy1 = y - yf;
-    const float wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-    // corner weights in torch's order (nw, ne, sw, se); corners outside contribute nothing
-    const float nw = wx0 * wy0, ne = wx1 * wy0, sw = wx0 * wy1, se = wx1 * wy1;
-    const bool x1ok = x1 <= Ws - 1, y1ok = y1 <= Hs - 1;
+    const Bilinear b = geom::bilinear_border(g, Hs, Ws);
     const float* sp = src + (long long)n * C * Hs * Ws;
     float* dp = dst + (long long)n * C * npix + p;
     for (int c = 0; c < C; ++c) {
       const float* s = sp + (long long)c * Hs * Ws;
-      float v = s[(long long)y0 * Ws + x0] * nw;
-      if (x1ok) v += s[(long long)y0 * Ws + x1] * ne;
-      if (y1ok) v += s[(long long)y1 * Ws + x0] * sw;
-      if (x1ok && y1ok) v += s[(long long)y1 * Ws + x1] * se;
-      dp[(long long)c * npix] = v;
+      dp[(long long)c * npix] = geom::bilinear_sum(b, [=](int y, int x) { return s[(long long)y * Ws + x]; });
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// depthViewTransWithConf.  Pass 1, one thread per SOURCE pixel (i, j) with r1 > 0:
-//   X1 = r1 * dir(i, j)  (float32 products in numpy's order)  X2 = R (X1 - t)  (float64)       r2 = |X2|
-//   I = clip(rint(H/2 - H * atan2(X2.y, X2.z) / (2 pi)), 0, H-1)      J = clip(rint(W/2 - W * asin(clip(X2.x / r2)) / pi), 0, W-1)
-// and a 64-bit atomic min of a key into key[I][J].
-// The reference scans the sources in row-major order and overwrites the target when r2 < view2[target] -- r2 in float64 against
-// the float32 value stored so far (initial value 100000).  Let m be the smallest float32(r2) over the sources of a target
-// (positive floats order like their bit patterns) and S the sources that round to m.  The first source of S always gets
-// stored (rounding is monotonic); a later source of S replaces it only if its float64 r2 is strictly below the float32 m.
-// Hence the survivor is the LAST source of L = {k in S : r2_k < m}, or the FIRST source of S when L is empty, and
-//   key = bits(m) << 32 | (k in L ? 0 : 1) << 31 | (k in L ? N-1-k : k)
-// has exactly that source as its minimum -- bit-identical to the sequential loop, in any execution order.
-// Pass 2, one thread per TARGET pixel: view2 = r2 of the winner (0 if none; capped at 1000), conf2 = conf1[winner] (0 if none).
-struct ViewXform {
-  double R[9];
-  double t[3];
-};
-
-// projection of one source pixel: returns false if it takes no part (r1 <= 0, r2 not below the initial 100000, r2 == 0)
-__device__ __forceinline__ bool project_pixel(float r1, float sin_phi, float cos_phi, float sin_theta, float cos_theta,
-                                              const ViewXform& xf, int H, int W, double& r2, long long& tgt) {
-#pragma clang fp contract(off)  // numpy's matmul / sum of squares round every product: no fused multiply-adds here
-  const double PI = 3.14159265358979323846;
-  if (!(r1 > 0.f)) return false;
-  // float32 products in numpy's order (geometry.py:126-128): r * sin(phi);  (r * cos(phi)) * sin(theta);  (r * cos(phi)) * cos(theta)
-  const float rc = r1 * cos_phi;
-  const float x1 = r1 * sin_phi, y1 = rc * sin_theta, z1 = rc * cos_theta;
-  const double ax = (double)x1 - xf.t[0], ay = (double)y1 - xf.t[1], az = (double)z1 - xf.t[2];
-  const double X = xf.R[0] * ax + xf.R[1] * ay + xf.R[2] * az;
-  const double Y = xf.R[3] * ax + xf.R[4] * ay + xf.R[5] * az;
-  const double Z = xf.R[6] * ax + xf.R[7] * ay + xf.R[8] * az;
-  r2 = sqrt(X * X + Y * Y + Z * Z);
-  if (!(r2 < 100000.0)) return false;  // never below the initial value (also drops NaN)
-  const double theta = atan2(Y, Z);
-  double sphi = X / r2;
-  sphi = sphi < -1.0 ? -1.0 : (sphi > 1.0 ? 1.0 : sphi);
-  const double phi = asin(sphi);
-  double fi = rint((double)H / 2 - (double)H * theta / (2 * PI));
-  double fj = rint((double)W / 2 - (double)W * phi / PI);
-  fi = fi < 0.0 ? 0.0 : (fi > (double)(H - 1) ? (double)(H - 1) : fi);
-  fj = fj < 0.0 ? 0.0 : (fj > (double)(W - 1) ? (double)(W - 1) : fj);
-  if (!(fi == fi) || !(fj == fj)) return false;  // r2 == 0: NaN angles; numpy's int16 cast of NaN is platform noise
-  tgt = (long long)fi * W + (long long)fj;
-  return true;
-}
-
-// z-buffer key of source `idx` (of n) with radius r2, see above
-__device__ __forceinline__ unsigned long long zkey(double r2, long long idx, long long n) {
-  const float m = (float)r2;
-  const bool inL = r2 < (double)m;
-  const unsigned lo = inL ? (unsigned)(n - 1 - idx) : (0x80000000u | (unsigned)idx);
-  return ((unsigned long long)__float_as_uint(m) << 32) | lo;
-}
-
+// depthViewTransWithConf: pass 1 projects every source pixel (geom::project_pixel) and keeps the reference's survivor of every
+// target by a 64-bit atomic min of geom::zkey; pass 2 (geom::resolve_key) turns the keys into depth and confidence.
 __global__ __launch_bounds__(NT) void view_trans_scatter_kernel(const float* __restrict__ view1, const float* __restrict__ trig,
                                                                 unsigned long long* __restrict__ keys, int H, int W, ViewXform xf) {
   const long long n = (long long)H * W;
@@ -140,8 +63,8 @@ __global__ __launch_bounds__(NT) void view_trans_scatter_kernel(const float* __r
     double r2;
     long long tgt;
     const int i = (int)(idx / W), j = (int)(idx - (long long)i * W);
-    if (project_pixel(view1[idx], trig[j], trig[W + j], trig[2 * W + i], trig[2 * W + H + i], xf, H, W, r2, tgt))
-      atomicMin(keys + tgt, zkey(r2, idx, n));
+    if (geom::project_pixel(view1[idx], trig[j], trig[W + j], trig[2 * W + i], trig[2 * W + H + i], xf, H, W, r2, tgt))
+      atomicMin(keys + tgt, geom::zkey(r2, idx, n));
   }
 }
 
@@ -153,7 +76,7 @@ __global__ __launch_bounds__(NT) void view_project_kernel(const float* __restric
     double r2 = 0.0;
     long long tgt = -1;
     const int i = (int)(idx / W), j = (int)(idx - (long long)i * W);
-    const bool ok = project_pixel(view1[idx], trig[j], trig[W + j], trig[2 * W + i], trig[2 * W + H + i], xf, H, W, r2, tgt);
+    const bool ok = geom::project_pixel(view1[idx], trig[j], trig[W + j], trig[2 * W + i], trig[2 * W + H + i], xf, H, W, r2, tgt);
     r2_out[idx] = r2;
     tgt_out[idx] = ok ? (int)tgt : -1;
   }
@@ -164,7 +87,7 @@ __global__ __launch_bounds__(NT) void zbuffer_scatter_kernel(const double* __res
                                                              unsigned long long* __restrict__ keys, long long n) {
   for (long long idx = (long long)blockIdx.x * NT + threadIdx.x; idx < n; idx += (long long)gridDim.x * NT) {
     const int t = tgt[idx];
-    if (t >= 0 && t < n && r2[idx] < 100000.0) atomicMin(keys + t, zkey(r2[idx], idx, n));
+    if (t >= 0 && t < n && r2[idx] < 100000.0) atomicMin(keys + t, geom::zkey(r2[idx], idx, n));
   }
 }
 
@@ -172,17 +95,9 @@ __global__ __launch_bounds__(NT) void view_trans_resolve_kernel(const unsigned l
                                                                 const float* __restrict__ conf1, float* __restrict__ view2,
                                                                 float* __restrict__ conf2, long long n) {
   for (long long idx = (long long)blockIdx.x * NT + threadIdx.x; idx < n; idx += (long long)gridDim.x * NT) {
-    const unsigned long long k = keys[idx];
-    float v = 0.f, c = 0.f;
-    if (k != ~0ull) {
-      v = __uint_as_float((unsigned)(k >> 32));
-      const unsigned lo = (unsigned)(k & 0xffffffffull);
-      c = conf1[(lo & 0x80000000u) ? (long long)(lo & 0x7fffffffu) : n - 1 - (long long)lo];
-      if (v == 100000.f) v = 0.f;  // "view_2[view_2 == 100000] = 0"
-      if (v > 1000.f) v = 1000.f;
-    }
-    view2[idx] = v;
-    conf2[idx] = c;
+    const float2 vc = geom::resolve_key(keys[idx], conf1, n);
+    view2[idx] = vc.x;
+    conf2[idx] = vc.y;
   }
 }
 

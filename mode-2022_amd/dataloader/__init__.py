@@ -2,4 +2,5 @@
 Host-side IO around the hot path; needs PIL and numpy only (the reference needs cv2 and torchvision)."""
 from . import list_file, preprocess
 from .list_file import list_deep360_disparity_train, list_deep360_disparity_test, list_deep360_fusion_train, list_deep360_fusion_test
+from .list_file import list_deep360_frames
 from .deep360_loader import Deep360DatasetDisparity, Deep360DatasetFusion

@@ -82,3 +82,15 @@ def list_deep360_fusion_train(input_path, dataset_path, soil):
 def list_deep360_fusion_test(input_path, dataset_path, soil):
   """-> test_depthes, test_confs, test_rgbs, test_gt (list_file.py:204-267)."""
   return tuple(_fusion_lists(input_path, dataset_path, soil, ('testing',))['testing'])
+
+
+def list_deep360_frames(filepath, subset, soiled=False):
+  """Whole frames of one subset ('training', 'validation' or 'testing') for models.ModeMultiView: a list with, per frame, the
+  frame's 12 panorama paths (sorted: pairs 12, 13, 14, 23, 24, 34 as left, right) and its ground-truth depth path.  Frame f of an
+  episode is rgb[12 f : 12 f + 12] and depth[f] of the sorted listings, the positional rule of the fusion lists (_fusion_subset)."""
+  frames = []
+  for ep in EPISODES:
+    rgb = _sorted_paths(os.path.join(filepath, ep, subset, 'rgb_soiled' if soiled else 'rgb'))
+    gt = _sorted_paths(os.path.join(filepath, ep, subset, 'depth'))
+    frames += [(rgb[12 * f:12 * f + 12], gt[f]) for f in range(len(gt))]
+  return frames

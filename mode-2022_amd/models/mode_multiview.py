@@ -1,0 +1,102 @@
+"""ModeMultiView: fused 360-degree depth of whole Deep360 frames in one call (inference only).
+
+The reference runs MODE as two scripts joined through the disk: save_output_disparity_stage.py evaluates one stereo pair at a time
+and writes a depth map (.npz) and an 8-bit confidence map (.png) per pair; test_fusion.py reads them back into the fusion network.
+Here the chain stays on the GPU:
+
+  stage 1   ONE ModeDisparity(out_conf=True) call over the six pairs of all F frames (batch 6F)
+  hand-off  utils.geometry.disp2depth_frames_gpu: depth and confidence of every pair in camera 1's Cassini frame, interleaved as
+            ModeFusion takes them (three launches; bit for bit what six disp2depth_gpu calls and a cat give)
+  stage 2   the fusion network's feature extraction on the hand-off and the RGB of cameras 1-4
+
+forward() returns (F, 1, H, W) depth in camera 1's Cassini frame; utils.geometry.cassini2Equirec(depth) gives the equirectangular
+(F, W, 2W) panorama.  conf_png=True (the default) feeds the fusion network the confidence as the reference's PNG export reads back,
+which is what the fusion checkpoints were trained and tested on."""
+import os
+
+import torch
+import torch.nn as nn
+
+from mode_hip import require_gpu
+from utils import geometry
+
+from .mode_disparity import ModeDisparity
+from .mode_fusion import Baseline, ModeFusion
+
+# panoramas of a frame that the fusion network sees: both images of pair 12 (cameras 1, 2) and both of pair 34 (cameras 3, 4), at
+# positions 0, 1, 10, 11 of the frame's 12 files (dataloader/list_file.py _FUSION_RGB)
+FUSION_RGB = (0, 1, 10, 11)
+
+
+def split_frames(frames):
+  """(F, 12, 3, H, W) panoramas in a frame's sorted file order -> (left (6F, 3, H, W), right (6F, 3, H, W), rgb (F, 12, H, W)).
+  Pair p of frame f is left[6f + p] = frames[f, 2p], right[6f + p] = frames[f, 2p + 1] (list_file.py _disparity_subset); rgb is
+  frames[f, FUSION_RGB] with the colour channels flattened.  Works on any device."""
+  if frames.dim() != 5 or frames.shape[1] != 12 or frames.shape[2] != 3:
+    raise ValueError('ModeMultiView: frames must be (F, 12, 3, H, W), got %s' % (tuple(frames.shape),))
+  F, _, C, H, W = frames.shape
+  left = frames[:, 0::2].reshape(F * 6, C, H, W)
+  right = frames[:, 1::2].reshape(F * 6, C, H, W)
+  rgb = torch.cat([frames[:, k] for k in FUSION_RGB], 1)  # (no index tensor: an upload cannot be captured into a graph)
+  return left, right, rgb
+
+
+def _state_dict_of(src):
+  """A path or a dict in the format of the reference's training scripts ({'state_dict': ...}, keys with or without the
+  DataParallel 'module.' prefix) -> a plain state_dict."""
+  if isinstance(src, (str, os.PathLike)):
+    src = torch.load(src, map_location='cpu')
+  sd = src.get('state_dict', src) if isinstance(src, dict) else src
+  return {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
+
+
+class ModeMultiView(nn.Module):
+  """Both MODE stages on whole frames.  Children: `disparity` (ModeDisparity with the confidence output) and `fusion` (ModeFusion,
+  or Baseline with fusion='Baseline'), so the state_dict is theirs under the prefixes 'disparity.' and 'fusion.'."""
+
+  def __init__(self, maxdisp=192, maxdepth=1000., height=1024, width=512, dbname='Deep360', fusion='ModeFusion',
+               channels=(32, 64, 128, 256), conf_png=True):
+    super(ModeMultiView, self).__init__()
+    if height % 16 or width % 16:
+      raise ValueError('ModeMultiView: %d x %d is not a multiple of 16 (the reference pads to 16; this module does not)' % (height, width))
+    if fusion not in ('ModeFusion', 'Baseline'):
+      raise ValueError('ModeMultiView: fusion must be ModeFusion or Baseline, not %r' % (fusion,))
+    geometry._baselines(dbname)  # 3D60 has no baselines in the reference: refused here, not at the first frame
+    self.height, self.width, self.dbname, self.conf_png, self.fusion_kind = height, width, dbname, conf_png, fusion
+    self.disparity = ModeDisparity(maxdisp, 'Sphere', height, width, 'Cassini', out_conf=True)
+    if fusion == 'ModeFusion':
+      self.fusion = ModeFusion(maxdepth, list(channels), {'depth': 12, 'rgb': 12})
+    else:
+      self.fusion = Baseline(maxdepth)
+
+  def load_checkpoints(self, disp=None, fusion=None):
+    """Load the checkpoints of the two training scripts (paths or dicts); either may be None."""
+    if disp is not None:
+      self.disparity.load_state_dict(_state_dict_of(disp))
+    if fusion is not None:
+      self.fusion.load_state_dict(_state_dict_of(fusion))
+    return self
+
+  def forward(self, frames, return_stages=False):
+    """frames (F, 12, 3, H, W): ImageNet-normalised panoramas of F frames in sorted file order -> depth (F, 1, H, W) in camera 1's
+    Cassini frame; with return_stages also {'disp', 'conf': (6F, 1, H, W) of stage 1, 'fusion_input': the hand-off}."""
+    if self.training:
+      raise RuntimeError('ModeMultiView is inference only: call .eval() first')
+    require_gpu(frames)
+    left, right, rgb = split_frames(frames)
+    H, W = frames.shape[-2:]
+    if H % 16 or W % 16:
+      raise ValueError('ModeMultiView: %d x %d is not a multiple of 16' % (H, W))
+    if (H, W) != (self.height, self.width):
+      raise ValueError('ModeMultiView: built for %d x %d, got %d x %d' % (self.height, self.width, H, W))
+    with torch.no_grad():
+      disp, conf = self.disparity(left, right)
+      fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png,
+                                                    depth_only=self.fusion_kind == 'Baseline')
+      if self.fusion_kind == 'ModeFusion':
+        depth = self.fusion.feature_extraction(fusion_input, rgb)
+      else:
+        depth = self.fusion.feature_extraction(fusion_input)
+    if return_stages:
+      return depth, {'disp': disp, 'conf': conf, 'fusion_input': fusion_input}
+    return depth

@@ -12,11 +12,13 @@ There is no CPU path: the native library is required (the reference, too, hard-c
 """
 import functools
 import math
+import threading
 
 import numpy as np
 import torch
 
 from mode_hip import check, lib, ptr, require_f32c, require_gpu, stream_of
+from mode_hip import functional as _HF
 
 _DEV = 'cuda'
 
@@ -223,6 +225,13 @@ def _baselines(dbname):
   return np.array([0.6 * math.sqrt(2), 0.6 * math.sqrt(2), 1.2, 1.2, 0.6 * math.sqrt(2), 0.6 * math.sqrt(2)]).astype(np.float32)
 
 
+# camera 1's frame from the others (save_output_disparity_stage.py:136-158): pairs 13 and 14 are rotations of the Cassini image by the
+# pitch below; pairs 23, 24 and 34 are depthViewTransWithConf(view, conf, y0, z0, x0, pitch, yaw, roll) with these arguments
+_ROT_PITCH = {'13': 0.5 * math.pi, '14': 0.25 * math.pi}
+_VIEW_POSES = {'23': (0, -math.sqrt(2) / 2, -math.sqrt(2) / 2, 0.75 * math.pi, 0, 0), '24': (0, -1, 0, 0.5 * math.pi, 0, 0),
+               '34': (0, 1, 0, 0, 0, 0)}
+
+
 def disp2depth_gpu(disp, conf_map, cam_pair, dbname='Deep360'):
   """disp, conf_map: (H, W) float32 device tensors -> (depth, conf) in the reference frame of camera 1, device tensors."""
   if cam_pair not in CAM_PAIRS:
@@ -237,15 +246,10 @@ def disp2depth_gpu(disp, conf_map, cam_pair, dbname='Deep360'):
     check(lib().mode_disp2depth(ptr(disp), ptr(depth_l), H, W, float(_baselines(dbname)[CAM_PAIRS[cam_pair]]), stream_of(disp)), 'mode_disp2depth')
   if cam_pair == '12':
     return depth_l, conf_map
-  if cam_pair in ('13', '14'):
-    angle = 0.5 * math.pi if cam_pair == '13' else 0.25 * math.pi
-    both = rotateCassini_gpu(torch.stack((depth_l, conf_map.to(depth_l.dtype))).unsqueeze(0), angle, 0, 0)[0]
+  if cam_pair in _ROT_PITCH:
+    both = rotateCassini_gpu(torch.stack((depth_l, conf_map.to(depth_l.dtype))).unsqueeze(0), _ROT_PITCH[cam_pair], 0, 0)[0]
     return both[0], both[1]
-  if cam_pair == '23':
-    return depthViewTransWithConf_gpu(depth_l, conf_map, 0, -math.sqrt(2) / 2, -math.sqrt(2) / 2, 0.75 * math.pi, 0, 0)
-  if cam_pair == '24':
-    return depthViewTransWithConf_gpu(depth_l, conf_map, 0, -1, 0, 0.5 * math.pi, 0, 0)
-  return depthViewTransWithConf_gpu(depth_l, conf_map, 0, 1, 0, 0, 0, 0)
+  return depthViewTransWithConf_gpu(depth_l, conf_map, *_VIEW_POSES[cam_pair])
 
 
 def disp2depth(disp, conf_map, cam_pair, dbname='Deep360'):
@@ -256,3 +260,70 @@ def disp2depth(disp, conf_map, cam_pair, dbname='Deep360'):
   if out is None:
     return None
   return out[0].cpu().numpy(), out[1].cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ the multi-view hand-off
+PAIRS = ('12', '13', '14', '23', '24', '34')  # the order of a frame's six pairs (CAM_PAIRS)
+MV_CONF_PNG, MV_DEPTH_ONLY = 1, 2  # MODE_MV_* of include/mode_hip.h
+_frames_cache = _HF._LRU(8)  # (H, W, device, dbname) -> constant tables of mode_multiview_handoff (graph-pinned while captured)
+_frames_lock = threading.Lock()
+
+
+def _frames_tables(H, W, device, dbname):
+  """(baselines float32 (6,) host, rotation grids (2, H, W, 2) device, trig device, 3 x (R, t) float64 (36,) host) -- the tables
+  disp2depth_gpu uses for the six pairs, built by the same functions."""
+  key = (H, W, str(device), dbname)
+  with _frames_lock:
+    hit = _frames_cache.get(key)
+    if hit is not None:
+      return hit
+    baselines = np.ascontiguousarray(_baselines(dbname), dtype=np.float32)
+    grids = torch.cat([_rotate_grid(H, W, float(_ROT_PITCH[p]), 0.0, 0.0, str(device)) for p in ('13', '14')]).contiguous()
+    trig = _trig_device(H, W, str(device)).clone()
+    xforms = []
+    for p in ('23', '24', '34'):
+      y0, z0, x0, pitch, yaw, roll = _VIEW_POSES[p]
+      xforms += [np.ascontiguousarray(_rotation(pitch, yaw, roll), dtype=np.float64).ravel(), np.array([x0, y0, z0], dtype=np.float64)]
+    entry = (baselines, grids, trig, np.ascontiguousarray(np.concatenate(xforms)))
+    _frames_cache[key] = entry
+    return entry
+
+
+def _as_frames(t, what):
+  """(F, 6, H, W), (6F, 1, H, W) or (6F, H, W) -> a (F, 6, H, W) view."""
+  if t.dim() == 4 and t.shape[1] == 6:
+    return t
+  if (t.dim() == 4 and t.shape[1] == 1) or t.dim() == 3:
+    if t.shape[0] % 6:
+      raise ValueError('disp2depth_frames_gpu: %s has %d maps, not six per frame' % (what, t.shape[0]))
+    return t.view(t.shape[0] // 6, 6, t.shape[-2], t.shape[-1])
+  raise ValueError('disp2depth_frames_gpu: %s of shape %s is not (F, 6, H, W), (6F, 1, H, W) or (6F, H, W)' % (what, tuple(t.shape)))
+
+
+def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_only=False):
+  """The six pairs of F frames at once: disp, conf (F, 6, H, W) float32 device tensors (pair order PAIRS; (6F, 1, H, W) and
+  (6F, H, W) are taken as views) -> (F, 12, H, W) with out[f, 2p], out[f, 2p + 1] = disp2depth_gpu(disp[f, p], conf[f, p], PAIRS[p],
+  dbname) -- ModeFusion's channel interleave -- bit for bit, in three launches (mode_multiview_handoff).  conf_png: every confidence
+  as the reference's 8-bit PNG export reads back, q(c) = float32(float64(clip(rint(c * 255), 0, 255)) / 255).  depth_only:
+  (F, 6, H, W) of the depths alone (the input of Baseline)."""
+  require_gpu(disp, conf)
+  disp, conf = _as_frames(disp.contiguous(), 'disp'), _as_frames(conf.contiguous(), 'conf')
+  require_f32c(disp, conf)
+  if disp.shape != conf.shape or disp.device != conf.device:
+    raise ValueError('disp2depth_frames_gpu: disp %s and conf %s differ' % (tuple(disp.shape), tuple(conf.shape)))
+  F, _, H, W = disp.shape
+  baselines, grids, trig, xforms = _frames_tables(H, W, disp.device, dbname)
+  out = torch.empty((F, 6 if depth_only else 12, H, W), dtype=torch.float32, device=disp.device)
+  ws = torch.empty(lib().mode_multiview_handoff_workspace_bytes(F, H, W) // 8, dtype=torch.int64, device=disp.device)
+  flags = (MV_CONF_PNG if conf_png else 0) | (MV_DEPTH_ONLY if depth_only else 0)
+  with torch.cuda.device_of(disp):
+    check(lib().mode_multiview_handoff(ptr(disp), ptr(conf), F, H, W, baselines.ctypes.data, ptr(grids), ptr(trig), xforms.ctypes.data, flags,
+                                       ptr(out), ptr(ws), stream_of(disp)), 'mode_multiview_handoff')
+  return out
+
+
+
+def conf_png_np(c):
+  """The q rule on the host (numpy float32 in and out): the 8-bit PNG round trip of the reference's confidence export."""
+  c = np.asarray(c, dtype=np.float32)
+  return (np.clip(np.rint(c * np.float32(255)), 0, 255).astype(np.float64) / 255.0).astype(np.float32)

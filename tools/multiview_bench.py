@@ -1,0 +1,141 @@
+"""Time ModeMultiView on whole Deep360 frames (1024 x 512, 192 disparities) and its multi-view hand-off.
+
+    python tools/multiview_bench.py [--frames 1 2 4] [--window 1.0] [--out profiles/multiview_bench.json]
+    python tools/multiview_bench.py --once      # one hand-off call and one six-call path at F = 1, for a kernel trace
+
+For every F: the frame time of the composed module, eager and replayed from a captured graph; the split between stage 1 (ModeDisparity
+at batch 6F), the hand-off (utils.geometry.disp2depth_frames_gpu) and stage 2 (the fusion network); and the hand-off against the
+six-call path it replaces (six disp2depth_gpu calls per frame + the interleave).  Device events around windows of at least
+--window seconds after a warm-up; weights from the test fixtures' recipes, seeded random panoramas (the timings do not depend on the values
+beyond the data-dependence of the z-buffer scatter).  Writes one JSON file."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'mode-2022_amd'), os.path.join(ROOT, 'tests', 'golden')):
+  if p not in sys.path:
+    sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+import models  # noqa: E402
+import numpy as np  # noqa: E402
+import recipe  # noqa: E402
+from mode_hip.graph_step import GraphedStep  # noqa: E402
+from models.mode_multiview import split_frames  # noqa: E402
+from utils import geometry as HG  # noqa: E402
+
+DEV = 'cuda:0'
+H, W, MAXDISP, MAXDEPTH = 1024, 512, 192, 1000.
+PAIRS = ('12', '13', '14', '23', '24', '34')
+
+
+def timed(fn, window, warmup=3):
+  """ms per call of fn over a window of at least `window` seconds (device events), after `warmup` calls."""
+  for _ in range(warmup):
+    fn()
+  torch.cuda.synchronize()
+  n = 1
+  while True:
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(n):
+      fn()
+    e.record()
+    e.synchronize()
+    ms = s.elapsed_time(e)
+    if ms >= 1000 * window:
+      return ms / n, n
+    n = max(n + 1, int(n * 1.25 * 1000 * window / max(ms, 1e-3)))
+
+
+def six_calls(disp, conf):
+  frames = []
+  for f in range(disp.shape[0]):
+    chans = []
+    for p, pair in enumerate(PAIRS):
+      chans += list(HG.disp2depth_gpu(disp[f, p], conf[f, p], pair))
+    frames.append(torch.stack(chans))
+  return torch.stack(frames)
+
+
+def make_frames(F, seed):
+  g = torch.Generator().manual_seed(seed)
+  return ((torch.rand(F, 12, 3, H, W, generator=g) - 0.45) / 0.226).to(DEV)
+
+
+def make_net():
+  """The well-conditioned full-size disparity fixture with its running statistics (on unit running statistics the eval forward of
+  the recipe weights is not finite) and a recipe fusion state."""
+  z = np.load(os.path.join(recipe.HERE, 'model_wc_full.npz'))
+  sd = recipe.fixture_state(z)
+  sd.update({k[3:]: torch.from_numpy(z[k]).clone() for k in z.files if k.startswith('bn/')})
+  net = models.ModeMultiView(MAXDISP, MAXDEPTH, H, W)
+  net.disparity.load_state_dict(sd)
+  net.fusion.load_state_dict(recipe.recipe_state(recipe.load_manifest('manifest_mode_fusion.json'), 101))
+  return net.to(DEV).eval()
+
+
+def once():
+  disp = (torch.rand(1, 6, H, W, device=DEV) * 40).contiguous()
+  conf = torch.rand(1, 6, H, W, device=DEV)
+  HG.disp2depth_frames_gpu(disp, conf, conf_png=True)
+  torch.cuda.synchronize()
+  six_calls(disp.view(1, 6, H, W), conf.view(1, 6, H, W))
+  torch.cuda.synchronize()
+  print('once: one hand-off call and one six-call path at F = 1, 1024 x 512')
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--frames', type=int, nargs='+', default=[1, 2, 4])
+  ap.add_argument('--window', type=float, default=1.0)
+  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'multiview_bench.json'))
+  ap.add_argument('--once', action='store_true')
+  args = ap.parse_args()
+  if args.once:
+    return once()
+  net = make_net()
+  rows = []
+  for F in args.frames:
+    t0 = time.time()
+    frames = make_frames(F, 100 + F)
+    with torch.no_grad():
+      left, right, rgb = split_frames(frames)
+      disp, conf = net.disparity(left, right)
+      fi = HG.disp2depth_frames_gpu(disp, conf, conf_png=True)
+      ms_eager, n_eager = timed(lambda: net(frames), args.window)
+      ms_s1, _ = timed(lambda: net.disparity(left, right), args.window)
+      ms_ho, _ = timed(lambda: HG.disp2depth_frames_gpu(disp, conf, conf_png=True), args.window)
+      ms_s2, _ = timed(lambda: net.fusion.feature_extraction(fi, rgb), args.window)
+      d4, c4 = disp.view(F, 6, H, W), conf.view(F, 6, H, W)
+      ms_six, _ = timed(lambda: six_calls(d4, c4), args.window)
+      assert torch.equal(six_calls(d4, c4)[:, 0::2], HG.disp2depth_frames_gpu(disp, conf)[:, 0::2])
+    static = frames.clone()
+    step = GraphedStep(lambda: net(static), static_inputs=(static,))
+    ms_graph, n_graph = timed(step.replay, args.window)
+    eager_out = net(frames)
+    same = bool(torch.equal(step.replay(), eager_out))
+    del step
+    torch.cuda.synchronize()
+    row = {'frames': F, 'eager_ms': ms_eager, 'eager_ms_per_frame': ms_eager / F, 'eager_calls_timed': n_eager,
+           'replay_ms': ms_graph, 'replay_ms_per_frame': ms_graph / F, 'replay_calls_timed': n_graph, 'replay_equals_eager': same,
+           'stage1_ms': ms_s1, 'handoff_ms': ms_ho, 'stage2_ms': ms_s2, 'six_call_handoff_ms': ms_six,
+           'handoff_speedup': ms_six / ms_ho, 'wall_s': time.time() - t0}
+    print(json.dumps(row), flush=True)
+    rows.append(row)
+    del frames, left, right, rgb, disp, conf, fi, static
+    torch.cuda.empty_cache()
+  out = {'tool': 'tools/multiview_bench.py', 'size': [H, W], 'maxdisp': MAXDISP, 'window_s': args.window,
+         'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'rows': rows}
+  os.makedirs(os.path.dirname(args.out), exist_ok=True)
+  with open(args.out, 'w') as f:
+    json.dump(out, f, indent=1)
+  print('wrote', args.out)
+
+
+if __name__ == '__main__':
+  main()
