@@ -810,6 +810,30 @@ int mode_silog_loss_fwd(const float* pred, const float* gt, const uint8_t* mask,
 int mode_silog_loss_bwd(const float* pred, const float* gt, const uint8_t* mask, long long n, float lamda, const double* stats,
                         const float* gloss, float* gpred, mode_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scoring in the equirectangular (ERP) domain (csrc/erp_metrics.hip): what the reference's test_fusion.py does per batch between
+ * the fusion network and its metric table (:82, :86-100).
+ *
+ * mode_erp_depth_metrics (test_fusion.py:86-100): for each of `frames` Cassini maps pred, gt (frames, H, W), H == 2 W, ONE pass that
+ *   resamples both to the ERP panorama (W rows, H columns) through `grid` -- (W, H, 2) normalised (x, y) sample points, the table of
+ *   cassini2Equirec; bilinear, border padding, align_corners = true: the arithmetic of mode_grid_sample_border --, selects the ERP
+ *   pixels with gt_erp <= maxdepth (plain fp32 comparison: NaN is not selected) and reduces the statistics of mode_masked_metrics over
+ *   them, per frame: out (frames, MODE_METRICS_COUNT) fp64, device.  pred_erp / gt_erp, each (frames, W, H) or NULL, receive the
+ *   resampled maps.  Two launches, no atomics, no host synchronisation (capturable into a graph).  Row f depends on frame f alone and
+ *   has the bits of mode_masked_metrics on that frame's ERP maps (from mode_grid_sample_border) and mask: within a frame, ERP pixel
+ *   quads are dealt to threads exactly as that entry deals the elements of a flat range of H * W.
+ *   workspace: device, 8-byte aligned, workspace_bytes >= mode_erp_depth_metrics_workspace_bytes(frames, H, W)
+ *   (= frames * mode_masked_metrics_workspace_bytes(H * W)).  grid: 8-byte aligned.  frames == 0 returns MODE_OK without a launch.
+ * mode_bicubic_up2 (test_fusion.py:82, --resize): (N, C, H, W) -> (N, C, 2H, 2W) as F.interpolate(scale_factor=[2, 2], mode='bicubic',
+ *   align_corners=True): source coordinate o * (in - 1) / (out - 1), cubic convolution with A = -0.75, border-clamped taps, 16 fp32
+ *   products per output.  The four corners of a plane are copied exactly.
+ * Bad arguments return MODE_ERR_BAD_ARG, a missing or small workspace MODE_ERR_WORKSPACE, before any launch. */
+size_t mode_erp_depth_metrics_workspace_bytes(int frames, int H, int W);
+int mode_erp_depth_metrics(const float* pred, const float* gt, const float* grid, int frames, int H, int W, float maxdepth,
+                           const mode_metrics_params* params, void* workspace, size_t workspace_bytes, double* out, float* pred_erp,
+                           float* gt_erp, mode_stream_t stream);
+int mode_bicubic_up2(const float* src, float* dst, int N, int C, int H, int W, mode_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

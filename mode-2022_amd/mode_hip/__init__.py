@@ -171,6 +171,10 @@ SIGNATURES = {
     'mode_masked_metrics': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong] + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 2),
     'mode_silog_loss_fwd': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong, ctypes.c_float, _c_ptr, _c_size] + [_c_ptr] * 3),
     'mode_silog_loss_bwd': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong, ctypes.c_float] + [_c_ptr] * 4),
+    # scoring in the ERP domain (csrc/erp_metrics.hip; reference test_fusion.py:82, 86-100)
+    'mode_erp_depth_metrics_workspace_bytes': (_c_size, [_c_int] * 3),
+    'mode_erp_depth_metrics': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [ctypes.c_float] + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 4),
+    'mode_bicubic_up2': (_c_int, [_c_ptr] * 2 + [_c_int] * 4 + [_c_ptr]),
 }
 
 ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against

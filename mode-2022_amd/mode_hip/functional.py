@@ -1813,13 +1813,9 @@ def _metrics_workspace(n, device):
   return torch.empty(max(lib().mode_masked_metrics_workspace_bytes(n) // 8, 1), dtype=torch.float64, device=device)
 
 
-def masked_metrics(pred, gt, mask=None, px=(), d1=(), ratio=()):
-  """The statistic vector of mode_masked_metrics (include/mode_hip.h) over the elements `mask` selects (None: all) as a float64 numpy
-  array of METRICS_COUNT entries (indices mode_hip.M_*): one launch pair and one small device-to-host copy.  px: thresholds of
-  pixel_error_pct; d1: (th_pixel, th_pct) pairs of D1; ratio: bounds of delta_acc / threshold_acc (each rounded to fp32 as torch does)."""
-  pred, gt, mask = _metrics_operands(pred, gt, mask, 'masked_metrics')
+def _metrics_params(px, d1, ratio, who):
   if max(len(px), len(d1), len(ratio)) > METRICS_MAX_THRESHOLDS:
-    raise ValueError('masked_metrics: at most %d thresholds of each kind' % METRICS_MAX_THRESHOLDS)
+    raise ValueError('%s: at most %d thresholds of each kind' % (who, METRICS_MAX_THRESHOLDS))
   prm = MetricsParams()
   prm.n_px, prm.n_d1, prm.n_ratio = len(px), len(d1), len(ratio)
   for k, t in enumerate(px):
@@ -1828,6 +1824,15 @@ def masked_metrics(pred, gt, mask=None, px=(), d1=(), ratio=()):
     prm.d1_px[k], prm.d1_pct[k] = float(tp), float(tc)
   for k, r in enumerate(ratio):
     prm.ratio[k] = float(r)
+  return prm
+
+
+def masked_metrics(pred, gt, mask=None, px=(), d1=(), ratio=()):
+  """The statistic vector of mode_masked_metrics (include/mode_hip.h) over the elements `mask` selects (None: all) as a float64 numpy
+  array of METRICS_COUNT entries (indices mode_hip.M_*): one launch pair and one small device-to-host copy.  px: thresholds of
+  pixel_error_pct; d1: (th_pixel, th_pct) pairs of D1; ratio: bounds of delta_acc / threshold_acc (each rounded to fp32 as torch does)."""
+  pred, gt, mask = _metrics_operands(pred, gt, mask, 'masked_metrics')
+  prm = _metrics_params(px, d1, ratio, 'masked_metrics')
   n = gt.numel()
   out = torch.empty(METRICS_COUNT, dtype=torch.float64, device=gt.device)
   with torch.cuda.device_of(gt), profiling.region('masked_metrics', (8 + (1 if mask is not None else 0)) * n, 0, gt.device):
@@ -1872,6 +1877,50 @@ def silog_loss(pred, gt, mask=None, lamda=0.5):
   the compaction: `mask` is the outer selection (gt <= maxdepth; None: every element), gt > 0 and pred > 0 are applied inside.  pred
   may be (B, 1, H, W) with gt and mask (B, H, W).  Returns a 0-d device tensor; no host synchronisation (graph-capturable)."""
   return SilogLossFunction.apply(pred, gt, mask, lamda)
+
+
+# ------------------------------------------------------------------------------------ scoring in the ERP domain
+# test_fusion.py:76-100 per batch: an optional x2 bicubic upsampling of the prediction, cassini2Equirec of prediction and ground truth,
+# the gt <= maxdepth selection and eight metrics -- here one upsampling launch and one fused launch pair for any number of frames.
+def erp_depth_metrics(pred, gt, grid, maxdepth, ratio=(), px=(), d1=(), return_erp=False):
+  """pred, gt (F, H, W) Cassini maps (H == 2 W), grid (1, W, H, 2) or (W, H, 2): the sample points of cassini2Equirec
+  (utils.geometry._c2e_grid) -> the (F, METRICS_COUNT) float64 DEVICE tensor of mode_erp_depth_metrics: row f is the statistic
+  vector of masked_metrics over frame f's ERP pixels with gt_erp <= maxdepth, bit for bit.  No host synchronisation
+  (graph-capturable).  return_erp: also the resampled (F, W, H) maps, (stats, pred_erp, gt_erp)."""
+  require_gpu(pred, gt, grid)
+  require_f32c(pred, gt, grid)
+  if pred.dim() != 3 or pred.shape != gt.shape:
+    raise ValueError('erp_depth_metrics: pred %s and gt %s must both be (F, H, W)' % (tuple(pred.shape), tuple(gt.shape)))
+  F, H, W = pred.shape
+  if H != 2 * W or H == 0:
+    raise ValueError('erp_depth_metrics: a Cassini frame is H = 2 W, got %d x %d' % (H, W))
+  if grid.numel() != 2 * H * W or tuple(grid.shape[-3:]) != (W, H, 2):
+    raise ValueError('erp_depth_metrics: grid %s is not (W, H, 2) = (%d, %d, 2)' % (tuple(grid.shape), W, H))
+  prm = _metrics_params(px, d1, ratio, 'erp_depth_metrics')
+  out = torch.empty((F, METRICS_COUNT), dtype=torch.float64, device=gt.device)
+  pe = torch.empty((F, W, H), dtype=torch.float32, device=gt.device) if return_erp else None
+  ge = torch.empty((F, W, H), dtype=torch.float32, device=gt.device) if return_erp else None
+  nbytes = (16 + (8 if return_erp else 0)) * F * H * W
+  with torch.cuda.device_of(gt), profiling.region('erp_depth_metrics', nbytes, 0, gt.device):
+    ws = torch.empty(max(lib().mode_erp_depth_metrics_workspace_bytes(F, H, W) // 8, 1), dtype=torch.float64, device=gt.device)
+    check(lib().mode_erp_depth_metrics(ptr(pred), ptr(gt), ptr(grid), F, H, W, float(maxdepth), ctypes.byref(prm), ptr(ws), ws.numel() * 8,
+                                       ptr(out), None if pe is None else ptr(pe), None if ge is None else ptr(ge), stream_of(gt)),
+          'mode_erp_depth_metrics')
+  return (out, pe, ge) if return_erp else out
+
+
+def bicubic_up2(x):
+  """(N, C, H, W) -> (N, C, 2H, 2W) as F.interpolate(x, scale_factor=[2, 2], mode='bicubic', align_corners=True) (test_fusion.py:82)
+  on mode_bicubic_up2."""
+  require_gpu(x)
+  require_f32c(x)
+  if x.dim() != 4 or 0 in x.shape[1:]:
+    raise ValueError('bicubic_up2: expected a non-empty (N, C, H, W) tensor, got %s' % (tuple(x.shape),))
+  N, C, H, W = x.shape
+  y = torch.empty((N, C, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
+  with torch.cuda.device_of(x), profiling.region('bicubic_up2', 4 * 5 * x.numel(), 2 * 20 * y.numel(), x.device):
+    check(lib().mode_bicubic_up2(ptr(x), ptr(y), N, C, H, W, stream_of(x)), 'mode_bicubic_up2')
+  return y
 
 
 # ------------------------------------------------------------------------------------ BatchNorm (+ add) (+ ReLU)

@@ -11,14 +11,17 @@ Here the chain stays on the GPU:
 
 forward() returns (F, 1, H, W) depth in camera 1's Cassini frame; utils.geometry.cassini2Equirec(depth) gives the equirectangular
 (F, W, 2W) panorama.  conf_png=True (the default) feeds the fusion network the confidence as the reference's PNG export reads back,
-which is what the fusion checkpoints were trained and tested on."""
+which is what the fusion checkpoints were trained and tested on.
+
+evaluate() goes one step further, to what test_fusion.py:76-100 reports: the ERP panorama and the per-frame metric rows against a
+ground truth, scored on the GPU (utils.panorama)."""
 import os
 
 import torch
 import torch.nn as nn
 
 from mode_hip import require_gpu
-from utils import geometry
+from utils import geometry, panorama
 
 from .mode_disparity import ModeDisparity
 from .mode_fusion import Baseline, ModeFusion
@@ -63,6 +66,7 @@ class ModeMultiView(nn.Module):
       raise ValueError('ModeMultiView: fusion must be ModeFusion or Baseline, not %r' % (fusion,))
     geometry._baselines(dbname)  # 3D60 has no baselines in the reference: refused here, not at the first frame
     self.height, self.width, self.dbname, self.conf_png, self.fusion_kind = height, width, dbname, conf_png, fusion
+    self.maxdepth = float(maxdepth)
     self.disparity = ModeDisparity(maxdisp, 'Sphere', height, width, 'Cassini', out_conf=True)
     if fusion == 'ModeFusion':
       self.fusion = ModeFusion(maxdepth, list(channels), {'depth': 12, 'rgb': 12})
@@ -100,3 +104,17 @@ class ModeMultiView(nn.Module):
     if return_stages:
       return depth, {'disp': disp, 'conf': conf, 'fusion_input': fusion_input}
     return depth
+
+  def evaluate(self, frames, gt, maxdepth=None):
+    """forward(frames) scored as test_fusion.py:86-100 scores a batch: gt (F, H, W) Cassini ground truth on the device ->
+    (depth_erp (F, W, H) device panorama, metrics (F, 8) float64 numpy rows [mae, rmse, absrel, sqrel, silog, delta 1, 2, 3] over the
+    ERP pixels with gt <= maxdepth; default: the maxdepth the module was built with).  Inference only, like forward()."""
+    if self.training:
+      raise RuntimeError('ModeMultiView is inference only: call .eval() first')
+    require_gpu(frames, gt)
+    want = (frames.shape[0], self.height, self.width)
+    if tuple(gt.shape) != want:
+      raise ValueError('ModeMultiView.evaluate: gt %s is not (F, H, W) = %s' % (tuple(gt.shape), want))
+    depth = self.forward(frames)
+    rows, depth_erp, _ = panorama.erp_depth_metrics(depth, gt, self.maxdepth if maxdepth is None else maxdepth, return_erp=True)
+    return depth_erp, rows

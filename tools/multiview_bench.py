@@ -2,10 +2,12 @@
 
     python tools/multiview_bench.py [--frames 1 2 4] [--window 1.0] [--out profiles/multiview_bench.json]
     python tools/multiview_bench.py --once      # one hand-off call and one six-call path at F = 1, for a kernel trace
+    python tools/multiview_bench.py --scoring   # the scoring line alone
 
 For every F: the frame time of the composed module, eager and replayed from a captured graph; the split between stage 1 (ModeDisparity
 at batch 6F), the hand-off (utils.geometry.disp2depth_frames_gpu) and stage 2 (the fusion network); and the hand-off against the
-six-call path it replaces (six disp2depth_gpu calls per frame + the interleave).  Device events around windows of at least
+six-call path it replaces (six disp2depth_gpu calls per frame + the interleave).  One more line for the scoring stage
+(utils.panorama.erp_depth_metrics against the per-frame composition it replaces, F = 1 and 4).  Device events around windows of at least
 --window seconds after a warm-up; weights from the test fixtures' recipes, seeded random panoramas (the timings do not depend on the values
 beyond the data-dependence of the z-buffer scatter).  Writes one JSON file."""
 import argparse
@@ -26,6 +28,7 @@ import numpy as np  # noqa: E402
 import recipe  # noqa: E402
 from mode_hip.graph_step import GraphedStep  # noqa: E402
 from models.mode_multiview import split_frames  # noqa: E402
+from utils import evaluation, panorama  # noqa: E402
 from utils import geometry as HG  # noqa: E402
 
 DEV = 'cuda:0'
@@ -79,6 +82,44 @@ def make_net():
   return net.to(DEV).eval()
 
 
+def unfused_scoring(pred, gt, maxdepth=MAXDEPTH):
+  """The scoring stage composed from its parts, per frame: cassini2Equirec twice, the aten `<=`, depth_metrics (one copy back each)."""
+  rows = []
+  for f in range(pred.shape[0]):
+    pe, ge = HG.cassini2Equirec(pred[f:f + 1]), HG.cassini2Equirec(gt[f:f + 1].unsqueeze(1))
+    rows.append(evaluation.depth_metrics(pe, ge, ge <= maxdepth))
+  return np.array(rows)
+
+
+def scoring_line(reps=50, warmup=5):
+  """Fused scoring call against the unfused composition at F = 1 and F = 4, 1024 x 512: alternating A B A B, `reps` repetitions of
+  each after a warm-up, device events around every single call (both end in their copy back); medians in ms."""
+  row = {'stage': 'scoring', 'size': [H, W], 'reps': reps}
+  for F in (1, 4):
+    g = torch.Generator().manual_seed(200 + F)
+    gt = (torch.rand(F, H, W, generator=g) * 1100).to(DEV)  # about a tenth beyond maxdepth
+    pred = (gt.unsqueeze(1) * (1 + 0.1 * torch.randn(F, 1, H, W, generator=g).to(DEV))).contiguous()
+    calls = {'fused': lambda: panorama.erp_depth_metrics(pred, gt, MAXDEPTH), 'unfused': lambda: unfused_scoring(pred, gt)}
+    assert calls['fused']().tobytes() == calls['unfused']().tobytes()
+    for _ in range(warmup):
+      for fn in calls.values():
+        fn()
+    ms = {k: [] for k in calls}
+    for _ in range(reps):
+      for k, fn in calls.items():
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        e.synchronize()
+        ms[k].append(s.elapsed_time(e))
+    for k in calls:
+      row['%s_ms_F%d' % (k, F)] = float(np.median(ms[k]))
+    row['speedup_F%d' % F] = row['unfused_ms_F%d' % F] / row['fused_ms_F%d' % F]
+  print(json.dumps(row), flush=True)
+  return row
+
+
 def once():
   disp = (torch.rand(1, 6, H, W, device=DEV) * 40).contiguous()
   conf = torch.rand(1, 6, H, W, device=DEV)
@@ -95,9 +136,12 @@ def main():
   ap.add_argument('--window', type=float, default=1.0)
   ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'multiview_bench.json'))
   ap.add_argument('--once', action='store_true')
+  ap.add_argument('--scoring', action='store_true', help='only the scoring line')
   args = ap.parse_args()
   if args.once:
     return once()
+  if args.scoring:
+    return scoring_line()
   net = make_net()
   rows = []
   for F in args.frames:
@@ -130,7 +174,7 @@ def main():
     del frames, left, right, rgb, disp, conf, fi, static
     torch.cuda.empty_cache()
   out = {'tool': 'tools/multiview_bench.py', 'size': [H, W], 'maxdisp': MAXDISP, 'window_s': args.window,
-         'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'rows': rows}
+         'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'rows': rows, 'scoring': scoring_line()}
   os.makedirs(os.path.dirname(args.out), exist_ok=True)
   with open(args.out, 'w') as f:
     json.dump(out, f, indent=1)
