@@ -441,7 +441,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restric
       if (AMAX) mx = max(mx, mag(r));
       gy[base + i] = r;
     }
-  if (AMAX) mode::absmax_block_commit(mx, amax, reinterpret_cast<unsigned*>(shd));
+  if (AMAX && amax) mode::absmax_block_commit(mx, amax, reinterpret_cast<unsigned*>(shd));  // (amax: the same for every thread)
 }
 
 int pick_nsplit(int C, long long S) {
@@ -701,13 +701,13 @@ extern "C" int mode_bn_train_bwd_amax(const float* gout, const float* y, const f
   const int BC = B * C;
   const char* who = "mode_bn_train_bwd";
   const double count = (double)(B / groups) * (double)S;
+  // One instantiation whether the maximum is asked for or not (a null `amax` only skips the commit): the compiler contracts
+  // A g + Bc y + Cc differently in an instantiation that does not track the maximum, and the plain entry would then differ from its
+  // `_amax` twin in the last bit of dL/dy.  The tracking costs the HBM-bound pass a few VALU operations per element.
 #define MODE_BN_BWD_APPLY(M, G)                                                                                                         \
-  (amax ? launch_apply(bn_bwd_apply_kernel<M, G, true>, BC, S, st, who, gout, y, o, save_scale, save_shift, partial, gamma, save_mean,    \
-                       save_invstd, ggamma, gbeta, accumulate, nsplit, count, groups, B / groups, gy, (G) ? gadd : gy, C, S,            \
-                       reinterpret_cast<unsigned*>(amax))                                                                             \
-        : launch_apply(bn_bwd_apply_kernel<M, G, false>, BC, S, st, who, gout, y, o, save_scale, save_shift, partial, gamma, save_mean,   \
-                       save_invstd, ggamma, gbeta, accumulate, nsplit, count, groups, B / groups, gy, (G) ? gadd : gy, C, S,            \
-                       (unsigned*)nullptr))
+  launch_apply(bn_bwd_apply_kernel<M, G, true>, BC, S, st, who, gout, y, o, save_scale, save_shift, partial, gamma, save_mean,          \
+               save_invstd, ggamma, gbeta, accumulate, nsplit, count, groups, B / groups, gy, (G) ? gadd : gy, C, S,                  \
+               reinterpret_cast<unsigned*>(amax))
   if (mode == 0) return gadd ? MODE_BN_BWD_APPLY(0, true) : MODE_BN_BWD_APPLY(0, false);
   if (mode == 1) return gadd ? MODE_BN_BWD_APPLY(1, true) : MODE_BN_BWD_APPLY(1, false);
   return gadd ? MODE_BN_BWD_APPLY(2, true) : MODE_BN_BWD_APPLY(2, false);
