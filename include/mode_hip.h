@@ -9,7 +9,8 @@
  *
  * Conventions (all entry points):
  *   - every pointer is a DEVICE pointer to a contiguous fp32 buffer allocated by the caller
- *     (the reference requires contiguous tensors too: sphere_conv_cuda.cpp:48, 138-140);
+ *     (the reference requires contiguous tensors too: sphere_conv_cuda.cpp:48, 138-140), unless
+ *     the entry says otherwise (index and table buffers; the 8-bit frames of the ingest entries);
  *   - the library never allocates or keeps device memory; scratch is passed in as `workspace`;
  *   - work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the default stream) and
  *     the call returns without synchronising (reference: at::cuda::getCurrentCUDAStream(),
@@ -833,6 +834,34 @@ int mode_erp_depth_metrics(const float* pred, const float* gt, const float* grid
                            const mode_metrics_params* params, void* workspace, size_t workspace_bytes, double* out, float* pred_erp,
                            float* gt_erp, mode_stream_t stream);
 int mode_bicubic_up2(const float* src, float* dst, int N, int C, int H, int W, mode_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * 8-bit ingest of whole frames (csrc/ingest.hip): what the reference's loaders do on the host between the decoded PNGs and the two
+ * networks.  frames_u8 is the one buffer of this header that is not fp32: (F, 12, H, W, 3) bytes, the 12 panoramas of a frame in
+ * sorted file order, each as np.asarray(PIL image) lays it out; 4-byte aligned.  lut is the device table (256, 3) fp32 with
+ * lut[v][c] = the bits of ((v / 255) - mean[c]) / std[c] as the host transform rounds it (dataloader/preprocess.py:8, 64-69:
+ * ToTensor + Normalize with the ImageNet statistics); the kernels only look values up.
+ *
+ * mode_frames_u8_ingest (deep360_loader.py:108-109, 161-163): norm = the table lookup on every byte, planar (3, H, W) fp32 out:
+ *     left[6 f + p] = norm(frames[f, 2 p]), right[6 f + p] = norm(frames[f, 2 p + 1])      (6 F, 3, H, W) each
+ *     rgb[f] = the 12 planes of panoramas 0, 1, 10, 11 of frame f                           (F, 12, H, W), or NULL = not wanted
+ *   H W % 4 == 0; outputs 16-byte aligned.  One launch: three dwords (four pixels) in and one 16-byte store per plane per thread.
+ * mode_rgb_half_pil (deep360_loader.py:151-153, 161-163): panoramas 0, 1, 10, 11 of every frame halved exactly as Pillow's
+ *   Image.resize((W / 2, H / 2)) halves an RGB image (Resample.c, bicubic a = -0.5, support 4, 8 bits per channel: the horizontal
+ *   pass, its result stored in 8 bits, the vertical pass; per pass clip((2^21 + sum_j px_j kk_j) >> 22, 0, 255) in 32-bit integers),
+ *   then norm: rgb_half (F, 12, H / 2, W / 2) fp32; half_u8 (F, 4, H / 2, W / 2, 3) bytes receives the 8-bit result, or NULL.
+ *   tab_w (W / 2, 10), tab_h (H / 2, 10) int32, device: per output index the first input index, the number of taps (<= 8) and 8
+ *   fixed-point coefficients kk = int(k 2^22 +/- 0.5), built on the host in double (dataloader.preprocess.pil_half_table).  H and W even.
+ *   One launch: a workgroup owns 16 x 32 output pixels and keeps the horizontal pass of the 38 input rows under them in LDS.
+ * mode_decimate2 (deep360_loader.py:147-150): out[n, y, x] = in[n, 2 y, 2 x] over `planes` fp32 planes (H, W) -> (ceil(H / 2), ceil(W / 2)),
+ *   the [::2, ::2] of the loader on the planes of mode_multiview_handoff.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, misaligned buffers, H, W <= 0, F or planes < 0, sizes
+ * the entry does not take and element counts (36 F H W, planes H W) >= 2^31.  F = 0 / planes = 0 is a no-op. */
+int mode_frames_u8_ingest(const uint8_t* frames_u8, const float* lut, int F, int H, int W, float* left, float* right, float* rgb,
+                          mode_stream_t stream);
+int mode_rgb_half_pil(const uint8_t* frames_u8, const int32_t* tab_w, const int32_t* tab_h, const float* lut, int F, int H, int W,
+                      float* rgb_half, uint8_t* half_u8, mode_stream_t stream);
+int mode_decimate2(const float* in, float* out, long long planes, int H, int W, mode_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -49,3 +49,50 @@ def get_transform_stage1(name='imagenet', normalize=None, augment=True):
 def get_transform_stage2(name='deep360', normalize=None, augment=False):
   """Depth transform (preprocess.py:72-74): to tensor, mean 0 / std 1."""
   return depth_normalize(deep360_stats)
+
+
+def norm_table(name='imagenet'):
+  """(256, 3) float32: row v = get_transform_stage1(augment=False) of a pixel whose three channels hold v -- the transform itself run
+  over the 256 byte values, so that a lookup has its bits (mode_frames_u8_ingest / mode_rgb_half_pil only look values up)."""
+  ramp = np.repeat(np.arange(256, dtype=np.uint8)[:, None, None], 3, axis=2)  # (256, 1, 3): an image holding every value in every channel
+  return get_transform_stage1(name, augment=False)(ramp)[:, :, 0].t().contiguous()
+
+
+def _pil_bicubic(x):
+  """Pillow's bicubic_filter (Resample.c, a = -0.5) in double."""
+  a = -0.5
+  x = abs(x)
+  if x < 1.0:
+    return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+  if x < 2.0:
+    return (((x - 5) * x + 8) * x - 4) * a
+  return 0.0
+
+
+PIL_PRECISION_BITS = 32 - 8 - 2  # Resample.c: 8-bit pixels, 2 bits of headroom for the bicubic overshoot
+
+
+def pil_half_table(n):
+  """The coefficients of one pass of PIL.Image.resize to n // 2 out of n (the fusion loader's --resize, reference
+  dataloader/deep360_loader.py:151-153), as Pillow's Resample.c builds them for 8-bit images (precompute_coeffs with the default
+  bicubic filter, scale 2, support 4, then normalize_coeffs_8bpc): -> (xmin (n/2,) int32, count (n/2,) int32, kk (n/2, 8) int32).
+  Output i is clip((2^21 + sum_{j < count[i]} px[xmin[i] + j] * kk[i, j]) >> 22, 0, 255).  All arithmetic in double, in Pillow's
+  order; rows past count are zero.  Only five distinct rows exist: two at each edge and the 8-tap interior one."""
+  if n < 2 or n % 2:
+    raise ValueError('pil_half_table: %r is not a positive even size (Pillow halves other sizes with another scale)' % (n,))
+  out, scale, support = n // 2, 2.0, 4.0
+  xmin = np.zeros(out, dtype=np.int32)
+  count = np.zeros(out, dtype=np.int32)
+  kk = np.zeros((out, 8), dtype=np.int32)
+  for i in range(out):
+    center = (i + 0.5) * scale
+    lo = max(0, int(center - support + 0.5))
+    hi = min(n, int(center + support + 0.5))
+    k = [_pil_bicubic((j + lo - center + 0.5) / scale) for j in range(hi - lo)]
+    ww = 0.0
+    for v in k:
+      ww += v
+    k = [v / ww for v in k] if ww != 0.0 else k
+    xmin[i], count[i] = lo, hi - lo
+    kk[i, :hi - lo] = [int(-0.5 + v * (1 << PIL_PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PIL_PRECISION_BITS)) for v in k]
+  return xmin, count, kk

@@ -175,6 +175,10 @@ SIGNATURES = {
     'mode_erp_depth_metrics_workspace_bytes': (_c_size, [_c_int] * 3),
     'mode_erp_depth_metrics': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [ctypes.c_float] + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 4),
     'mode_bicubic_up2': (_c_int, [_c_ptr] * 2 + [_c_int] * 4 + [_c_ptr]),
+    # 8-bit ingest of whole frames (csrc/ingest.hip; reference dataloader/deep360_loader.py:108-109, 146-163)
+    'mode_frames_u8_ingest': (_c_int, [_c_ptr] * 2 + [_c_int] * 3 + [_c_ptr] * 4),
+    'mode_rgb_half_pil': (_c_int, [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr] * 3),
+    'mode_decimate2': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
 }
 
 ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against

@@ -1923,6 +1923,76 @@ def bicubic_up2(x):
   return y
 
 
+# ------------------------------------------------------------------------------------ 8-bit ingest of whole frames
+def require_u8_frames(frames_u8, who):
+  """(F, 12, H, W, 3) contiguous uint8 on a GPU, or TypeError / NotImplementedError / ValueError."""
+  if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
+    raise TypeError('%s: frames must be a uint8 tensor (got %s)' % (who, getattr(frames_u8, 'dtype', type(frames_u8))))
+  require_gpu(frames_u8)
+  if not frames_u8.is_contiguous():
+    raise TypeError('%s: frames must be contiguous' % who)
+  if frames_u8.dim() != 5 or frames_u8.shape[1] != 12 or frames_u8.shape[4] != 3:
+    raise ValueError('%s: frames must be (F, 12, H, W, 3), got %s' % (who, tuple(frames_u8.shape)))
+
+
+def frames_u8_ingest(frames_u8, lut, want_rgb=True):
+  """(F, 12, H, W, 3) uint8 frames and the (256, 3) normalisation table -> (left (6F, 3, H, W), right (6F, 3, H, W), rgb (F, 12, H, W)
+  or None) on mode_frames_u8_ingest (dataloader.gpu_ingest.frames_u8_gpu builds the table)."""
+  require_u8_frames(frames_u8, 'frames_u8_ingest')
+  require_gpu(lut)
+  require_f32c(lut)
+  F, _, H, W, _ = frames_u8.shape
+  if tuple(lut.shape) != (256, 3) or (H * W) % 4 or H * W == 0:
+    raise ValueError('frames_u8_ingest: lut %s must be (256, 3) and H W = %d x %d a positive multiple of 4' % (tuple(lut.shape), H, W))
+  dev = frames_u8.device
+  left = torch.empty((6 * F, 3, H, W), dtype=torch.float32, device=dev)
+  right = torch.empty((6 * F, 3, H, W), dtype=torch.float32, device=dev)
+  rgb = torch.empty((F, 12, H, W), dtype=torch.float32, device=dev) if want_rgb else None
+  nbytes = frames_u8.numel() * 5 + (0 if rgb is None else 4 * rgb.numel())
+  with torch.cuda.device_of(frames_u8), profiling.region('frames_u8_ingest', nbytes, 0, dev):
+    check(lib().mode_frames_u8_ingest(ptr(frames_u8), ptr(lut), F, H, W, ptr(left), ptr(right), None if rgb is None else ptr(rgb),
+                                      stream_of(frames_u8)), 'mode_frames_u8_ingest')
+  return left, right, rgb
+
+
+def rgb_half_pil(frames_u8, tab_w, tab_h, lut, return_u8=False):
+  """Panoramas 0, 1, 10, 11 of (F, 12, H, W, 3) uint8 frames halved as PIL.Image.resize((W / 2, H / 2)) halves them and normalised ->
+  (F, 12, H/2, W/2) float32 (with return_u8: and the 8-bit result (F, 4, H/2, W/2, 3)) on mode_rgb_half_pil.  tab_w (W/2, 10), tab_h
+  (H/2, 10): int32 device tables of dataloader.gpu_ingest.half_table_rows."""
+  require_u8_frames(frames_u8, 'rgb_half_pil')
+  require_gpu(tab_w, tab_h, lut)
+  require_f32c(lut)
+  F, _, H, W, _ = frames_u8.shape
+  if H % 2 or W % 2 or H * W == 0:
+    raise ValueError('rgb_half_pil: %d x %d is not even' % (H, W))
+  for t, n in ((tab_w, W // 2), (tab_h, H // 2)):
+    if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (n, 10):
+      raise ValueError('rgb_half_pil: a table must be contiguous int32 (%d, 10), got %s %s' % (n, t.dtype, tuple(t.shape)))
+  if tuple(lut.shape) != (256, 3):
+    raise ValueError('rgb_half_pil: lut %s must be (256, 3)' % (tuple(lut.shape),))
+  dev = frames_u8.device
+  out = torch.empty((F, 12, H // 2, W // 2), dtype=torch.float32, device=dev)
+  u8 = torch.empty((F, 4, H // 2, W // 2, 3), dtype=torch.uint8, device=dev) if return_u8 else None
+  with torch.cuda.device_of(frames_u8), profiling.region('rgb_half_pil', F * 4 * H * W * 3 + 4 * out.numel(), 0, dev):
+    check(lib().mode_rgb_half_pil(ptr(frames_u8), ptr(tab_w), ptr(tab_h), ptr(lut), F, H, W, ptr(out), None if u8 is None else ptr(u8),
+                                  stream_of(frames_u8)), 'mode_rgb_half_pil')
+  return (out, u8) if return_u8 else out
+
+
+def decimate2(x):
+  """x[..., ::2, ::2] of a contiguous float32 (..., H, W) tensor, contiguous, on mode_decimate2 (the reference loader's --resize
+  subsampling of the depth and confidence maps, dataloader/deep360_loader.py:147-150)."""
+  require_gpu(x)
+  require_f32c(x)
+  if x.dim() < 2 or 0 in x.shape[-2:]:
+    raise ValueError('decimate2: expected a (..., H, W) tensor with H, W > 0, got %s' % (tuple(x.shape),))
+  H, W = x.shape[-2:]
+  y = torch.empty(tuple(x.shape[:-2]) + ((H + 1) // 2, (W + 1) // 2), dtype=x.dtype, device=x.device)
+  with torch.cuda.device_of(x), profiling.region('decimate2', 4 * (x.numel() // 2 + y.numel()), 0, x.device):
+    check(lib().mode_decimate2(ptr(x), ptr(y), x.numel() // (H * W), H, W, stream_of(x)), 'mode_decimate2')
+  return y
+
+
 # ------------------------------------------------------------------------------------ BatchNorm (+ add) (+ ReLU)
 def _tag_bn(name, y):
   """Profiling label with the tensor shape (like the convolution labels), e.g. bn_train_fwd[2x32 48x256x128]."""

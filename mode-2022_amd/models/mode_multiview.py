@@ -14,12 +14,21 @@ forward() returns (F, 1, H, W) depth in camera 1's Cassini frame; utils.geometry
 which is what the fusion checkpoints were trained and tested on.
 
 evaluate() goes one step further, to what test_fusion.py:76-100 reports: the ERP panorama and the per-frame metric rows against a
-ground truth, scored on the GPU (utils.panorama)."""
+ground truth, scored on the GPU (utils.panorama).
+
+Frames may also arrive as they decode: (F, 12, H, W, 3) uint8 on the device.  Normalisation and the split are then one kernel
+(dataloader.gpu_ingest.frames_u8_gpu) and the result is bit for bit that of the float path on the host-normalised frames.  8-bit
+frames are what resize=True needs: the reference's --resize path (train_fusion.py / test_fusion.py --resize,
+dataloader/deep360_loader.py:146-155) runs the fusion network at half size, on every second pixel of the hand-off and on the RGB
+panoramas halved by PIL.Image.resize -- 8-bit fixed-point arithmetic, reproduced on the GPU bit for bit (rgb_half_gpu) -- and
+upsamples the result x2 (test_fusion.py:82)."""
 import os
 
 import torch
 import torch.nn as nn
 
+from dataloader import gpu_ingest
+from mode_hip import functional as HF
 from mode_hip import require_gpu
 from utils import geometry, panorama
 
@@ -44,6 +53,15 @@ def split_frames(frames):
   return left, right, rgb
 
 
+def fusion_size_multiple(fusion):
+  """The multiple of which the fusion network's input height and width must be: every nn.MaxPool2d(2) on its deepest path halves
+  the map (floor) and the 2x2 transposed convolutions double it back, so the skip connections only line up when the input divides by
+  2^(number of poolings) -- 8 for ModeFusion (three poolings on the depth branch), 1 for Baseline (none)."""
+  net = fusion.feature_extraction
+  pools = sum(isinstance(m, nn.MaxPool2d) for name, m in net.named_modules() if name.startswith('depth_layer'))
+  return 2 ** pools
+
+
 def _state_dict_of(src):
   """A path or a dict in the format of the reference's training scripts ({'state_dict': ...}, keys with or without the
   DataParallel 'module.' prefix) -> a plain state_dict."""
@@ -58,7 +76,7 @@ class ModeMultiView(nn.Module):
   or Baseline with fusion='Baseline'), so the state_dict is theirs under the prefixes 'disparity.' and 'fusion.'."""
 
   def __init__(self, maxdisp=192, maxdepth=1000., height=1024, width=512, dbname='Deep360', fusion='ModeFusion',
-               channels=(32, 64, 128, 256), conf_png=True):
+               channels=(32, 64, 128, 256), conf_png=True, resize=False):
     super(ModeMultiView, self).__init__()
     if height % 16 or width % 16:
       raise ValueError('ModeMultiView: %d x %d is not a multiple of 16 (the reference pads to 16; this module does not)' % (height, width))
@@ -66,12 +84,18 @@ class ModeMultiView(nn.Module):
       raise ValueError('ModeMultiView: fusion must be ModeFusion or Baseline, not %r' % (fusion,))
     geometry._baselines(dbname)  # 3D60 has no baselines in the reference: refused here, not at the first frame
     self.height, self.width, self.dbname, self.conf_png, self.fusion_kind = height, width, dbname, conf_png, fusion
+    self.resize = bool(resize)
     self.maxdepth = float(maxdepth)
     self.disparity = ModeDisparity(maxdisp, 'Sphere', height, width, 'Cassini', out_conf=True)
     if fusion == 'ModeFusion':
       self.fusion = ModeFusion(maxdepth, list(channels), {'depth': 12, 'rgb': 12})
     else:
       self.fusion = Baseline(maxdepth)
+    if self.resize:
+      m = 2 * fusion_size_multiple(self.fusion)
+      if height % m or width % m:
+        raise ValueError('ModeMultiView(resize=True): %d x %d is not a multiple of %d: the fusion network runs at half size, and %s takes '
+                         'sizes that its %d poolings halve exactly' % (height, width, m, fusion, (m // 2).bit_length() - 1))
 
   def load_checkpoints(self, disp=None, fusion=None):
     """Load the checkpoints of the two training scripts (paths or dicts); either may be None."""
@@ -82,13 +106,25 @@ class ModeMultiView(nn.Module):
     return self
 
   def forward(self, frames, return_stages=False):
-    """frames (F, 12, 3, H, W): ImageNet-normalised panoramas of F frames in sorted file order -> depth (F, 1, H, W) in camera 1's
-    Cassini frame; with return_stages also {'disp', 'conf': (6F, 1, H, W) of stage 1, 'fusion_input': the hand-off}."""
+    """frames (F, 12, 3, H, W) float32: ImageNet-normalised panoramas of F frames in sorted file order, or (F, 12, H, W, 3) uint8: the
+    same panoramas as they decode -> depth (F, 1, H, W) in camera 1's Cassini frame; with return_stages also {'disp', 'conf':
+    (6F, 1, H, W) of stage 1, 'fusion_input': the hand-off}.  resize=True (uint8 frames only): the fusion network runs at half size
+    and its output is upsampled x2; the stages then hold the half-size 'fusion_input' and 'rgb' the network saw."""
     if self.training:
       raise RuntimeError('ModeMultiView is inference only: call .eval() first')
+    u8 = frames.dtype == torch.uint8
+    if self.resize and not u8:
+      raise ValueError('ModeMultiView(resize=True) takes uint8 frames (F, 12, H, W, 3), not %s: the reference halves the 8-bit images '
+                       '(PIL.Image.resize, fixed-point arithmetic on bytes), and that result cannot be reproduced from normalised '
+                       'floats' % (frames.dtype,))
     require_gpu(frames)
-    left, right, rgb = split_frames(frames)
-    H, W = frames.shape[-2:]
+    want_rgb = self.fusion_kind == 'ModeFusion'
+    if u8:
+      left, right, rgb = gpu_ingest.frames_u8_gpu(frames.contiguous(), want_rgb=want_rgb and not self.resize)
+      H, W = frames.shape[2:4]
+    else:
+      left, right, rgb = split_frames(frames)
+      H, W = frames.shape[-2:]
     if H % 16 or W % 16:
       raise ValueError('ModeMultiView: %d x %d is not a multiple of 16' % (H, W))
     if (H, W) != (self.height, self.width):
@@ -97,16 +133,24 @@ class ModeMultiView(nn.Module):
       disp, conf = self.disparity(left, right)
       fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png,
                                                     depth_only=self.fusion_kind == 'Baseline')
+      if self.resize:  # deep360_loader.py:146-155 on the hand-off and the 8-bit panoramas; test_fusion.py:82 on the result
+        fusion_input = HF.decimate2(fusion_input)
+        rgb = gpu_ingest.rgb_half_gpu(frames.contiguous()) if want_rgb else None
       if self.fusion_kind == 'ModeFusion':
         depth = self.fusion.feature_extraction(fusion_input, rgb)
       else:
         depth = self.fusion.feature_extraction(fusion_input)
+      if self.resize:
+        depth = panorama.bicubic_up2(depth)
     if return_stages:
-      return depth, {'disp': disp, 'conf': conf, 'fusion_input': fusion_input}
+      stages = {'disp': disp, 'conf': conf, 'fusion_input': fusion_input}
+      if self.resize:
+        stages['rgb'] = rgb
+      return depth, stages
     return depth
 
   def evaluate(self, frames, gt, maxdepth=None):
-    """forward(frames) scored as test_fusion.py:86-100 scores a batch: gt (F, H, W) Cassini ground truth on the device ->
+    """forward(frames), float or uint8, scored as test_fusion.py:86-100 scores a batch: gt (F, H, W) Cassini ground truth on the device ->
     (depth_erp (F, W, H) device panorama, metrics (F, 8) float64 numpy rows [mae, rmse, absrel, sqrel, silog, delta 1, 2, 3] over the
     ERP pixels with gt <= maxdepth; default: the maxdepth the module was built with).  Inference only, like forward()."""
     if self.training:

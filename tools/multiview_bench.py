@@ -3,13 +3,20 @@
     python tools/multiview_bench.py [--frames 1 2 4] [--window 1.0] [--out profiles/multiview_bench.json]
     python tools/multiview_bench.py --once      # one hand-off call and one six-call path at F = 1, for a kernel trace
     python tools/multiview_bench.py --scoring   # the scoring line alone
+    python tools/multiview_bench.py --u8        # the ingest line alone: float frames from the host against 8-bit frames, and resize=True
 
 For every F: the frame time of the composed module, eager and replayed from a captured graph; the split between stage 1 (ModeDisparity
 at batch 6F), the hand-off (utils.geometry.disp2depth_frames_gpu) and stage 2 (the fusion network); and the hand-off against the
 six-call path it replaces (six disp2depth_gpu calls per frame + the interleave).  One more line for the scoring stage
 (utils.panorama.erp_depth_metrics against the per-frame composition it replaces, F = 1 and 4).  Device events around windows of at least
 --window seconds after a warm-up; weights from the test fixtures' recipes, seeded random panoramas (the timings do not depend on the values
-beyond the data-dependence of the z-buffer scatter).  Writes one JSON file."""
+beyond the data-dependence of the z-buffer scatter).  Writes one JSON file.
+
+--u8 times one frame from decoded 8-bit panoramas in host memory to the fused depth on the device, three ways, alternating A B C A B C:
+  A  host normalisation (dataloader.preprocess on the 12 panoramas) + upload of the float frame (75 MB) + the float forward
+  B  upload of the 8-bit frame (19 MB) + the uint8 forward (normalisation and split in one kernel)
+  C  upload of the 8-bit frame + the uint8 forward of ModeMultiView(resize=True) (fusion network at half size)
+Host clock around work that ends in a device synchronise; medians in ms."""
 import argparse
 import json
 import os
@@ -70,13 +77,13 @@ def make_frames(F, seed):
   return ((torch.rand(F, 12, 3, H, W, generator=g) - 0.45) / 0.226).to(DEV)
 
 
-def make_net():
+def make_net(resize=False):
   """The well-conditioned full-size disparity fixture with its running statistics (on unit running statistics the eval forward of
   the recipe weights is not finite) and a recipe fusion state."""
   z = np.load(os.path.join(recipe.HERE, 'model_wc_full.npz'))
   sd = recipe.fixture_state(z)
   sd.update({k[3:]: torch.from_numpy(z[k]).clone() for k in z.files if k.startswith('bn/')})
-  net = models.ModeMultiView(MAXDISP, MAXDEPTH, H, W)
+  net = models.ModeMultiView(MAXDISP, MAXDEPTH, H, W, resize=resize)
   net.disparity.load_state_dict(sd)
   net.fusion.load_state_dict(recipe.recipe_state(recipe.load_manifest('manifest_mode_fusion.json'), 101))
   return net.to(DEV).eval()
@@ -120,6 +127,52 @@ def scoring_line(reps=50, warmup=5):
   return row
 
 
+def u8_line(reps=20, warmup=3):
+  """The ingest line (see the module docstring).  A and B compute the same depth, bit for bit (asserted)."""
+  from dataloader import preprocess
+  norm = preprocess.get_transform_stage1(augment=False)
+  net, half = make_net(), make_net(resize=True)
+  frame = np.random.RandomState(300).randint(0, 256, (1, 12, H, W, 3)).astype(np.uint8)  # decoded panoramas, host memory
+  frame_t = torch.from_numpy(frame)  # pageable, like the float frame the host transform produces
+  parts = {'host_norm': [], 'upload_f32': [], 'forward_f32': [], 'upload_u8': [], 'forward_u8': [], 'forward_u8_resize': []}
+
+  def clock(key, fn):
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    parts[key].append(1e3 * (time.perf_counter() - t0))
+    return out
+
+  def a():
+    f32 = clock('host_norm', lambda: torch.stack([norm(p) for p in frame[0]]).unsqueeze(0))
+    dev = clock('upload_f32', lambda: f32.to(DEV))
+    return clock('forward_f32', lambda: net(dev))
+
+  def b():
+    dev = clock('upload_u8', lambda: frame_t.to(DEV))
+    return clock('forward_u8', lambda: net(dev))
+
+  def c():
+    dev = frame_t.to(DEV)
+    torch.cuda.synchronize()  # (the upload is B's: only the forward is timed here)
+    return clock('forward_u8_resize', lambda: half(dev))
+
+  assert torch.equal(a(), b()) and c().shape == (1, 1, H, W)
+  for _ in range(warmup):
+    a(), b(), c()
+  for v in parts.values():
+    del v[:]
+  for _ in range(reps):
+    a(), b(), c()
+  row = {'stage': 'u8_ingest', 'size': [H, W], 'frames': 1, 'reps': reps, 'host_threads': torch.get_num_threads()}
+  row.update({k + '_ms': float(np.median(v)) for k, v in parts.items()})
+  row['A_host_norm_upload_float_forward_ms'] = float(np.median(np.sum([parts[k] for k in ('host_norm', 'upload_f32', 'forward_f32')], 0)))
+  row['B_upload_uint8_forward_ms'] = float(np.median(np.sum([parts[k] for k in ('upload_u8', 'forward_u8')], 0)))
+  row['C_upload_uint8_forward_resize_ms'] = float(np.median(np.sum([parts['upload_u8'], parts['forward_u8_resize']], 0)))
+  print(json.dumps(row), flush=True)
+  return row
+
+
 def once():
   disp = (torch.rand(1, 6, H, W, device=DEV) * 40).contiguous()
   conf = torch.rand(1, 6, H, W, device=DEV)
@@ -137,11 +190,14 @@ def main():
   ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'multiview_bench.json'))
   ap.add_argument('--once', action='store_true')
   ap.add_argument('--scoring', action='store_true', help='only the scoring line')
+  ap.add_argument('--u8', action='store_true', help='only the ingest line: float frames from the host against 8-bit frames, and resize=True')
   args = ap.parse_args()
   if args.once:
     return once()
   if args.scoring:
     return scoring_line()
+  if args.u8:
+    return u8_line()
   net = make_net()
   rows = []
   for F in args.frames:
