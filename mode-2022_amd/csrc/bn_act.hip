@@ -270,11 +270,16 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
 // Backward reduce: g = RELU ? (out > 0 ? gout : 0) : gout;  partial = sum(g), sum(g*y).
 // RELU = 1: the mask is read from the forward output; RELU = 2 (no residual add): it is rebuilt from y with the forward's own
 // float32 coefficients, out = fma(y, scale, shift) -- bit-identical, and one tensor less to read in both backward passes.
-template <int RELU>
+// GADD (RELU = 1, residual add in front of the ReLU): g is also the gradient of the skip branch, and it is stored to `gadd` here,
+// where it is formed anyway -- the apply pass then reads gadd and y instead of gout, y and out, and writes gy only (7 tensor passes
+// for the pair instead of 8).  Every element is visited by exactly one thread of this grid, so each is stored once.
+template <int RELU, bool GADD = false>
 __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restrict__ gout, const float* __restrict__ y,
                                                           const float* __restrict__ out, const float* __restrict__ mscale,
                                                           const float* __restrict__ mshift, float* __restrict__ partial, int B, int C,
-                                                          long long S, int nsplit, unsigned* __restrict__ zero) {
+                                                          long long S, int nsplit, unsigned* __restrict__ zero,
+                                                          float* __restrict__ gadd = nullptr) {
+  static_assert(!GADD || RELU == 1, "the masked gradient is stored only where the mask comes from the forward output");
   __shared__ float sh[2 * NW];
   const int c = blockIdx.y, split = blockIdx.x;
   const int Bg = B / gridDim.z, b0 = blockIdx.z * Bg;
@@ -290,10 +295,12 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
     const float4* gp = reinterpret_cast<const float4*>(gout + base);
     const float4* yp = reinterpret_cast<const float4*>(y + base);
     const float4* op = reinterpret_cast<const float4*>(out + base);
+    float4* gap = reinterpret_cast<float4*>(GADD ? gadd + base : nullptr);
     // (four independent loads of every operand per iteration; sums in element order)
-    auto acc1 = [&](float4 g, const float4& v, const float4& o) {
+    auto acc1 = [&](long long i, float4 g, const float4& v, const float4& o) {
       if (RELU == 1) {
         g.x = o.x > 0.f ? g.x : 0.f; g.y = o.y > 0.f ? g.y : 0.f; g.z = o.z > 0.f ? g.z : 0.f; g.w = o.w > 0.f ? g.w : 0.f;
+        if (GADD) gap[i] = g;
       } else if (RELU == 2) {
         g.x = __builtin_fmaf(v.x, msc, msh) > 0.f ? g.x : 0.f;
         g.y = __builtin_fmaf(v.y, msc, msh) > 0.f ? g.y : 0.f;
@@ -312,16 +319,17 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
       if (RELU == 1) {
         o0 = op[i]; o1 = op[i + st]; o2 = op[i + 2 * st]; o3 = op[i + 3 * st];
       }
-      acc1(g0, v0, o0);
-      acc1(g1, v1, o1);
-      acc1(g2, v2, o2);
-      acc1(g3, v3, o3);
+      acc1(i, g0, v0, o0);
+      acc1(i + st, g1, v1, o1);
+      acc1(i + 2 * st, g2, v2, o2);
+      acc1(i + 3 * st, g3, v3, o3);
     }
-    for (; i < S4; i += st) acc1(gp[i], yp[i], RELU == 1 ? op[i] : yp[i]);
+    for (; i < S4; i += st) acc1(i, gp[i], yp[i], RELU == 1 ? op[i] : yp[i]);
     for (long long i = (S4 << 2) + (long long)split * NT + threadIdx.x; i < S; i += (long long)nsplit * NT) {  // scalar path (S % 4 != 0)
         float g = gout[base + i];
         if (RELU == 1) g = out[base + i] > 0.f ? g : 0.f;
         if (RELU == 2) g = __builtin_fmaf(y[base + i], msc, msh) > 0.f ? g : 0.f;
+        if (GADD) gadd[base + i] = g;
         s0 += g;
         s1 += g * y[base + i];
       }
@@ -338,7 +346,18 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
 //   Cc = A*(mean*invstd*dgamma - sum(g))/count
 // derived by every block from the partial sums; the block (chunk 0, sample 0) of each channel stores (or, with
 // `accumulate`, adds into) ggamma / gbeta.
-template <int RELU, bool GADD, bool AMAX = false>
+//
+// PINNED (the skip-gradient route of mode_bn_train_bwd: `gout` is the masked gradient the statistics pass stored, RELU = 0, nothing else
+// to read): this instantiation must give the bits of the mask-reading one it replaces, and `A g + Bc y + Cc` does not say which bits
+// those are -- the compiler contracts it per instantiation AND per place in the loops.  What it chose for <1, *, true> (read from the ISA
+// of both instantiations; a compiler that chooses otherwise one day fails the test named below, and this is the place to follow it) is
+//   the first of the four 16-byte pieces of the unrolled loop:   fma(Bc, y, A * g) + Cc
+//   every other piece and the 16-byte tail loop:                  (A * g + Bc * y) + Cc, each operation rounded
+//   the scalar path (rows that are not multiples of 16 bytes), which the compiler unrolled by two: the fused form for a thread's
+//   iterations in pairs, the rounded one for the odd iteration left over
+// and the pinned instantiation spells exactly that, with opaque asm between the operations so that nothing is re-contracted
+// (tests/test_gpu_bn_bwd_gadd.py compares the two routes bit for bit).
+template <int RELU, bool GADD, bool AMAX = false, bool PINNED = false>
 __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restrict__ gout, const float* __restrict__ y,
                                                           const float* __restrict__ out, const float* __restrict__ mscale,
                                                           const float* __restrict__ mshift, const float* __restrict__ partial,
@@ -399,7 +418,14 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restric
   float4* gyp = reinterpret_cast<float4*>(gy + base);
   float4* gap = reinterpret_cast<float4*>(gadd + base);
   // (four independent loads of every operand per thread and iteration, see bn_apply_kernel)
-  auto one = [&](long long i, float4 g, const float4& v, const float4& o) {
+  auto pinned = [&](float g, float v, bool fused) {
+    float t = A * g, u = Bc * v;
+    asm volatile("" : "+v"(t), "+v"(u));
+    float r = fused ? __builtin_fmaf(Bc, v, t) : t + u;
+    asm volatile("" : "+v"(r));
+    return r + Cc;
+  };
+  auto one = [&](long long i, float4 g, const float4& v, const float4& o, bool first = false) {
     if (RELU == 1) {
       g.x = o.x > 0.f ? g.x : 0.f; g.y = o.y > 0.f ? g.y : 0.f; g.z = o.z > 0.f ? g.z : 0.f; g.w = o.w > 0.f ? g.w : 0.f;
     } else if (RELU == 2) {
@@ -410,10 +436,14 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restric
     }
     if (GADD) gap[i] = g;
     float4 r;
-    r.x = A * g.x + Bc * v.x + Cc;
-    r.y = A * g.y + Bc * v.y + Cc;
-    r.z = A * g.z + Bc * v.z + Cc;
-    r.w = A * g.w + Bc * v.w + Cc;
+    if (PINNED) {
+      r.x = pinned(g.x, v.x, first); r.y = pinned(g.y, v.y, first); r.z = pinned(g.z, v.z, first); r.w = pinned(g.w, v.w, first);
+    } else {
+      r.x = A * g.x + Bc * v.x + Cc;
+      r.y = A * g.y + Bc * v.y + Cc;
+      r.z = A * g.z + Bc * v.z + Cc;
+      r.w = A * g.w + Bc * v.w + Cc;
+    }
     if (AMAX) mx = max(max(mx, mag(r.x)), max(max(mag(r.y), mag(r.z)), mag(r.w)));
     gyp[i] = r;
   };
@@ -426,18 +456,24 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restric
     if (RELU == 1) {
       o0 = op[i]; o1 = op[i + st]; o2 = op[i + 2 * st]; o3 = op[i + 3 * st];
     }
-    one(i, g0, v0, o0);
+    one(i, g0, v0, o0, true);
     one(i + st, g1, v1, o1);
     one(i + 2 * st, g2, v2, o2);
     one(i + 3 * st, g3, v3, o3);
   }
   for (; i < S4; i += st) one(i, gp[i], yp[i], RELU == 1 ? op[i] : yp[i]);
+  long long paired = 0;  // (PINNED) the end of this thread's scalar iterations that come in pairs
+  if (PINNED) {
+    const long long i0 = (S4 << 2) + (long long)blockIdx.x * NT + threadIdx.x;
+    const long long n = i0 < S ? (S - i0 + st - 1) / st : 0;
+    paired = i0 + (n & ~1LL) * st;
+  }
   for (long long i = (S4 << 2) + (long long)blockIdx.x * NT + threadIdx.x; i < S; i += (long long)gridDim.x * NT) {  // scalar path (S % 4 != 0)
       float g = gout[base + i];
       if (RELU == 1) g = out[base + i] > 0.f ? g : 0.f;
       if (RELU == 2) g = __builtin_fmaf(y[base + i], msc, msh) > 0.f ? g : 0.f;
       if (GADD) gadd[base + i] = g;
-      const float r = A * g + Bc * y[base + i] + Cc;
+      const float r = PINNED ? pinned(g, y[base + i], i < paired) : A * g + Bc * y[base + i] + Cc;
       if (AMAX) mx = max(mx, mag(r));
       gy[base + i] = r;
     }
@@ -685,6 +721,14 @@ extern "C" int mode_bn_train_bwd_amax(const float* gout, const float* y, const f
                    (!gadd || aligned_rows(gadd, S)) && aligned16(workspace),
                MODE_ERR_UNSUPPORTED, "mode_bn_train_bwd: unaligned buffer");
   MODE_REQUIRE(groups >= 1 && B % groups == 0, MODE_ERR_BAD_ARG, "mode_bn_train_bwd: batch %d not divisible into %d groups", B, groups);
+  if (gadd) {
+    // gadd is written by the statistics pass and read back by the apply pass (mask from `out`), or written by the apply pass while
+    // other blocks still read their part of the inputs: it is a tensor of its own
+    const long long n = (long long)B * C * S;
+    auto overlaps = [&](const float* p) { return p && p < gadd + n && gadd < p + n; };
+    MODE_REQUIRE(!overlaps(gout) && !overlaps(y) && !overlaps(out) && !overlaps(gy), MODE_ERR_BAD_ARG,
+                 "mode_bn_train_bwd: gadd aliases gout, y, out or gy (in-place operation is not possible)");
+  }
   hipStream_t st = mode::as_stream(stream);
   const int nsplit = pick_nsplit(C * groups, S);
   float* partial = workspace;
@@ -694,6 +738,9 @@ extern "C" int mode_bn_train_bwd_amax(const float* gout, const float* y, const f
   unsigned* zero = reinterpret_cast<unsigned*>(amax);  // (the maximum's buffer is zeroed by the statistics pass)
   if (mode == 0)
     hipLaunchKernelGGL(bn_bwd_stats_kernel<0>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero);
+  else if (mode == 1 && gadd)  // (the masked gradient is the skip branch's: stored by this pass, see the kernel)
+    hipLaunchKernelGGL((bn_bwd_stats_kernel<1, true>), dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S,
+                       nsplit, zero, gadd);
   else if (mode == 1)
     hipLaunchKernelGGL(bn_bwd_stats_kernel<1>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero);
   else
@@ -704,14 +751,19 @@ extern "C" int mode_bn_train_bwd_amax(const float* gout, const float* y, const f
   // One instantiation whether the maximum is asked for or not (a null `amax` only skips the commit): the compiler contracts
   // A g + Bc y + Cc differently in an instantiation that does not track the maximum, and the plain entry would then differ from its
   // `_amax` twin in the last bit of dL/dy.  The tracking costs the HBM-bound pass a few VALU operations per element.
-#define MODE_BN_BWD_APPLY(M, G)                                                                                                         \
-  launch_apply(bn_bwd_apply_kernel<M, G, true>, BC, S, st, who, gout, y, o, save_scale, save_shift, partial, gamma, save_mean,          \
+#define MODE_BN_BWD_APPLY_OF(GIN, M, G, PIN)                                                                                            \
+  launch_apply(bn_bwd_apply_kernel<M, G, true, PIN>, BC, S, st, who, GIN, y, o, save_scale, save_shift, partial, gamma, save_mean,      \
                save_invstd, ggamma, gbeta, accumulate, nsplit, count, groups, B / groups, gy, (G) ? gadd : gy, C, S,                  \
                reinterpret_cast<unsigned*>(amax))
+#define MODE_BN_BWD_APPLY(M, G) MODE_BN_BWD_APPLY_OF(gout, M, G, false)
   if (mode == 0) return gadd ? MODE_BN_BWD_APPLY(0, true) : MODE_BN_BWD_APPLY(0, false);
-  if (mode == 1) return gadd ? MODE_BN_BWD_APPLY(1, true) : MODE_BN_BWD_APPLY(1, false);
+  // gadd already holds g = out > 0 ? gout : 0 (the statistics pass above): what is left is the pass of a layer without ReLU over
+  // (gadd, y), which reads neither gout nor out and writes gy only -- in the arithmetic of the mask-reading instantiation (PINNED)
+  if (mode == 1 && gadd) return MODE_BN_BWD_APPLY_OF(gadd, 0, false, true);
+  if (mode == 1) return MODE_BN_BWD_APPLY(1, false);
   return gadd ? MODE_BN_BWD_APPLY(2, true) : MODE_BN_BWD_APPLY(2, false);
 #undef MODE_BN_BWD_APPLY
+#undef MODE_BN_BWD_APPLY_OF
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

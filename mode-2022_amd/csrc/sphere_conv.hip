@@ -432,12 +432,23 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_adj_kernel(const flo
 
 // Software-pipelined variant of the kernel above for 3x3 kernels (KK = 9).  The first EC = 4 adjoint entries of every
 // (tap, input pixel) of the tile -- all of them for the tables of the network away from the poles -- are cached in LDS once
-// per tile; the gy loads of the next chunk (2 channels x 9 taps x 4 entries per thread) are issued before the MFMA phase of
+// per tile; the gy loads of the next chunk (1 channel x 9 taps x 4 entries per thread) are issued before the MFMA phase of
 // the current chunk and combined after it.  Entries beyond the fourth are added by a (rare) synchronous tail loop.
-__global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_adj9_kernel(const float* __restrict__ gy, const int* __restrict__ rowptr,
-                                                                         const int2* __restrict__ entries,
-                                                                         const float4* __restrict__ wp, float* __restrict__ gx, Dims d,
-                                                                         int MTc, int NCHo, int qtiles, const int* __restrict__ tile_list) {
+//
+// 8 waves per 64-pixel tile (ADJ9_THREADS; the other kernels of this file have 4): the grid of the polar tile list is smaller than
+// the chip (192 workgroups at the benchmark's layers), so what a launch takes is the serial chain of ONE wave.  With 4 waves a wave
+// carried both 32-pixel accumulators through 2 x 9 x 4 dependent MFMAs per chunk and gathered two output channels (72 loads) per
+// chunk; here waves 0-3 own pixels 0-31 of their 32 input channels and waves 4-7 pixels 32-63 (acc), and each of the 8 waves gathers
+// ONE of the chunk's CCH = 8 output channels (36 loads): half the chain in both phases.  Every output element still sees the same
+// sequence of operations -- the same (chunk, quad, a4.x .. a4.w) MFMA order into the same accumulator lanes, the same FMA chain per
+// column element -- so the results are the 4-wave kernel's bit for bit (tests/test_gpu_polar_bits.py).  (The other way to the same
+// count, 4-wave workgroups of (tile, half) with two or three resident per CU, measured 81.7 us per launch against 76.6 for this one.)
+constexpr int ADJ9_THREADS = 512;
+static_assert(ADJ9_THREADS / P == CCH, "one wave per output channel of a chunk");
+__global__ __launch_bounds__(ADJ9_THREADS) void sphere_bwd_data_adj9_kernel(const float* __restrict__ gy, const int* __restrict__ rowptr,
+                                                                            const int2* __restrict__ entries,
+                                                                            const float4* __restrict__ wp, float* __restrict__ gx, Dims d,
+                                                                            int MTc, int NCHo, int qtiles, const int* __restrict__ tile_list) {
   constexpr int KT = 9, EC = 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int4* ent_p = reinterpret_cast<int4*>(smem);                          // [KT][P] output pixels of the first 4 entries
@@ -454,10 +465,11 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_adj9_kernel(const fl
   const int g = blockIdx.z;
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
-  const int mt = blockIdx.y * 4 + wave;
+  const int mt = blockIdx.y * 4 + (wave & 3);  // the 32 input channels of this wave's MFMA tile ...
+  const int half = wave >> 2;                  // ... and which 32 of the tile's 64 pixels it accumulates
   const bool active = mt < MTc;
 
-  for (int item = tid; item < KT * P; item += NTHREADS) {
+  for (int item = tid; item < KT * P; item += ADJ9_THREADS) {
     const int k = item / P, pp = item % P;
     const int qq = q0 + pp;
     int beg = 0, cnt = 0;
@@ -481,58 +493,50 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_adj9_kernel(const fl
   __syncthreads();
 
   const int p = tid & (P - 1);
-  static_assert(P == 64, "one wave per output-channel pair of the chunk");
-  const int qd = __builtin_amdgcn_readfirstlane(tid / P);  // output channels 2qd, 2qd+1 of the chunk (wave-uniform -> scalar bases)
+  static_assert(P == 64, "one wave per output channel of the chunk");
+  const int qd = __builtin_amdgcn_readfirstlane(tid / P);  // output channel qd of the chunk (wave-uniform -> scalar base)
   const float* gyg = gy + ((long long)b * d.Co + (long long)g * d.Cog) * d.npix;
-  float lv[KT * 2 * EC];
+  float lv[KT * EC];
   bool has_tail = false;
 #pragma unroll
   for (int k = 0; k < KT; ++k) has_tail |= span[k * P + p].y > EC;
 
   auto issue = [&](int ch) {
-    const int o0 = ch * CCH + qd * 2;
+    const int o0 = ch * CCH + qd;
     const float* g0 = gyg + (long long)(o0 < d.Cog ? o0 : 0) * d.npix;
-    const float* g1 = gyg + (long long)(o0 + 1 < d.Cog ? o0 + 1 : 0) * d.npix;
 #pragma unroll
     for (int k = 0; k < KT; ++k) {
       const int4 pe = ent_p[k * P + p];
       const char* c0 = reinterpret_cast<const char*>(g0);
-      const char* c1 = reinterpret_cast<const char*>(g1);
 #define MODE_LD(base, off) (*reinterpret_cast<const float*>((base) + (unsigned)(off)))
-      lv[k * 8 + 0] = MODE_LD(c0, pe.x); lv[k * 8 + 1] = MODE_LD(c0, pe.y); lv[k * 8 + 2] = MODE_LD(c0, pe.z); lv[k * 8 + 3] = MODE_LD(c0, pe.w);
-      lv[k * 8 + 4] = MODE_LD(c1, pe.x); lv[k * 8 + 5] = MODE_LD(c1, pe.y); lv[k * 8 + 6] = MODE_LD(c1, pe.z); lv[k * 8 + 7] = MODE_LD(c1, pe.w);
+      lv[k * 4 + 0] = MODE_LD(c0, pe.x); lv[k * 4 + 1] = MODE_LD(c0, pe.y); lv[k * 4 + 2] = MODE_LD(c0, pe.z); lv[k * 4 + 3] = MODE_LD(c0, pe.w);
 #undef MODE_LD
     }
   };
   auto finish = [&](int ch, float* buf) {
-    const int o0 = ch * CCH + qd * 2;
-    const bool ok0 = o0 < d.Cog, ok1 = o0 + 1 < d.Cog;
+    const int o0 = ch * CCH + qd;
+    const bool ok0 = o0 < d.Cog;
     const float* g0 = gyg + (long long)(ok0 ? o0 : 0) * d.npix;
-    const float* g1 = gyg + (long long)(ok1 ? o0 + 1 : 0) * d.npix;
-    float v0[KT], v1[KT];
+    float v0[KT];
 #pragma unroll
     for (int k = 0; k < KT; ++k) {
       const float4 we = ent_w[k * P + p];
-      // Two SCALAR FMA chains, kept apart by opaque asm.  Written as plain expressions the two chains are SLP-packed into
+      // SCALAR FMA chains, kept apart by opaque asm (with 4 waves a thread ran the chains of two channels side by side; now its
+      // neighbours are the chains of the other taps).  Written as plain expressions two chains are SLP-packed into
       // v_pk_mul_f32 / v_pk_fma_f32 on register pairs whose halves are the results of two different gathers, and that form was not
       // repeatable: with a second process on the GPU (loads slow enough for the wave to sit in its s_waitcnt) one (channel, tap) row of
       // the column tile came out wrong in lanes 48..63 -- about one call in 300; in-kernel checks showed the gathered registers equal
       // to memory afterwards and the combined value not (round 4; tools/determinism_hunt.py: 22-46 differing steps in 232
       // with the packed form, 0 in 232 with this one).
-      float a = we.x * lv[k * 8 + 0];
-      float b = we.x * lv[k * 8 + 4];
-      asm volatile("" : "+v"(a), "+v"(b));
-      a = fmaf(we.y, lv[k * 8 + 1], a);
-      b = fmaf(we.y, lv[k * 8 + 5], b);
-      asm volatile("" : "+v"(a), "+v"(b));
-      a = fmaf(we.z, lv[k * 8 + 2], a);
-      b = fmaf(we.z, lv[k * 8 + 6], b);
-      asm volatile("" : "+v"(a), "+v"(b));
-      a = fmaf(we.w, lv[k * 8 + 3], a);
-      b = fmaf(we.w, lv[k * 8 + 7], b);
-      asm volatile("" : "+v"(a), "+v"(b));
+      float a = we.x * lv[k * 4 + 0];
+      asm volatile("" : "+v"(a));
+      a = fmaf(we.y, lv[k * 4 + 1], a);
+      asm volatile("" : "+v"(a));
+      a = fmaf(we.z, lv[k * 4 + 2], a);
+      asm volatile("" : "+v"(a));
+      a = fmaf(we.w, lv[k * 4 + 3], a);
+      asm volatile("" : "+v"(a));
       v0[k] = a;
-      v1[k] = b;
     }
     if (has_tail) {  // this pixel has a list longer than EC entries for some tap (near the poles): one branch per chunk
 #pragma unroll
@@ -541,28 +545,24 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_adj9_kernel(const fl
         for (int e = EC; e < s.y; ++e) {
           const int2 ent = entries[s.x + e];
           const float wt = __int_as_float(ent.y);
-          float a = g0[ent.x], b = g1[ent.x];
-          asm volatile("" : "+v"(a), "+v"(b));  // (no v_pk_fma_f32 on the pair of freshly loaded values: see above)
+          float a = g0[ent.x];
+          asm volatile("" : "+v"(a));  // (no packed FMA on freshly loaded values: see above)
           v0[k] = fmaf(wt, a, v0[k]);
           asm volatile("" : "+v"(v0[k]));
-          v1[k] = fmaf(wt, b, v1[k]);
         }
       }
     }
 #pragma unroll
-    for (int k = 0; k < KT; ++k) {
-      buf[((qd * 2) * KT + k) * P + p] = ok0 ? v0[k] : 0.f;
-      buf[((qd * 2 + 1) * KT + k) * P + p] = ok1 ? v1[k] : 0.f;
-    }
+    for (int k = 0; k < KT; ++k) buf[(qd * KT + k) * P + p] = ok0 ? v0[k] : 0.f;
   };
 
-  f32x16 acc0 = {0}, acc1 = {0};
+  f32x16 acc = {0};
   const float4* wpa = wp + ((long long)(g * MTc + (active ? mt : 0)) * NCHo) * KT * 64 + lane;
 
   // Weight fragments of chunk ch+1 (9 x float4) are requested BEFORE the gathers of chunk ch+1, so that by the time the MFMAs
   // of chunk ch+1 run they are long complete and nothing in the MFMA phase waits on the (in-order) vector-memory counter;
-  // the 8 LDS operands of quad q+1 are read before the 16 MFMAs of quad q are issued.  (The straightforward loop waited for an
-  // LDS round trip every two MFMAs and for an L1/L2 round trip -- and with it for all 72 gathers in flight -- every quad.)
+  // the 4 LDS operands of quad q+1 are read before the 4 MFMAs of quad q are issued.  (The straightforward loop waited for an
+  // LDS round trip every two MFMAs and for an L1/L2 round trip -- and with it for all the gathers in flight -- every quad.)
   float4 wcur[KT], wnxt[KT];
 #pragma unroll
   for (int quad = 0; quad < KT; ++quad) wcur[quad] = wpa[quad * 64];
@@ -579,30 +579,26 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_adj9_kernel(const fl
       issue(ch + 1);
     }
     if (active) {
-      const float* bp = cur + (lane >> 5) * P + (lane & 31);
-      float bn[8];
+      const float* bp = cur + (lane >> 5) * P + half * 32 + (lane & 31);
+      float bn[4];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) bn[i] = bp[(i >> 1) * 2 * P + (i & 1) * 32];
+      for (int i = 0; i < 4; ++i) bn[i] = bp[i * 2 * P];
 #pragma unroll
       for (int quad = 0; quad < KT; ++quad) {
         const float4 a4 = wcur[quad];
-        float bc[8];
+        float bc[4];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) bc[i] = bn[i];
+        for (int i = 0; i < 4; ++i) bc[i] = bn[i];
         if (quad + 1 < KT) {
           const float* bq = bp + (quad + 1) * 8 * P;
 #pragma unroll
-          for (int i = 0; i < 8; ++i) bn[i] = bq[(i >> 1) * 2 * P + (i & 1) * 32];
+          for (int i = 0; i < 4; ++i) bn[i] = bq[i * 2 * P];
         }
         __builtin_amdgcn_sched_barrier(0);
-        acc0 = mfma32(a4.x, bc[0], acc0);
-        acc1 = mfma32(a4.x, bc[1], acc1);
-        acc0 = mfma32(a4.y, bc[2], acc0);
-        acc1 = mfma32(a4.y, bc[3], acc1);
-        acc0 = mfma32(a4.z, bc[4], acc0);
-        acc1 = mfma32(a4.z, bc[5], acc1);
-        acc0 = mfma32(a4.w, bc[6], acc0);
-        acc1 = mfma32(a4.w, bc[7], acc1);
+        acc = mfma32(a4.x, bc[0], acc);
+        acc = mfma32(a4.y, bc[1], acc);
+        acc = mfma32(a4.z, bc[2], acc);
+        acc = mfma32(a4.w, bc[3], acc);
       }
     }
     if (ch + 1 < NCHo) {
@@ -619,10 +615,9 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_adj9_kernel(const fl
     for (int r = 0; r < 16; ++r) {
       const int c = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
       if (c < d.Cig) {
-        const int qq = q0 + (lane & 31);
+        const int qq = q0 + half * 32 + (lane & 31);
         float* o0 = gxb + (long long)c * HWin + qq;
-        if (qq < HWin) o0[0] = d.accumulate ? o0[0] + acc0[r] : acc0[r];
-        if (qq + 32 < HWin) o0[32] = d.accumulate ? o0[32] + acc1[r] : acc1[r];
+        if (qq < HWin) o0[0] = d.accumulate ? o0[0] + acc[r] : acc[r];
       }
     }
   }
@@ -1117,7 +1112,7 @@ static int bwd_data_adj_impl(const float* gy, const float* w, float* gx, float* 
     const size_t lds = (size_t)9 * P * 40 + 2 * (size_t)CCH * 9 * P * 4;
     rc = mode::allow_lds(sphere_bwd_data_adj9_kernel, lds, "mode_sphere_conv_bwd_data_adj");
     if (rc != MODE_OK) return rc;
-    hipLaunchKernelGGL(sphere_bwd_data_adj9_kernel, grid, dim3(NTHREADS), lds, st, gy, adj_rowptr,
+    hipLaunchKernelGGL(sphere_bwd_data_adj9_kernel, grid, dim3(ADJ9_THREADS), lds, st, gy, adj_rowptr,
                        reinterpret_cast<const int2*>(adj_entries), reinterpret_cast<const float4*>(wpack), gx, d, MTc, NCHo, qtiles, tile_list);
   } else {
     const size_t lds = (size_t)d.KK * P * 8 + 2 * (size_t)CCH * d.KK * P * 4;

@@ -2283,55 +2283,56 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_split_kernel(const 
 #undef MODE_BS_TERM
   };
 
+  // Staging of an item without serial round trips (it used to be: the item's table words, then four `#pragma unroll 1` rounds of
+  // 16 x loads -> LDS stores, then the gy loads -> stores, then the tap records -- six or seven exposed memory latencies in front of
+  // about 1 us of MFMAs, with one workgroup per CU and nothing else to hide them).  Now every global load of the item (64 x words, 8 gy
+  // words, the 3 tap records) is issued in one batch into registers BEFORE the barrier that waits for the previous item's consumers --
+  // a wave that is done with item t has the loads of the next item in flight while the others finish -- and committed to LDS after it;
+  // the table words of the item after that are requested behind the batch and are there a whole item later.  (No room for a second
+  // window buffer in LDS.  Keeping the batch of item t + S in registers across the sample / MFMA phase of item t was built too -- it fits
+  // in 256 registers once the phase holds the gy fragments of two row blocks at a time -- and measured the same 62.6 us per launch:
+  // with the round trips gone the loads are no longer what an item waits for, so the simpler form stayed.)  What lands in LDS, and
+  // everything from there on, is unchanged.
+  auto item_words = [&](int t, int (&pv)[6]) {
+    const int* pi = pitems + (long long)(t % nitems) * BP_ITEM_INTS;
+    pv[0] = pi[0]; pv[1] = pi[1];
+    pv[2] = pi[2 + k0]; pv[3] = pi[2 + KT + k0]; pv[4] = pi[2 + k1]; pv[5] = pi[2 + KT + k1];
+  };
+  int pv[6] = {0, 0, 0, 0, 0, 0};
+  if (s < T) item_words(s, pv);
   for (int t = s; t < T; t += S) {
     const int b = t / nitems, it = t - b * nitems;
-    const int* pi = pitems + (long long)it * BP_ITEM_INTS;
-    const int h0 = pi[0], w = pi[1];
-    __syncthreads();  // previous item consumed (first pass: zero fill done)
+    const int h0 = pv[0], w = pv[1];
+    const int rb0 = pv[2], cb0 = pv[3], rb1 = pv[4], cb1 = pv[5];
+    const bool xok0 = cb0 + col0 < d.W, xok1 = has1 && cb1 + col1 < d.W;
+    // (opaque copies: the 32 + 4 lane masks of the channel bounds are loop invariants, and hoisted they cost 70 scalar registers)
+    int cmx = cmax, omx = omax;
+    asm volatile("" : "+s"(cmx), "+s"(omx));
+    float xv0[BW_CG], xv1[BW_CG];
     {
-      const int rb0 = pi[2 + k0], cb0 = pi[2 + KT + k0], rb1 = pi[2 + k1], cb1 = pi[2 + KT + k1];
-      const bool ok0 = cb0 + col0 < d.W, ok1 = has1 && cb1 + col1 < d.W;
       const float* xg = x + ((long long)b * d.Ci + (long long)g * d.Cig + (long long)cg * BW_CG) * HW;
-      const long long a0 = ok0 ? (long long)((rb0 + r0) % d.H) * d.sh + (long long)(cb0 + col0) * d.sw : 0;
-      const long long a1 = ok1 ? (long long)((rb1 + r1) % d.H) * d.sh + (long long)(cb1 + col1) * d.sw : 0;
-#pragma unroll 1
-      for (int c8 = 0; c8 < BW_CG; c8 += 8) {
-        float v0[8], v1[8];
+      const long long a0 = xok0 ? (long long)((rb0 + r0) % d.H) * d.sh + (long long)(cb0 + col0) * d.sw : 0;
+      const long long a1 = xok1 ? (long long)((rb1 + r1) % d.H) * d.sh + (long long)(cb1 + col1) * d.sw : 0;
+      const float* xc = xg;  // channel min(c, cmax - 1), stepped (32 hoisted 64-bit plane offsets do not fit the scalar registers)
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const long long co = (long long)min(c8 + c, cmax - 1) * HW;
-          v0[c] = xg[co + a0];
-          v1[c] = xg[co + a1];
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          xw[(c8 + c) * BP_CP + e0] = (ok0 && c8 + c < cmax) ? v0[c] : 0.f;
-          if (has1) xw[(c8 + c) * BP_CP + e1] = (ok1 && c8 + c < cmax) ? v1[c] : 0.f;
-        }
+      for (int c = 0; c < BW_CG; ++c) {
+        xv0[c] = xc[a0];
+        xv1[c] = xc[a1];
+        if (c + 1 < cmx) xc += HW;
       }
     }
+    const int gh = h0 + 2 * gpp;
+    const bool gok0 = gh < d.H && w < d.W, gok1 = gh + 1 < d.H && w < d.W;
+    float gv0[4], gv1[4];
     {
-      const int h = h0 + 2 * gpp;
-      const bool ok0 = h < d.H && w < d.W, ok1 = h + 1 < d.H && w < d.W;
       const float* gyb0 = gy + ((long long)b * d.Co + (long long)g * d.Cog + (long long)mg * 128) * HW +
-                          (ok0 ? (long long)h * d.sh + (long long)w * d.sw : 0);
-      const long long step1 = ok1 ? d.sh : 0;
-      float v0[4], v1[4];
+                          (gok0 ? (long long)gh * d.sh + (long long)w * d.sw : 0);
+      const long long step1 = gok1 ? d.sh : 0;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const float* p = gyb0 + (long long)min(go0 + 32 * u, omax - 1) * HW;
-        v0[u] = p[0];
-        v1[u] = p[step1];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bool oo = go0 + 32 * u < omax;
-        uint32_t p1, p2, p3;
-        sp_split2((ok0 && oo) ? v0[u] : 0.f, (ok1 && oo) ? v1[u] : 0.f, p1, p2, p3);
-        uint32_t* dst = gyb + (go0 + 32 * u) * BS_GP + gpp;
-        dst[0] = p1;
-        dst[128 * BS_GP] = p2;
-        dst[2 * 128 * BS_GP] = p3;
+        const float* p = gyb0 + (long long)min(go0 + 32 * u, omx - 1) * HW;
+        gv0[u] = p[0];
+        gv1[u] = p[step1];
       }
     }
     const long long rbase = (long long)it * BW_NREC;
@@ -2340,6 +2341,23 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_split_kernel(const 
     const float4 rw8 = rec_w[rbase + 8 * BW_TH + 16 * ks8 + px0];
     const int ro0 = rec_off[rbase + wave * BW_TH + px0], ro1 = rec_off[rbase + wave * BW_TH + 16 + px0];
     const int ro8 = rec_off[rbase + 8 * BW_TH + 16 * ks8 + px0];
+    if (t + S < T) item_words(t + S, pv);  // (read at the top of the next pass)
+    __syncthreads();  // previous item consumed (first pass: zero fill done)
+#pragma unroll
+    for (int c = 0; c < BW_CG; ++c) {
+      xw[c * BP_CP + e0] = (xok0 && c < cmx) ? xv0[c] : 0.f;
+      if (has1) xw[c * BP_CP + e1] = (xok1 && c < cmx) ? xv1[c] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool oo = go0 + 32 * u < omx;
+      uint32_t p1, p2, p3;
+      sp_split2((gok0 && oo) ? gv0[u] : 0.f, (gok1 && oo) ? gv1[u] : 0.f, p1, p2, p3);
+      uint32_t* dst = gyb + (go0 + 32 * u) * BS_GP + gpp;
+      dst[0] = p1;
+      dst[128 * BS_GP] = p2;
+      dst[2 * 128 * BS_GP] = p3;
+    }
     __syncthreads();
     uint4 a[4][3], b0[3], b1[3], b8[3];
     sample(rw0, ro0, b0);

@@ -2111,7 +2111,12 @@ class BnActFunction(torch.autograd.Function):
     fused = sink_g is not None and sink_b is not None and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]
     ggamma = sink_g if fused else torch.empty_like(gamma)
     gbeta = sink_b if fused else torch.empty_like(gamma)
-    nbytes = 4 * y.numel() * (2 * (2 + (1 if out is not None else 0)) + 1 + (1 if need_gadd else 0))
+    # tensor passes of the two kernels: the statistics pass reads gout, y (, out); the apply pass reads them again and writes gy -- or,
+    # with a skip gradient behind a ReLU, the statistics pass also writes gadd and the apply pass reads only gadd and y (3 + 1 + 2 + 1)
+    if need_gadd and out is not None:
+      nbytes = 4 * y.numel() * 7
+    else:
+      nbytes = 4 * y.numel() * (2 * (2 + (1 if out is not None else 0)) + 1 + (1 if need_gadd else 0))
     gy_amax = None
     if CONV_ARITH == 'bf16x6' and ((CONV3D_S1_F16 and y.dim() == 5) or (SPHERE_BWD_F16 and y.dim() == 4 and C % 16 == 0)):
       gy_amax = torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=y.device)  # the convolution in front reads gy in both of its gradients
