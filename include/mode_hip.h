@@ -863,6 +863,46 @@ int mode_rgb_half_pil(const uint8_t* frames_u8, const int32_t* tab_w, const int3
                       float* rgb_half, uint8_t* half_u8, mode_stream_t stream);
 int mode_decimate2(const float* in, float* out, long long planes, int H, int W, mode_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 3D60 ingest (csrc/erp_ingest.hip): what the reference's Dataset3D60Disparity.__getitem__ (dataloader/dataset3D60Loader.py:123-248)
+ * does on the host per sample between the decoded equirectangular (ERP) files and ModeDisparity, for a batch of N pairs.
+ *
+ * The re-projection of both entries is F.grid_sample(bilinear, border, align_corners = true) with the BITS of torch's CPU kernel
+ * (the RGB result is truncated to bytes; a sum that is only close is off by one on saturated regions).  Per output pixel, in fp32,
+ * every operation rounded to nearest, for a source of (Hs, Ws) and a grid point (gx, gy):
+ *     x  = min(max((gx + 1) * ((Ws - 1) / 2), 0), Ws - 1)             likewise y with Hs
+ *     x0 = floor(x); ex = x - x0; wx = 1 - ex                         likewise y0, ey, wy
+ *     nw = wx * wy; ne = ex * wy; sw = wx * ey; se = ex * ey
+ *     v  = fma(p_se, se, fma(p_sw, sw, fma(p_ne, ne, p_nw * nw)))     corners outside the image are not read and count as 0
+ *
+ * mode_erp_pairs_u8_cassini (dataset3D60Loader.py:177-180, 192-193, 202-205, 232-236):
+ *   pairs_u8 (N, 2, He, We, 3) bytes: left and right ERP panorama of N samples as np.asarray(PIL RGB image) lays them out.
+ *   grid (G, H, W, 2) fp32, G = 1 or N: the sample points of utils.geometry.erp2rect_cassini for the pair's rotation, built on the
+ *     host (utils.geometry.erp2rect_grid); 16-byte aligned.  G = 1: one grid serves every sample.
+ *   lut (256, 3): the table of mode_frames_u8_ingest.
+ *   left, right (N, 3, H, W) fp32 = lut[trunc(bilinear)]: erp2rect_cassini(...).astype(np.uint8), then the stage-1 transform.
+ *   left_flip, right_flip (N, 3, H, W) or both NULL: the mirrored twin (:193):
+ *     left_flip[.., x] = right[.., W-1-x], right_flip[.., x] = left[.., W-1-x].
+ *   cassini_u8 (N, 2, H, W, 3) or NULL: the 8-bit Cassini images themselves; 4-byte aligned.
+ * mode_erp_depth_disp (dataset3D60Loader.py:182-185, 192-196, 209-210, 258-270):
+ *   depth_erp (N, He, We) fp32 -> disparity ground truth disp (N, 1, H, W):
+ *     d = bilinear (same arithmetic, fp32 result kept); d > maxdepth -> 0; invalid (d <= 0) -> NaN; else
+ *     disp = W * (asin(clip((d*s_j + b) / sqrt(d*d + b*b - 2*d*b*c_j), -1, 1)) - phi_j) / pi, negative -> 0,
+ *   in numpy's order of operations and numpy 2's types: the products of two arrays (d*s_j, d*d) in fp32, everything from the first
+ *   scalar on in fp64 (the reference's masked array is promoted there), one rounding to fp32 on the store.  `baseline` is widened to
+ *   fp64 as it is: 0.26f lies 3.7e-8 (relative) below the reference's double 0.26, which moves a disparity by at most 2e-6 px.
+ *   cols (3, W) fp32, 16-byte aligned: phi_j, s_j = sin(phi_j), c_j = cos(phi_j + pi/2) as numpy rounds them, host-built.
+ *   mirror != 0 writes column W-1-x of the re-projected depth to column x BEFORE the sine rule (the flip twin, fed the right view's
+ *     depth).  depth_cassini (N, H, W) or NULL: the re-projected, thresholded depth.
+ * One launch each: a thread owns four consecutive pixels of a Cassini row (one 16-byte store per fp32 plane) and forms the weights
+ * once for both images, all channels and -- with G = 1 -- all samples it walks.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, misaligned grid / cols / outputs (16 bytes),
+ * G not in {1, N}, He or We < 2, W % 4 != 0, N < 0 and element counts (6 N He We, 6 N H W, 2 G H W) >= 2^31.  N = 0 is a no-op. */
+int mode_erp_pairs_u8_cassini(const uint8_t* pairs_u8, const float* grid, const float* lut, int N, int He, int We, int H, int W, int G,
+                              float* left, float* right, float* left_flip, float* right_flip, uint8_t* cassini_u8, mode_stream_t stream);
+int mode_erp_depth_disp(const float* depth_erp, const float* grid, const float* cols, int N, int He, int We, int H, int W, int G,
+                        float baseline, float maxdepth, int mirror, float* disp, float* depth_cassini, mode_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

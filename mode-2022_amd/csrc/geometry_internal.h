@@ -1,6 +1,7 @@
 // Per-pixel arithmetic of the export-stage geometry, shared by the single-map entries (geometry.hip) and the batched multi-view
 // hand-off (multiview.hip).  Every helper here is a piece of one of geometry.hip's kernels moved out of it unchanged, so whatever
 // includes this header computes the old entries' bits (DESIGN 12 records the instruction-stream comparison of the move).
+// (One later addition, bilinear_border_exact / bilinear_sum_exact for erp_ingest.hip, is new arithmetic beside them; it changes none.)
 // Contraction: the helpers carry no fp-contract pragma of their own except project_pixel's (which was there before); do not add one
 // and build with no fast-math flag: the bilinear `v += s * w` sums are where a fused multiply-add could appear or disappear.
 #pragma once
@@ -64,6 +65,47 @@ __device__ __forceinline__ float bilinear_sum(const Bilinear& b, At at) {
   if (b.y1ok) v += at(b.y1, b.x0) * b.sw;
   if (b.x1ok && b.y1ok) v += at(b.y1, b.x1) * b.se;
   return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same tap with the BITS of ATen's CPU kernel (GridSamplerKernel.cpp, the vectorised path torch 2.x takes for contiguous fp32
+// input), for results that are truncated to bytes afterwards (erp_ingest.hip).  It differs from bilinear_border in the
+// unnormalisation -- (g + 1) * ((size - 1) / 2), the scale formed first -- and from bilinear_sum in the sum, one fused multiply-add
+// per corner after the first product, corners in the order nw, ne, sw, se:
+//   v = fma(p_se, se, fma(p_sw, sw, fma(p_ne, ne, p_nw * nw)))
+// Every operation goes through one of the helpers below, so neither the compiler's contraction nor a build flag can change it.
+// HIP's __fmul_rn / __fadd_rn / __fsub_rn are plain operators compiled under the header's own contraction setting: inlined next to each
+// other the backend may still fuse them.  These carry `contract(off)` themselves (an instruction without the contract flag is never
+// fused, whatever its neighbour allows); __fmaf_rn is a genuine fused multiply-add.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return __fmul_rn(a, b);
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return __fadd_rn(a, b);
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return __fsub_rn(a, b);
+}
+
+__device__ __forceinline__ Bilinear bilinear_border_exact(float2 g, int Hs, int Ws) {
+  const float xmax = (float)(Ws - 1), ymax = (float)(Hs - 1);
+  float x = mul_rn(add_rn(g.x, 1.f), mul_rn(xmax, 0.5f));  // ((size - 1) / 2 is exact in fp32 below 2^24)
+  float y = mul_rn(add_rn(g.y, 1.f), mul_rn(ymax, 0.5f));
+  x = fminf(fmaxf(x, 0.f), xmax);
+  y = fminf(fmaxf(y, 0.f), ymax);
+  const float xf = floorf(x), yf = floorf(y);
+  const int x0 = (int)xf, y0 = (int)yf;
+  const float ex = sub_rn(x, xf), ey = sub_rn(y, yf);
+  const float wx = sub_rn(1.f, ex), wy = sub_rn(1.f, ey);
+  return Bilinear{x0, y0, x0 + 1, y0 + 1, mul_rn(wx, wy), mul_rn(ex, wy), mul_rn(wx, ey), mul_rn(ex, ey), x0 + 1 < Ws, y0 + 1 < Hs};
+}
+
+// The sum over four corner VALUES (a corner outside the image is passed as 0, as ATen's masked gather returns it; its weight is 0).
+__device__ __forceinline__ float bilinear_sum_exact(const Bilinear& b, float p_nw, float p_ne, float p_sw, float p_se) {
+  return __fmaf_rn(p_se, b.se, __fmaf_rn(p_sw, b.sw, __fmaf_rn(p_ne, b.ne, mul_rn(p_nw, b.nw))));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -179,6 +179,9 @@ SIGNATURES = {
     'mode_frames_u8_ingest': (_c_int, [_c_ptr] * 2 + [_c_int] * 3 + [_c_ptr] * 4),
     'mode_rgb_half_pil': (_c_int, [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr] * 3),
     'mode_decimate2': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
+    # 3D60 ingest: ERP pairs and depth to rectified Cassini (csrc/erp_ingest.hip; reference dataloader/dataset3D60Loader.py:123-270)
+    'mode_erp_pairs_u8_cassini': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr] * 6),
+    'mode_erp_depth_disp': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 3),
 }
 
 ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against

@@ -64,6 +64,11 @@ class _LRU(object):
   def __len__(self):
     return len(self.d) + len(self.pinned)
 
+  def clear(self):
+    """Drop every entry, pinned ones included (for callers that know no graph that used them is left)."""
+    self.d.clear()
+    self.pinned.clear()
+
   def release_graph_pins(self):
     """Make the pinned entries evictable again (they re-enter the LRU order as the most recent ones)."""
     for key, value in self.pinned.items():
@@ -1991,6 +1996,72 @@ def decimate2(x):
   with torch.cuda.device_of(x), profiling.region('decimate2', 4 * (x.numel() // 2 + y.numel()), 0, x.device):
     check(lib().mode_decimate2(ptr(x), ptr(y), x.numel() // (H * W), H, W, stream_of(x)), 'mode_decimate2')
   return y
+
+
+# ------------------------------------------------------------------------------------ 3D60 ingest: ERP -> rectified Cassini
+def _require_erp_grid(grid, N, who):
+  require_gpu(grid)
+  require_f32c(grid)
+  if grid.dim() != 4 or grid.shape[3] != 2 or grid.shape[0] not in (1, N) or grid.shape[2] % 4 or 0 in grid.shape:
+    raise ValueError('%s: grid must be (1 or %d, H, W, 2) with W a positive multiple of 4, got %s' % (who, N, tuple(grid.shape)))
+
+
+def erp_pairs_u8_cassini(pairs_u8, grid, lut, flip=True, return_u8=False):
+  """(N, 2, He, We, 3) uint8 ERP pairs -> the rectified Cassini pairs of the reference's 3D60 loader on mode_erp_pairs_u8_cassini
+  (dataloader/dataset3D60Loader.py:177-180, 192-193, 202-205, 232-236): erp2rect_cassini(...).astype(np.uint8) of both panoramas through
+  `grid` ((1 or N, H, W, 2) float32, utils.geometry.erp2rect_grid), then the stage-1 transform as a lookup in `lut` ((256, 3), the table
+  of frames_u8_ingest).  -> (left, right, left_flip, right_flip, cassini_u8): (N, 3, H, W) float32 each, the flip twins None without
+  `flip`, the 8-bit images (N, 2, H, W, 3) None without `return_u8`."""
+  who = 'erp_pairs_u8_cassini'
+  if not torch.is_tensor(pairs_u8) or pairs_u8.dtype != torch.uint8:
+    raise TypeError('%s: pairs must be a uint8 tensor (got %s)' % (who, getattr(pairs_u8, 'dtype', type(pairs_u8))))
+  require_gpu(pairs_u8, lut)
+  if not pairs_u8.is_contiguous():
+    raise TypeError('%s: pairs must be contiguous' % who)
+  if pairs_u8.dim() != 5 or pairs_u8.shape[1] != 2 or pairs_u8.shape[4] != 3 or pairs_u8.shape[2] < 2 or pairs_u8.shape[3] < 2:
+    raise ValueError('%s: pairs must be (N, 2, He, We, 3) with He, We >= 2, got %s' % (who, tuple(pairs_u8.shape)))
+  N, _, He, We, _ = pairs_u8.shape
+  _require_erp_grid(grid, N, who)
+  require_f32c(lut)
+  if tuple(lut.shape) != (256, 3):
+    raise ValueError('%s: lut %s must be (256, 3)' % (who, tuple(lut.shape)))
+  G, H, W, _ = grid.shape
+  dev = pairs_u8.device
+  outs = [torch.empty((N, 3, H, W), dtype=torch.float32, device=dev) for _ in range(4 if flip else 2)] + [None] * (0 if flip else 2)
+  u8 = torch.empty((N, 2, H, W, 3), dtype=torch.uint8, device=dev) if return_u8 else None
+  nbytes = pairs_u8.numel() + 4 * grid.numel() + sum(4 * o.numel() for o in outs if o is not None) + (0 if u8 is None else u8.numel())
+  with torch.cuda.device_of(pairs_u8), profiling.region('erp_pairs_u8_cassini', nbytes, 0, dev):
+    check(lib().mode_erp_pairs_u8_cassini(ptr(pairs_u8), ptr(grid), ptr(lut), N, He, We, H, W, G, ptr(outs[0]), ptr(outs[1]),
+                                          None if outs[2] is None else ptr(outs[2]), None if outs[3] is None else ptr(outs[3]),
+                                          None if u8 is None else ptr(u8), stream_of(pairs_u8)), 'mode_erp_pairs_u8_cassini')
+  return outs[0], outs[1], outs[2], outs[3], u8
+
+
+def erp_depth_disp(depth_erp, grid, cols, baseline, maxdepth, mirror=False, return_depth=False):
+  """(N, He, We) float32 ERP depth -> the disparity ground truth (N, 1, H, W) of the reference's 3D60 loader on mode_erp_depth_disp
+  (dataloader/dataset3D60Loader.py:182-185, 192-196, 209-210 and __depth2disp, :258-270): erp2rect_cassini through `grid`, depth above
+  `maxdepth` zeroed, the sine rule on `cols` ((3, W): phi, sin(phi), cos(phi + pi / 2)), NaN where the depth is invalid.  `mirror`
+  flips the re-projected depth left to right before the sine rule (the flip twin).  With return_depth also the thresholded Cassini
+  depth (N, H, W)."""
+  who = 'erp_depth_disp'
+  require_gpu(depth_erp, cols)
+  require_f32c(depth_erp, cols)
+  if depth_erp.dim() != 3 or depth_erp.shape[1] < 2 or depth_erp.shape[2] < 2:
+    raise ValueError('%s: depth must be (N, He, We) with He, We >= 2, got %s' % (who, tuple(depth_erp.shape)))
+  N, He, We = depth_erp.shape
+  _require_erp_grid(grid, N, who)
+  G, H, W, _ = grid.shape
+  if tuple(cols.shape) != (3, W):
+    raise ValueError('%s: cols %s must be (3, %d)' % (who, tuple(cols.shape), W))
+  dev = depth_erp.device
+  disp = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+  dc = torch.empty((N, H, W), dtype=torch.float32, device=dev) if return_depth else None
+  nbytes = 4 * (depth_erp.numel() + grid.numel() + disp.numel() + (0 if dc is None else dc.numel()))
+  with torch.cuda.device_of(depth_erp), profiling.region('erp_depth_disp', nbytes, 0, dev):
+    check(lib().mode_erp_depth_disp(ptr(depth_erp), ptr(grid), ptr(cols), N, He, We, H, W, G, float(baseline), float(maxdepth),
+                                    1 if mirror else 0, ptr(disp), None if dc is None else ptr(dc), stream_of(depth_erp)),
+          'mode_erp_depth_disp')
+  return (disp, dc) if return_depth else disp
 
 
 # ------------------------------------------------------------------------------------ BatchNorm (+ add) (+ ReLU)

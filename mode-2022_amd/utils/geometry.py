@@ -138,17 +138,66 @@ def cassini2Equirec(cassini):
   return _from_nchw(out, a).squeeze()
 
 
+# ------------------------------------------------------------------------------------------------ the rotations of the 3D60 pairs
+# rotation vectors of the 3D60 stereo pairs as the reference writes them (dataloader/dataset3D60Loader.py:141, 147, 153): float32
+PAIR_VECTORS = {'lr': np.array([0, 0, 0]).astype(np.float32), 'ud': np.array([0, 0, -np.pi / 2]).astype(np.float32),
+                'ur': np.array([0, 0, -np.pi / 4]).astype(np.float32)}
+
+
+def rodrigues(rvec):
+  """Rotation vector -> 3x3 matrix by Rodrigues' formula, R = cos(t) I + (1 - cos(t)) r r^T + sin(t) [r]x with t = |rvec|, r = rvec / t,
+  evaluated in float64 and returned in the vector's dtype, which is what cv2.Rodrigues does.  (The reference calls cv2.Rodrigues; cv2
+  is not a dependency here, so its last bits for a non-zero rotation are not pinned.  The zero vector gives the exact identity.)"""
+  v = np.asarray(rvec)
+  r = v.astype(np.float64).reshape(3)
+  theta = float(np.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]))
+  if theta < np.finfo(np.float64).eps:
+    return np.eye(3, dtype=v.dtype)
+  c, s = np.cos(theta), np.sin(theta)
+  r = r / theta
+  rrt = np.outer(r, r)
+  r_x = np.array([[0, -r[2], r[1]], [r[2], 0, -r[0]], [-r[1], r[0], 0]])
+  return (c * np.eye(3) + (1 - c) * rrt + s * r_x).astype(v.dtype)
+
+
+def pair_rotation(pair):
+  """The float32 rotation matrix of a 3D60 stereo pair ('lr', 'ud' or 'ur'), dataset3D60Loader.py:136-153, 175."""
+  if pair not in PAIR_VECTORS:
+    raise ValueError("3D60 pair %r is not one of 'lr', 'ud', 'ur'" % (pair,))
+  return rodrigues(PAIR_VECTORS[pair])
+
+
 # ------------------------------------------------------------------------------------------------ erp2rect_cassini
+_erp2rect_grids = {}  # (bytes of R, its dtype and shape, ca_h, ca_w) -> read-only float32 (ca_h, ca_w, 2); bounded below
+_erp2rect_lock = threading.Lock()
+
+
+def erp2rect_grid(R, ca_h, ca_w):
+  """The sample points of erp2rect_cassini (geometry.py:170-193) as a float32 (ca_h, ca_w, 2) array of normalised (x, y): for every
+  pixel of the rectified Cassini image the point of the equirectangular source, under rotation R (3x3).  A function of (R, ca_h, ca_w)
+  alone, cached (the array is shared and read-only)."""
+  R = np.asarray(R)
+  key = (R.tobytes(), R.dtype.str, R.shape, int(ca_h), int(ca_w))
+  with _erp2rect_lock:
+    hit = _erp2rect_grids.get(key)
+    if hit is None:
+      dirs = _unit_dirs(ca_h, ca_w)
+      X = np.expand_dims(np.dstack((dirs[0], dirs[1], dirs[2])), axis=-1)
+      X2 = np.matmul(np.linalg.inv(R), X)
+      phi_erp_map = np.arcsin(X2[:, :, 1, :])
+      theta_erp_map = np.arctan2(X2[:, :, 0, :], X2[:, :, 2, :])
+      hit = np.concatenate((np.clip(-theta_erp_map / np.pi, -1, 1), np.clip(-phi_erp_map / (0.5 * np.pi), -1, 1)), axis=-1).astype(np.float32)
+      hit.setflags(write=False)
+      if len(_erp2rect_grids) >= 32:
+        _erp2rect_grids.pop(next(iter(_erp2rect_grids)))
+      _erp2rect_grids[key] = hit
+    return hit
+
+
 def erp2rect_cassini(erp, R, ca_h, ca_w, devcice='cuda'):
   """geometry.py:160-198: equirectangular image -> rectified Cassini (ca_h, ca_w) under rotation R (3x3).  The misspelt
   keyword is the reference's."""
-  dirs = _unit_dirs(ca_h, ca_w)
-  X = np.expand_dims(np.dstack((dirs[0], dirs[1], dirs[2])), axis=-1)
-  X2 = np.matmul(np.linalg.inv(R), X)
-  phi_erp_map = np.arcsin(X2[:, :, 1, :])
-  theta_erp_map = np.arctan2(X2[:, :, 0, :], X2[:, :, 2, :])
-  grid = np.concatenate((np.clip(-theta_erp_map / np.pi, -1, 1), np.clip(-phi_erp_map / (0.5 * np.pi), -1, 1)), axis=-1).astype(np.float32)
-  grid = torch.from_numpy(grid).unsqueeze(0).to(devcice)
+  grid = torch.from_numpy(erp2rect_grid(R, ca_h, ca_w).copy()).unsqueeze(0).to(devcice)
   if isinstance(erp, torch.Tensor) and erp.dim() == 4:
     return _grid_sample(erp, grid).squeeze(1)
   a = np.asarray(erp)
