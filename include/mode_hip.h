@@ -701,6 +701,27 @@ size_t mode_multiview_handoff_workspace_bytes(int F, int H, int W);
 int mode_multiview_handoff(const float* disp, const float* conf, int F, int H, int W, const float* baselines6, const float* rot_grids,
                            const float* trig, const double* xforms, int flags, float* out, void* workspace, mode_stream_t stream);
 
+/* The gradient of the hand-off's DEPTH channels with respect to the disparities, in two launches and without a memset (every element
+ * of gdisp (F, 6, H, W) is written; graph-capturable).  gout is the gradient of `out` in the forward's layout, (F, 12, H, W) or
+ * (F, 6, H, W) under MODE_MV_DEPTH_ONLY; its confidence channels are not read: the confidence has no gradient (q is piecewise constant,
+ * and the head's confidence map has no backward).  With S(d, j) = -(pi / W) baseline cos(phi_l) / sin^2(d pi / W) where d != 0 and the
+ * unclipped sine-rule depth lies in [0, 1000], and exactly +0 elsewhere:
+ *   12        gdisp = gout S
+ *   13, 14    gdisp[s] = S sum_k weight[k] gout[target[k]] over the adjoint list of source s (float32, stored order, no atomics)
+ *   23 24 34  the z-buffer's winner alone: gdisp[winner(t)] = gout[t] (r1 - dir . t_xf) / r2 S unless the target is capped at 1000;
+ *             every other source +0.  The winner is decoded from the forward's key.
+ *   keys        device, 8-byte aligned: the forward's workspace after mode_multiview_handoff on the same disp (3 F H W keys)
+ *   baselines6, trig, xforms   as the forward's
+ *   adj_rowptr  device int32 (2, H W + 1): for grid 13, then 14, the range of entries of every source pixel; offsets into
+ *   adj_target, adj_weight     device, n_adj entries (n_adj <= 8 H W): target pixel and bilinear weight, sorted by source, target, corner
+ * Arguments are checked before any launch as the forward's are (MODE_ERR_WORKSPACE for missing or unaligned keys).  F = 0 is a no-op.
+ * The CONTENTS of the device arrays cannot be checked on the host: the kernels stay inside the buffers whatever they hold (list ranges
+ * are clamped to [0, n_adj], targets and decoded winners outside the plane are skipped), but a malformed list, or keys of another
+ * size or another disp, give undefined gradient values, not a diagnostic. */
+int mode_multiview_handoff_bwd(const float* disp, const float* gout, const void* keys, int F, int H, int W, const float* baselines6,
+                               const float* trig, const double* xforms, const int32_t* adj_rowptr, const int32_t* adj_target,
+                               const float* adj_weight, int n_adj, int flags, float* gdisp, mode_stream_t stream);
+
 /* Training forward of convbn_3d (models/submodule.py:20-22) without the statistics pass: the stride-1 split-bf16 convolution kernel
  * takes the BatchNorm batch statistics of its output from the accumulators (per channel: sum(y - K), sum((y - K)^2), K = the layer's own
  * first output value) and leaves them in `stats` = the BatchNorm workspace (>= mode_bn_workspace_bytes(Co) bytes) as

@@ -88,6 +88,108 @@ __global__ __launch_bounds__(NT) void mv_resolve_kernel(const unsigned long long
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The gradient of the hand-off's depth channels with respect to the disparities (mode_multiview_handoff_bwd, DESIGN 12 "Gradient").
+// The confidence channels have none: q is piecewise constant and the head's confidence map has no backward either.
+//   launch A  one thread per SOURCE pixel of the F x 6 maps: planes 12, 13, 14 get their value, planes 23, 24, 34 get +0
+//   launch B  one thread per TARGET pixel of the F x 3 view-transformed maps: the winner of its key gets the target's gradient
+// A source bids for one target, so it wins at most one: launch B's stores never collide, and no sum is formed with atomics.
+
+// the sine rule without its clip, operation for operation as geom::sine_rule_depth forms it (d != 0)
+__device__ __forceinline__ float sine_rule_raw(float d, int j, int W, float baseline, float& phi_l) {
+  const float pi_f = 3.14159265358979323846f, half_pi_f = 1.57079632679489661923f;
+  const double start = 0.5 * 3.14159265358979323846 - (0.5 * 3.14159265358979323846 / W);
+  const double step = 3.14159265358979323846 / W;
+  phi_l = (float)(start + (double)j * (-step));
+  const float phi_r = d * pi_f / (float)W + phi_l;
+  return baseline * sinf(half_pi_f - phi_r) / sinf(phi_r - phi_l);
+}
+
+// S(d, j) = d depth / d disparity = -(pi / W) baseline cos(phi_l) / sin^2(d pi / W) where the sine rule passes a gradient: d != 0 and
+// 0 <= raw <= 1000 (the reference clips by assigning to the values strictly outside, so the boundary passes); exactly +0 elsewhere
+// (NaN included).  The closed form has none of the forward's phi_r - phi_l cancellation.
+__device__ __forceinline__ float sine_rule_slope(float d, int j, int W, float baseline) {
+  if (d == 0.f) return 0.f;
+  float phi_l;
+  const float raw = sine_rule_raw(d, j, W, baseline, phi_l);
+  if (!(raw >= 0.f && raw <= 1000.f)) return 0.f;
+  const float pi_f = 3.14159265358979323846f;
+  const float s = sinf(d * pi_f / (float)W);
+  return -(pi_f / (float)W) * baseline * cosf(phi_l) / (s * s);
+}
+
+__global__ __launch_bounds__(NT) void mv_bwd_sources_kernel(const float* __restrict__ disp, const float* __restrict__ gout,
+                                                            const int* __restrict__ rowptr, const int* __restrict__ target,
+                                                            const float* __restrict__ weight, int n_adj, float* __restrict__ gdisp,
+                                                            int F, int H, int W, MvArgs a) {
+  const long long hw = (long long)H * W;
+  const long long total = (long long)F * 6 * hw;
+  for (long long idx = (long long)blockIdx.x * NT + threadIdx.x; idx < total; idx += (long long)gridDim.x * NT) {
+    const long long plane = idx / hw;  // f * 6 + p
+    const long long pix = idx - plane * hw;
+    const int p = (int)(plane % 6);
+    float g = 0.f;  // pairs 23, 24, 34: launch B fills the winners in
+    if (p < 3) {
+      const int j = (int)(pix % W);
+      const float s = sine_rule_slope(disp[idx], j, W, a.baseline[p]);
+      if (s != 0.f) {
+        const float* gd = gout + plane * a.oc * hw;  // gout[f, oc * p]
+        if (p == 0) {
+          g = gd[pix] * s;
+        } else {
+          // the (target, weight) entries of the rotation grid whose corner this source is, in the list's stored order
+          const int* rp = rowptr + (p - 1) * (hw + 1) + pix;
+          const int k0 = max(rp[0], 0), k1 = min(rp[1], n_adj);
+          float acc = 0.f;
+          for (int k = k0; k < k1; ++k) {
+            const int t = target[k];
+            if ((unsigned)t < (unsigned)hw) acc += weight[k] * gd[t];
+          }
+          g = s * acc;
+        }
+      }
+    }
+    gdisp[idx] = g;
+  }
+}
+
+__global__ __launch_bounds__(NT) void mv_bwd_winners_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ disp,
+                                                            const float* __restrict__ gout, const float* __restrict__ trig,
+                                                            float* __restrict__ gdisp, int F, int H, int W, MvArgs a) {
+#pragma clang fp contract(off)  // r2 as geom::project_pixel rounds it
+  const long long hw = (long long)H * W;
+  const long long total = (long long)F * 3 * hw;
+  for (long long idx = (long long)blockIdx.x * NT + threadIdx.x; idx < total; idx += (long long)gridDim.x * NT) {
+    const unsigned long long k = keys[idx];
+    if (k == ~0ull) continue;  // no source reached this target
+    const float v = __uint_as_float((unsigned)(k >> 32));
+    if (v > 1000.f) continue;  // geom::resolve_key: capped (strictly above; its 100000 -> 0 rule lies above the cap too): a constant
+    const unsigned lo = (unsigned)(k & 0xffffffffull);
+    const long long src = (lo & 0x80000000u) ? (long long)(lo & 0x7fffffffu) : hw - 1 - (long long)lo;
+    if (src < 0 || src >= hw) continue;  // (not a key of this size's forward)
+    const long long kp = idx / hw;  // f * 3 + (p - 3)
+    const long long pix = idx - kp * hw;
+    const int v3 = (int)(kp % 3);
+    const long long plane = (kp / 3) * 6 + 3 + v3;  // f * 6 + p
+    const int i = (int)(src / W), j = (int)(src - (long long)i * W);
+    const float baseline = a.baseline[3 + v3];
+    const float d = disp[plane * hw + src];
+    const float s = sine_rule_slope(d, j, W, baseline);
+    if (s == 0.f) continue;
+    // r2 = |r1 dir - t| (R is orthonormal), so d r2 / d r1 = (r1 - dir . t) / r2 with |dir| = 1
+    const geom::ViewXform& xf = a.xf[v3];
+    const float r1 = geom::sine_rule_depth(d, j, W, baseline);
+    const float sin_phi = trig[j], cos_phi = trig[W + j], sin_theta = trig[2 * W + i], cos_theta = trig[2 * W + H + i];
+    const float rc = r1 * cos_phi;
+    const float x1 = r1 * sin_phi, y1 = rc * sin_theta, z1 = rc * cos_theta;
+    const double ax = (double)x1 - xf.t[0], ay = (double)y1 - xf.t[1], az = (double)z1 - xf.t[2];
+    const double r2 = sqrt(ax * ax + ay * ay + az * az);
+    const double dir_t = (double)sin_phi * xf.t[0] + (double)(cos_phi * sin_theta) * xf.t[1] + (double)(cos_phi * cos_theta) * xf.t[2];
+    const float slope = (float)(((double)r1 - dir_t) / r2);
+    gdisp[plane * hw + src] = gout[plane * a.oc * hw + pix] * slope * s;
+  }
+}
+
 int grid_for(long long n) { return (int)std::min<long long>(mode::cdiv(n, NT), 8LL * kNumCU); }
 
 }  // namespace
@@ -125,4 +227,36 @@ extern "C" int mode_multiview_handoff(const float* disp, const float* conf, int 
   hipLaunchKernelGGL(mv_pairs_kernel, dim3(grid_for(6LL * F * hw)), dim3(NT), 0, st, disp, conf, rot_grids, trig, keys, out, F, H, W, a);
   hipLaunchKernelGGL(mv_resolve_kernel, dim3(grid_for(3LL * F * hw)), dim3(NT), 0, st, keys, conf, out, F, H, W, a);
   return mode::check_launch("mode_multiview_handoff");
+}
+
+extern "C" int mode_multiview_handoff_bwd(const float* disp, const float* gout, const void* keys, int F, int H, int W,
+                                          const float* baselines6, const float* trig, const double* xforms, const int32_t* adj_rowptr,
+                                          const int32_t* adj_target, const float* adj_weight, int n_adj, int flags, float* gdisp,
+                                          mode_stream_t stream) {
+  MODE_REQUIRE(F >= 0 && H > 0 && W > 0 && 3LL * F * H * W < (1LL << 31), MODE_ERR_BAD_ARG,
+               "mode_multiview_handoff_bwd: bad size %d x %dx%d", F, H, W);
+  MODE_REQUIRE((flags & ~(MODE_MV_CONF_PNG | MODE_MV_DEPTH_ONLY)) == 0, MODE_ERR_BAD_ARG, "mode_multiview_handoff_bwd: unknown flags 0x%x",
+               flags);
+  MODE_REQUIRE(n_adj >= 0 && n_adj <= 8LL * H * W, MODE_ERR_BAD_ARG, "mode_multiview_handoff_bwd: %d adjoint entries for two %dx%d grids",
+               n_adj, H, W);
+  if (F == 0) return MODE_OK;
+  MODE_REQUIRE(disp && gout && baselines6 && trig && xforms && adj_rowptr && gdisp && (n_adj == 0 || (adj_target && adj_weight)),
+               MODE_ERR_BAD_ARG, "mode_multiview_handoff_bwd: null pointer");
+  MODE_REQUIRE(keys, MODE_ERR_WORKSPACE, "mode_multiview_handoff_bwd: the forward's key planes are required");
+  MODE_REQUIRE((reinterpret_cast<uintptr_t>(keys) & 7) == 0, MODE_ERR_WORKSPACE, "mode_multiview_handoff_bwd: unaligned key planes");
+  MvArgs a;
+  for (int p = 0; p < 6; ++p) a.baseline[p] = baselines6[p];
+  for (int v = 0; v < 3; ++v) {
+    for (int k = 0; k < 9; ++k) a.xf[v].R[k] = xforms[12 * v + k];
+    for (int k = 0; k < 3; ++k) a.xf[v].t[k] = xforms[12 * v + 9 + k];
+  }
+  a.png = 0;  // (the confidence channels of gout are not read)
+  a.oc = (flags & MODE_MV_DEPTH_ONLY) ? 1 : 2;
+  hipStream_t st = mode::as_stream(stream);
+  const long long hw = (long long)H * W;
+  hipLaunchKernelGGL(mv_bwd_sources_kernel, dim3(grid_for(6LL * F * hw)), dim3(NT), 0, st, disp, gout, adj_rowptr, adj_target, adj_weight,
+                     n_adj, gdisp, F, H, W, a);
+  hipLaunchKernelGGL(mv_bwd_winners_kernel, dim3(grid_for(3LL * F * hw)), dim3(NT), 0, st, reinterpret_cast<const unsigned long long*>(keys),
+                     disp, gout, trig, gdisp, F, H, W, a);
+  return mode::check_launch("mode_multiview_handoff_bwd");
 }

@@ -1,4 +1,4 @@
-"""ModeMultiView: fused 360-degree depth of whole Deep360 frames in one call (inference only).
+"""ModeMultiView: fused 360-degree depth of whole Deep360 frames in one call (forward / evaluate: inference; fusion_loss: training).
 
 The reference runs MODE as two scripts joined through the disk: save_output_disparity_stage.py evaluates one stereo pair at a time
 and writes a depth map (.npz) and an 8-bit confidence map (.png) per pair; test_fusion.py reads them back into the fusion network.
@@ -105,13 +105,9 @@ class ModeMultiView(nn.Module):
       self.fusion.load_state_dict(_state_dict_of(fusion))
     return self
 
-  def forward(self, frames, return_stages=False):
-    """frames (F, 12, 3, H, W) float32: ImageNet-normalised panoramas of F frames in sorted file order, or (F, 12, H, W, 3) uint8: the
-    same panoramas as they decode -> depth (F, 1, H, W) in camera 1's Cassini frame; with return_stages also {'disp', 'conf':
-    (6F, 1, H, W) of stage 1, 'fusion_input': the hand-off}.  resize=True (uint8 frames only): the fusion network runs at half size
-    and its output is upsampled x2; the stages then hold the half-size 'fusion_input' and 'rgb' the network saw."""
-    if self.training:
-      raise RuntimeError('ModeMultiView is inference only: call .eval() first')
+  def _ingest(self, frames):
+    """The checks and the split that forward() and fusion_loss() share: frames -> (left, right (6F, 3, H, W), rgb (F, 12, H, W) or None,
+    whether the fusion network takes the RGB)."""
     u8 = frames.dtype == torch.uint8
     if self.resize and not u8:
       raise ValueError('ModeMultiView(resize=True) takes uint8 frames (F, 12, H, W, 3), not %s: the reference halves the 8-bit images '
@@ -129,6 +125,16 @@ class ModeMultiView(nn.Module):
       raise ValueError('ModeMultiView: %d x %d is not a multiple of 16' % (H, W))
     if (H, W) != (self.height, self.width):
       raise ValueError('ModeMultiView: built for %d x %d, got %d x %d' % (self.height, self.width, H, W))
+    return left, right, rgb, want_rgb
+
+  def forward(self, frames, return_stages=False):
+    """frames (F, 12, 3, H, W) float32: ImageNet-normalised panoramas of F frames in sorted file order, or (F, 12, H, W, 3) uint8: the
+    same panoramas as they decode -> depth (F, 1, H, W) in camera 1's Cassini frame; with return_stages also {'disp', 'conf':
+    (6F, 1, H, W) of stage 1, 'fusion_input': the hand-off}.  resize=True (uint8 frames only): the fusion network runs at half size
+    and its output is upsampled x2; the stages then hold the half-size 'fusion_input' and 'rgb' the network saw."""
+    if self.training:
+      raise RuntimeError('ModeMultiView is inference only: call .eval() first')
+    left, right, rgb, want_rgb = self._ingest(frames)
     with torch.no_grad():
       disp, conf = self.disparity(left, right)
       fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png,
@@ -162,3 +168,50 @@ class ModeMultiView(nn.Module):
     depth = self.forward(frames)
     rows, depth_erp, _ = panorama.erp_depth_metrics(depth, gt, self.maxdepth if maxdepth is None else maxdepth, return_erp=True)
     return depth_erp, rows
+
+  def fusion_loss(self, frames, gt, lamda=0.5, maxdepth=None):
+    """The body of the reference's fusion training iteration between zero_grad() and backward() (train_fusion.py:90-112), on frames:
+        output = model(depthes, confs, rgbs);  mask = gt <= maxdepth;  loss = silog_loss(lamda, output[mask], gt[mask])
+    frames as forward() takes them, gt (F, H, W) Cassini ground truth on the device -> (loss, depth.detach()).  An extension (the
+    reference trains from exported files), after the precedent of ModeDisparity.forward_loss.  The fusion network must be in training
+    mode; the state of `disparity` selects what is trained:
+      disparity.eval()   the reference's recipe (net.train(); net.disparity.eval()): stage 1 runs without a gradient exactly as in
+                         forward(), the hand-off and the fusion network with autograd.  resize=True is taken as
+                         Deep360DatasetFusion(resize=True, training=True) takes it: hand-off decimated, 8-bit RGB halved, gt[:, ::2, ::2],
+                         no upsampling of the output.
+      disparity.train()  joint fine-tuning: the disparity of the third head with its gradient (BatchNorm on the statistics of the batch
+                         of 6F pairs), the confidence from the same logits without one, and the gradient of the loss reaches every
+                         stage-1 parameter through the hand-off's backward (utils.geometry.disp2depth_frames_gpu).  resize=True is
+                         refused: the decimation has no backward.
+    forward() and evaluate() stay inference only."""
+    if not self.fusion.training:
+      raise RuntimeError('ModeMultiView.fusion_loss is the training step of the fusion network: call .train() first '
+                         '(.disparity.eval() afterwards keeps stage 1 frozen)')
+    joint = self.disparity.training
+    if joint and self.resize:
+      raise ValueError('ModeMultiView(resize=True).fusion_loss cannot fine-tune the disparity stage: the decimation of the hand-off has '
+                       'no backward; call .disparity.eval() to train the fusion network alone')
+    left, right, rgb, want_rgb = self._ingest(frames)
+    require_gpu(gt)
+    H, W = left.shape[-2:]
+    if tuple(gt.shape) != (left.shape[0] // 6, H, W):
+      raise ValueError('ModeMultiView.fusion_loss: gt %s is not (F, H, W) = %s' % (tuple(gt.shape), (left.shape[0] // 6, H, W)))
+    if joint:
+      size = (self.disparity.maxdisp, H, W)
+      cost3 = self.disparity._logits(left, right)[2]
+      disp = HF.head(cost3, size)
+      conf = HF.head_fwd(cost3.detach(), size, with_confidence=True)[1]
+    else:
+      with torch.no_grad():
+        disp, conf = self.disparity(left, right)
+    fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png, depth_only=self.fusion_kind == 'Baseline')
+    if self.resize:  # deep360_loader.py:146-155 with training=True
+      fusion_input = HF.decimate2(fusion_input)
+      rgb = gpu_ingest.rgb_half_gpu(frames.contiguous()) if want_rgb else None
+      gt = gt[:, ::2, ::2]
+    if self.fusion_kind == 'ModeFusion':
+      output = self.fusion.feature_extraction(fusion_input, rgb)
+    else:
+      output = self.fusion.feature_extraction(fusion_input)
+    loss = HF.silog_loss(output, gt, gt <= (self.maxdepth if maxdepth is None else maxdepth), lamda)
+    return loss, output.detach()

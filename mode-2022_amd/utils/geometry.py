@@ -16,6 +16,7 @@ import threading
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from mode_hip import check, lib, ptr, require_f32c, require_gpu, stream_of
 from mode_hip import functional as _HF
@@ -349,17 +350,70 @@ def _as_frames(t, what):
   raise ValueError('disp2depth_frames_gpu: %s of shape %s is not (F, 6, H, W), (6F, 1, H, W) or (6F, H, W)' % (what, tuple(t.shape)))
 
 
-def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_only=False):
-  """The six pairs of F frames at once: disp, conf (F, 6, H, W) float32 device tensors (pair order PAIRS; (6F, 1, H, W) and
-  (6F, H, W) are taken as views) -> (F, 12, H, W) with out[f, 2p], out[f, 2p + 1] = disp2depth_gpu(disp[f, p], conf[f, p], PAIRS[p],
-  dbname) -- ModeFusion's channel interleave -- bit for bit, in three launches (mode_multiview_handoff).  conf_png: every confidence
-  as the reference's 8-bit PNG export reads back, q(c) = float32(float64(clip(rint(c * 255), 0, 255)) / 255).  depth_only:
-  (F, 6, H, W) of the depths alone (the input of Baseline)."""
-  require_gpu(disp, conf)
-  disp, conf = _as_frames(disp.contiguous(), 'disp'), _as_frames(conf.contiguous(), 'conf')
-  require_f32c(disp, conf)
-  if disp.shape != conf.shape or disp.device != conf.device:
-    raise ValueError('disp2depth_frames_gpu: disp %s and conf %s differ' % (tuple(disp.shape), tuple(conf.shape)))
+_adjoint_cache = _HF._LRU(8)  # (H, W, device) -> adjoint lists of the two rotation grids (mode_multiview_handoff_bwd)
+
+
+def _bilinear_border_np(grid, Hs, Ws):
+  """geom::bilinear_border (csrc/geometry_internal.h) on a (..., 2) float32 grid, operation for operation in numpy float32:
+  (x0, y0, x1ok, y1ok, (nw, ne, sw, se))."""
+  f32 = np.float32
+  gx, gy = grid[..., 0].astype(f32), grid[..., 1].astype(f32)
+  x = (gx + f32(1)) * f32(0.5) * f32(Ws - 1)
+  y = (gy + f32(1)) * f32(0.5) * f32(Hs - 1)
+  x = np.minimum(np.maximum(x, f32(0)), f32(Ws - 1))
+  y = np.minimum(np.maximum(y, f32(0)), f32(Hs - 1))
+  xf, yf = np.floor(x), np.floor(y)
+  x0, y0 = xf.astype(np.int64), yf.astype(np.int64)
+  wx1, wy1 = x - xf, y - yf
+  wx0, wy0 = f32(1) - wx1, f32(1) - wy1
+  return x0, y0, x0 + 1 <= Ws - 1, y0 + 1 <= Hs - 1, (wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1)
+
+
+def _grid_adjoint_np(grid, H, W):
+  """The adjoint list of one (H, W, 2) sampling grid over an (H, W) source: for every source pixel the (target, weight) entries of the
+  bilinear taps whose corner it is, sorted by source, then target, then corner (nw, ne, sw, se); corners outside the image are left
+  out.  -> (counts per source int64 (H W,), target int32 (n,), weight float32 (n,))."""
+  x0, y0, x1ok, y1ok, w = _bilinear_border_np(grid.reshape(H * W, 2), H, W)
+  tgt = np.arange(H * W, dtype=np.int64)
+  corners = ((y0 * W + x0, np.ones(H * W, dtype=bool)), (y0 * W + x0 + 1, x1ok), ((y0 + 1) * W + x0, y1ok),
+             ((y0 + 1) * W + x0 + 1, x1ok & y1ok))
+  src = np.concatenate([s[ok] for s, ok in corners])
+  t = np.concatenate([tgt[ok] for _, ok in corners])
+  c = np.concatenate([np.full(int(ok.sum()), k, dtype=np.int64) for k, (_, ok) in enumerate(corners)])
+  wt = np.concatenate([w[k][ok] for k, (_, ok) in enumerate(corners)])
+  order = np.lexsort((c, t, src))
+  return np.bincount(src, minlength=H * W), t[order].astype(np.int32), wt[order].astype(np.float32)
+
+
+def _frames_adjoint(H, W, device):
+  """(rowptr int32 (2, H W + 1), target int32 (n,), weight float32 (n,)) on the device: the adjoint lists of the rotation grids of
+  pairs 13 and 14 in CSR form, the second grid's entries behind the first's (rowptr[1, 0] == rowptr[0, H W]; n <= 8 H W).  Built once
+  per (H, W, device) on the host from the cached grids."""
+  key = (H, W, str(device))
+  with _frames_lock:
+    hit = _adjoint_cache.get(key)
+    if hit is not None:
+      return hit
+    rowptr, targets, weights, base = [], [], [], 0
+    for p in ('13', '14'):
+      grid = _rotate_grid(H, W, float(_ROT_PITCH[p]), 0.0, 0.0, str(device))[0].cpu().numpy()
+      counts, t, w = _grid_adjoint_np(grid, H, W)
+      rowptr.append(base + np.concatenate(([0], np.cumsum(counts))))
+      targets.append(t)
+      weights.append(w)
+      base += len(t)
+    rowptr = np.stack(rowptr)
+    # the kernel cannot report a malformed list (it clamps and skips), so the only producer checks what it hands over
+    if rowptr[0, 0] != 0 or rowptr[1, 0] != rowptr[0, -1] or rowptr[1, -1] != base or (np.diff(rowptr.ravel()) < 0).any() or base > 8 * H * W:
+      raise RuntimeError('_frames_adjoint: inconsistent adjoint lists for %d x %d' % (H, W))
+    entry = (torch.from_numpy(rowptr.astype(np.int32)).to(device), torch.from_numpy(np.concatenate(targets)).to(device),
+             torch.from_numpy(np.concatenate(weights)).to(device))
+    _adjoint_cache[key] = entry
+    return entry
+
+
+def _handoff_fwd(disp, conf, dbname, conf_png, depth_only):
+  """disp, conf (F, 6, H, W) contiguous -> (out, the key planes (F, 3, H, W) int64 the launches leave behind)."""
   F, _, H, W = disp.shape
   baselines, grids, trig, xforms = _frames_tables(H, W, disp.device, dbname)
   out = torch.empty((F, 6 if depth_only else 12, H, W), dtype=torch.float32, device=disp.device)
@@ -368,8 +422,71 @@ def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_on
   with torch.cuda.device_of(disp):
     check(lib().mode_multiview_handoff(ptr(disp), ptr(conf), F, H, W, baselines.ctypes.data, ptr(grids), ptr(trig), xforms.ctypes.data, flags,
                                        ptr(out), ptr(ws), stream_of(disp)), 'mode_multiview_handoff')
-  return out
+  return out, ws.view(F, 3, H, W)
 
+
+def disp2depth_frames_bwd(disp, gout, keys, dbname='Deep360', depth_only=False):
+  """The gradient of disp2depth_frames_gpu's depth channels with respect to disp (mode_multiview_handoff_bwd): disp (F, 6, H, W) or one
+  of the views the forward takes, gout the gradient of the output in its layout, keys the key planes of the forward on the same disp (return_keys) -> gdisp (F, 6, H, W).
+  The confidence channels of gout are ignored and the confidence gets no gradient: q(c) is piecewise constant, and the head's
+  confidence map has no backward either.  Bit-repeatable: sums over the cached adjoint lists in their stored order, no atomics."""
+  require_gpu(disp, gout, keys)
+  disp, gout, keys = _as_frames(disp.contiguous(), 'disp'), gout.contiguous(), keys.contiguous()
+  require_f32c(disp, gout)
+  F, six, H, W = disp.shape
+  if six != 6 or tuple(gout.shape) != (F, 6 if depth_only else 12, H, W) or keys.dtype != torch.int64 or keys.numel() != 3 * F * H * W:
+    raise ValueError('disp2depth_frames_bwd: disp %s, gout %s and keys %s %s do not belong together' %
+                     (tuple(disp.shape), tuple(gout.shape), keys.dtype, tuple(keys.shape)))
+  baselines, _, trig, xforms = _frames_tables(H, W, disp.device, dbname)
+  rowptr, target, weight = _frames_adjoint(H, W, disp.device)
+  gdisp = torch.empty_like(disp)
+  with torch.cuda.device_of(disp):
+    check(lib().mode_multiview_handoff_bwd(ptr(disp), ptr(gout), ptr(keys), F, H, W, baselines.ctypes.data, ptr(trig), xforms.ctypes.data,
+                                           ptr(rowptr), ptr(target), ptr(weight), target.numel(), MV_DEPTH_ONLY if depth_only else 0,
+                                           ptr(gdisp), stream_of(disp)), 'mode_multiview_handoff_bwd')
+  return gdisp
+
+
+class _HandoffFunction(torch.autograd.Function):
+  """disp2depth_frames_gpu with a gradient for disp: the forward's launches and bits, disp and the key planes kept for the backward."""
+
+  @staticmethod
+  def forward(ctx, disp, conf, dbname, conf_png, depth_only):
+    out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only)
+    ctx.save_for_backward(disp, keys)
+    ctx.dbname, ctx.depth_only = dbname, depth_only
+    ctx.mark_non_differentiable(keys)
+    return out, keys
+
+  @staticmethod
+  @once_differentiable  # (the kernel has no second derivative: create_graph=True raises instead of returning a detached gradient)
+  def backward(ctx, gout, _gkeys):
+    disp, keys = ctx.saved_tensors
+    gdisp = disp2depth_frames_bwd(disp, gout, keys, ctx.dbname, ctx.depth_only) if ctx.needs_input_grad[0] else None
+    return gdisp, None, None, None, None
+
+
+def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_only=False, return_keys=False):
+  """The six pairs of F frames at once: disp, conf (F, 6, H, W) float32 device tensors (pair order PAIRS; (6F, 1, H, W) and
+  (6F, H, W) are taken as views) -> (F, 12, H, W) with out[f, 2p], out[f, 2p + 1] = disp2depth_gpu(disp[f, p], conf[f, p], PAIRS[p],
+  dbname) -- ModeFusion's channel interleave -- bit for bit, in three launches (mode_multiview_handoff).  conf_png: every confidence
+  as the reference's 8-bit PNG export reads back, q(c) = float32(float64(clip(rint(c * 255), 0, 255)) / 255).  depth_only:
+  (F, 6, H, W) of the depths alone (the input of Baseline).
+
+  Differentiable in disp (disp2depth_frames_bwd): the depth channels pass their gradient through the sine rule, the bilinear taps
+  of the rotation and, for the view-transformed pairs, to the z-buffer's winner alone.  The confidence gets no gradient (None for
+  conf): q(c) is piecewise constant, and the head's confidence map has no backward either.  return_keys: (out, keys) with the forward's
+  z-buffer key planes (F, 3, H, W) int64 (layout: csrc/geometry_internal.h)."""
+  require_gpu(disp, conf)
+  disp, conf = _as_frames(disp.contiguous(), 'disp'), _as_frames(conf.contiguous(), 'conf')
+  require_f32c(disp, conf)
+  if disp.shape != conf.shape or disp.device != conf.device:
+    raise ValueError('disp2depth_frames_gpu: disp %s and conf %s differ' % (tuple(disp.shape), tuple(conf.shape)))
+  if torch.is_grad_enabled() and (disp.requires_grad or conf.requires_grad):
+    out, keys = _HandoffFunction.apply(disp, conf, dbname, bool(conf_png), bool(depth_only))
+  else:
+    out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only)
+  return (out, keys) if return_keys else out
 
 
 def conf_png_np(c):

@@ -4,6 +4,7 @@
     python tools/multiview_bench.py --once      # one hand-off call and one six-call path at F = 1, for a kernel trace
     python tools/multiview_bench.py --scoring   # the scoring line alone
     python tools/multiview_bench.py --u8        # the ingest line alone: float frames from the host against 8-bit frames, and resize=True
+    python tools/multiview_bench.py --train     # the training line alone: fusion_loss + backward per frame, both modes; the hand-off's backward
 
 For every F: the frame time of the composed module, eager and replayed from a captured graph; the split between stage 1 (ModeDisparity
 at batch 6F), the hand-off (utils.geometry.disp2depth_frames_gpu) and stage 2 (the fusion network); and the hand-off against the
@@ -16,7 +17,11 @@ beyond the data-dependence of the z-buffer scatter).  Writes one JSON file.
   A  host normalisation (dataloader.preprocess on the 12 panoramas) + upload of the float frame (75 MB) + the float forward
   B  upload of the 8-bit frame (19 MB) + the uint8 forward (normalisation and split in one kernel)
   C  upload of the 8-bit frame + the uint8 forward of ModeMultiView(resize=True) (fusion network at half size)
-Host clock around work that ends in a device synchronise; medians in ms."""
+Host clock around work that ends in a device synchronise; medians in ms.
+
+--train times one ModeMultiView.fusion_loss + backward on one frame (F = 1), with stage 1 frozen (net.train(); net.disparity.eval()) and
+with stage 1 fine-tuned (net.train(), batch statistics at batch 6), and the hand-off's forward and backward alone on the disparities of
+that frame.  Device events around every single call after a warm-up; medians in ms.  One JSON line."""
 import argparse
 import json
 import os
@@ -173,6 +178,59 @@ def u8_line(reps=20, warmup=3):
   return row
 
 
+def train_line(reps=10, warmup=2):
+  """The training line (see the module docstring).  The joint mode is timed last: if the training forward of stage 1 at batch 6 does not
+  fit, the line still carries the other figures and the reason."""
+  net = make_net()
+  frames = make_frames(1, 400)
+  gt = (torch.rand(1, H, W, generator=torch.Generator().manual_seed(401)) * 1100).to(DEV)  # about a tenth beyond maxdepth
+  row = {'stage': 'train', 'size': [H, W], 'frames': 1, 'reps': reps}
+
+  def each(fn):
+    for _ in range(warmup):
+      fn()
+    ms = []
+    for _ in range(reps):
+      s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      s.record()
+      fn()
+      e.record()
+      e.synchronize()
+      ms.append(s.elapsed_time(e))
+    return float(np.median(ms))
+
+  with torch.no_grad():
+    left, right, _ = split_frames(frames)
+    disp, conf = net.disparity(left, right)
+    del left, right
+  out, keys = HG.disp2depth_frames_gpu(disp, conf, conf_png=True, return_keys=True)
+  gout = torch.randn_like(out)
+  row['handoff_fwd_ms'] = each(lambda: HG.disp2depth_frames_gpu(disp, conf, conf_png=True))
+  row['handoff_bwd_ms'] = each(lambda: HG.disp2depth_frames_bwd(disp, gout, keys))
+  del out, keys, gout, disp, conf
+
+  def step():
+    net.zero_grad(set_to_none=True)
+    loss, _ = net.fusion_loss(frames, gt)
+    loss.backward()
+    return loss
+
+  net.train()
+  net.disparity.eval()
+  row['frozen_stage1_step_ms'] = each(step)
+  row['frozen_stage1_loss'] = float(step().detach())
+  net.train()
+  try:
+    row['fine_tuning_step_ms'] = each(step)
+    row['fine_tuning_loss'] = float(step().detach())
+    row['fine_tuning_peak_GiB'] = torch.cuda.max_memory_allocated() / 2.0 ** 30
+  except torch.cuda.OutOfMemoryError as e:
+    row['fine_tuning_step_ms'] = None
+    row['fine_tuning_error'] = str(e).splitlines()[0]
+  print(json.dumps(row), flush=True)
+  return row
+
+
 def once():
   disp = (torch.rand(1, 6, H, W, device=DEV) * 40).contiguous()
   conf = torch.rand(1, 6, H, W, device=DEV)
@@ -191,6 +249,7 @@ def main():
   ap.add_argument('--once', action='store_true')
   ap.add_argument('--scoring', action='store_true', help='only the scoring line')
   ap.add_argument('--u8', action='store_true', help='only the ingest line: float frames from the host against 8-bit frames, and resize=True')
+  ap.add_argument('--train', action='store_true', help='only the training line: fusion_loss + backward in both modes, the hand-off\'s backward')
   args = ap.parse_args()
   if args.once:
     return once()
@@ -198,6 +257,8 @@ def main():
     return scoring_line()
   if args.u8:
     return u8_line()
+  if args.train:
+    return train_line()
   net = make_net()
   rows = []
   for F in args.frames:
