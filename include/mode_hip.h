@@ -400,6 +400,13 @@ int mode_deconv3d_fwd_bn(const float* x, const float* w, const mode_bn_epilogue*
  * more than one output channel).  mode_conv3d_fwd_split takes an optional folded-BatchNorm epilogue (NULL: plain convolution);
  * wpack as mode_conv3d_fwd; mode_conv3d_bwd_weight_split: arguments and workspace as mode_conv3d_bwd_weight with stride 1. */
 int mode_conv3d_split_supported(int Ci, int Co, int stride, int which /* 0 forward, 1 input gradient, 2 weight gradient */);
+/* Host only, launches nothing.  1 exactly when mode_conv3d_split_supported(Ci, Co, stride, which) == 1 AND the volume is inside every
+ * 32-bit contract of the split kernel that the corresponding entry launches (descriptor sizes and lane offsets of its buffer loads,
+ * element offsets of its epilogue; even sizes / W % 8 where the stride-2 entries need them; csrc/size_contracts.h has the derivations).
+ * (Ci, Co, D, H, W, stride) describe the CONVOLUTION x (Ci, D, H, W) -> y (Co, D / stride, ...) whichever of its GEMMs `which` names; a
+ * transposed convolution (Cin, d, h, w) -> (Cout, 2d, 2h, 2w) asks (Cout, Cin, 2d, 2h, 2w, 2, 1).  Every split entry below refuses
+ * (MODE_ERR_UNSUPPORTED, before it looks at a pointer) exactly where this says 0: a caller falls back to the fp32 entries there. */
+int mode_conv3d_split_shape_supported(int Ci, int Co, int D, int H, int W, int stride, int which);
 /* Stride-2 forward (k3 p1) on the split-bf16 kernel (csrc/conv3d_split_s2.hip): hourglass conv1 / conv3 (mode_disparity.py:17-19) and
  * the input gradient of the transposed convolutions conv5 / conv6 (w = their (Cin, Cout, 27) weight read as (Co = Cin, Ci = Cout));
  * 33..64 output channels, input channels a multiple of 8: mode_conv3d_split_supported(Ci, Co, 2, 0) == 1.  bn: optional folded
@@ -483,6 +490,10 @@ int mode_conv3d_bwd_weight_split(const float* gy, const float* x, float* gw, flo
  * a multiple of 16, <= 512 output channels of the GEMM (one launch per block of 64); arguments and wpack as mode_conv2d_fwd / _bwd_data
  * (+ optional epilogue). */
 int mode_conv2d_split_supported(int Ci, int Co, int dilation, int which /* 0 forward, 1 input gradient */);
+/* Host only, launches nothing: the same for an H x W image -- the layer is supported (which 2, the weight gradient: any channel counts)
+ * AND the image is inside the 32-bit contracts of the split kernel of `which` (csrc/size_contracts.h).  The 3 x 3 weight gradient of a
+ * layer of up to 32 channels ends just below 2048 x 4096 pixels. */
+int mode_conv2d_split_shape_supported(int Ci, int Co, int H, int W, int dilation, int which /* 0, 1, 2 weight gradient */);
 int mode_conv2d_fwd_split(const float* x, const float* w, const mode_bn_epilogue* bn, float* y, float* wpack, int B, int Ci, int H, int W,
                           int Co, int dilation, mode_stream_t stream);
 int mode_conv2d_bwd_data_split(const float* gy, const float* w, float* gx, float* wpack, int B, int Ci, int H, int W, int Co, int dilation,

@@ -116,7 +116,7 @@ __device__ __forceinline__ float fold_shift(const mode_bn_epilogue& e, int o) { 
 // Buffer-addressed loads (a 128-bit descriptor in scalar registers + a 32-bit lane offset + a scalar offset): no 64-bit vector
 // address arithmetic per request, and a lane offset at or beyond `bytes` reads as ZERO -- the zero padding of a haloed tile costs one
 // select of the OFFSET per position instead of one select per loaded value.  The descriptor must be built from wave-uniform values.
-// kBufOOB is the offset of a lane that must read zero (bytes < 2^31 is the caller's contract).
+// kBufOOB is the offset of a lane that must read zero (bytes < 2^31 is the caller's contract: the predicates of size_contracts.h).
 constexpr unsigned kBufOOB = 0x80000000u;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);

@@ -261,6 +261,17 @@ extern "C" int mode_conv2d_split_supported(int Ci, int Co, int dilation, int whi
   return which == 1 ? mode::conv2d_split_supported(Co, Ci, dilation) : mode::conv2d_split_supported(Ci, Co, dilation);
 }
 
+// Host only, launches nothing: 1 exactly when the layer is supported (which 0 / 1: mode_conv2d_split_supported; the weight gradient,
+// which 2, takes any channel counts in masked 32 x 32 blocks) AND the image is inside every 32-bit contract of the kernel that the
+// corresponding split entry launches (size_contracts.h has the derivations).
+extern "C" int mode_conv2d_split_shape_supported(int Ci, int Co, int H, int W, int dilation, int which) {
+  if (Ci <= 0 || Co <= 0 || H <= 0 || W <= 0 || (dilation != 1 && dilation != 2)) return 0;
+  if (which == 2) return mode::conv2d_bww_split_fits(Ci, Co, H, W, dilation) ? 1 : 0;
+  if (which != 0 && which != 1) return 0;
+  if (mode_conv2d_split_supported(Ci, Co, dilation, which) != 1) return 0;
+  return mode::conv2d_split_fits(which == 1 ? Co : Ci, which == 1 ? Ci : Co, (long long)H * W) ? 1 : 0;
+}
+
 extern "C" int mode_conv2d_fwd_split(const float* x, const float* w, const mode_bn_epilogue* bn, float* y, float* wpack, int B, int Ci, int H,
                                      int W, int Co, int dilation, mode_stream_t stream) {
   if (bn) {

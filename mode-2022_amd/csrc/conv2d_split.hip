@@ -161,7 +161,7 @@ __global__ __launch_bounds__(NT) void conv2d_split_kernel(const float* __restric
   const int t_count = xcd < rr ? q + 1 : q;
   const int mine = slot < t_count ? (t_count - slot + nwx - 1) / nwx : 0;
   const int G = mine * d.NCHUNK;
-  const int HWi = d.H * d.W;  // (host guarantees max(K, Co) * H * W < 2^29)
+  const int HWi = d.H * d.W;  // (max(K, Co) * H * W < 2^29: mode::conv2d_split_fits)
 
   auto tile_of = [&](int k, int& b, int& h0, int& w0) {
     int t = t_begin + slot + k * nwx;
@@ -543,7 +543,7 @@ int conv2d_split_run(const float* x, const float* w, float* y, float* wpack, int
   MODE_REQUIRE(!acc_in || acc_in != y, MODE_ERR_BAD_ARG, "%s: acc must not be the output tensor", who);
   MODE_REQUIRE(conv2d_split_supported(K, rows, dilation), MODE_ERR_UNSUPPORTED,
                "%s: %d output / %d reduction channels, dilation %d not covered by the split kernel", who, rows, K, dilation);
-  MODE_REQUIRE((long long)std::max(K, rows) * H * W < (1ll << 29), MODE_ERR_UNSUPPORTED, "%s: a sample larger than 2^29 elements", who);
+  MODE_REQUIRE(conv2d_split_fits(K, rows, (long long)H * W), MODE_ERR_UNSUPPORTED, "%s: a sample larger than 2^29 elements", who);
   if (B == 0) return amax_y ? mode::absmax_begin(amax_y, st, who) : MODE_OK;
   MODE_REQUIRE(x && w && y && wpack, MODE_ERR_BAD_ARG, "%s: null pointer", who);
   S2Dims d;

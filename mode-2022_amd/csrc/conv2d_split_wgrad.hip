@@ -126,8 +126,9 @@ __global__ __launch_bounds__(NT) void conv2d_bww_split_kernel(const float* __res
   // beyond the layer's.  The requests are buffer loads (round 6, as in conv3d_split_wgrad.hip): an offset at or beyond the descriptor's
   // size reads as ZERO and a row outside the image takes the empty descriptor, so the zero padding needs no validity masks -- and +
   // compare + select per loaded value were 170 of a group's ~520 vector instructions beside 54 MFMAs.
-  // (markers: an invalid column / channel and an invalid row each contribute kHalfOOB = 2^30 -- above every valid offset, which the host
-  // keeps below 2^30 -- so that their sum cannot wrap back into the block: a 32-bit kBufOOB + kBufOOB would be 0)
+  // (markers: an invalid column / channel and an invalid row each contribute kHalfOOB = 2^30, so that their sum cannot wrap back into the
+  // block -- a 32-bit kBufOOB + kBufOOB would be 0.  The smallest marker sum is kHalfOOB + 4 * r0 * W with r0 = -DIL, the top halo: the
+  // entry keeps block_bytes below it, mode::conv2d_bww_split_fits)
   constexpr unsigned kHalfOOB = 0x40000000u;
   unsigned xo0[XIT], xo1[XIT], go0[GIT], go1[GIT];
   int xdst[XIT], gdst[GIT];
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(NT) void conv2d_bww_split_kernel(const float* __res
       go1[k] = (ook & (unsigned)(gw + 1 < d.W)) ? base + 4u : kHalfOOB;
     }
   };
-  const unsigned block_bytes = 128u * (unsigned)HWi;  // 32 channel planes of an image (the host guarantees < 2^30)
+  const unsigned block_bytes = 128u * (unsigned)HWi;  // 32 channel planes of an image (< 2^30 - 4 * DIL * W: mode::conv2d_bww_split_fits)
   // x rows [r0, r0 + 4) of the image into ring slots (slot0 + row) % RING; gy rows [r0, r0 + 4) into buffer `buf`
   auto load_x = [&](int k, int r0) {
     const __amdgpu_buffer_rsrc_t rs = buf_rsrc(xb, block_bytes);

@@ -301,7 +301,9 @@ static int conv2d_bwd_weight_split(const char* who, const float* gy, const float
                                    float* workspace, int B, int Ci, int H, int W, int Co, int dilation, int accumulate, mode_stream_t stream) {
   MODE_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && H > 0 && W > 0, MODE_ERR_BAD_ARG, "%s: non-positive size", who);
   MODE_REQUIRE(dilation == 1 || dilation == 2, MODE_ERR_UNSUPPORTED, "%s: dilation %d not implemented (1 or 2)", who, dilation);
-  MODE_REQUIRE((long long)std::max(Ci, Co) * H * W < (1ll << 29), MODE_ERR_UNSUPPORTED, "%s: a sample larger than 2^29 elements", who);
+  MODE_REQUIRE(mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 2) == 1, MODE_ERR_UNSUPPORTED,
+               "%s: %dx%d at %d -> %d channels is beyond the 32-bit offsets of the split kernel (mode_conv2d_split_shape_supported)", who, H, W, Ci,
+               Co);
   hipStream_t st = mode::as_stream(stream);
   if (B == 0) {
     if (!accumulate) return mode::zero_floats(gw, (size_t)Co * Ci * 9, st, "mode_conv2d_bwd_weight");

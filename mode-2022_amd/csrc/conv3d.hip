@@ -552,12 +552,47 @@ int deconv3d(const float* x, const float* w, float* y, float* wpack, int B, int 
   return mode::check_launch(who);
 }
 
-int check_conv_args(const void* a, const void* b, const void* c, const void* wp, int B, int Ci, int D, int H, int W, int Co,
-                    int stride, const char* who, bool allow_s2 = false) {
+int check_conv_sizes(int B, int Ci, int D, int H, int W, int Co, int stride, const char* who, bool allow_s2) {
   MODE_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0, MODE_ERR_BAD_ARG, "%s: non-positive size", who);
   MODE_REQUIRE(stride == 1 || (stride == 2 && allow_s2), MODE_ERR_UNSUPPORTED, "%s: stride %d not implemented", who, stride);
   MODE_REQUIRE((long long)std::max(Ci, 8) * D * H * W < (1ll << 31) && (long long)std::max(Co, 8) * D * H * W < (1ll << 31),
                MODE_ERR_UNSUPPORTED, "%s: a sample larger than 2^31 elements", who);
+  return MODE_OK;
+}
+
+int check_conv_args(const void* a, const void* b, const void* c, const void* wp, int B, int Ci, int D, int H, int W, int Co,
+                    int stride, const char* who, bool allow_s2 = false) {
+  int rc = check_conv_sizes(B, Ci, D, H, W, Co, stride, who, allow_s2);
+  if (rc != MODE_OK || B == 0) return rc;
+  MODE_REQUIRE(a && b && c && wp, MODE_ERR_BAD_ARG, "%s: null pointer", who);
+  return MODE_OK;
+}
+
+// The same for an entry of the split kernels: sizes first, then the layer and the 32-bit contracts of the kernel the entry launches
+// (mode_conv3d_split_shape_supported of the CONVOLUTION (Ci, Co, D, H, W, stride) whose forward / input gradient / weight gradient
+// `which` the call is -- size_contracts.h), pointers last: a shape beyond a limit is MODE_ERR_UNSUPPORTED whatever the pointers are.
+int check_split_args(const void* a, const void* b, const void* c, const void* wp, int B, int Ci, int D, int H, int W, int Co, int stride,
+                     int which, const char* who) {
+  int rc = check_conv_sizes(B, Ci, D, H, W, Co, stride, who, true);
+  if (rc != MODE_OK) return rc;
+  MODE_REQUIRE(mode_conv3d_split_shape_supported(Ci, Co, D, H, W, stride, which) == 1, MODE_ERR_UNSUPPORTED,
+               "%s: %d -> %d channels at %dx%dx%d, stride %d: not covered by the split kernel, or beyond its 32-bit offsets "
+               "(mode_conv3d_split_shape_supported)", who, Ci, Co, D, H, W, stride);
+  if (B == 0) return MODE_OK;
+  MODE_REQUIRE(a && b && c && wp, MODE_ERR_BAD_ARG, "%s: null pointer", who);
+  return MODE_OK;
+}
+
+// ... and for the transposed convolution x (Cin, D, H, W) -> (Cout, 2D, 2H, 2W): the input gradient of the stride-2 convolution
+// Cout -> Cin over the doubled volume
+int check_deconv_split_args(const void* a, const void* b, const void* c, const void* wp, int B, int Cin, int D, int H, int W, int Cout,
+                            const char* who) {
+  int rc = check_conv_sizes(B, Cin, D, H, W, Cout, 1, who, false);
+  if (rc != MODE_OK) return rc;
+  MODE_REQUIRE(D < (1 << 30) && H < (1 << 30) && W < (1 << 30) &&
+                   mode_conv3d_split_shape_supported(Cout, Cin, 2 * D, 2 * H, 2 * W, 2, 1) == 1,
+               MODE_ERR_UNSUPPORTED, "%s: %d -> %d channels at %dx%dx%d: not covered by the split kernel, or beyond its 32-bit offsets "
+               "(mode_conv3d_split_shape_supported)", who, Cin, Cout, D, H, W);
   if (B == 0) return MODE_OK;
   MODE_REQUIRE(a && b && c && wp, MODE_ERR_BAD_ARG, "%s: null pointer", who);
   return MODE_OK;
@@ -589,10 +624,28 @@ extern "C" int mode_conv3d_split_supported(int Ci, int Co, int stride, int which
   return which == 1 ? mode::conv3d_split_supported(Co, Ci) : mode::conv3d_split_supported(Ci, Co);
 }
 
+// Host only, launches nothing: 1 exactly when the layer's channel counts are supported (mode_conv3d_split_supported) AND the volume is
+// inside every 32-bit contract of the kernel that the corresponding split entry launches (size_contracts.h has the derivations).
+// (Ci, Co, D, H, W, stride) describe the CONVOLUTION -- x (Ci, D, H, W) -> y (Co, D / stride, ...) -- whichever of its three GEMMs
+// `which` asks for; a transposed convolution x (Cin, d, h, w) -> (Cout, 2d, 2h, 2w) is the input gradient (which 1) of the stride-2
+// convolution (Ci = Cout, Co = Cin, 2d, 2h, 2w).
+extern "C" int mode_conv3d_split_shape_supported(int Ci, int Co, int D, int H, int W, int stride, int which) {
+  if (D <= 0 || H <= 0 || W <= 0 || which < 0 || which > 2) return 0;
+  if (mode_conv3d_split_supported(Ci, Co, stride, which) != 1) return 0;
+  const long long DHW = (long long)D * H * W;
+  if (stride == 1) {
+    if (which == 2) return mode::conv3d_bww_split_fits(Ci, Co, DHW) ? 1 : 0;
+    return mode::conv3d_s1_split_fits(which == 1 ? Ci : Co, DHW) ? 1 : 0;
+  }
+  if (which == 0) return mode::conv3d_s2_split_fits(DHW) ? 1 : 0;
+  if (which == 2) return (D % 2 == 0 && H % 2 == 0 && W % 8 == 0 && mode::conv3d_bww_s2_split_fits(Ci, Co, D, H, W)) ? 1 : 0;
+  return (D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && mode::deconv3d_split_fits(Ci, DHW / 8)) ? 1 : 0;  // (gy at half the volume -> gx)
+}
+
 extern "C" int mode_conv3d_fwd_split(const float* x, const float* w, const mode_bn_epilogue* bn, float* y, float* wpack, int B, int Ci,
                                      int D, int H, int W, int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_fwd_split";
-  int rc = check_conv_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, who);
+  int rc = check_split_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, 0, who);
   if (rc == MODE_OK && bn) rc = mode::check_bn(bn, who);
   if (rc != MODE_OK || B == 0) return rc;
   return mode::conv3d_s1_split(x, w, y, wpack, B, Ci, Co, D, H, W, 0, mode::as_stream(stream), who, bn);
@@ -606,7 +659,7 @@ extern "C" int mode_conv3d_fwd_split_stats_partials(void) { return mode::conv3d_
 extern "C" int mode_conv3d_fwd_split_stats(const float* x, const float* w, float* y, float* wpack, float* stats, int B, int Ci, int D, int H,
                                            int W, int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_fwd_split_stats";
-  int rc = check_conv_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, who);
+  int rc = check_split_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, 0, who);
   if (rc != MODE_OK) return rc;
   MODE_REQUIRE(stats, MODE_ERR_WORKSPACE, "%s: statistics workspace required", who);
   MODE_REQUIRE(B > 0, MODE_ERR_BAD_ARG, "%s: empty batch has no statistics", who);
@@ -618,7 +671,7 @@ extern "C" int mode_conv3d_fwd_split_stats(const float* x, const float* w, float
 extern "C" int mode_conv3d_fwd_s2_split_amax(const float* x, const float* w, const mode_bn_epilogue* bn, float* y, float* out_absmax, float* wpack,
                                              int B, int Ci, int D, int H, int W, int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_fwd_s2_split";
-  int rc = check_conv_args(x, w, y, wpack, B, Ci, D, H, W, Co, 2, who, true);
+  int rc = check_split_args(x, w, y, wpack, B, Ci, D, H, W, Co, 2, 0, who);
   if (rc == MODE_OK && bn) rc = mode::check_bn(bn, who);
   if (rc != MODE_OK) return rc;
   MODE_REQUIRE(!out_absmax || bn, MODE_ERR_BAD_ARG, "%s: the output maximum comes out of the eval epilogue (bn is NULL)", who);
@@ -636,9 +689,8 @@ extern "C" int mode_conv3d_fwd_s2_split(const float* x, const float* w, const mo
 extern "C" int mode_conv3d_bwd_data_s2_split(const float* gy, const float* w, float* gx, float* wpack, int B, int Ci, int D, int H, int W,
                                              int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_bwd_data_s2_split";
-  int rc = check_conv_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, 2, who, true);
+  int rc = check_split_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, 2, 1, who);  // (even D, H, W among the rest)
   if (rc != MODE_OK || B == 0) return rc;
-  MODE_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, MODE_ERR_UNSUPPORTED, "%s: stride 2 needs even input sizes (got %dx%dx%d)", who, D, H, W);
   return mode::deconv3d_split(gy, w, gx, wpack, B, Co, Ci, D / 2, H / 2, W / 2, mode::as_stream(stream), who);
 }
 
@@ -655,7 +707,7 @@ extern "C" int mode_abs_max_batch(const float* const* device_ptrs, const long lo
 extern "C" int mode_conv3d_fwd_split_f16(const float* x, const float* w, const float* amax_x, const float* amax_w, float* y, float* wpack, int B,
                                          int Ci, int D, int H, int W, int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_fwd_split_f16";
-  int rc = check_conv_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, who);
+  int rc = check_split_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, 0, who);
   if (rc != MODE_OK || B == 0) return rc;
   MODE_REQUIRE(amax_x && amax_w, MODE_ERR_BAD_ARG, "%s: null operand maximum", who);
   return mode::conv3d_s1_split(x, w, y, wpack, B, Ci, Co, D, H, W, 0, mode::as_stream(stream), who, nullptr, nullptr, nullptr, amax_x, amax_w);
@@ -666,7 +718,7 @@ extern "C" int mode_conv3d_fwd_split_f16(const float* x, const float* w, const f
 extern "C" int mode_conv3d_fwd_split_f16_bn(const float* x, const float* w, const float* amax_x, const mode_bn_epilogue* bn, float* y,
                                             float* amax_y, float* wpack, int B, int Ci, int D, int H, int W, int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_fwd_split_f16_bn";
-  int rc = check_conv_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, who);
+  int rc = check_split_args(x, w, y, wpack, B, Ci, D, H, W, Co, 1, 0, who);
   if (rc == MODE_OK) {
     MODE_REQUIRE(bn, MODE_ERR_BAD_ARG, "%s: null BatchNorm epilogue", who);
     rc = mode::check_bn(bn, who);
@@ -681,7 +733,7 @@ extern "C" int mode_conv3d_fwd_split_f16_bn(const float* x, const float* w, cons
 extern "C" int mode_conv3d_bwd_data_split_f16(const float* gy, const float* w, const float* amax_g, const float* amax_w, const float* acc, float* gx,
                                               float* wpack, int B, int Ci, int D, int H, int W, int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_bwd_data_split_f16";
-  int rc = check_conv_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, 1, who);
+  int rc = check_split_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, 1, 1, who);
   if (rc != MODE_OK || B == 0) return rc;
   MODE_REQUIRE(amax_g && amax_w && acc != gx, MODE_ERR_BAD_ARG, "%s: null operand maximum, or acc is the output tensor", who);
   return mode::conv3d_s1_split(gy, w, gx, wpack, B, Co, Ci, D, H, W, 1, mode::as_stream(stream), who, nullptr, nullptr, acc, amax_g, amax_w);
@@ -697,12 +749,11 @@ extern "C" int mode_conv3d_bwd_data_split_acc_supported(int Ci, int Co, int stri
 extern "C" int mode_conv3d_bwd_data_split_acc(const float* gy, const float* w, const float* acc, float* gx, float* wpack, int B, int Ci, int D,
                                               int H, int W, int Co, int stride, mode_stream_t stream) {
   const char* who = "mode_conv3d_bwd_data_split_acc";
-  int rc = check_conv_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, stride, who, stride == 2);
+  MODE_REQUIRE(stride == 1 || stride == 2, MODE_ERR_UNSUPPORTED, "%s: stride %d not implemented", who, stride);
+  int rc = check_split_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, stride, 1, who);  // (stride 2: even D, H, W among the rest)
   if (rc != MODE_OK || B == 0) return rc;
   MODE_REQUIRE(acc && acc != gx, MODE_ERR_BAD_ARG, "%s: acc must be a tensor of gx's shape that is not gx", who);
   if (stride == 1) return mode::conv3d_s1_split(gy, w, gx, wpack, B, Co, Ci, D, H, W, 1, mode::as_stream(stream), who, nullptr, nullptr, acc);
-  MODE_REQUIRE(stride == 2 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0, MODE_ERR_UNSUPPORTED, "%s: stride 1, or stride 2 with even input sizes (got stride %d, %dx%dx%d)",
-               who, stride, D, H, W);
   return mode::deconv3d_split(gy, w, gx, wpack, B, Co, Ci, D / 2, H / 2, W / 2, mode::as_stream(stream), who, nullptr, acc);
 }
 
@@ -712,7 +763,7 @@ extern "C" int mode_deconv3d_split_supported(int Cin, int Cout) { return mode::d
 extern "C" int mode_deconv3d_fwd_split(const float* x, const float* w, float* y, float* wpack, int B, int Cin, int D, int H, int W, int Cout,
                                        mode_stream_t stream) {
   const char* who = "mode_deconv3d_fwd_split";
-  int rc = check_conv_args(x, w, y, wpack, B, Cin, D, H, W, Cout, 1, who);
+  int rc = check_deconv_split_args(x, w, y, wpack, B, Cin, D, H, W, Cout, who);
   if (rc != MODE_OK || B == 0) return rc;
   return mode::deconv3d_split(x, w, y, wpack, B, Cin, Cout, D, H, W, mode::as_stream(stream), who);
 }
@@ -722,7 +773,7 @@ extern "C" int mode_deconv3d_split_bn_supported(int Cin, int Cout) { return mode
 extern "C" int mode_deconv3d_fwd_split_bn_amax(const float* x, const float* w, const mode_bn_epilogue* bn, float* y, float* out_absmax,
                                                float* wpack, int B, int Cin, int D, int H, int W, int Cout, mode_stream_t stream) {
   const char* who = "mode_deconv3d_fwd_split_bn";
-  int rc = check_conv_args(x, w, y, wpack, B, Cin, D, H, W, Cout, 1, who);
+  int rc = check_deconv_split_args(x, w, y, wpack, B, Cin, D, H, W, Cout, who);
   if (rc == MODE_OK) rc = mode::check_bn(bn, who);
   if (rc != MODE_OK) return rc;
   if (B == 0) return out_absmax ? mode::absmax_begin(out_absmax, mode::as_stream(stream), who) : MODE_OK;
@@ -737,7 +788,7 @@ extern "C" int mode_deconv3d_fwd_split_bn(const float* x, const float* w, const 
 extern "C" int mode_conv3d_bwd_data_split(const float* gy, const float* w, float* gx, float* wpack, int B, int Ci, int D, int H, int W,
                                           int Co, mode_stream_t stream) {
   const char* who = "mode_conv3d_bwd_data_split";
-  int rc = check_conv_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, 1, who);
+  int rc = check_split_args(gy, w, gx, wpack, B, Ci, D, H, W, Co, 1, 1, who);
   if (rc != MODE_OK || B == 0) return rc;
   return mode::conv3d_s1_split(gy, w, gx, wpack, B, Co, Ci, D, H, W, 1, mode::as_stream(stream), who, nullptr);
 }
@@ -1420,10 +1471,8 @@ extern "C" int mode_conv3d_bwd_weight_split_f16(const float* gy, const float* x,
 
 static int bwd_weight_split(const float* gy, const float* x, const float* amax_g, const float* amax_x, float* gw, float* workspace, int B, int Ci,
                             int D, int H, int W, int Co, int accumulate, mode_stream_t stream, const char* who) {
-  int rc = check_conv_args(gy, x, gw, workspace, B, Ci, D, H, W, Co, 1, who);
+  int rc = check_split_args(gy, x, gw, workspace, B, Ci, D, H, W, Co, 1, 2, who);
   if (rc != MODE_OK) return rc;
-  MODE_REQUIRE(mode_conv3d_split_supported(Ci, Co, 1, 2) == 1 && (long long)std::max(Ci, Co) * D * H * W < (1ll << 29), MODE_ERR_UNSUPPORTED,
-               "%s: layer not covered by the split kernels (single output channel, or a sample beyond 2^29 elements)", who);
   hipStream_t st = mode::as_stream(stream);
   if (B == 0) {
     if (!accumulate) return mode::zero_floats(gw, (size_t)Co * Ci * 27, st, "mode_conv3d_bwd_weight");
@@ -1455,14 +1504,8 @@ static int bwd_weight_split(const float* gy, const float* x, const float* amax_g
 extern "C" int mode_conv3d_bwd_weight_s2_split(const float* gy, const float* x, float* gw, float* workspace, int B, int Ci, int D, int H,
                                                int W, int Co, int accumulate, mode_stream_t stream) {
   const char* who = "mode_conv3d_bwd_weight_s2_split";
-  int rc = check_conv_args(gy, x, gw, workspace, B, Ci, D, H, W, Co, 2, who, true);
+  int rc = check_split_args(gy, x, gw, workspace, B, Ci, D, H, W, Co, 2, 2, who);  // (even D, H and W a multiple of 8 among the rest)
   if (rc != MODE_OK) return rc;
-  MODE_REQUIRE(mode_conv3d_split_supported(Ci, Co, 2, 2) == 1, MODE_ERR_UNSUPPORTED, "%s: %d -> %d channels are not covered by the split kernel",
-               who, Ci, Co);
-  MODE_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 8 == 0, MODE_ERR_UNSUPPORTED, "%s: needs even D, H and W a multiple of 8 (got %dx%dx%d)", who,
-               D, H, W);
-  MODE_REQUIRE(std::max((long long)std::min(Ci, 32) * D * H * W, (long long)std::min(Co, 64) * (D / 2) * (H / 2) * (W / 2)) < (1ll << 29),
-               MODE_ERR_UNSUPPORTED, "%s: a channel block of one sample exceeds 2^29 elements", who);
   hipStream_t st = mode::as_stream(stream);
   if (B == 0) {
     if (!accumulate) return mode::zero_floats(gw, (size_t)Co * Ci * 27, st, "mode_conv3d_bwd_weight");

@@ -1,6 +1,7 @@
 // Internal (non-ABI) entry points shared between the conv3d translation units.
 #pragma once
 #include "common.h"
+#include "size_contracts.h"
 
 namespace mode {
 

@@ -310,7 +310,7 @@ __global__ __launch_bounds__(NT) void conv3d_split_kernel(const float* __restric
     st_d0 = sd * TD;
     st_h0 = sh * TH;
     st_w0 = sw * 32;
-    st_rs = buf_rsrc(x + ((long long)sb * d.K + s_ch * 8) * DHW, (unsigned)DHW * 32u);
+    st_rs = buf_rsrc(x + ((long long)sb * d.K + s_ch * 8) * DHW, (unsigned)DHW * 32u);  // (< 2^31: mode::conv3d_s1_split_fits)
     st_base = (st_d0 - 1) * (int)HW + (st_h0 - 1) * d.W + (st_w0 - 1);
   };
   auto stage_load = [&](int k) {  // the 8 channel values of position k
@@ -767,7 +767,8 @@ int conv3d_s1_split(const float* x, const float* w, float* y, float* wpack, int 
   d.NCHUNK = cdiv(K, 8);
   MODE_REQUIRE(conv3d_split_supported(K, rows), MODE_ERR_UNSUPPORTED, "%s: %d output / %d reduction channels not supported by the split kernel", who,
                rows, K);
-  MODE_REQUIRE((long long)rows * D * H * W < (1ll << 31), MODE_ERR_UNSUPPORTED, "%s: a sample of the output has 2^31 elements or more", who);
+  MODE_REQUIRE(conv3d_s1_split_fits(rows, (long long)D * H * W), MODE_ERR_UNSUPPORTED,
+               "%s: volume beyond the 32-bit offsets of the split kernel (8 planes of 2^31 bytes or more, or an output sample of 2^31 elements)", who);
   // The 16-row tile: the plain-store fp16 instantiation (and the eval epilogue without a residual), where the rows divide and the 8-row tiling has at least four rounds of
   // tiles per output block (half as many tiles: fewer would leave CUs without one)
   static const char* tall_env = getenv("MODE_SPLIT_TALL");  // (tuning override: 0 keeps the 8-row tile everywhere)

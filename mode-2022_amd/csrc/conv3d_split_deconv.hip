@@ -466,7 +466,7 @@ int deconv3d_split(const float* x, const float* w, float* y, float* wpack, int B
   MODE_REQUIRE(deconv3d_split_supported(K, Co), MODE_ERR_UNSUPPORTED, "%s: %d output / %d input channels not supported by the split kernel", who, Co, K);
   MODE_REQUIRE(!(bn || acc_in) || deconv3d_split_bn_supported(K, Co), MODE_ERR_UNSUPPORTED,
                "%s: the epilogue forms need whole 32-channel output tiles, got %d", who, Co);
-  MODE_REQUIRE((long long)D * H * W * 8 * std::max(Co, 8) < (1ll << 31) && (long long)D * H * W < (1ll << 27), MODE_ERR_UNSUPPORTED,
+  MODE_REQUIRE(deconv3d_split_fits(Co, (long long)D * H * W), MODE_ERR_UNSUPPORTED,
                "%s: volume beyond the 32-bit offsets of the split kernel", who);
   DcDims d;
   d.B = B; d.K = K; d.Co = Co; d.D = D; d.H = H; d.W = W;

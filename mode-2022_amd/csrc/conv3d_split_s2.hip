@@ -423,7 +423,7 @@ int conv3d_s2_split(const float* x, const float* w, float* y, float* wpack, int 
   MODE_REQUIRE(!amax_y || bn, MODE_ERR_BAD_ARG, "%s: the output maximum belongs to the eval epilogue", who);
   MODE_REQUIRE(conv3d_s2_split_supported(K, rows), MODE_ERR_UNSUPPORTED, "%s: %d output / %d reduction channels not supported by the stride-2 split kernel",
                who, rows, K);
-  MODE_REQUIRE((long long)D * H * W < (1ll << 26), MODE_ERR_UNSUPPORTED, "%s: volume beyond the 32-bit lane offsets of the split kernel", who);  // (8 planes < 2^31 bytes)
+  MODE_REQUIRE(conv3d_s2_split_fits((long long)D * H * W), MODE_ERR_UNSUPPORTED, "%s: volume beyond the 32-bit lane offsets of the split kernel", who);  // (8 planes < 2^31 bytes)
   S2Dims d;
   d.B = B; d.K = K; d.Co = rows; d.D = D; d.H = H; d.W = W;
   d.Do = (D - 1) / 2 + 1; d.Ho = (H - 1) / 2 + 1; d.Wo = (W - 1) / 2 + 1;

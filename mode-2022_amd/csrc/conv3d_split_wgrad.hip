@@ -102,7 +102,7 @@ __global__ __launch_bounds__(NT) void conv3d_bww_split_kernel(const float* __res
   uint16_t* gl = lds + XALL;   // [2 buffers][32 o][3 pieces][2 rows][32]
   const int s = blockIdx.x, ob = blockIdx.y, cb = blockIdx.z;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5;
-  const int HWi = d.H * d.W, DHWi = d.D * HWi;  // (host guarantees 32-bit element offsets within a sample)
+  const int HWi = d.H * d.W, DHWi = d.D * HWi;  // (32-bit element offsets within a sample: mode::conv3d_bww_split_fits)
 
   // taps of this wave: slots 0..2 = group wave, 3..5 = group wave + 4 (kw = slot % 3), slot 6 = tap 24 + wave (wave 3: tap 26 again,
   // dropped)
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(NT) void conv3d_bww_split_kernel(const float* __res
       go1[k] = (rowok & (unsigned)(gw + 1 < d.W)) ? base + 4u : kBufOOB;
     }
   };
-  const unsigned block_bytes = 128u * (unsigned)DHWi;  // 32 channels of a sample (the host guarantees < 2^31)
+  const unsigned block_bytes = 128u * (unsigned)DHWi;  // 32 channels of a sample (< 2^31: mode::conv3d_bww_split_fits, asked by the entry)
   // loads of x plane z and of the gy rows of depth z: unconditional; a plane outside the volume reads through an EMPTY descriptor
   const float* xb = x;
   const float* gb = gy;

@@ -144,9 +144,12 @@ def conv2d_bwd_weight(gy, x, dilation=1, into=None):
   with torch.cuda.device_of(x), profiling.region('conv2d_bwd_weight[%d->%d d%d %dx%d]' % (Ci, Co, dilation, H, W) if profiling.ENABLED
                                                  else 'conv2d_bwd_weight', nbytes, flops, x.device):
     ws = torch.empty(max(lib().mode_conv2d_bwd_weight_workspace_bytes(B, Ci, H, W, Co) // 4, 1), dtype=torch.float32, device=x.device)
-    entry = 'mode_conv2d_bwd_weight_split' if CONV_ARITH == 'bf16x6' else 'mode_conv2d_bwd_weight'  # (any channel counts: masked blocks)
+    # (any channel counts: masked blocks; an image beyond the split kernel's 32-bit offsets -- 2048 x 4096 at up to 32 channels is the
+    # first -- runs on the fp32 kernel)
+    split = CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 2) == 1
+    entry = 'mode_conv2d_bwd_weight_split' if split else 'mode_conv2d_bwd_weight'
     am = ()
-    if _conv2d_f16(True):  # (a weight gradient is a training step: the two-piece fp16 arithmetic)
+    if split and _conv2d_f16(True):  # (a weight gradient is a training step: the two-piece fp16 arithmetic)
       entry, am = entry + '_f16', (ptr(_tagged_abs_max(gy)), ptr(_tagged_abs_max(x)))
     check(getattr(lib(), entry)(ptr(gy), ptr(x), *am, ptr(gw), ptr(ws), B, Ci, H, W, Co, dilation, 1 if into is not None else 0, stream_of(x)),
           entry)
@@ -169,9 +172,14 @@ def _conv2d_own(x, w):
           max(co, ci) * x.shape[2] * x.shape[3] < 2**29)
 
 
-def conv2d_wgrad_supported(x, w):
-  """mode_conv2d_bwd_weight addresses a sample with 32-bit lane offsets (csrc/conv2d_wgrad.hip: max(Ci, Co) * H * W < 2^29)."""
-  return max(w.shape[0], w.shape[1]) * x.shape[2] * x.shape[3] < 2**29
+def conv2d_wgrad_supported(x, w, dilation=1):
+  """Whether conv2d_bwd_weight has a kernel that is right at this size: the split kernel inside its 32-bit contracts
+  (mode_conv2d_split_shape_supported, which 2), else the fp32 kernel, which addresses a sample with 32-bit lane offsets
+  (csrc/conv2d_wgrad.hip: max(Ci, Co) * H * W < 2^29)."""
+  co, ci, H, W = int(w.shape[0]), int(w.shape[1]), int(x.shape[2]), int(x.shape[3])
+  if CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(ci, co, H, W, dilation, 2) == 1:
+    return True
+  return max(co, ci) * H * W < 2**29
 
 
 CONV2D_F16 = True  # forward and input gradient of the 3 x 3 layers of a TRAINING step on two fp16 pieces / three MFMAs per product (DESIGN 3v)
@@ -193,7 +201,7 @@ def _conv2d_run(entry, name, src, w, out_channels, dilation, f16=False, w_amax=N
                                                    nbytes, flops, src.device):
     wp = torch.empty(lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, dtype=torch.float32, device=src.device)
     which = int(entry == 'mode_conv2d_bwd_data')
-    if CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_supported(Ci, Co, dilation, which) == 1:
+    if CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, which) == 1:
       if _conv2d_f16(f16):
         aw = _weight_abs_max(w, w_amax)
         if amax_out is not None:
@@ -232,7 +240,8 @@ def conv2d_bwd_data(gy, w, dilation=1, acc=None, f16=True, w_amax=None):
   require_f32c(gy, w, acc)
   B, _, H, W = gy.shape
   Co, Ci = w.shape[:2]
-  if not (CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_supported(Ci, Co, dilation, 1) == 1 and tuple(acc.shape) == (B, Ci, H, W)):
+  if not (CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 1) == 1 and
+          tuple(acc.shape) == (B, Ci, H, W)):
     return _conv2d_run('mode_conv2d_bwd_data', 'conv2d_bwd_data', gy, w, Ci, dilation, f16, w_amax=w_amax).add_(acc)
   gx = torch.empty((B, Ci, H, W), dtype=gy.dtype, device=gy.device)
   with torch.cuda.device_of(gy), profiling.region('conv2d_bwd_data[%d->%d d%d %dx%d]' % (Ci, Co, dilation, H, W) if profiling.ENABLED else 'conv2d_bwd_data',
@@ -1363,15 +1372,21 @@ def set_conv_arith(kind):
   CONV_ARITH = kind
 
 
-def _split3d(ci, co, stride, which):
-  """which: 0 forward, 1 input gradient, 2 weight gradient."""
-  return CONV_ARITH == 'bf16x6' and lib().mode_conv3d_split_supported(ci, co, stride, int(which)) == 1
+def _split3d(ci, co, stride, which, vol=None):
+  """which: 0 forward, 1 input gradient, 2 weight gradient.  vol = (D, H, W) of the convolution's input: the layer runs on the split
+  kernel AT THIS SIZE (mode_conv3d_split_shape_supported: the channel counts and every 32-bit contract of the kernel, csrc/size_contracts.h;
+  a volume beyond them runs on the fp32 kernel instead of failing).  Without vol: the channel counts alone."""
+  if CONV_ARITH != 'bf16x6':
+    return False
+  if vol is None:
+    return lib().mode_conv3d_split_supported(ci, co, stride, int(which)) == 1
+  return lib().mode_conv3d_split_shape_supported(ci, co, int(vol[0]), int(vol[1]), int(vol[2]), stride, int(which)) == 1
 
 
-def _deconv_split_fits(lowres_voxels, cout):
-  """The 32-bit offset limits of deconv3d_split (csrc/conv3d_split_deconv.hip: MODE_REQUIRE in deconv3d_split), in the voxels of its
-  LOW-resolution input and the channels of its output; volumes beyond them run on the fp32 kernel instead of failing."""
-  return lowres_voxels * 8 * max(cout, 8) < 2**31 and lowres_voxels < 2**27
+def _deconv_split3d(cin, cout, vol):
+  """The transposed convolution (cin, D, H, W) -> (cout, 2D, 2H, 2W) on the split kernel: it is the input gradient of the stride-2
+  convolution cout -> cin over the doubled volume."""
+  return _split3d(cout, cin, 2, 1, (2 * vol[0], 2 * vol[1], 2 * vol[2]))
 
 
 def _out3(n, stride):
@@ -1412,9 +1427,10 @@ def abs_max_value(buf):
   return float(buf.max())
 
 
-def conv3d_s1_f16(ci, co, which):
-  """True when the stride-1 layer ci -> co runs its forward (which 0) / input gradient (1) / weight gradient (2) on the fp16 arithmetic."""
-  return CONV3D_S1_F16 and _split3d(ci, co, 1, which)
+def conv3d_s1_f16(ci, co, which, vol=None):
+  """True when the stride-1 layer ci -> co runs its forward (which 0) / input gradient (1) / weight gradient (2) on the fp16 arithmetic
+  (vol = (D, H, W): at this size)."""
+  return CONV3D_S1_F16 and _split3d(ci, co, 1, which, vol)
 
 
 def conv3d_fwd(x, w, stride=1, amax=None):
@@ -1432,14 +1448,15 @@ def conv3d_fwd(x, w, stride=1, amax=None):
   with torch.cuda.device_of(x), profiling.region(_tag3('conv3d_fwd', Ci, Co, stride, D, H, W), 4 * (x.numel() + y.numel() + w.numel()),
                                                  flops, x.device):
     wp = _wpack3d(Ci, Co, x.device)
-    if _split3d(Ci, Co, stride, False) and stride == 2 and D * H * W < 2**26:
+    split = _split3d(Ci, Co, stride, 0, (D, H, W))
+    if split and stride == 2:
       check(lib().mode_conv3d_fwd_s2_split(ptr(x), ptr(w), None, ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)),
             'mode_conv3d_fwd_s2_split')
-    elif _split3d(Ci, Co, stride, False) and stride == 1 and CONV3D_S1_F16:
+    elif split and stride == 1 and CONV3D_S1_F16:
       ax, aw = amax if amax is not None else (abs_max(x), abs_max(w))
       check(lib().mode_conv3d_fwd_split_f16(ptr(x), ptr(w), ptr(ax), ptr(aw), ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)),
             'mode_conv3d_fwd_split_f16')
-    elif _split3d(Ci, Co, stride, False) and stride == 1:
+    elif split and stride == 1:
       check(lib().mode_conv3d_fwd_split(ptr(x), ptr(w), None, ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)), 'mode_conv3d_fwd_split')
     else:
       check(lib().mode_conv3d_fwd(ptr(x), ptr(w), ptr(y), ptr(wp), B, Ci, D, H, W, Co, stride, stream_of(x)), 'mode_conv3d_fwd')
@@ -1458,8 +1475,7 @@ def conv3d_bwd_data(gy, w, in_shape, stride=1, acc=None, amax=None):
   flops = 2 * gy.numel() * Ci * 27
   if acc is not None:
     acc = acc.contiguous()
-    s2_ok = stride == 2 and D % 2 == 0 and H % 2 == 0 and W % 2 == 0 and _deconv_split_fits(D * H * W // 8, Ci)
-    if (tuple(acc.shape) == tuple(gx.shape) and acc.dtype == gx.dtype and CONV_ARITH == 'bf16x6' and (stride == 1 or s2_ok) and
+    if (tuple(acc.shape) == tuple(gx.shape) and acc.dtype == gx.dtype and _split3d(Ci, Co, stride, 1, (D, H, W)) and
         lib().mode_conv3d_bwd_data_split_acc_supported(Ci, Co, stride) == 1):
       with torch.cuda.device_of(gy), profiling.region(_tag3('conv3d_bwd_data', Ci, Co, stride, D, H, W),
                                                       4 * (2 * gx.numel() + gy.numel() + w.numel()), flops, gy.device):
@@ -1476,14 +1492,15 @@ def conv3d_bwd_data(gy, w, in_shape, stride=1, acc=None, amax=None):
   with torch.cuda.device_of(gy), profiling.region(_tag3('conv3d_bwd_data', Ci, Co, stride, D, H, W),
                                                   4 * (gx.numel() + gy.numel() + w.numel()), flops, gy.device):
     wp = _wpack3d(Ci, Co, gy.device)
-    if stride == 2 and _split3d(Ci, Co, stride, True) and D % 2 == 0 and H % 2 == 0 and W % 2 == 0 and _deconv_split_fits(D * H * W // 8, Ci):
+    split = _split3d(Ci, Co, stride, 1, (D, H, W))
+    if stride == 2 and split:
       check(lib().mode_conv3d_bwd_data_s2_split(ptr(gy), ptr(w), ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stream_of(gy)),
             'mode_conv3d_bwd_data_s2_split')
-    elif stride == 1 and _split3d(Ci, Co, stride, True) and CONV3D_S1_F16:
+    elif stride == 1 and split and CONV3D_S1_F16:
       ag, aw = amax if amax is not None else (abs_max(gy), abs_max(w))
       check(lib().mode_conv3d_bwd_data_split_f16(ptr(gy), ptr(w), ptr(ag), ptr(aw), None, ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stream_of(gy)),
             'mode_conv3d_bwd_data_split_f16')
-    elif stride == 1 and _split3d(Ci, Co, stride, True):
+    elif stride == 1 and split:
       check(lib().mode_conv3d_bwd_data_split(ptr(gy), ptr(w), ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stream_of(gy)),
             'mode_conv3d_bwd_data_split')
     else:
@@ -1508,14 +1525,15 @@ def conv3d_bwd_weight(gy, x, stride=1, into=None, amax=None):
                                                   4 * (x.numel() + gy.numel() + gw.numel()), flops, gy.device):
     n = lib().mode_conv3d_bwd_weight_workspace_bytes(B, Ci, D, H, W, Co, stride)
     ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=gy.device)
-    if stride == 2 and _split3d(Ci, Co, 2, 2) and D % 2 == 0 and H % 2 == 0 and W % 8 == 0 and 32 * D * H * W < 2**29:
+    split = _split3d(Ci, Co, stride, 2, (D, H, W))
+    if stride == 2 and split:
       check(lib().mode_conv3d_bwd_weight_s2_split(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, D, H, W, Co, int(into is not None), stream_of(gy)),
             'mode_conv3d_bwd_weight_s2_split')
-    elif stride == 1 and _split3d(Ci, Co, stride, 2) and max(Ci, Co) * D * H * W < 2**29 and CONV3D_S1_F16:
+    elif stride == 1 and split and CONV3D_S1_F16:
       ag, ax = amax if amax is not None else (abs_max(gy), abs_max(x))
       check(lib().mode_conv3d_bwd_weight_split_f16(ptr(gy), ptr(x), ptr(ag), ptr(ax), ptr(gw), ptr(ws), B, Ci, D, H, W, Co, int(into is not None),
                                                    stream_of(gy)), 'mode_conv3d_bwd_weight_split_f16')
-    elif stride == 1 and _split3d(Ci, Co, stride, 2) and max(Ci, Co) * D * H * W < 2**29:
+    elif stride == 1 and split:
       check(lib().mode_conv3d_bwd_weight_split(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, D, H, W, Co, int(into is not None), stream_of(gy)),
             'mode_conv3d_bwd_weight_split')
     else:
@@ -1537,7 +1555,7 @@ def deconv3d_fwd(x, w):
   flops = 2 * x.numel() * Cout * 27
   with torch.cuda.device_of(x), profiling.region('deconv3d_fwd', 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
     wp = _wpack3d(Cin, Cout, x.device)
-    if CONV_ARITH == 'bf16x6' and lib().mode_deconv3d_split_supported(Cin, Cout) == 1 and _deconv_split_fits(D * H * W, Cout):
+    if _deconv_split3d(Cin, Cout, (D, H, W)):
       check(lib().mode_deconv3d_fwd_split(ptr(x), ptr(w), ptr(y), ptr(wp), B, Cin, D, H, W, Cout, stream_of(x)), 'mode_deconv3d_fwd_split')
     else:
       check(lib().mode_deconv3d_fwd(ptr(x), ptr(w), ptr(y), ptr(wp), B, Cin, D, H, W, Cout, stream_of(x)), 'mode_deconv3d_fwd')
@@ -1553,7 +1571,7 @@ class Conv3dFunction(torch.autograd.Function):
     ctx.stride = stride
     ctx.carrier = carrier  # GradCarrier of x (x has one other consumer), or None
     ctx.amax = None
-    if stride == 1 and x.is_cuda and CONV3D_S1_F16 and _split3d(x.shape[1], w.shape[0], 1, False):
+    if stride == 1 and x.is_cuda and CONV3D_S1_F16 and _split3d(x.shape[1], w.shape[0], 1, 0, x.shape[2:]):
       ax = known_abs_max(x)  # left by the BatchNorm pass that wrote x, where there is one
       ctx.amax = (ax if ax is not None else abs_max(x.contiguous()), _weight_abs_max(w.contiguous()))  # the backward reads both tensors again
     return conv3d_fwd(x, w, stride, amax=ctx.amax)
@@ -1624,7 +1642,7 @@ def conv3d_stats_supported(x, w, bn):
   """Training-mode convbn_3d whose stride-1 convolution runs on the split kernel: the BatchNorm batch statistics can be taken in the
   convolution's epilogue (mode_conv3d_fwd_split_stats) instead of by a pass over its output."""
   return (CONV3D_BN_STATS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[0] > 0 and bn.training and
-          bn.momentum is not None and _split3d(x.shape[1], w.shape[0], 1, False) and x.shape[0] * w.shape[0] < 65536)
+          bn.momentum is not None and _split3d(x.shape[1], w.shape[0], 1, 0, x.shape[2:]) and x.shape[0] * w.shape[0] < 65536)
 
 
 class Conv3dStatsFunction(torch.autograd.Function):
@@ -2650,7 +2668,8 @@ def conv3d_bn_eval(x, w, bn, stride=1, add=None, relu=False):
   flops = 2 * y.numel() * Ci * 27
   with torch.cuda.device_of(x), profiling.region(_tag3('conv3d_bn_eval', Ci, Co, stride, D, H, W), 4 * (x.numel() + y.numel() + w.numel()),
                                                  flops, x.device):
-    if stride == 1 and _split3d(Ci, Co, stride, False) and CONV3D_EVAL_F16:
+    split = _split3d(Ci, Co, stride, 0, (D, H, W))
+    if stride == 1 and split and CONV3D_EVAL_F16:
       # two fp16 pieces (round 6): the input's maximum is the tag the producing eval kernel left (this one: y's below), else a pass;
       # the folded weights' maximum is taken inside the call, with the pack, and lives in the kept workspace
       wp, reuse = _eval_wpack(bn, 'conv3d_fwd_split_f16_bn', w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
@@ -2660,12 +2679,12 @@ def conv3d_bn_eval(x, w, bn, stride=1, add=None, relu=False):
         check(lib().mode_conv3d_fwd_split_f16_bn(ptr(x), ptr(w), ptr(ax), ctypes.byref(e), ptr(y), ptr(ay), ptr(wp), B, Ci, D, H, W, Co,
                                                  stream_of(x)), 'mode_conv3d_fwd_split_f16_bn')
       y._mode_amax = (ay, y._version, y.data_ptr())
-    elif stride == 1 and _split3d(Ci, Co, stride, False):
+    elif stride == 1 and split:
       wp, reuse = _eval_wpack(bn, 'conv3d_fwd_split', w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
       with reuse:
         check(lib().mode_conv3d_fwd_split(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)),
               'mode_conv3d_fwd_split')
-    elif stride == 2 and _split3d(Ci, Co, stride, False) and D * H * W < 2**26:
+    elif stride == 2 and split:
       wp, reuse = _eval_wpack(bn, 'conv3d_fwd_s2_split', w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
       ay = _eval_amax_buffer(x.device)  # (the stride-1 layer behind it runs on the fp16 arithmetic: its operand maximum out of this epilogue)
       with reuse:
@@ -2690,7 +2709,7 @@ def deconv3d_bn_eval(x, w, bn, add=None, relu=False):
   e, keep = _epilogue(bn, add, relu, y)
   flops = 2 * x.numel() * Cout * 27
   with torch.cuda.device_of(x), profiling.region('deconv3d_bn_eval', 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
-    if CONV_ARITH == 'bf16x6' and lib().mode_deconv3d_split_bn_supported(Cin, Cout) == 1 and _deconv_split_fits(D * H * W, Cout):
+    if lib().mode_deconv3d_split_bn_supported(Cin, Cout) == 1 and _deconv_split3d(Cin, Cout, (D, H, W)):
       # (round 5: the split kernel with its own epilogue instantiation -- residual values of four channels requested ahead of their
       # stores; round 3 had measured it no faster than the fp32 kernel with one load next to every store)
       wp, reuse = _eval_wpack(bn, 'deconv3d_fwd_split_bn', w, lib().mode_conv3d_wpack_bytes(Cin, Cout) // 4, x.device)
@@ -2719,7 +2738,8 @@ def conv2d_bn_eval(x, w, bn, dilation=1, add=None, relu=False):
   flops = 2 * y.numel() * Ci * 9
   with torch.cuda.device_of(x), profiling.region('conv2d_bn_eval[%d->%d d%d %dx%d]' % (Ci, Co, dilation, H, W) if profiling.ENABLED
                                                  else 'conv2d_bn_eval', 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
-    if CONV_ARITH == 'bf16x6' and CONV2D_EVAL_F16 and lib().mode_conv2d_split_supported(Ci, Co, dilation, 0) == 1:
+    split = CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 0) == 1
+    if split and CONV2D_EVAL_F16:
       # two fp16 pieces (round 6): the input's maximum from its producer's tag (this kernel's own, in the residual blocks) or a pass
       wp, reuse = _eval_wpack(bn, 'conv2d_fwd_split_f16_bn', w, lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, x.device)
       ax = _tagged_abs_max(x)
@@ -2728,7 +2748,7 @@ def conv2d_bn_eval(x, w, bn, dilation=1, add=None, relu=False):
         check(lib().mode_conv2d_fwd_split_f16_bn(ptr(x), ptr(w), ptr(ax), ctypes.byref(e), ptr(y), ptr(ay), ptr(wp), B, Ci, H, W, Co, dilation,
                                                  stream_of(x)), 'mode_conv2d_fwd_split_f16_bn')
       _tag_amax(y, ay)
-    elif CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_supported(Ci, Co, dilation, 0) == 1:
+    elif split:
       wp, reuse = _eval_wpack(bn, 'conv2d_fwd_split', w, lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, x.device)
       with reuse:
         check(lib().mode_conv2d_fwd_split(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(x)),
