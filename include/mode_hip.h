@@ -935,6 +935,35 @@ int mode_erp_pairs_u8_cassini(const uint8_t* pairs_u8, const float* grid, const 
 int mode_erp_depth_disp(const float* depth_erp, const float* grid, const float* cols, int N, int He, int We, int H, int W, int G,
                         float baseline, float maxdepth, int mirror, float* disp, float* depth_cassini, mode_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Spatial pyramid pooling of the PSMNet extractor, ModeDisparity(conv='Regular') (models/submodule.py:228-268):
+ * the poolings, the bilinear upsamplings and the concatenation around the four branch convolutions.  csrc/spp.hip; NCHW fp32, no
+ * atomics, fixed summation order (bit-repeatable), nothing allocated.  Level l = 0..3 pools k = 8 << l; its planes have
+ * floor(H / k) x floor(W / k) pixels (torch's floor semantics: trailing rows and columns belong to no block).
+ *
+ * mode_spp_pool_fwd: x (planes, H, W) -> the four nn.AvgPool2d((k, k), stride=(k, k)) results y8, y16, y32, y64 in one pass that reads
+ *   x once (a workgroup reduces a 64 x 64 region level by level; block j of level 2k is blocks 2j, 2j+1 of level k).
+ * mode_spp_pool_bwd: gskip (N, Cs, H, W), written once, = channels c0 .. c0 + Cs of gcat (N, C, H, W), read where they lie (gcat NULL:
+ *   no such term), + for every level g_k[n, c, h / k, w / k] / k^2 inside the level's crop; g_k (N, Cs, H / k, W / k).
+ * mode_spp_concat_fwd: out (N, Cr + Cs + 4 Cb, H, W) = cat(raw (N, Cr, H, W), skip (N, Cs, H, W), up(b8), up(b16), up(b32), up(b64)), the
+ *   reference's order; b_k (N, Cb, H / k, W / k); up = F.interpolate(size=(H, W), mode='bilinear', align_corners=True) with aten's fp32
+ *   arithmetic: scale = (in - 1) / (out - 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1 (a
+ *   1-pixel source axis broadcasts).  One launch; every output element written exactly once.
+ * mode_spp_concat_bwd: from gcat (N, Cr + Cs + 4 Cb, H, W): graw (N, Cr, H, W), a contiguous copy, and the four branch gradients
+ *   gb_k (N, Cb, H / k, W / k), the adjoint of the upsampling in gather form: every low-resolution pixel sums the pixels whose taps
+ *   touch it (support and weights from the forward's index arithmetic), one wave or one workgroup per pixel with a fixed tree.  The
+ *   skip channels of gcat are left to mode_spp_pool_bwd.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, non-positive sizes and a channel range outside gcat;
+ * MODE_ERR_UNSUPPORTED for H or W < 64 (the k = 64 level would be empty; the reference's pooling fails there too), planes of 2^30
+ * elements or more, more than 65535 planes (N x channels) in one call or 2^31 workgroups.  N = 0 / planes = 0 is a no-op. */
+int mode_spp_pool_fwd(const float* x, float* y8, float* y16, float* y32, float* y64, long long planes, int H, int W, mode_stream_t stream);
+int mode_spp_pool_bwd(const float* gcat, int C, int c0, const float* g8, const float* g16, const float* g32, const float* g64, float* gskip,
+                      int N, int Cs, int H, int W, mode_stream_t stream);
+int mode_spp_concat_fwd(const float* raw, const float* skip, const float* b8, const float* b16, const float* b32, const float* b64, float* out,
+                        int N, int Cr, int Cs, int Cb, int H, int W, mode_stream_t stream);
+int mode_spp_concat_bwd(const float* gcat, float* graw, float* gb8, float* gb16, float* gb32, float* gb64, int N, int Cr, int Cs, int Cb,
+                        int H, int W, mode_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,11 @@ SIGNATURES = {
     # 3D60 ingest: ERP pairs and depth to rectified Cassini (csrc/erp_ingest.hip; reference dataloader/dataset3D60Loader.py:123-270)
     'mode_erp_pairs_u8_cassini': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr] * 6),
     'mode_erp_depth_disp': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 3),
+    # spatial pyramid pooling of the conv='Regular' extractor (csrc/spp.hip; reference models/submodule.py:228-268)
+    'mode_spp_pool_fwd': (_c_int, [_c_ptr] * 5 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
+    'mode_spp_pool_bwd': (_c_int, [_c_ptr] + [_c_int] * 2 + [_c_ptr] * 5 + [_c_int] * 4 + [_c_ptr]),
+    'mode_spp_concat_fwd': (_c_int, [_c_ptr] * 7 + [_c_int] * 6 + [_c_ptr]),
+    'mode_spp_concat_bwd': (_c_int, [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr]),
 }
 
 ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against

@@ -2364,6 +2364,132 @@ def classif_head_train(y, bn, conv, add=None):
                                    bn.running_var if update else None, bn.momentum, bn.eps, nbt)
 
 
+# ------------------------------------------------------------------------------------ spatial pyramid pooling (conv='Regular' extractor)
+SPP_KERNELS = (8, 16, 32, 64)  # the levels of csrc/spp.hip, in the order of its arguments (branch4, branch3, branch2, branch1 of the reference)
+
+
+def _spp_plane(t, who):
+  if t.dim() != 4:
+    raise ValueError('%s takes (N, C, H, W) tensors (got %s)' % (who, tuple(t.shape)))
+
+
+class SppPoolFunction(torch.autograd.Function):
+  """The four nn.AvgPool2d((k, k), stride=(k, k)), k = 8, 16, 32, 64, of the SPP branches (submodule.py:228-246) in one pass over
+  `skip` (mode_spp_pool_fwd).  Fifth output: `skip` itself, for its other consumer -- the concatenation.  That way both gradients of
+  `skip` arrive HERE, and the backward writes their sum in one pass (mode_spp_pool_bwd: the slice of the concatenation's gradient,
+  read where it lies, plus the four broadcast block gradients) instead of a slice copy and four adds by autograd."""
+
+  @staticmethod
+  def forward(ctx, skip):
+    require_gpu(skip)
+    _spp_plane(skip, 'spp_pool')
+    require_f32c(skip)
+    N, C, H, W = skip.shape
+    ys = tuple(torch.empty((N, C, H // k, W // k), dtype=skip.dtype, device=skip.device) for k in SPP_KERNELS)
+    with torch.cuda.device_of(skip), profiling.region('spp_pool_fwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_pool_fwd',
+                                                      4 * (skip.numel() + sum(y.numel() for y in ys)), 0, skip.device):
+      check(lib().mode_spp_pool_fwd(ptr(skip), ptr(ys[0]), ptr(ys[1]), ptr(ys[2]), ptr(ys[3]), N * C, H, W, stream_of(skip)), 'mode_spp_pool_fwd')
+    ctx.shape = tuple(skip.shape)
+    ctx.set_materialize_grads(False)
+    return ys + (skip,)
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, g8, g16, g32, g64, gslice):
+    N, C, H, W = ctx.shape
+    gs = [g8, g16, g32, g64]
+    like = next((g for g in gs + [gslice] if g is not None), None)
+    if like is None:
+      return None
+    for i, k in enumerate(SPP_KERNELS):
+      gs[i] = torch.zeros((N, C, H // k, W // k), dtype=like.dtype, device=like.device) if gs[i] is None else gs[i].contiguous()
+    Cg = C
+    if gslice is not None:
+      st = gslice.stride()
+      if N == 1 and st[1:] == (H * W, W, 1):
+        pass  # one sample: channels c of a (1, C', H, W) tensor lie where a (1, C, H, W) one has them
+      elif st[1:] == (H * W, W, 1) and st[0] % (H * W) == 0 and st[0] >= C * H * W:
+        Cg = st[0] // (H * W)  # C consecutive channels of a contiguous (N, Cg, H, W) tensor: read in place
+      else:
+        gslice = gslice.contiguous()
+    require_gpu(like)
+    require_f32c(*gs)
+    if gslice is not None and gslice.dtype != torch.float32:
+      raise TypeError('libmode_hip kernels are fp32 (got %s)' % gslice.dtype)
+    gskip = torch.empty((N, C, H, W), dtype=like.dtype, device=like.device)
+    nbytes = 4 * (gskip.numel() * (2 if gslice is not None else 1) + sum(g.numel() for g in gs))
+    with torch.cuda.device_of(gskip), profiling.region('spp_pool_bwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_pool_bwd', nbytes, 0,
+                                                       gskip.device):
+      check(lib().mode_spp_pool_bwd(ptr(gslice) if gslice is not None else None, Cg, 0, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gskip),
+                                    N, C, H, W, stream_of(gskip)), 'mode_spp_pool_bwd')
+    return gskip
+
+
+class SppPooled(tuple):
+  """The four pooled tensors (k = 8, 16, 32, 64); `.skip` is the input as SppPoolFunction hands it on -- pass it to spp_concat in
+  place of the original, so that the gradient of `skip` is written in one pass."""
+  skip = None
+
+
+def spp_pool(skip):
+  """(pool8, pool16, pool32, pool64) of skip (N, C, H, W), H and W >= 64: nn.AvgPool2d((k, k), stride=(k, k)) each, floor semantics."""
+  out = SppPoolFunction.apply(skip)
+  pooled = SppPooled(out[:4])
+  pooled.skip = out[4]
+  return pooled
+
+
+class SppConcatFunction(torch.autograd.Function):
+  """torch.cat((raw, skip, up(b4), up(b3), up(b2), up(b1)), 1) with up = F.interpolate(size=skip's, mode='bilinear',
+  align_corners=True) (submodule.py:253-266) as one launch (mode_spp_concat_fwd).  Backward (mode_spp_concat_bwd): raw's gradient as a
+  contiguous copy, the branch gradients by the adjoint of the upsampling in gather form (no atomics); skip's gradient is the slice
+  of the incoming gradient, returned as a VIEW -- SppPoolFunction's backward reads it in place."""
+
+  @staticmethod
+  def forward(ctx, raw, skip, b4, b3, b2, b1):
+    ts = (raw, skip, b4, b3, b2, b1)
+    require_gpu(*ts)
+    for t in ts:
+      _spp_plane(t, 'spp_concat')
+    require_f32c(*ts)
+    N, Cs, H, W = skip.shape
+    Cr, Cb = raw.shape[1], b4.shape[1]
+    if tuple(raw.shape) != (N, Cr, H, W):
+      raise ValueError('spp_concat: raw %s does not match skip %s' % (tuple(raw.shape), tuple(skip.shape)))
+    for b, k in zip((b4, b3, b2, b1), SPP_KERNELS):
+      if tuple(b.shape) != (N, Cb, H // k, W // k):
+        raise ValueError('spp_concat: the k = %d branch is %s, expected %s' % (k, tuple(b.shape), (N, Cb, H // k, W // k)))
+    out = torch.empty((N, Cr + Cs + 4 * Cb, H, W), dtype=skip.dtype, device=skip.device)
+    with torch.cuda.device_of(skip), profiling.region('spp_concat_fwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_concat_fwd',
+                                                      4 * (raw.numel() + skip.numel() + out.numel()), 0, skip.device):
+      check(lib().mode_spp_concat_fwd(ptr(raw), ptr(skip), ptr(b4), ptr(b3), ptr(b2), ptr(b1), ptr(out), N, Cr, Cs, Cb, H, W, stream_of(skip)),
+            'mode_spp_concat_fwd')
+    ctx.dims = (N, Cr, Cs, Cb, H, W)
+    return out
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, gcat):
+    N, Cr, Cs, Cb, H, W = ctx.dims
+    require_gpu(gcat)
+    gcat = gcat.contiguous()
+    require_f32c(gcat)
+    graw = torch.empty((N, Cr, H, W), dtype=gcat.dtype, device=gcat.device)
+    gbs = [torch.empty((N, Cb, H // k, W // k), dtype=gcat.dtype, device=gcat.device) for k in SPP_KERNELS]
+    nbytes = 4 * (2 * graw.numel() + 4 * N * Cb * H * W + sum(g.numel() for g in gbs))
+    with torch.cuda.device_of(gcat), profiling.region('spp_concat_bwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_concat_bwd', nbytes, 0,
+                                                      gcat.device):
+      check(lib().mode_spp_concat_bwd(ptr(gcat), ptr(graw), ptr(gbs[0]), ptr(gbs[1]), ptr(gbs[2]), ptr(gbs[3]), N, Cr, Cs, Cb, H, W,
+                                      stream_of(gcat)), 'mode_spp_concat_bwd')
+    return (graw, gcat[:, Cr:Cr + Cs]) + tuple(gbs)
+
+
+def spp_concat(raw, skip, b4, b3, b2, b1):
+  """(N, Cr + Cs + 4 Cb, H, W): raw, skip and the branch outputs b4 (k = 8), b3 (16), b2 (32), b1 (64) upsampled to (H, W), concatenated
+  in the reference's order.  `skip`: SppPooled.skip when the branches come from spp_pool of the same tensor."""
+  return SppConcatFunction.apply(raw, skip, b4, b3, b2, b1)
+
+
 # ------------------------------------------------------------------------------------ fusion network: pooling, 2x2 transposed conv, head
 class MaxPool2x2Function(torch.autograd.Function):
   """nn.MaxPool2d(2, stride=2) (mode_fusion.py:146, :161, :190) on csrc/fusion_ops.hip; the backward recomputes the picks from x."""

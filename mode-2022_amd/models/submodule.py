@@ -1,8 +1,7 @@
 """Sub-networks of the disparity stage (module tree and state_dict names of the reference's
-models/submodule.py; regular 2D convolutions run on the vendor library, spherical ones on libmode_hip)."""
+models/submodule.py; regular and spherical convolutions, BatchNorm and the SPP pyramid all run on libmode_hip)."""
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import stage3d
 from .basic import SphereConv
@@ -48,7 +47,7 @@ class disparityregression(nn.Module):
 
 
 def _run_convbn_relu_chain(seq, x):
-  """Sequential(convbn, ReLU, convbn, ReLU, ...) with every BatchNorm+ReLU as one fused pass."""
+  """Sequential(convbn, ReLU, convbn, ReLU, ...) (or a list of its modules) with every BatchNorm+ReLU as one fused pass."""
   mods = list(seq)
   i = 0
   while i < len(mods):
@@ -56,7 +55,10 @@ def _run_convbn_relu_chain(seq, x):
     if isinstance(mods[i], nn.Sequential) and len(mods[i]) == 2 and isinstance(mods[i][1], nn.BatchNorm2d):
       x = stage3d.conv_bn(mods[i], x, relu=relu)
       i += 2 if relu else 1
-    else:  # anything else (a bare Conv2d, pooling, ...) runs as is
+    elif isinstance(mods[i], nn.Conv2d):  # a bare convolution (the closing 1x1 of the SPP extractor's lastconv): the own kernels' dispatch
+      x = stage3d.conv3(mods[i], x)
+      i += 1
+    else:  # anything else runs as is
       x = mods[i](x)
       i += 1
   return x
@@ -187,9 +189,11 @@ class sphere_feature_extraction(nn.Module):
 
 
 class feature_extraction(nn.Module):
-  """PSMNet SPP feature extractor of ModeDisparity(conv='Regular') (submodule.py:205-268).  Vendor 2D
-  convolutions, poolings and bilinear upsampling; every BatchNorm (+ residual add) (+ ReLU) on the fused HIP kernels, like the
-  spherical extractor."""
+  """PSMNet SPP feature extractor of ModeDisparity(conv='Regular') (submodule.py:205-268).  Entirely on
+  libmode_hip, like the spherical extractor: the convolutions on the 3x3 / 1x1 / tabled kernels, every BatchNorm (+ residual add)
+  (+ ReLU) on the fused kernels, and the pyramid -- four average poolings, four bilinear upsamplings, the concatenation -- on
+  csrc/spp.hip (HF.spp_pool / HF.spp_concat).  The nn.AvgPool2d modules stay in the branches for the module tree; forward() pools
+  all four levels in one pass instead of calling them."""
 
   def __init__(self):
     super(feature_extraction, self).__init__()
@@ -216,7 +220,8 @@ class feature_extraction(nn.Module):
   def forward(self, x):
     raw = self.layer2(self.layer1(_run_convbn_relu_chain(self.firstconv, x)))
     skip = self.layer4(self.layer3(raw))
-    size = skip.shape[2:]
-    pooled = [F.interpolate(_run_convbn_relu_chain(getattr(self, 'branch%d' % i), skip), size, mode='bilinear', align_corners=True)
-              for i in (4, 3, 2, 1)]
-    return _run_convbn_relu_chain(self.lastconv, torch.cat([raw, skip] + pooled, 1))
+    HF = stage3d.HF
+    pooled = HF.spp_pool(skip)  # k = 8, 16, 32, 64: the poolings of branch4, branch3, branch2, branch1
+    # (each branch: AvgPool2d, convbn, ReLU -- the pooling is done, the rest runs on the pooled tensor)
+    outs = [_run_convbn_relu_chain(list(getattr(self, 'branch%d' % i))[1:], p) for i, p in zip((4, 3, 2, 1), pooled)]
+    return _run_convbn_relu_chain(self.lastconv, HF.spp_concat(raw, pooled.skip, *outs))

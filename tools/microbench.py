@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel timings at the benchmark shapes (GPU box).  Prints one line per kernel: avg ms, GB/s, TFLOP/s.
 
-  python tools/microbench.py [--batch 2] [--iters 10] [--only cost,sphere,conv3d,head,vendor,stages,export,fusion]
+  python tools/microbench.py [--batch 2] [--iters 10] [--only cost,sphere,conv3d,conv2d,spp,head,vendor,stages,export,fusion]
 """
 import argparse
 import os
@@ -39,7 +39,7 @@ def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batch', type=int, default=2)
   ap.add_argument('--iters', type=int, default=10)
-  ap.add_argument('--only', default='cost,sphere,conv3d,conv2d,head,vendor,stages,export,fusion')
+  ap.add_argument('--only', default='cost,sphere,conv3d,conv2d,spp,head,vendor,stages,export,fusion')
   a = ap.parse_args()
   only = a.only.split(',')
   dev = 'cuda:0'
@@ -182,6 +182,30 @@ def main():
       report('  (vendor conv2d weight gradient)', timeit(lambda: torch.ops.aten.convolution_backward(
           gy, x, wt, None, [1, 1], [dil, dil], [dil, dil], False, [0, 0], 1, [False, True, False]), a.iters), nb, fl)
       del x, wt, gy
+
+  if 'spp' in only:
+    # the pyramid of the conv='Regular' extractor at the step's 4 images (quarter plane 256 x 128): poolings, upsamplings and the
+    # concatenation, forward + backward, csrc/spp.hip against torch's composition
+    B4, h, w_ = 2 * B, 256, 128
+    raw = torch.randn(B4, 64, h, w_, device=dev, requires_grad=True)
+    skip = torch.randn(B4, 128, h, w_, device=dev, requires_grad=True)
+    bs = [torch.randn(B4, 32, h // k, w_ // k, device=dev, requires_grad=True) for k in HF.SPP_KERNELS]
+    gcat = torch.randn(B4, 320, h, w_, device=dev)
+    gps = [torch.randn(B4, 128, h // k, w_ // k, device=dev) for k in HF.SPP_KERNELS]
+    nb = 4 * (raw.numel() + skip.numel() + gcat.numel())  # one read of raw and of skip, one write of the 320 channels (each way)
+
+    def spp_own():
+      ps = HF.spp_pool(skip)
+      torch.autograd.backward([HF.spp_concat(raw, ps.skip, *bs)] + list(ps), [gcat] + gps)
+
+    def spp_torch():
+      ps = [F.avg_pool2d(skip, (k, k), stride=(k, k)) for k in HF.SPP_KERNELS]
+      cat = torch.cat([raw, skip] + [F.interpolate(b, (h, w_), mode='bilinear', align_corners=True) for b in bs], 1)
+      torch.autograd.backward([cat] + ps, [gcat] + gps)
+
+    report('spp pool + upsample + cat fwd+bwd @%dx%d B=%d' % (h, w_, B4), timeit(spp_own, a.iters), 2 * nb)
+    report('  (torch avg_pool2d + interpolate + cat)', timeit(spp_torch, a.iters), 2 * nb)
+    del raw, skip, bs, gcat, gps
 
   if 'head' in only:
     lg = torch.randn(B, 1, 48, 256, 128, device=dev)
