@@ -549,6 +549,19 @@ size_t mode_head_bwd_workspace_bytes(int B, int D4, int H, int W);
 int mode_head_bwd(const float* logits, const float* gpred, float* glogits, float* workspace, int B, int D4, int H4,
                   int W4, int D, int H, int W, mode_stream_t stream);
 
+/* The head's backward with the gradient of the confidence map as well, in one pass over the pixels (same launches, same workspace
+ * as mode_head_bwd): glogits = d(sum(gpred * pred) + sum(gconf * conf)) / d logits, written; deterministic.  pred, conf (B, H, W) are
+ * the forward's own outputs of mode_head_fwd on the same logits: the gradient is that of the confidence that was reported.  With
+ * p_d the softmax of the up-sampled column, r = rintf(pred), i_k = clamp(r + k, 0, D - 1) for k = -1, 0, 1 and m_d the number of k
+ * with i_k == d (0 .. 3: at the borders an index counts twice, which is why conf can exceed 1), the value scattered to the two nodes
+ * of disparity d is
+ *   gv_d = p_d * (gpred * (d - pred) + gconf * (m_d - conf))
+ * The rounding passes no gradient (the reference's grid_sample(mode='nearest') passes it to the probabilities alone).  With
+ * gconf == 0 the result has the bits of mode_head_bwd.  Arguments are checked before any launch as mode_head_bwd checks them;
+ * B = 0 is a no-op. */
+int mode_head_bwd_conf(const float* logits, const float* pred, const float* conf, const float* gpred, const float* gconf,
+                       float* glogits, float* workspace, int B, int D4, int H4, int W4, int D, int H, int W, mode_stream_t stream);
+
 /* The loss of the training step next to the head (train_disparity.py:151-158: masked smooth-L1 of the three predictions, weights
  * 0.5 / 0.7 / 1.0, mean over the valid pixels), so that nothing elementwise is launched between the head and the optimizer:
  *   mode_smooth_l1_masked: out[0] = scale[0] * sum_i w_i * sum_pix [gt == gt] * smooth_l1(pred_i[pix] - gt[pix])   (beta = 1);
@@ -714,8 +727,7 @@ int mode_multiview_handoff(const float* disp, const float* conf, int F, int H, i
 
 /* The gradient of the hand-off's DEPTH channels with respect to the disparities, in two launches and without a memset (every element
  * of gdisp (F, 6, H, W) is written; graph-capturable).  gout is the gradient of `out` in the forward's layout, (F, 12, H, W) or
- * (F, 6, H, W) under MODE_MV_DEPTH_ONLY; its confidence channels are not read: the confidence has no gradient (q is piecewise constant,
- * and the head's confidence map has no backward).  With S(d, j) = -(pi / W) baseline cos(phi_l) / sin^2(d pi / W) where d != 0 and the
+ * (F, 6, H, W) under MODE_MV_DEPTH_ONLY; its confidence channels are not read by this entry (the entry below reads them).  With S(d, j) = -(pi / W) baseline cos(phi_l) / sin^2(d pi / W) where d != 0 and the
  * unclipped sine-rule depth lies in [0, 1000], and exactly +0 elsewhere:
  *   12        gdisp = gout S
  *   13, 14    gdisp[s] = S sum_k weight[k] gout[target[k]] over the adjoint list of source s (float32, stored order, no atomics)
@@ -732,6 +744,20 @@ int mode_multiview_handoff(const float* disp, const float* conf, int F, int H, i
 int mode_multiview_handoff_bwd(const float* disp, const float* gout, const void* keys, int F, int H, int W, const float* baselines6,
                                const float* trig, const double* xforms, const int32_t* adj_rowptr, const int32_t* adj_target,
                                const float* adj_weight, int n_adj, int flags, float* gdisp, mode_stream_t stream);
+
+/* The same with the gradient of the CONFIDENCE channels beside it: the arguments of the entry above and gconf (F, 6, H, W), both
+ * outputs written in the same two launches (every element; structural zeros are +0.0; the adjoint lists are walked once per source
+ * for both).  gdisp has the bits of the entry above.  With q the identity the confidence channels are linear in conf:
+ *   12        gconf = gout[f, 1], copied
+ *   13, 14    gconf[s] = sum_k weight[k] gout[f, 2p + 1, target[k]] over the adjoint list of source s (float32, stored order), for
+ *             every source: the confidence does not depend on the disparity, so sources with disp == 0 get their sum too
+ *   23 24 34  gconf[winner(t)] = gout[f, 2p + 1, t], every other source +0; a winner capped at 1000 or without a slope passed its
+ *             confidence on in the forward and gets this gradient all the same
+ * MODE_ERR_BAD_ARG under MODE_MV_DEPTH_ONLY (no confidence channels) and under MODE_MV_CONF_PNG (the 8-bit rounding q is piecewise
+ * constant: it has no gradient); otherwise the checks of the entry above. */
+int mode_multiview_handoff_bwd_full(const float* disp, const float* gout, const void* keys, int F, int H, int W, const float* baselines6,
+                                    const float* trig, const double* xforms, const int32_t* adj_rowptr, const int32_t* adj_target,
+                                    const float* adj_weight, int n_adj, int flags, float* gdisp, float* gconf, mode_stream_t stream);
 
 /* Training forward of convbn_3d (models/submodule.py:20-22) without the statistics pass: the stride-1 split-bf16 convolution kernel
  * takes the BatchNorm batch statistics of its output from the accumulators (per channel: sum(y - K), sum((y - K)^2), K = the layer's own
@@ -887,6 +913,8 @@ int mode_bicubic_up2(const float* src, float* dst, int N, int C, int H, int W, m
  *   One launch: a workgroup owns 16 x 32 output pixels and keeps the horizontal pass of the 38 input rows under them in LDS.
  * mode_decimate2 (deep360_loader.py:147-150): out[n, y, x] = in[n, 2 y, 2 x] over `planes` fp32 planes (H, W) -> (ceil(H / 2), ceil(W / 2)),
  *   the [::2, ::2] of the loader on the planes of mode_multiview_handoff.
+ * mode_decimate2_bwd: its adjoint, gin[n, y, x] = gout[n, y / 2, x / 2] where y and x are both even and +0.0 elsewhere; every element of
+ *   gin (planes, H, W) is written, in one launch with 16-byte stores (gin 16-byte aligned; single stores otherwise).  Sizes as the forward.
  * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, misaligned buffers, H, W <= 0, F or planes < 0, sizes
  * the entry does not take and element counts (36 F H W, planes H W) >= 2^31.  F = 0 / planes = 0 is a no-op. */
 int mode_frames_u8_ingest(const uint8_t* frames_u8, const float* lut, int F, int H, int W, float* left, float* right, float* rgb,
@@ -894,6 +922,7 @@ int mode_frames_u8_ingest(const uint8_t* frames_u8, const float* lut, int F, int
 int mode_rgb_half_pil(const uint8_t* frames_u8, const int32_t* tab_w, const int32_t* tab_h, const float* lut, int F, int H, int W,
                       float* rgb_half, uint8_t* half_u8, mode_stream_t stream);
 int mode_decimate2(const float* in, float* out, long long planes, int H, int W, mode_stream_t stream);
+int mode_decimate2_bwd(const float* gout, float* gin, long long planes, int H, int W, mode_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 3D60 ingest (csrc/erp_ingest.hip): what the reference's Dataset3D60Disparity.__getitem__ (dataloader/dataset3D60Loader.py:123-248)

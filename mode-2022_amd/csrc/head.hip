@@ -9,7 +9,8 @@
 //
 // Backward (d pred / d logit): gv_d = g * p_d * (d - pred); its transpose-interpolation along d is accumulated per pixel
 // (kernel 1, writes G = (B,D4,H,W)), and the (h,w) transpose is a deterministic gather over the <= ~(2*scale)^2 pixels that
-// touch a low-resolution node (kernel 2).  No atomics.
+// touch a low-resolution node (kernel 2).  No atomics.  mode_head_bwd_conf adds the confidence map's gradient in the same pass:
+// gv_d = p_d * (g * (d - pred) + gconf * (m_d - conf)), m_d the multiplicity of d in the confidence window.
 #include "common.h"
 
 #include <algorithm>
@@ -91,8 +92,13 @@ __global__ __launch_bounds__(NT) void head_fwd_kernel(const float* __restrict__ 
 }
 
 // Backward kernel 1: G[b][d4][h][w] = sum_d (lerp weight of d4 at d) * gpred * p_d * (d - pred)
+// CONF (mode_head_bwd_conf): + gconf * p_d * (m_d - conf), m_d = how many of the three window indices clamp(rint(pred) + k, 0, D - 1),
+// k = -1, 0, 1, equal d (0 .. 3: at the borders an index counts twice); pred and conf are the forward's own outputs, the rounding
+// passes no gradient.  The new arguments stand behind `d`: the plain instantiation reads its arguments where it always did.
+template <bool CONF>
 __global__ __launch_bounds__(NT) void head_bwd_pix_kernel(const float* __restrict__ L, const float* __restrict__ gpred,
-                                                          float* __restrict__ G, HDims d) {
+                                                          float* __restrict__ G, HDims d, const float* __restrict__ pred,
+                                                          const float* __restrict__ conf, const float* __restrict__ gconf) {
   extern __shared__ __attribute__((aligned(16))) float u[];  // [D4][NT]: logits column
   const long long npix = (long long)d.B * d.H * d.W;
   const long long pix = (long long)blockIdx.x * NT + threadIdx.x;
@@ -110,6 +116,17 @@ __global__ __launch_bounds__(NT) void head_bwd_pix_kernel(const float* __restric
   }
   const float p = s1 / s0;
   const float g = gpred[pix] / s0;
+  float gc = 0.f, cf = 0.f;
+  int i0 = 0, i1 = 0, i2 = 0;
+  if (CONF) {
+    gc = gconf[pix] / s0;
+    cf = conf[pix];
+    const float r = rintf(pred[pix]);
+    const float top = (float)(d.D - 1);
+    i0 = (int)fminf(fmaxf(r - 1.f, 0.f), top);
+    i1 = (int)fminf(fmaxf(r, 0.f), top);
+    i2 = (int)fminf(fmaxf(r + 1.f, 0.f), top);
+  }
   // The source node d0 of disparity dd grows monotonically with dd (d1 = d0 + 1, or d0 at the last node): the gradient of a
   // node is complete once d0 has moved past it, so two running sums replace the read-modify-write column in LDS (half the LDS:
   // three workgroups per CU instead of one) and every node is written exactly once, straight to G, in a fixed order.
@@ -128,7 +145,9 @@ __global__ __launch_bounds__(NT) void head_bwd_pix_kernel(const float* __restric
       ++cur;
     }
     const float v = (1.f - ld) * ucol[d0 * NT] + ld * ucol[d1 * NT];
-    const float gv = g * __expf(v - m) * ((float)dd - p);
+    const float e = __expf(v - m);
+    float gv = g * e * ((float)dd - p);
+    if (CONF) gv += gc * e * ((float)((dd == i0) + (dd == i1) + (dd == i2)) - cf);
     a0 += (1.f - ld) * gv;
     if (d1 != d0)
       a1 += ld * gv;
@@ -218,8 +237,9 @@ struct HeadConst {
 };
 
 // a[k] = (bilinear column value - max over the column) * log2(e), in registers
+// (returns the maximum: the confidence variants of the backward need it for the window's nodes)
 template <int D4>
-__device__ __forceinline__ void fill_column_regs(const float* __restrict__ Lb, const HDims& d, int h, int w, float (&a)[D4]) {
+__device__ __forceinline__ float fill_column_regs(const float* __restrict__ Lb, const HDims& d, int h, int w, float (&a)[D4]) {
   int h0, h1, w0, w1;
   float lh, lw;
   src_index(h, d.sh, d.H4, h0, h1, lh);
@@ -237,6 +257,7 @@ __device__ __forceinline__ void fill_column_regs(const float* __restrict__ Lb, c
   }
 #pragma unroll
   for (int k = 0; k < D4; ++k) a[k] = (a[k] - m) * kLog2e;
+  return m;
 }
 
 template <int D4, bool CONF>
@@ -284,13 +305,75 @@ __global__ __launch_bounds__(NT) void head_fwd_fast_kernel(const float* __restri
   }
 }
 
+// The confidence term of the fast backward kernels (mode_head_bwd_conf).  With i_j = clamp(rint(pred) + j, 0, D - 1), j = -1, 0, 1, the
+// window sum of the forward is c = sum_j e_{i_j} (conf = c / s0), and its gradient at node k is
+//   gconf / s0 * (Wn_k - conf A_k),   Wn_k = sum_j w_k(i_j) e_{i_j}
+// -- the scatter of gconf p_d (m_d - conf) to the two nodes of d, the multiplicity m_d carried by the sum over j.  Three neighbouring
+// disparities lie on at most three neighbouring nodes n0, n0 + 1, n0 + 2 (4 disparities per node).  The register column is never
+// indexed at run time: the three nodes are interpolated again from the logits (12 loads the thread has just made: cache hits), after
+// the walk over the disparities, which stays the code of the plain kernels.  The window is placed by the forward's own `pred` (the
+// gradient of the confidence that was reported); wn[t] = Wn_{n0 + t}.
+//
+// opaque(): a value the compiler knows nothing about.  The confidence term reads the shared quantities (the column's maximum, s0, A_k,
+// the finished gradient) through it, so that its arithmetic is not vectorised or contracted together with the plain kernel's.
+__device__ __forceinline__ float opaque(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+template <int D4>
+__device__ __forceinline__ void conf_window(const float* __restrict__ Lb, const HDims& d, int h, int w, float m, float predv, int& n0,
+                                            float (&wn)[3]) {
+  using C = HeadConst<D4>;
+  const float r = rintf(predv);
+  int i0[3], i1[3];
+  float l[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int idx = (int)fminf(fmaxf(r + (float)(j - 1), 0.f), (float)(C::D - 1));  // (NaN -> 0: always inside the column)
+    src_index(idx, C::sd, D4, i0[j], i1[j], l[j]);
+  }
+  n0 = i0[0];
+  int h0, h1, w0, w1;
+  float lh, lw;
+  src_index(h, d.sh, d.H4, h0, h1, lh);
+  src_index(w, d.sw, d.W4, w0, w1, lw);
+  const float uh = 1.f - lh, uw = 1.f - lw;
+  const unsigned plane = (unsigned)(d.H4 * d.W4);
+  const unsigned o00 = h0 * d.W4 + w0, o01 = h0 * d.W4 + w1, o10 = h1 * d.W4 + w0, o11 = h1 * d.W4 + w1;
+  float c[3];
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const float* p = Lb + (unsigned)min(n0 + t, D4 - 1) * plane;  // (n0 + 2 may lie behind the column: clamped, and then not used)
+    c[t] = (uh * (uw * p[o00] + lw * p[o01]) + lh * (uw * p[o10] + lw * p[o11]) - m) * kLog2e;
+  }
+  wn[0] = wn[1] = wn[2] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int r0 = i0[j] - n0, r1 = i1[j] - n0;  // r0 in {0, 1}, r1 in {r0, r0 + 1}
+    const float v0 = r0 == 0 ? c[0] : c[1];
+    const float v1 = r1 == 0 ? c[0] : (r1 == 1 ? c[1] : c[2]);
+    const float e = __builtin_amdgcn_exp2f((1.f - l[j]) * v0 + l[j] * v1);
+    const float e0 = (1.f - l[j]) * e, e1 = l[j] * e;
+    wn[0] += (r0 == 0 ? e0 : 0.f) + (r1 == 0 ? e1 : 0.f);
+    wn[1] += (r0 == 1 ? e0 : 0.f) + (r1 == 1 ? e1 : 0.f);
+    wn[2] += (r1 == 2 ? e1 : 0.f);
+  }
+}
+
+__device__ __forceinline__ float conf_window_at(int k, int n0, const float (&wn)[3]) {
+  return k == n0 ? wn[0] : (k == n0 + 1 ? wn[1] : (k == n0 + 2 ? wn[2] : 0.f));
+}
+
 // Backward, one pass: with e_dd = exp(v_dd - m), A_k = sum_dd w_k(dd) e_dd and B_k = sum_dd w_k(dd) e_dd (dd - c_k) (w_k = the lerp
 // weight of node k at disparity dd, c_k = a constant near the node: keeps the products small), the gradient of node k is
 //   G_k = g / s0 * (B_k - (p - c_k) A_k),   s0 = sum_k A_k,   p = sum_k (B_k + c_k A_k) / s0
 // -- the same sums as gv_dd = g p_dd (dd - pred) scattered to the two nodes of dd, without a second walk over the disparities.
-template <int D4>
+// CONF: + the confidence term above (the arguments behind `d`).
+template <int D4, bool CONF>
 __global__ __launch_bounds__(NT) void head_bwd_pix_fast_kernel(const float* __restrict__ L, const float* __restrict__ gpred,
-                                                               float* __restrict__ G, HDims d) {
+                                                               float* __restrict__ G, HDims d, const float* __restrict__ pred,
+                                                               const float* __restrict__ conf, const float* __restrict__ gconf) {
   using C = HeadConst<D4>;
   const long long npix = (long long)d.B * d.H * d.W;
   const long long pix = (long long)blockIdx.x * NT + threadIdx.x;
@@ -299,7 +382,8 @@ __global__ __launch_bounds__(NT) void head_bwd_pix_fast_kernel(const float* __re
   const int h = (int)((pix / d.W) % d.H);
   const int b = (int)(pix / ((long long)d.W * d.H));
   float a[D4];
-  fill_column_regs<D4>(L + (long long)b * D4 * d.H4 * d.W4, d, h, w, a);
+  const float* Lb = L + (long long)b * D4 * d.H4 * d.W4;
+  const float m = fill_column_regs<D4>(Lb, d, h, w, a);
   float A[D4], Bc[D4];
 #pragma unroll
   for (int k = 0; k < D4; ++k) A[k] = Bc[k] = 0.f;
@@ -329,6 +413,21 @@ __global__ __launch_bounds__(NT) void head_bwd_pix_fast_kernel(const float* __re
   const float g = gpred[pix] / s0;
   const long long hw = (long long)d.H * d.W;
   float* Gb = G + (long long)b * D4 * hw + (long long)h * d.W + w;
+  if (CONF) {
+    // The confidence term lives in a branch of its own (a pixel without a confidence gradient takes the plain stores below): the
+    // compiler forms and contracts the arithmetic of a basic block together, and the walk above is to stay the plain kernel's.
+    const float gcv = gconf[pix];
+    if (gcv != 0.f) {
+      int n0;
+      float wn[3];
+      conf_window<D4>(Lb, d, h, w, opaque(m), pred[pix], n0, wn);
+      const float gc = gcv / opaque(s0), cf = conf[pix];
+#pragma unroll
+      for (int k = 0; k < D4; ++k)
+        Gb[(long long)k * hw] = opaque(g * (Bc[k] - (p - (float)(4 * k)) * A[k])) + gc * (conf_window_at(k, n0, wn) - cf * opaque(A[k]));
+      return;
+    }
+  }
 #pragma unroll
   for (int k = 0; k < D4; ++k) Gb[(long long)k * hw] = g * (Bc[k] - (p - (float)(4 * k)) * A[k]);
 }
@@ -388,10 +487,12 @@ __global__ __launch_bounds__(NT) void head_bwd_cols_kernel(const float* __restri
 constexpr int HR_KC = 16;   // nodes per LDS pass
 constexpr int HR_MAXS = 12;  // pixels in the support of a low-resolution node (x4 up-sampling: 8-9)
 
-template <int D4, bool LOSS>
+// CONF (mode_head_bwd_conf): + the confidence term (conf_window above); `pred` is then the forward's prediction that places the window.
+template <int D4, bool LOSS, bool CONF>
 __global__ __launch_bounds__(512) void head_bwd_pixrows_kernel(const float* __restrict__ L, const float* __restrict__ gpred,
                                                                 const float* __restrict__ pred, const float* __restrict__ gt, float weight,
-                                                                const float* __restrict__ scale, float* __restrict__ R, HDims d) {
+                                                                const float* __restrict__ scale, float* __restrict__ R, HDims d,
+                                                                const float* __restrict__ conf, const float* __restrict__ gconf) {
   using C = HeadConst<D4>;
   extern __shared__ __attribute__((aligned(16))) float gl[];  // [HR_KC][pitch], element w of a row at w + (w >> 2): the stride-4 reads of
   const int pitch = d.W + (d.W >> 2) + 1;                      // neighbouring nodes then fall on different banks
@@ -400,9 +501,13 @@ __global__ __launch_bounds__(512) void head_bwd_pixrows_kernel(const float* __re
   const bool live = w < d.W;
   float A[D4], Bc[D4];
   float gscale = 0.f, p = 0.f;
+  int n0 = 0;
+  float wn[3] = {0.f, 0.f, 0.f}, gcs = 0.f, cf = 0.f;
+  bool cterm = false;  // CONF: this pixel has a confidence gradient
   if (live) {
     float a[D4];
-    fill_column_regs<D4>(L + (long long)b * D4 * d.H4 * d.W4, d, h, w, a);
+    const float* Lb = L + (long long)b * D4 * d.H4 * d.W4;
+    const float m = fill_column_regs<D4>(Lb, d, h, w, a);
 #pragma unroll
     for (int k = 0; k < D4; ++k) A[k] = Bc[k] = 0.f;
 #pragma unroll
@@ -437,6 +542,16 @@ __global__ __launch_bounds__(512) void head_bwd_pixrows_kernel(const float* __re
       g = gpred[pix];
     }
     gscale = g / s0;
+    if (CONF) {
+      // (a branch of its own, taken where there is a confidence gradient: see head_bwd_pix_fast_kernel)
+      const float gcv = gconf[pix];
+      if (gcv != 0.f) {
+        conf_window<D4>(Lb, d, h, w, opaque(m), pred[pix], n0, wn);
+        gcs = gcv / opaque(s0);
+        cf = conf[pix];
+        cterm = true;
+      }
+    }
   }
   // this thread's output nodes: w4 = threadIdx.x % W4 for the node rows kq, kq + nkq, ... of a pass (host: blockDim.x % W4 == 0)
   const int w4 = threadIdx.x % d.W4, kq = threadIdx.x / d.W4, nkq = blockDim.x / d.W4;
@@ -455,7 +570,13 @@ __global__ __launch_bounds__(512) void head_bwd_pixrows_kernel(const float* __re
   const long long rplane = (long long)d.H * d.W4;
 #pragma unroll
   for (int k0 = 0; k0 < D4; k0 += HR_KC) {
-    if (live) {
+    if (CONF && cterm) {
+#pragma unroll
+      for (int kk = 0; kk < HR_KC; ++kk)
+        if (k0 + kk < D4)
+          gl[kk * pitch + w + (w >> 2)] = opaque(gscale * (Bc[k0 + kk] - (p - (float)(4 * (k0 + kk))) * A[k0 + kk])) +
+                                          gcs * (conf_window_at(k0 + kk, n0, wn) - cf * opaque(A[k0 + kk]));
+    } else if (live) {
 #pragma unroll
       for (int kk = 0; kk < HR_KC; ++kk)
         if (k0 + kk < D4) gl[kk * pitch + w + (w >> 2)] = gscale * (Bc[k0 + kk] - (p - (float)(4 * (k0 + kk))) * A[k0 + kk]);
@@ -539,11 +660,17 @@ int launch_fwd_fast(const float* logits, float* pred, float* conf, const HDims& 
   return mode::check_launch("mode_head_fwd");
 }
 
-template <int D4>
-int launch_bwd_fast(const float* logits, const float* gpred, float* ws, const HDims& d, hipStream_t st) {
+// (pred, conf, gconf: the forward's outputs and the confidence's upstream gradient of mode_head_bwd_conf; NULL and unread otherwise)
+struct HeadConfArgs {
+  const float *pred, *conf, *gconf;
+};
+
+template <int D4, bool CONF>
+int launch_bwd_fast(const float* logits, const float* gpred, float* ws, const HDims& d, const HeadConfArgs& c, hipStream_t st) {
   const long long npix = (long long)d.B * d.H * d.W;
-  hipLaunchKernelGGL(head_bwd_pix_fast_kernel<D4>, dim3(mode::cdiv(npix, NT)), dim3(NT), 0, st, logits, gpred, ws, d);
-  return mode::check_launch("mode_head_bwd(pixels)");
+  hipLaunchKernelGGL((head_bwd_pix_fast_kernel<D4, CONF>), dim3(mode::cdiv(npix, NT)), dim3(NT), 0, st, logits, gpred, ws, d, c.pred, c.conf,
+                     c.gconf);
+  return mode::check_launch(CONF ? "mode_head_bwd_conf(pixels)" : "mode_head_bwd(pixels)");
 }
 
 // one block per image row: W <= 512 pixels (8 waves: the 48-node kernel needs 2 waves per SIMD = 256 registers; wider rows take the
@@ -574,13 +701,14 @@ bool pixrows_fits(const HDims& d) {
          (size_t)HR_KC * (d.W + (d.W >> 2) + 1) * sizeof(float) <= 64 * 1024 && pixrows_support_fits(d);
 }
 
-template <int D4, bool LOSS>
+template <int D4, bool LOSS, bool CONF = false>
 int launch_bwd_pixrows(const float* logits, const float* gpred, const float* pred, const float* gt, float weight, const float* scale,
-                       float* R, const HDims& d, hipStream_t st) {
+                       float* R, const HDims& d, hipStream_t st, const float* conf = nullptr, const float* gconf = nullptr) {
   const int nt = ((d.W + 63) / 64) * 64;
   const size_t lds = (size_t)HR_KC * (d.W + (d.W >> 2) + 1) * sizeof(float);
-  hipLaunchKernelGGL((head_bwd_pixrows_kernel<D4, LOSS>), dim3(d.B * d.H), dim3(nt), lds, st, logits, gpred, pred, gt, weight, scale, R, d);
-  return mode::check_launch("mode_head_bwd(pixels + rows)");
+  hipLaunchKernelGGL((head_bwd_pixrows_kernel<D4, LOSS, CONF>), dim3(d.B * d.H), dim3(nt), lds, st, logits, gpred, pred, gt, weight, scale, R,
+                     d, conf, gconf);
+  return mode::check_launch(CONF ? "mode_head_bwd_conf(pixels + rows)" : "mode_head_bwd(pixels + rows)");
 }
 
 // the compile-time instantiations: D4 = maxdisp / 4 of the configurations in use (16 ... 256 disparities)
@@ -631,38 +759,46 @@ extern "C" size_t mode_head_bwd_workspace_bytes(int B, int D4, int H, int W) {
   return 2 * (size_t)B * D4 * H * W * sizeof(float);
 }
 
-extern "C" int mode_head_bwd(const float* logits, const float* gpred, float* glogits, float* workspace, int B, int D4, int H4,
-                             int W4, int D, int H, int W, mode_stream_t stream) {
-  HDims d;
-  int rc = make_hdims(d, B, D4, H4, W4, D, H, W, "mode_head_bwd");
-  if (rc != MODE_OK) return rc;
-  if (B == 0) return MODE_OK;
-  MODE_REQUIRE(logits && gpred && glogits, MODE_ERR_BAD_ARG, "mode_head_bwd: null pointer");
-  MODE_REQUIRE(workspace, MODE_ERR_WORKSPACE, "mode_head_bwd: workspace required");
-  hipStream_t st = mode::as_stream(stream);
+namespace {
+
+// The one-block-per-row kernel with the confidence term exists up to D4 = 48 (228 registers, nothing spilled).  At D4 = 64 the plain
+// kernel already fills all 256 registers and spills, and so would the variant: those sizes take the per-pixel fast kernel
+// (168 registers, nothing spilled) and the separate rows pass.
+constexpr int kPixrowsConfMaxD4 = 48;
+
+// mode_head_bwd (CONF = false: c unread) and mode_head_bwd_conf: the same routing between the three forms, the same workspace
+template <bool CONF>
+int head_bwd_run(const float* logits, const float* gpred, const HeadConfArgs& c, float* glogits, float* workspace, const HDims& d,
+                 hipStream_t st) {
+  const int B = d.B, D4 = d.D4, H4 = d.H4, W4 = d.W4, H = d.H, W = d.W;
+  const char* who = CONF ? "mode_head_bwd_conf" : "mode_head_bwd";
+  int rc = MODE_OK;
   const long long npix = (long long)B * H * W;
   bool fast = false;
-  if (head_fast(d) && pixrows_fits(d)) {  // per-pixel pass and row sums in one kernel, then the column sums
+  if (head_fast(d) && pixrows_fits(d) && (!CONF || D4 <= kPixrowsConfMaxD4)) {  // per-pixel pass and row sums in one kernel, then the column sums
     float* R = workspace;
-#define X(N) if (D4 == N) rc = launch_bwd_pixrows<N, false>(logits, gpred, nullptr, nullptr, 0.f, nullptr, R, d, st);
+#define X(N)                                                                                                                       \
+  if constexpr (!CONF || N <= kPixrowsConfMaxD4)                                                                                   \
+    if (D4 == N) rc = launch_bwd_pixrows<N, false, CONF>(logits, gpred, c.pred, nullptr, 0.f, nullptr, R, d, st, c.conf, c.gconf);
     MODE_HEAD_FAST_D4(X)
 #undef X
     if (rc != MODE_OK) return rc;
     const long long n = (long long)B * D4 * H4 * W4;
     hipLaunchKernelGGL(head_bwd_cols_kernel, dim3(mode::cdiv(n, NT)), dim3(NT), 0, st, R, glogits, d);
-    return mode::check_launch("mode_head_bwd(columns)");
+    return mode::check_launch(CONF ? "mode_head_bwd_conf(columns)" : "mode_head_bwd(columns)");
   }
   if (head_fast(d)) {
-#define X(N) if (D4 == N) { rc = launch_bwd_fast<N>(logits, gpred, workspace, d, st); fast = true; }
+#define X(N) if (D4 == N) { rc = launch_bwd_fast<N, CONF>(logits, gpred, workspace, d, c, st); fast = true; }
     MODE_HEAD_FAST_D4(X)
 #undef X
   }
   if (!fast) {
     const size_t lds = (size_t)D4 * NT * sizeof(float);
-    rc = mode::allow_lds(head_bwd_pix_kernel, lds, "mode_head_bwd");
+    rc = mode::allow_lds(head_bwd_pix_kernel<CONF>, lds, who);
     if (rc != MODE_OK) return rc;
-    hipLaunchKernelGGL(head_bwd_pix_kernel, dim3(mode::cdiv(npix, NT)), dim3(NT), lds, st, logits, gpred, workspace, d);
-    rc = mode::check_launch("mode_head_bwd(pixels)");
+    hipLaunchKernelGGL(head_bwd_pix_kernel<CONF>, dim3(mode::cdiv(npix, NT)), dim3(NT), lds, st, logits, gpred, workspace, d, c.pred, c.conf,
+                       c.gconf);
+    rc = mode::check_launch(CONF ? "mode_head_bwd_conf(pixels)" : "mode_head_bwd(pixels)");
   }
   if (rc != MODE_OK) return rc;
   if (W4 <= W) {  // separable gather: rows, then columns
@@ -671,11 +807,37 @@ extern "C" int mode_head_bwd(const float* logits, const float* gpred, float* glo
     hipLaunchKernelGGL(head_bwd_rows_kernel, dim3(mode::cdiv(rows * W4, NT)), dim3(NT), 0, st, workspace, R, d, rows);
     const long long n = (long long)B * D4 * H4 * W4;
     hipLaunchKernelGGL(head_bwd_cols_kernel, dim3(mode::cdiv(n, NT)), dim3(NT), 0, st, R, glogits, d);
-    return mode::check_launch("mode_head_bwd(gather)");
+    return mode::check_launch(CONF ? "mode_head_bwd_conf(gather)" : "mode_head_bwd(gather)");
   }
   const long long n = (long long)B * D4 * H4 * W4;
   hipLaunchKernelGGL(head_bwd_gather_kernel, dim3(mode::cdiv(n, NT)), dim3(NT), 0, st, workspace, glogits, d);
-  return mode::check_launch("mode_head_bwd(gather)");
+  return mode::check_launch(CONF ? "mode_head_bwd_conf(gather)" : "mode_head_bwd(gather)");
+}
+
+}  // namespace
+
+extern "C" int mode_head_bwd(const float* logits, const float* gpred, float* glogits, float* workspace, int B, int D4, int H4,
+                             int W4, int D, int H, int W, mode_stream_t stream) {
+  HDims d;
+  int rc = make_hdims(d, B, D4, H4, W4, D, H, W, "mode_head_bwd");
+  if (rc != MODE_OK) return rc;
+  if (B == 0) return MODE_OK;
+  MODE_REQUIRE(logits && gpred && glogits, MODE_ERR_BAD_ARG, "mode_head_bwd: null pointer");
+  MODE_REQUIRE(workspace, MODE_ERR_WORKSPACE, "mode_head_bwd: workspace required");
+  return head_bwd_run<false>(logits, gpred, HeadConfArgs{nullptr, nullptr, nullptr}, glogits, workspace, d, mode::as_stream(stream));
+}
+
+// The head's backward with the confidence map's gradient (see include/mode_hip.h): one pass over the pixels for both outputs.
+extern "C" int mode_head_bwd_conf(const float* logits, const float* pred, const float* conf, const float* gpred, const float* gconf,
+                                  float* glogits, float* workspace, int B, int D4, int H4, int W4, int D, int H, int W,
+                                  mode_stream_t stream) {
+  HDims d;
+  int rc = make_hdims(d, B, D4, H4, W4, D, H, W, "mode_head_bwd_conf");
+  if (rc != MODE_OK) return rc;
+  if (B == 0) return MODE_OK;
+  MODE_REQUIRE(logits && pred && conf && gpred && gconf && glogits, MODE_ERR_BAD_ARG, "mode_head_bwd_conf: null pointer");
+  MODE_REQUIRE(workspace, MODE_ERR_WORKSPACE, "mode_head_bwd_conf: workspace required");
+  return head_bwd_run<true>(logits, gpred, HeadConfArgs{pred, conf, gconf}, glogits, workspace, d, mode::as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -180,6 +180,39 @@ __global__ __launch_bounds__(NT) void decimate2_kernel(const float* __restrict__
   }
 }
 
+// The adjoint of decimate2: gin[n, y, x] = gout[n, y / 2, x / 2] where y and x are both even, +0 elsewhere.  One thread per four
+// consecutive elements of gin taken as one flat array (a quad may straddle rows and planes: any H and W); kVec (16-byte aligned gin):
+// one 16-byte store per whole quad, single stores for the last, partial one.
+template <bool kVec>
+__global__ __launch_bounds__(NT) void decimate2_bwd_kernel(const float* __restrict__ gout, float* __restrict__ gin, long long total, int H,
+                                                           int W) {
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const long long quads = (total + 3) / 4;
+  for (long long q = (long long)blockIdx.x * NT + threadIdx.x; q < quads; q += (long long)gridDim.x * NT) {
+    const long long i0 = 4 * q;
+    long long row = i0 / W;  // n * H + y
+    int x = (int)(i0 - row * W);
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int y = (int)(row % H);
+      const long long n = row / H;
+      v[e] = (i0 + e < total && !((x | y) & 1)) ? gout[(n * Ho + (y >> 1)) * Wo + (x >> 1)] : 0.f;
+      if (++x == W) {
+        x = 0;
+        ++row;
+      }
+    }
+    if (kVec && i0 + 4 <= total) {
+      *reinterpret_cast<float4*>(gin + i0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (i0 + e < total) gin[i0 + e] = v[e];
+    }
+  }
+}
+
 int grid_for(long long n) { return (int)std::min<long long>(std::max<long long>((n + NT - 1) / NT, 1), 8LL * kNumCU); }
 
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
@@ -238,5 +271,21 @@ extern "C" int mode_decimate2(const float* in, float* out, long long planes, int
     hipLaunchKernelGGL(decimate2_kernel<true>, dim3(grid_for(planes * Ho * (W / 4))), dim3(NT), 0, st, in, out, planes, H, W);
   else
     hipLaunchKernelGGL(decimate2_kernel<false>, dim3(grid_for(planes * Ho * Wo)), dim3(NT), 0, st, in, out, planes, H, W);
+  return mode::check_launch(who);
+}
+
+extern "C" int mode_decimate2_bwd(const float* gout, float* gin, long long planes, int H, int W, mode_stream_t stream) {
+  const char* who = "mode_decimate2_bwd";
+  MODE_REQUIRE(planes >= 0 && H > 0 && W > 0, MODE_ERR_BAD_ARG, "%s: bad size %lld x %d x %d", who, planes, H, W);
+  MODE_REQUIRE(fits31(planes, H, W, 1), MODE_ERR_BAD_ARG, "%s: bad size %lld x %d x %d (too large)", who, planes, H, W);
+  if (planes == 0) return MODE_OK;
+  MODE_REQUIRE(gout && gin, MODE_ERR_BAD_ARG, "%s: null pointer", who);
+  MODE_REQUIRE(gout != gin, MODE_ERR_BAD_ARG, "%s: in-place operation is not possible", who);
+  const long long total = planes * H * W;
+  hipStream_t st = mode::as_stream(stream);
+  if (aligned(gin, 16))
+    hipLaunchKernelGGL(decimate2_bwd_kernel<true>, dim3(grid_for((total + 3) / 4)), dim3(NT), 0, st, gout, gin, total, H, W);
+  else
+    hipLaunchKernelGGL(decimate2_bwd_kernel<false>, dim3(grid_for((total + 3) / 4)), dim3(NT), 0, st, gout, gin, total, H, W);
   return mode::check_launch(who);
 }

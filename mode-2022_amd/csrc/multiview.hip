@@ -90,7 +90,12 @@ __global__ __launch_bounds__(NT) void mv_resolve_kernel(const unsigned long long
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The gradient of the hand-off's depth channels with respect to the disparities (mode_multiview_handoff_bwd, DESIGN 12 "Gradient").
-// The confidence channels have none: q is piecewise constant and the head's confidence map has no backward either.
+// The confidence channels are not read there.  With q the identity they are linear in the confidence maps, and FULL
+// (mode_multiview_handoff_bwd_full, DESIGN 12 "Gradient of the confidence") writes that gradient beside gdisp in the same two launches:
+// the copy (12), the same walk over the adjoint list with the confidence channel's upstream gradient (13, 14; for EVERY source: the
+// confidence does not depend on the disparity), the target's gradient to the winner of its key (23, 24, 34; capped winners and
+// winners without a slope included: geom::resolve_key passes their confidence on).  Under MODE_MV_CONF_PNG q is piecewise constant
+// and there is no such gradient: the entry refuses it.
 //   launch A  one thread per SOURCE pixel of the F x 6 maps: planes 12, 13, 14 get their value, planes 23, 24, 34 get +0
 //   launch B  one thread per TARGET pixel of the F x 3 view-transformed maps: the winner of its key gets the target's gradient
 // A source bids for one target, so it wins at most one: launch B's stores never collide, and no sum is formed with atomics.
@@ -118,44 +123,50 @@ __device__ __forceinline__ float sine_rule_slope(float d, int j, int W, float ba
   return -(pi_f / (float)W) * baseline * cosf(phi_l) / (s * s);
 }
 
+template <bool FULL>
 __global__ __launch_bounds__(NT) void mv_bwd_sources_kernel(const float* __restrict__ disp, const float* __restrict__ gout,
                                                             const int* __restrict__ rowptr, const int* __restrict__ target,
                                                             const float* __restrict__ weight, int n_adj, float* __restrict__ gdisp,
-                                                            int F, int H, int W, MvArgs a) {
+                                                            int F, int H, int W, MvArgs a, float* __restrict__ gconf) {
   const long long hw = (long long)H * W;
   const long long total = (long long)F * 6 * hw;
   for (long long idx = (long long)blockIdx.x * NT + threadIdx.x; idx < total; idx += (long long)gridDim.x * NT) {
     const long long plane = idx / hw;  // f * 6 + p
     const long long pix = idx - plane * hw;
     const int p = (int)(plane % 6);
-    float g = 0.f;  // pairs 23, 24, 34: launch B fills the winners in
+    float g = 0.f, gc = 0.f;  // pairs 23, 24, 34: launch B fills the winners in
     if (p < 3) {
       const int j = (int)(pix % W);
       const float s = sine_rule_slope(disp[idx], j, W, a.baseline[p]);
-      if (s != 0.f) {
-        const float* gd = gout + plane * a.oc * hw;  // gout[f, oc * p]
-        if (p == 0) {
-          g = gd[pix] * s;
-        } else {
-          // the (target, weight) entries of the rotation grid whose corner this source is, in the list's stored order
-          const int* rp = rowptr + (p - 1) * (hw + 1) + pix;
-          const int k0 = max(rp[0], 0), k1 = min(rp[1], n_adj);
-          float acc = 0.f;
-          for (int k = k0; k < k1; ++k) {
-            const int t = target[k];
-            if ((unsigned)t < (unsigned)hw) acc += weight[k] * gd[t];
+      const float* gd = gout + plane * a.oc * hw;  // gout[f, oc * p]; FULL (oc = 2): gd + hw = gout[f, 2p + 1]
+      if (p == 0) {
+        if (s != 0.f) g = gd[pix] * s;
+        if (FULL) gc = gd[hw + pix];
+      } else if (FULL || s != 0.f) {
+        // the (target, weight) entries of the rotation grid whose corner this source is, in the list's stored order
+        const int* rp = rowptr + (p - 1) * (hw + 1) + pix;
+        const int k0 = max(rp[0], 0), k1 = min(rp[1], n_adj);
+        float acc = 0.f;
+        for (int k = k0; k < k1; ++k) {
+          const int t = target[k];
+          if ((unsigned)t < (unsigned)hw) {
+            acc += weight[k] * gd[t];
+            if (FULL) gc += weight[k] * gd[hw + t];
           }
-          g = s * acc;
         }
+        if (s != 0.f) g = s * acc;
       }
     }
     gdisp[idx] = g;
+    if (FULL) gconf[idx] = gc;
   }
 }
 
+template <bool FULL>
 __global__ __launch_bounds__(NT) void mv_bwd_winners_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ disp,
                                                             const float* __restrict__ gout, const float* __restrict__ trig,
-                                                            float* __restrict__ gdisp, int F, int H, int W, MvArgs a) {
+                                                            float* __restrict__ gdisp, int F, int H, int W, MvArgs a,
+                                                            float* __restrict__ gconf) {
 #pragma clang fp contract(off)  // r2 as geom::project_pixel rounds it
   const long long hw = (long long)H * W;
   const long long total = (long long)F * 3 * hw;
@@ -163,7 +174,9 @@ __global__ __launch_bounds__(NT) void mv_bwd_winners_kernel(const unsigned long 
     const unsigned long long k = keys[idx];
     if (k == ~0ull) continue;  // no source reached this target
     const float v = __uint_as_float((unsigned)(k >> 32));
-    if (v > 1000.f) continue;  // geom::resolve_key: capped (strictly above; its 100000 -> 0 rule lies above the cap too): a constant
+    // geom::resolve_key: capped (strictly above; its 100000 -> 0 rule lies above the cap too): a constant depth.  Its confidence is
+    // the winner's all the same, so FULL decodes the winner first.
+    if (!FULL && v > 1000.f) continue;
     const unsigned lo = (unsigned)(k & 0xffffffffull);
     const long long src = (lo & 0x80000000u) ? (long long)(lo & 0x7fffffffu) : hw - 1 - (long long)lo;
     if (src < 0 || src >= hw) continue;  // (not a key of this size's forward)
@@ -171,6 +184,10 @@ __global__ __launch_bounds__(NT) void mv_bwd_winners_kernel(const unsigned long 
     const long long pix = idx - kp * hw;
     const int v3 = (int)(kp % 3);
     const long long plane = (kp / 3) * 6 + 3 + v3;  // f * 6 + p
+    if (FULL) {
+      gconf[plane * hw + src] = gout[(plane * 2 + 1) * hw + pix];
+      if (v > 1000.f) continue;
+    }
     const int i = (int)(src / W), j = (int)(src - (long long)i * W);
     const float baseline = a.baseline[3 + v3];
     const float d = disp[plane * hw + src];
@@ -229,34 +246,58 @@ extern "C" int mode_multiview_handoff(const float* disp, const float* conf, int 
   return mode::check_launch("mode_multiview_handoff");
 }
 
-extern "C" int mode_multiview_handoff_bwd(const float* disp, const float* gout, const void* keys, int F, int H, int W,
-                                          const float* baselines6, const float* trig, const double* xforms, const int32_t* adj_rowptr,
-                                          const int32_t* adj_target, const float* adj_weight, int n_adj, int flags, float* gdisp,
-                                          mode_stream_t stream) {
-  MODE_REQUIRE(F >= 0 && H > 0 && W > 0 && 3LL * F * H * W < (1LL << 31), MODE_ERR_BAD_ARG,
-               "mode_multiview_handoff_bwd: bad size %d x %dx%d", F, H, W);
-  MODE_REQUIRE((flags & ~(MODE_MV_CONF_PNG | MODE_MV_DEPTH_ONLY)) == 0, MODE_ERR_BAD_ARG, "mode_multiview_handoff_bwd: unknown flags 0x%x",
-               flags);
-  MODE_REQUIRE(n_adj >= 0 && n_adj <= 8LL * H * W, MODE_ERR_BAD_ARG, "mode_multiview_handoff_bwd: %d adjoint entries for two %dx%d grids",
-               n_adj, H, W);
+namespace {
+
+// mode_multiview_handoff_bwd (FULL = false, gconf unread) and mode_multiview_handoff_bwd_full: the same checks and the same two launches
+template <bool FULL>
+int handoff_bwd_run(const char* who, const float* disp, const float* gout, const void* keys, int F, int H, int W, const float* baselines6,
+                    const float* trig, const double* xforms, const int32_t* adj_rowptr, const int32_t* adj_target,
+                    const float* adj_weight, int n_adj, int flags, float* gdisp, float* gconf, mode_stream_t stream) {
+  MODE_REQUIRE(F >= 0 && H > 0 && W > 0 && 3LL * F * H * W < (1LL << 31), MODE_ERR_BAD_ARG, "%s: bad size %d x %dx%d", who, F, H, W);
+  MODE_REQUIRE((flags & ~(MODE_MV_CONF_PNG | MODE_MV_DEPTH_ONLY)) == 0, MODE_ERR_BAD_ARG, "%s: unknown flags 0x%x", who, flags);
+  if (FULL) {
+    MODE_REQUIRE(!(flags & MODE_MV_DEPTH_ONLY), MODE_ERR_BAD_ARG, "%s: MODE_MV_DEPTH_ONLY has no confidence channels", who);
+    MODE_REQUIRE(!(flags & MODE_MV_CONF_PNG), MODE_ERR_BAD_ARG,
+                 "%s: MODE_MV_CONF_PNG rounds the confidence to 8 bits, which is piecewise constant: it has no gradient", who);
+  }
+  MODE_REQUIRE(n_adj >= 0 && n_adj <= 8LL * H * W, MODE_ERR_BAD_ARG, "%s: %d adjoint entries for two %dx%d grids", who, n_adj, H, W);
   if (F == 0) return MODE_OK;
-  MODE_REQUIRE(disp && gout && baselines6 && trig && xforms && adj_rowptr && gdisp && (n_adj == 0 || (adj_target && adj_weight)),
-               MODE_ERR_BAD_ARG, "mode_multiview_handoff_bwd: null pointer");
-  MODE_REQUIRE(keys, MODE_ERR_WORKSPACE, "mode_multiview_handoff_bwd: the forward's key planes are required");
-  MODE_REQUIRE((reinterpret_cast<uintptr_t>(keys) & 7) == 0, MODE_ERR_WORKSPACE, "mode_multiview_handoff_bwd: unaligned key planes");
+  MODE_REQUIRE(disp && gout && baselines6 && trig && xforms && adj_rowptr && gdisp && (!FULL || gconf) &&
+                   (n_adj == 0 || (adj_target && adj_weight)),
+               MODE_ERR_BAD_ARG, "%s: null pointer", who);
+  MODE_REQUIRE(keys, MODE_ERR_WORKSPACE, "%s: the forward's key planes are required", who);
+  MODE_REQUIRE((reinterpret_cast<uintptr_t>(keys) & 7) == 0, MODE_ERR_WORKSPACE, "%s: unaligned key planes", who);
   MvArgs a;
   for (int p = 0; p < 6; ++p) a.baseline[p] = baselines6[p];
   for (int v = 0; v < 3; ++v) {
     for (int k = 0; k < 9; ++k) a.xf[v].R[k] = xforms[12 * v + k];
     for (int k = 0; k < 3; ++k) a.xf[v].t[k] = xforms[12 * v + 9 + k];
   }
-  a.png = 0;  // (the confidence channels of gout are not read)
+  a.png = 0;  // (q is the identity wherever the confidence channels of gout are read)
   a.oc = (flags & MODE_MV_DEPTH_ONLY) ? 1 : 2;
   hipStream_t st = mode::as_stream(stream);
   const long long hw = (long long)H * W;
-  hipLaunchKernelGGL(mv_bwd_sources_kernel, dim3(grid_for(6LL * F * hw)), dim3(NT), 0, st, disp, gout, adj_rowptr, adj_target, adj_weight,
-                     n_adj, gdisp, F, H, W, a);
-  hipLaunchKernelGGL(mv_bwd_winners_kernel, dim3(grid_for(3LL * F * hw)), dim3(NT), 0, st, reinterpret_cast<const unsigned long long*>(keys),
-                     disp, gout, trig, gdisp, F, H, W, a);
-  return mode::check_launch("mode_multiview_handoff_bwd");
+  hipLaunchKernelGGL(mv_bwd_sources_kernel<FULL>, dim3(grid_for(6LL * F * hw)), dim3(NT), 0, st, disp, gout, adj_rowptr, adj_target,
+                     adj_weight, n_adj, gdisp, F, H, W, a, gconf);
+  hipLaunchKernelGGL(mv_bwd_winners_kernel<FULL>, dim3(grid_for(3LL * F * hw)), dim3(NT), 0, st,
+                     reinterpret_cast<const unsigned long long*>(keys), disp, gout, trig, gdisp, F, H, W, a, gconf);
+  return mode::check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int mode_multiview_handoff_bwd(const float* disp, const float* gout, const void* keys, int F, int H, int W,
+                                          const float* baselines6, const float* trig, const double* xforms, const int32_t* adj_rowptr,
+                                          const int32_t* adj_target, const float* adj_weight, int n_adj, int flags, float* gdisp,
+                                          mode_stream_t stream) {
+  return handoff_bwd_run<false>("mode_multiview_handoff_bwd", disp, gout, keys, F, H, W, baselines6, trig, xforms, adj_rowptr, adj_target,
+                                adj_weight, n_adj, flags, gdisp, nullptr, stream);
+}
+
+extern "C" int mode_multiview_handoff_bwd_full(const float* disp, const float* gout, const void* keys, int F, int H, int W,
+                                               const float* baselines6, const float* trig, const double* xforms,
+                                               const int32_t* adj_rowptr, const int32_t* adj_target, const float* adj_weight, int n_adj,
+                                               int flags, float* gdisp, float* gconf, mode_stream_t stream) {
+  return handoff_bwd_run<true>("mode_multiview_handoff_bwd_full", disp, gout, keys, F, H, W, baselines6, trig, xforms, adj_rowptr,
+                               adj_target, adj_weight, n_adj, flags, gdisp, gconf, stream);
 }

@@ -130,6 +130,7 @@ SIGNATURES = {
     'mode_head_fwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr]),
     'mode_head_bwd_workspace_bytes': (_c_size, [_c_int] * 4),
     'mode_head_bwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
+    'mode_head_bwd_conf': (_c_int, [_c_ptr] * 7 + [_c_int] * 7 + [_c_ptr]),
     'mode_smooth_l1_workspace_bytes': (_c_size, [ctypes.c_longlong]),
     'mode_smooth_l1_masked': (_c_int, [_c_ptr] * 4 + [ctypes.c_float] * 3 + [_c_ptr] * 3 + [ctypes.c_longlong, _c_ptr]),
     'mode_head_loss_supported': (_c_int, [_c_int] * 7),
@@ -144,6 +145,7 @@ SIGNATURES = {
     'mode_multiview_handoff_workspace_bytes': (_c_size, [_c_int] * 3),
     'mode_multiview_handoff': (_c_int, [_c_ptr] * 2 + [_c_int] * 3 + [_c_ptr] * 4 + [_c_int] + [_c_ptr] * 3),
     'mode_multiview_handoff_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr] * 6 + [_c_int] * 2 + [_c_ptr] * 2),
+    'mode_multiview_handoff_bwd_full': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr] * 6 + [_c_int] * 2 + [_c_ptr] * 3),
     'mode_classif_workspace_bytes': (_c_size, [_c_int] * 5),
     'mode_classif_train_fwd': (_c_int, [_c_ptr] * 6 + [ctypes.c_float] * 2 + [_c_ptr] * 8 + [_c_int] * 5 + [_c_ptr]),
     'mode_classif_train_bwd': (_c_int, [_c_ptr] * 13 + [_c_int] + [_c_ptr] + [_c_int] * 5 + [_c_ptr]),
@@ -182,6 +184,7 @@ SIGNATURES = {
     'mode_frames_u8_ingest': (_c_int, [_c_ptr] * 2 + [_c_int] * 3 + [_c_ptr] * 4),
     'mode_rgb_half_pil': (_c_int, [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr] * 3),
     'mode_decimate2': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
+    'mode_decimate2_bwd': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
     # 3D60 ingest: ERP pairs and depth to rectified Cassini (csrc/erp_ingest.hip; reference dataloader/dataset3D60Loader.py:123-270)
     'mode_erp_pairs_u8_cassini': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr] * 6),
     'mode_erp_depth_disp': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 3),

@@ -1749,6 +1749,54 @@ def head(logits, size):
   return HeadFunction.apply(logits, size)
 
 
+def head_bwd_conf(logits, pred, conf, gpred, gconf, size):
+  """The gradient of head_fwd(logits, size, with_confidence=True) = (pred, conf) with respect to the logits for the upstream gradients
+  (gpred, gconf), in the launches of head_bwd (mode_head_bwd_conf): pred and conf are the forward's own outputs, the rounding that
+  places the confidence window passes no gradient."""
+  require_gpu(logits, pred, conf, gpred, gconf)
+  logits, pred, conf, gpred, gconf = [t.contiguous() for t in (logits, pred, conf, gpred, gconf)]
+  require_f32c(logits, pred, conf, gpred, gconf)
+  B, _, D4, H4, W4 = logits.shape
+  D, H, W = size
+  for name, t in (('pred', pred), ('conf', conf), ('gpred', gpred), ('gconf', gconf)):
+    if t.numel() != B * H * W:
+      raise ValueError('head_bwd_conf: %s %s is not (B, 1, H, W) = %s' % (name, tuple(t.shape), (B, 1, H, W)))
+  gl = torch.empty_like(logits)
+  nbytes = 4 * (2 * logits.numel() + 4 * gpred.numel())
+  with torch.cuda.device_of(logits), profiling.region(_tag_head('head_bwd_conf', D4, H, W), nbytes, 0, logits.device):
+    n = lib().mode_head_bwd_workspace_bytes(B, D4, H, W)
+    ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=logits.device)
+    check(lib().mode_head_bwd_conf(ptr(logits), ptr(pred), ptr(conf), ptr(gpred), ptr(gconf), ptr(gl), ptr(ws), B, D4, H4, W4, D, H, W,
+                                   stream_of(logits)), 'mode_head_bwd_conf')
+  return gl
+
+
+class HeadConfFunction(torch.autograd.Function):
+  """(pred, conf) = head_fwd(logits, size, with_confidence=True) as ONE node: one head pass forward, one backward for both outputs."""
+
+  @staticmethod
+  def forward(ctx, logits, size):
+    pred, conf = head_fwd(logits, size, with_confidence=True)
+    ctx.save_for_backward(logits, pred, conf)
+    ctx.size = tuple(size)
+    return pred, conf
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable  # (the kernel has no second derivative)
+  def backward(ctx, gpred, gconf):
+    logits, pred, conf = ctx.saved_tensors
+    gpred = torch.zeros_like(pred) if gpred is None else gpred  # an output that nothing downstream used
+    gconf = torch.zeros_like(conf) if gconf is None else gconf
+    return head_bwd_conf(logits, pred, conf, gpred, gconf, ctx.size), None
+
+
+def head_conf(logits, size):
+  """logits (B, 1, D/4, H/4, W/4) -> (pred, conf) (B, 1, H, W) each, the bits of head_fwd(..., with_confidence=True), differentiable in
+  the logits through BOTH outputs (mode_head_bwd_conf; models/mode_disparity.py:157-183 is differentiable in the probability volume:
+  grid_sample(mode='nearest') passes the gradient to its input, round(pred) passes none)."""
+  return HeadConfFunction.apply(logits, size)
+
+
 # ------------------------------------------------------------------------------------ the three heads + the training loss, fused
 # train_disparity.py:151-158: loss = 0.5 sl1(pred1[mask], gt[mask]) + 0.7 sl1(pred2[mask], ...) + sl1(pred3[mask], ...), smooth-L1 with
 # mean reduction over the valid pixels.  As torch ops on the three (B, 1, H, W) maps that is ~25 small elementwise launches forward
@@ -2002,18 +2050,52 @@ def rgb_half_pil(frames_u8, tab_w, tab_h, lut, return_u8=False):
   return (out, u8) if return_u8 else out
 
 
-def decimate2(x):
-  """x[..., ::2, ::2] of a contiguous float32 (..., H, W) tensor, contiguous, on mode_decimate2 (the reference loader's --resize
-  subsampling of the depth and confidence maps, dataloader/deep360_loader.py:147-150)."""
-  require_gpu(x)
-  require_f32c(x)
-  if x.dim() < 2 or 0 in x.shape[-2:]:
-    raise ValueError('decimate2: expected a (..., H, W) tensor with H, W > 0, got %s' % (tuple(x.shape),))
+def _decimate2_fwd(x):
   H, W = x.shape[-2:]
   y = torch.empty(tuple(x.shape[:-2]) + ((H + 1) // 2, (W + 1) // 2), dtype=x.dtype, device=x.device)
   with torch.cuda.device_of(x), profiling.region('decimate2', 4 * (x.numel() // 2 + y.numel()), 0, x.device):
     check(lib().mode_decimate2(ptr(x), ptr(y), x.numel() // (H * W), H, W, stream_of(x)), 'mode_decimate2')
   return y
+
+
+def decimate2_bwd(gy, shape):
+  """The adjoint of decimate2 for an input of `shape` (..., H, W): gy in the even rows and columns, +0.0 elsewhere (mode_decimate2_bwd)."""
+  require_gpu(gy)
+  gy = gy.contiguous()
+  require_f32c(gy)
+  H, W = shape[-2:]
+  if tuple(gy.shape) != tuple(shape[:-2]) + ((H + 1) // 2, (W + 1) // 2):
+    raise ValueError('decimate2_bwd: gradient %s does not belong to an input of shape %s' % (tuple(gy.shape), tuple(shape)))
+  gx = torch.empty(tuple(shape), dtype=gy.dtype, device=gy.device)
+  with torch.cuda.device_of(gy), profiling.region('decimate2_bwd', 4 * (gy.numel() + gx.numel()), 0, gy.device):
+    check(lib().mode_decimate2_bwd(ptr(gy), ptr(gx), gx.numel() // (H * W), H, W, stream_of(gy)), 'mode_decimate2_bwd')
+  return gx
+
+
+class Decimate2Function(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, x):
+    ctx.shape = tuple(x.shape)
+    return _decimate2_fwd(x)
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, gy):
+    return decimate2_bwd(gy, ctx.shape)
+
+
+def decimate2(x):
+  """x[..., ::2, ::2] of a contiguous float32 (..., H, W) tensor, contiguous, on mode_decimate2 (the reference loader's --resize
+  subsampling of the depth and confidence maps, dataloader/deep360_loader.py:147-150).  Differentiable where x requires a gradient
+  (mode_decimate2_bwd); the values are the same either way."""
+  require_gpu(x)
+  require_f32c(x)
+  if x.dim() < 2 or 0 in x.shape[-2:]:
+    raise ValueError('decimate2: expected a (..., H, W) tensor with H, W > 0, got %s' % (tuple(x.shape),))
+  if torch.is_grad_enabled() and x.requires_grad:
+    return Decimate2Function.apply(x)
+  return _decimate2_fwd(x)
 
 
 # ------------------------------------------------------------------------------------ 3D60 ingest: ERP -> rectified Cassini

@@ -73,11 +73,20 @@ def _state_dict_of(src):
 
 class ModeMultiView(nn.Module):
   """Both MODE stages on whole frames.  Children: `disparity` (ModeDisparity with the confidence output) and `fusion` (ModeFusion,
-  or Baseline with fusion='Baseline'), so the state_dict is theirs under the prefixes 'disparity.' and 'fusion.'."""
+  or Baseline with fusion='Baseline'), so the state_dict is theirs under the prefixes 'disparity.' and 'fusion.'.
+  handoff_grad selects what fusion_loss fine-tunes stage 1 through when disparity.train(): 'depth' (the default) the depth channels of the
+  hand-off alone; 'full' the confidence channels as well (needs conf_png=False with ModeFusion) and, with resize=True, the decimation.
+  It changes nothing else: forward(), evaluate(), fusion_loss with disparity.eval() and the state_dict do not depend on it."""
 
   def __init__(self, maxdisp=192, maxdepth=1000., height=1024, width=512, dbname='Deep360', fusion='ModeFusion',
-               channels=(32, 64, 128, 256), conf_png=True, resize=False):
+               channels=(32, 64, 128, 256), conf_png=True, resize=False, handoff_grad='depth'):
     super(ModeMultiView, self).__init__()
+    if handoff_grad not in ('depth', 'full'):
+      raise ValueError("ModeMultiView: handoff_grad must be 'depth' or 'full', not %r" % (handoff_grad,))
+    if handoff_grad == 'full' and fusion == 'ModeFusion' and conf_png:
+      raise ValueError("ModeMultiView(handoff_grad='full') needs conf_png=False: with conf_png=True the fusion network reads the confidence "
+                       'through the rounding to 8 bits of the PNG export, which is piecewise constant and passes no gradient')
+    self.handoff_grad = handoff_grad
     if height % 16 or width % 16:
       raise ValueError('ModeMultiView: %d x %d is not a multiple of 16 (the reference pads to 16; this module does not)' % (height, width))
     if fusion not in ('ModeFusion', 'Baseline'):
@@ -182,21 +191,29 @@ class ModeMultiView(nn.Module):
       disparity.train()  joint fine-tuning: the disparity of the third head with its gradient (BatchNorm on the statistics of the batch
                          of 6F pairs), the confidence from the same logits without one, and the gradient of the loss reaches every
                          stage-1 parameter through the hand-off's backward (utils.geometry.disp2depth_frames_gpu).  resize=True is
-                         refused: the decimation has no backward.
+                         refused under handoff_grad='depth', where the decimation has no backward.
+                         handoff_grad='full': disparity and confidence from ONE head pass with a gradient for both
+                         (HF.head_conf), the hand-off with conf_grad=True, and resize=True is taken through the differentiable
+                         HF.decimate2 (the halving of the 8-bit RGB needs no backward: the frames are data).
     forward() and evaluate() stay inference only."""
     if not self.fusion.training:
       raise RuntimeError('ModeMultiView.fusion_loss is the training step of the fusion network: call .train() first '
                          '(.disparity.eval() afterwards keeps stage 1 frozen)')
     joint = self.disparity.training
-    if joint and self.resize:
-      raise ValueError('ModeMultiView(resize=True).fusion_loss cannot fine-tune the disparity stage: the decimation of the hand-off has '
-                       'no backward; call .disparity.eval() to train the fusion network alone')
+    full = joint and self.handoff_grad == 'full'
+    if joint and self.resize and not full:
+      raise ValueError("ModeMultiView(resize=True, handoff_grad='depth').fusion_loss cannot fine-tune the disparity stage: on this path "
+                       "the decimation of the hand-off has no backward; build the module with handoff_grad='full', or call "
+                       '.disparity.eval() to train the fusion network alone')
     left, right, rgb, want_rgb = self._ingest(frames)
     require_gpu(gt)
     H, W = left.shape[-2:]
     if tuple(gt.shape) != (left.shape[0] // 6, H, W):
       raise ValueError('ModeMultiView.fusion_loss: gt %s is not (F, H, W) = %s' % (tuple(gt.shape), (left.shape[0] // 6, H, W)))
-    if joint:
+    if full:
+      size = (self.disparity.maxdisp, H, W)
+      disp, conf = HF.head_conf(self.disparity._logits(left, right)[2], size)
+    elif joint:
       size = (self.disparity.maxdisp, H, W)
       cost3 = self.disparity._logits(left, right)[2]
       disp = HF.head(cost3, size)
@@ -204,7 +221,9 @@ class ModeMultiView(nn.Module):
     else:
       with torch.no_grad():
         disp, conf = self.disparity(left, right)
-    fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png, depth_only=self.fusion_kind == 'Baseline')
+    depth_only = self.fusion_kind == 'Baseline'
+    fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png, depth_only=depth_only,
+                                                  conf_grad=full and not depth_only)
     if self.resize:  # deep360_loader.py:146-155 with training=True
       fusion_input = HF.decimate2(fusion_input)
       rgb = gpu_ingest.rgb_half_gpu(frames.contiguous()) if want_rgb else None

@@ -425,11 +425,13 @@ def _handoff_fwd(disp, conf, dbname, conf_png, depth_only):
   return out, ws.view(F, 3, H, W)
 
 
-def disp2depth_frames_bwd(disp, gout, keys, dbname='Deep360', depth_only=False):
+def disp2depth_frames_bwd(disp, gout, keys, dbname='Deep360', depth_only=False, conf_grad=False):
   """The gradient of disp2depth_frames_gpu's depth channels with respect to disp (mode_multiview_handoff_bwd): disp (F, 6, H, W) or one
   of the views the forward takes, gout the gradient of the output in its layout, keys the key planes of the forward on the same disp (return_keys) -> gdisp (F, 6, H, W).
-  The confidence channels of gout are ignored and the confidence gets no gradient: q(c) is piecewise constant, and the head's
-  confidence map has no backward either.  Bit-repeatable: sums over the cached adjoint lists in their stored order, no atomics."""
+  The confidence channels of gout are not read.  conf_grad=True (the forward with conf_png=False: q the identity) -> (gdisp, gconf):
+  the gradient with respect to the confidence maps as well, from the confidence channels of gout, in the same two launches
+  (mode_multiview_handoff_bwd_full; gdisp has the same bits; gconf is None with depth_only, which has no confidence channels).
+  Bit-repeatable: sums over the cached adjoint lists in their stored order, no atomics."""
   require_gpu(disp, gout, keys)
   disp, gout, keys = _as_frames(disp.contiguous(), 'disp'), gout.contiguous(), keys.contiguous()
   require_f32c(disp, gout)
@@ -440,21 +442,29 @@ def disp2depth_frames_bwd(disp, gout, keys, dbname='Deep360', depth_only=False):
   baselines, _, trig, xforms = _frames_tables(H, W, disp.device, dbname)
   rowptr, target, weight = _frames_adjoint(H, W, disp.device)
   gdisp = torch.empty_like(disp)
+  if conf_grad and not depth_only:
+    gconf = torch.empty_like(disp)
+    with torch.cuda.device_of(disp):
+      check(lib().mode_multiview_handoff_bwd_full(ptr(disp), ptr(gout), ptr(keys), F, H, W, baselines.ctypes.data, ptr(trig),
+                                                  xforms.ctypes.data, ptr(rowptr), ptr(target), ptr(weight), target.numel(), 0, ptr(gdisp),
+                                                  ptr(gconf), stream_of(disp)), 'mode_multiview_handoff_bwd_full')
+    return gdisp, gconf
   with torch.cuda.device_of(disp):
     check(lib().mode_multiview_handoff_bwd(ptr(disp), ptr(gout), ptr(keys), F, H, W, baselines.ctypes.data, ptr(trig), xforms.ctypes.data,
                                            ptr(rowptr), ptr(target), ptr(weight), target.numel(), MV_DEPTH_ONLY if depth_only else 0,
                                            ptr(gdisp), stream_of(disp)), 'mode_multiview_handoff_bwd')
-  return gdisp
+  return (gdisp, None) if conf_grad else gdisp
 
 
 class _HandoffFunction(torch.autograd.Function):
-  """disp2depth_frames_gpu with a gradient for disp: the forward's launches and bits, disp and the key planes kept for the backward."""
+  """disp2depth_frames_gpu with a gradient for disp (and, with conf_grad, for conf): the forward's launches and bits, disp and the key
+  planes kept for the backward."""
 
   @staticmethod
-  def forward(ctx, disp, conf, dbname, conf_png, depth_only):
+  def forward(ctx, disp, conf, dbname, conf_png, depth_only, conf_grad=False):
     out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only)
     ctx.save_for_backward(disp, keys)
-    ctx.dbname, ctx.depth_only = dbname, depth_only
+    ctx.dbname, ctx.depth_only, ctx.conf_grad = dbname, depth_only, conf_grad
     ctx.mark_non_differentiable(keys)
     return out, keys
 
@@ -462,11 +472,14 @@ class _HandoffFunction(torch.autograd.Function):
   @once_differentiable  # (the kernel has no second derivative: create_graph=True raises instead of returning a detached gradient)
   def backward(ctx, gout, _gkeys):
     disp, keys = ctx.saved_tensors
+    if ctx.conf_grad and not ctx.depth_only and ctx.needs_input_grad[1]:
+      gdisp, gconf = disp2depth_frames_bwd(disp, gout, keys, ctx.dbname, conf_grad=True)
+      return (gdisp if ctx.needs_input_grad[0] else None), gconf, None, None, None, None
     gdisp = disp2depth_frames_bwd(disp, gout, keys, ctx.dbname, ctx.depth_only) if ctx.needs_input_grad[0] else None
-    return gdisp, None, None, None, None
+    return gdisp, None, None, None, None, None
 
 
-def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_only=False, return_keys=False):
+def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_only=False, return_keys=False, conf_grad=False):
   """The six pairs of F frames at once: disp, conf (F, 6, H, W) float32 device tensors (pair order PAIRS; (6F, 1, H, W) and
   (6F, H, W) are taken as views) -> (F, 12, H, W) with out[f, 2p], out[f, 2p + 1] = disp2depth_gpu(disp[f, p], conf[f, p], PAIRS[p],
   dbname) -- ModeFusion's channel interleave -- bit for bit, in three launches (mode_multiview_handoff).  conf_png: every confidence
@@ -474,16 +487,22 @@ def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_on
   (F, 6, H, W) of the depths alone (the input of Baseline).
 
   Differentiable in disp (disp2depth_frames_bwd): the depth channels pass their gradient through the sine rule, the bilinear taps
-  of the rotation and, for the view-transformed pairs, to the z-buffer's winner alone.  The confidence gets no gradient (None for
-  conf): q(c) is piecewise constant, and the head's confidence map has no backward either.  return_keys: (out, keys) with the forward's
-  z-buffer key planes (F, 3, H, W) int64 (layout: csrc/geometry_internal.h)."""
+  of the rotation and, for the view-transformed pairs, to the z-buffer's winner alone.  By default the confidence gets no gradient
+  (None for conf).  conf_grad=True: conf gets the gradient of the confidence channels too -- they are linear in it: the copy, the
+  rotation's taps, the winner's pick -- from the same two launches (mode_multiview_handoff_bwd_full).  That needs q the identity:
+  with conf_png=True it raises ValueError (the 8-bit rounding is piecewise constant); with depth_only there are no confidence
+  channels and conf gets None.  return_keys: (out, keys) with the forward's z-buffer key planes (F, 3, H, W) int64 (layout:
+  csrc/geometry_internal.h)."""
+  if conf_grad and conf_png:
+    raise ValueError('disp2depth_frames_gpu: conf_grad=True needs conf_png=False: the 8-bit PNG rounding of the confidence is piecewise '
+                     'constant and passes no gradient')
   require_gpu(disp, conf)
   disp, conf = _as_frames(disp.contiguous(), 'disp'), _as_frames(conf.contiguous(), 'conf')
   require_f32c(disp, conf)
   if disp.shape != conf.shape or disp.device != conf.device:
     raise ValueError('disp2depth_frames_gpu: disp %s and conf %s differ' % (tuple(disp.shape), tuple(conf.shape)))
   if torch.is_grad_enabled() and (disp.requires_grad or conf.requires_grad):
-    out, keys = _HandoffFunction.apply(disp, conf, dbname, bool(conf_png), bool(depth_only))
+    out, keys = _HandoffFunction.apply(disp, conf, dbname, bool(conf_png), bool(depth_only), bool(conf_grad))
   else:
     out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only)
   return (out, keys) if return_keys else out

@@ -21,7 +21,10 @@ Host clock around work that ends in a device synchronise; medians in ms.
 
 --train times one ModeMultiView.fusion_loss + backward on one frame (F = 1), with stage 1 frozen (net.train(); net.disparity.eval()) and
 with stage 1 fine-tuned (net.train(), batch statistics at batch 6), and the hand-off's forward and backward alone on the disparities of
-that frame.  Device events around every single call after a warm-up; medians in ms.  One JSON line."""
+that frame.  Device events around every single call after a warm-up; medians in ms.  One JSON line.  It also carries the figures of
+fine-tuning through the confidence (ModeMultiView(handoff_grad='full', conf_png=False)): the head's backward with and without the
+confidence gradient at B = 6, D4 = 48, 1024 x 512, timed alternately (head_bwd_ms, head_bwd_conf_ms), the hand-off's backward for both
+outputs (handoff_bwd_full_ms) and the 'full' step and its peak memory (fine_tuning_full_step_ms, fine_tuning_full_peak_GiB)."""
 import argparse
 import json
 import os
@@ -38,6 +41,7 @@ import torch  # noqa: E402
 import models  # noqa: E402
 import numpy as np  # noqa: E402
 import recipe  # noqa: E402
+from mode_hip import functional as HF  # noqa: E402
 from mode_hip.graph_step import GraphedStep  # noqa: E402
 from models.mode_multiview import split_frames  # noqa: E402
 from utils import evaluation, panorama  # noqa: E402
@@ -82,13 +86,13 @@ def make_frames(F, seed):
   return ((torch.rand(F, 12, 3, H, W, generator=g) - 0.45) / 0.226).to(DEV)
 
 
-def make_net(resize=False):
+def make_net(resize=False, **kw):
   """The well-conditioned full-size disparity fixture with its running statistics (on unit running statistics the eval forward of
   the recipe weights is not finite) and a recipe fusion state."""
   z = np.load(os.path.join(recipe.HERE, 'model_wc_full.npz'))
   sd = recipe.fixture_state(z)
   sd.update({k[3:]: torch.from_numpy(z[k]).clone() for k in z.files if k.startswith('bn/')})
-  net = models.ModeMultiView(MAXDISP, MAXDEPTH, H, W, resize=resize)
+  net = models.ModeMultiView(MAXDISP, MAXDEPTH, H, W, resize=resize, **kw)
   net.disparity.load_state_dict(sd)
   net.fusion.load_state_dict(recipe.recipe_state(recipe.load_manifest('manifest_mode_fusion.json'), 101))
   return net.to(DEV).eval()
@@ -207,7 +211,29 @@ def train_line(reps=10, warmup=2):
   gout = torch.randn_like(out)
   row['handoff_fwd_ms'] = each(lambda: HG.disp2depth_frames_gpu(disp, conf, conf_png=True))
   row['handoff_bwd_ms'] = each(lambda: HG.disp2depth_frames_bwd(disp, gout, keys))
+  row['handoff_bwd_full_ms'] = each(lambda: HG.disp2depth_frames_bwd(disp, gout, keys, conf_grad=True))
   del out, keys, gout, disp, conf
+
+  # the head's backward at the shape of one frame's six pairs, the two entries in turn (A B A B ...), every call between device events
+  size = (MAXDISP, H, W)
+  logits = torch.randn(6, 1, MAXDISP // 4, H // 4, W // 4, device=DEV, generator=torch.Generator(DEV).manual_seed(402)) * 3
+  gp = torch.randn(6, 1, H, W, device=DEV, generator=torch.Generator(DEV).manual_seed(403))
+  gc = torch.randn(6, 1, H, W, device=DEV, generator=torch.Generator(DEV).manual_seed(404))
+  pred, cf = HF.head_fwd(logits, size, with_confidence=True)
+  pair = {'head_bwd_ms': lambda: HF.head_bwd(logits, gp, size), 'head_bwd_conf_ms': lambda: HF.head_bwd_conf(logits, pred, cf, gp, gc, size)}
+  ms = {k: [] for k in pair}
+  for i in range(warmup + 2 * reps):
+    for k, fn in pair.items():
+      s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      s.record()
+      fn()
+      e.record()
+      e.synchronize()
+      if i >= warmup:
+        ms[k].append(s.elapsed_time(e))
+  row.update({k: float(np.median(v)) for k, v in ms.items()})
+  row['head_bwd_conf_over_head_bwd'] = row['head_bwd_conf_ms'] / row['head_bwd_ms']
+  del logits, gp, gc, pred, cf
 
   def step():
     net.zero_grad(set_to_none=True)
@@ -227,6 +253,19 @@ def train_line(reps=10, warmup=2):
   except torch.cuda.OutOfMemoryError as e:
     row['fine_tuning_step_ms'] = None
     row['fine_tuning_error'] = str(e).splitlines()[0]
+  # the same step through the confidence as well: one head pass for both outputs, the hand-off's backward for both
+  del net
+  torch.cuda.empty_cache()
+  net = make_net(conf_png=False, handoff_grad='full')
+  net.train()
+  torch.cuda.reset_peak_memory_stats()
+  try:
+    row['fine_tuning_full_step_ms'] = each(step)
+    row['fine_tuning_full_loss'] = float(step().detach())
+    row['fine_tuning_full_peak_GiB'] = torch.cuda.max_memory_allocated() / 2.0 ** 30
+  except torch.cuda.OutOfMemoryError as e:
+    row['fine_tuning_full_step_ms'] = None
+    row['fine_tuning_full_error'] = str(e).splitlines()[0]
   print(json.dumps(row), flush=True)
   return row
 
