@@ -163,7 +163,8 @@ int mode_sphere_conv_bwd_data_win_split_f16(const float* gy, const float* w, con
                                             int Kw, int groups, int transposed, mode_stream_t stream);
 
 /* Windowed forward (csrc/sphere_conv_win.hip): same result as mode_sphere_conv_fwd for stride 1 and 3x3 taps, ~2x faster on
- * tables whose samples are spatially compact (the gnomonic tables of the network).  The caller plans the table once on the HOST:
+ * tables whose samples are spatially compact (the gnomonic tables of the network).  The caller plans the table once on the HOST
+ * (the mode_sphere_*plan* entries: csrc/sphere_plan.hip, host code only):
  *   mode_sphere_plan_build(pos_host, ...) fills tiles_host[4 * mode_sphere_plan_max_tiles(H, W)] with (h0, w0, rbase, cbase)
  *   per 64x4 tile of output pixels (the window class is packed into bits 16.. of the 4th word) and counts[4] = tiles per
  *   class (81-row window, 145-row window, whole-axis window, does-not-fit).  If counts[3] != 0 the table is not compact: use mode_sphere_conv_fwd.
@@ -428,15 +429,18 @@ int mode_deconv3d_fwd_split(const float* x, const float* w, float* y, float* wpa
 /* The same with the folded eval-mode BatchNorm (+ residual) (+ ReLU) epilogue of mode_deconv3d_fwd_bn (convbn_3d around the
  * ConvTranspose3d of hourglass conv5 / conv6 in eval mode, mode_disparity.py:23-25, 38-45): whole 32-channel output tiles
  * (mode_deconv3d_split_bn_supported(Cin, Cout) == 1); wpack >= mode_conv3d_wpack_bytes(Cin, Cout). */
-/* The arithmetic of the stride-1 3x3x3 layers in a TRAINING step (nn.Conv3d of convbn_3d, models/submodule.py:20-22; the product
- * default since round 5, functional.CONV3D_S1_F16): fp32 operands split into TWO fp16 pieces, three v_mfma_f32_32x32x16_f16 per product
+/* The arithmetic of the stride-1 3x3x3 layers (nn.Conv3d of convbn_3d, models/submodule.py:20-22) in a training step (the product
+ * default since round 5, functional.CONV3D_S1_F16) AND, by default, in an inference forward (mode_conv3d_fwd_split_f16_bn below and
+ * mode_conv2d_fwd_split_f16_bn; functional.CONV3D_EVAL_F16 / CONV2D_EVAL_F16.  Opting out: a caller of this interface calls the three-piece
+ * entries, mode_conv3d_fwd_split / mode_conv2d_fwd_split with the epilogue; the Python layer sets those two module globals to False, which
+ * is what `bench.py --no-eval-f16` does): fp32 operands split into TWO fp16 pieces, three v_mfma_f32_32x32x16_f16 per product
  * instead of six bf16 ones (2^-22 per product).  fp16's range is narrow, so each operand is scaled by a power of two that brings its
  * tensor's largest finite magnitude to [2^14, 2^15): amax_* = DEVICE buffers of MODE_BN_ABSMAX_FLOATS floats, one per operand (layout:
  * see MODE_BN_ABSMAX_FLOATS below), filled by mode_abs_max (an order-independent maximum over bit patterns; no host synchronisation,
  * graph-capturable) or by the `_amax` BatchNorm entries that write the tensor; a tensor's maximum can be computed once and passed to
  * every call that reads the tensor.  PRECISION CONTRACT: an element keeps 22 significant bits down to ~2^-17 of its tensor's maximum,
  * fewer below that, none below ~2^-39 of it (it contributes less than 2^-17 of the tensor's scale to any sum either way; the three-piece
- * bf16 entries keep 24 bits for every element) -- DESIGN.md 3u.
+ * bf16 entries keep 24 bits for every element) -- csrc/split_arith.h states both arithmetics and defines their primitives; DESIGN.md 3u.
  * mode_conv3d_bwd_data_split_f16: acc may be NULL.  mode_conv3d_bwd_weight_split_f16: other arguments and workspace as
  * mode_conv3d_bwd_weight_split. */
 int mode_abs_max(const float* x, long long n, float* out_device_buffer, mode_stream_t stream);

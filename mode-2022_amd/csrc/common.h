@@ -108,7 +108,9 @@ inline Epi make_epi(const mode_bn_epilogue* e, const float* shift) {
   return r;
 }
 
-#ifdef __HIPCC__
+// Device helpers.  A translation unit of pure host code defines MODE_HOST_ONLY in front of this header and gets none of them (the
+// static kernel below would otherwise be compiled into its code object): sphere_plan.hip.
+#if defined(__HIPCC__) && !defined(MODE_HOST_ONLY)
 // Eval-mode BatchNorm folded into the convolution in front of it (torch semantics: y = (x - mean) / sqrt(var + eps) * gamma + beta):
 // the packing kernels scale output channel o of the weights by fold_scale and write fold_shift(o) next to the packed weights.
 __device__ __forceinline__ float fold_scale(const mode_bn_epilogue& e, int o) { return e.gamma[o] / sqrtf(e.var[o] + e.eps); }

@@ -1,6 +1,6 @@
 // Regular 3x3 Conv2d layers (stride 1, dilation 1 / 2, pad = dilation) of the extractor as fp32 convolutions on the bf16 matrix pipe:
 // conv3d_split.hip one dimension down.  Operands are split exactly into three bf16 pieces when a tile is staged, a product is six
-// v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the arithmetic and its error analysis: conv3d_split.hip).
+// v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the arithmetic and its error analysis: split_arith.h).
 //
 // Reference: the stock nn.Conv2d 3x3 layers of convbn (models/submodule.py:13-17) in firstconv / layer1-3 (submodule.py:155-172) and
 // the tap products of the folded cost volume -- cuDNN NCHW fp32 there.
@@ -16,13 +16,11 @@
 
 #include "bn_internal.h"
 #include "conv3d_internal.h"
+#include "split_arith.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace mode::split;
 
 constexpr int NT = 256;
 // Tile geometry for TH output rows (16, or 8 when the layer has fewer than two 16-row tiles per CU) and dilation DIL
@@ -45,45 +43,9 @@ struct S2Dims {
   int o0;  // first output channel of this launch
 };
 
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split2(float a, float b, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  // (the subtractions of a pair stay scalar: packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed fp32
-  // instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
-  p1 = pack2(a, b);
-  float ra = a - __builtin_bit_cast(float, p1 << 16), rb = b - __builtin_bit_cast(float, p1 & 0xffff0000u);
-  asm("" : "+v"(ra), "+v"(rb));
-  p2 = pack2(ra, rb);
-  float sa = ra - __builtin_bit_cast(float, p2 << 16), sb = rb - __builtin_bit_cast(float, p2 & 0xffff0000u);
-  asm("" : "+v"(sa), "+v"(sb));
-  p3 = pack2(sa, sb);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ f32x16 mfma_bf16(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// ---- F16: the two-piece fp16 arithmetic of conv3d_split.hip for the training step's 3 x 3 layers: two fp16 pieces per value,
-// three v_mfma_f32_32x32x16_f16 per product (lo x hi, hi x lo, hi x hi), a power-of-two scale per operand tensor from its maximum buffer
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float f16_scale_of(float m) {  // as in conv3d_split.hip: m * scale in [2^14, 2^15)
-  const unsigned e = min(max((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu, 64u), 254u);
-  return m == 0.f ? 1.f : __builtin_bit_cast(float, (268u - e) << 23);
-}
-__device__ __forceinline__ void split2_f16(float a, float b, uint32_t& p1, uint32_t& p2) {
-  const f32x2 v = {a, b};
-  const f16x2 h1 = __builtin_convertvector(v, f16x2);
-  p1 = __builtin_bit_cast(uint32_t, h1);
-  float ra = a - (float)h1[0], rb = b - (float)h1[1];
-  asm("" : "+v"(ra), "+v"(rb));
-  const f32x2 r = {ra, rb};
-  p2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
-}
-__device__ __forceinline__ f32x16 mfma_f16(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
+// F16 of the kernels below: the two-piece fp16 arithmetic (split_arith.h) for the training step's 3 x 3 layers: two fp16 pieces
+// per value, three v_mfma_f32_32x32x16_f16 per product (lo x hi, hi x lo, hi x hi), a power-of-two scale per operand tensor from its
+// maximum buffer.  This file splits with split3_bf16_pinned and split2_f16_pinned.
 
 // wp[(((m * NCHUNK + ch) * 9 + tap) * 3 + piece) * 64 + lane] = 8 bf16: piece of Wsrc(o = m*32 + (lane & 31), c = ch*16 + 8 * (lane >> 5)
 // + j, tap), j = 0..7; zero for o >= rows, c >= K.  flip 0: Wsrc = w[o][c][tap] (forward, w is (rows, K, 9)); flip 1: w[c][o][8 - tap]
@@ -118,10 +80,10 @@ __global__ void pack_w2d_split(const float* __restrict__ w, uint4* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if constexpr (F16) {
-        split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
+        split2_f16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
         q3[j] = 0u;
       } else {
-        split2(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
+        split3_bf16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
       }
     }
     uint4* dst = wp + (idx - lane) * 3 + lane;
@@ -139,7 +101,7 @@ template <int MT, int TH, int DIL, int EPI, bool F16 = false>
 __global__ __launch_bounds__(NT) void conv2d_split_kernel(const float* __restrict__ x, const uint4* __restrict__ wp, float* __restrict__ y,
                                                           S2Dims d, Epi epi, const float* __restrict__ amax_x,
                                                           const float* __restrict__ amax_w) {
-  constexpr int NP = F16 ? 2 : 3;  // pieces per value
+  constexpr int NP = Arith<F16>::NP;  // pieces per value
   float sx = 1.f, unscale = 1.f;
   if (F16) {
     sx = f16_scale_of(mode::absmax_load(amax_x));
@@ -236,9 +198,9 @@ __global__ __launch_bounds__(NT) void conv2d_split_kernel(const float* __restric
       for (int j = 0; j < 4; ++j) {
         const float v0 = raw[k][8 * oct + 2 * j], v1 = raw[k][8 * oct + 2 * j + 1];
         if constexpr (F16)
-          split2_f16(v0 * sx, v1 * sx, sq[0][j], sq[1][j]);
+          split2_f16_pinned(v0 * sx, v1 * sx, sq[0][j], sq[1][j]);
         else
-          split2(v0, v1, sq[0][j], sq[1][j], sq[2][j]);
+          split3_bf16_pinned(v0, v1, sq[0][j], sq[1][j], sq[2][j]);
       }
 #pragma unroll
       for (int p = 0; p < NP; ++p) dst[(2 * p + oct) * PIECE] = make_uint4(sq[p][0], sq[p][1], sq[p][2], sq[p][3]);

@@ -1,5 +1,5 @@
 // Weight gradient of the regular 3x3 Conv2d layers (stride 1, dilation 1 / 2) on the split-bf16 matrix path: conv3d_split_wgrad.hip
-// one dimension down (arithmetic: conv3d_split.hip / DESIGN.md 3j).
+// one dimension down (arithmetic: split_arith.h / DESIGN.md 3j).
 //
 //     gW[o][c][kh][kw] = sum_{b,h,w} gy[b,o,h,w] * x[b,c, h + (kh-1) d, w + (kw-1) d]        D[i = o][j = c] per tap, GEMM-K = pixels
 //
@@ -17,13 +17,11 @@
 
 #include "bn_internal.h"
 #include "conv3d_internal.h"
+#include "split_arith.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace mode::split;
 
 constexpr int NT = 256;
 constexpr int RING = 12;                 // x rows in LDS
@@ -39,51 +37,14 @@ constexpr size_t SUM_BYTES = (size_t)3 * 9 * 1024 * sizeof(float);  // partial s
 constexpr size_t LDS_BYTES = TILE_BYTES > SUM_BYTES ? TILE_BYTES : SUM_BYTES;
 constexpr int GIT = 32 * 4 * 16 / NT;    // 8 pixel pairs of a gy group per thread
 
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split2(float a, float b, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  // (the subtractions of a pair stay scalar: packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed fp32
-  // instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
-  p1 = pack2(a, b);
-  float ra = a - __builtin_bit_cast(float, p1 << 16), rb = b - __builtin_bit_cast(float, p1 & 0xffff0000u);
-  asm("" : "+v"(ra), "+v"(rb));
-  p2 = pack2(ra, rb);
-  float sa = ra - __builtin_bit_cast(float, p2 << 16), sb = rb - __builtin_bit_cast(float, p2 & 0xffff0000u);
-  asm("" : "+v"(sa), "+v"(sb));
-  p3 = pack2(sa, sb);
-}
-__device__ __forceinline__ f32x16 mfma_bf16(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// ---- F16: the two-piece fp16 arithmetic of conv3d_split_wgrad.hip: both operands scaled by their tensor's power of two
-// when staged, three v_mfma_f32_32x32x16_f16 per product, the block's sums unscaled when they are written
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float f16_scale_of(float m) {  // as in conv3d_split.hip: m * scale in [2^14, 2^15)
-  const unsigned e = min(max((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu, 64u), 254u);
-  return m == 0.f ? 1.f : __builtin_bit_cast(float, (268u - e) << 23);
-}
-__device__ __forceinline__ void split2_f16(float a, float b, uint32_t& p1, uint32_t& p2) {
-  const f32x2 v = {a, b};
-  const f16x2 h1 = __builtin_convertvector(v, f16x2);
-  p1 = __builtin_bit_cast(uint32_t, h1);
-  float ra = a - (float)h1[0], rb = b - (float)h1[1];
-  asm("" : "+v"(ra), "+v"(rb));
-  const f32x2 r = {ra, rb};
-  p2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
-}
-__device__ __forceinline__ f32x16 mfma_f16(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
+// F16: the two-piece fp16 arithmetic (split_arith.h) as in conv3d_split_wgrad.hip: both operands scaled by their tensor's
+// power of two when staged, three v_mfma_f32_32x32x16_f16 per product, the block's sums unscaled when they are written.  This file
+// splits with split3_bf16_pinned and split2_f16_pinned.
 template <int DIL, bool F16>
 __global__ __launch_bounds__(NT) void conv2d_bww_split_kernel(const float* __restrict__ gy, const float* __restrict__ x,
                                                               float* __restrict__ part, mode::Wgrad2SplitDims d,
                                                               const float* __restrict__ amax_g, const float* __restrict__ amax_x) {
-  constexpr int NPC = F16 ? 2 : 3;                     // pieces per value
+  constexpr int NPC = Arith<F16>::NP;                  // pieces per value
   float sg = 1.f, sx = 1.f, unscale = 1.f;
   if (F16) {
     sg = f16_scale_of(mode::absmax_load(amax_g));
@@ -169,9 +130,9 @@ __global__ __launch_bounds__(NT) void conv2d_bww_split_kernel(const float* __res
     sl = sl >= RING ? sl - RING : sl;
     uint32_t* dst = reinterpret_cast<uint32_t*>(xl + xdst[k] + sl * XROWP);
     if constexpr (F16) {
-      split2_f16(v0 * sx, v1 * sx, p1, p2);
+      split2_f16_pinned(v0 * sx, v1 * sx, p1, p2);
     } else {
-      split2(v0, v1, p1, p2, p3);
+      split3_bf16_pinned(v0, v1, p1, p2, p3);
       dst[XPIECE] = p3;
     }
     dst[0] = p1;  // (threads beyond the last item repeat it: same address, same value)
@@ -188,9 +149,9 @@ __global__ __launch_bounds__(NT) void conv2d_bww_split_kernel(const float* __res
     const float v0 = gr[k][0], v1 = gr[k][1];
     uint32_t* dst = reinterpret_cast<uint32_t*>(gl + buf * GBUF + gdst[k]);
     if constexpr (F16) {
-      split2_f16(v0 * sg, v1 * sg, p1, p2);
+      split2_f16_pinned(v0 * sg, v1 * sg, p1, p2);
     } else {
-      split2(v0, v1, p1, p2, p3);
+      split3_bf16_pinned(v0, v1, p1, p2, p3);
       dst[GPIECE] = p3;
     }
     dst[0] = p1;

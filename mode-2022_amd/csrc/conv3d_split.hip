@@ -1,10 +1,7 @@
 // 3x3x3 stride-1 convolution (pad 1) of the 3D regulariser on the bf16 matrix pipe with fp32 operands: every fp32 value is split
-// EXACTLY into three bf16 pieces,  a = a1 + a2 + a3  (a1 = rne(a), a2 = rne(a - a1), a3 = rne(a - a1 - a2): 24 mantissa bits),
-// and a product a*b is the sum of the six partial products of weight >= 2^-16 relative to |a||b|,
-//     a3*b1 + a1*b3 + a2*b2 + a2*b1 + a1*b2 + a1*b1        (dropped: a2*b3, a3*b2, a3*b3 <= 3 * 2^-24 |a||b|),
-// each exact in the fp32 accumulator of v_mfma_f32_32x32x16_bf16 and added smallest first.  The result carries the rounding of an
-// fp32 convolution (tools/experiments/conv3d_bf16x6.hip measures it against an exact evaluation: max 4.5e-6 / rms 4.3e-7 at
-// |y| <= 4.8, a sequential fp32 fma loop 4.7e-6 / 5.1e-7) at 6 / 16 of the bf16 MFMA rate = 2.7 x the fp32 MFMA rate.
+// EXACTLY into three bf16 pieces and a product is six v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- or, template parameter F16,
+// into two fp16 pieces and three v_mfma_f32_32x32x16_f16.  split_arith.h states both arithmetics, their error and their precision
+// contract, and defines their primitives; this comment is about the kernel.
 //
 // Reference: the same nn.Conv3d layers as conv3d.hip (models/submodule.py:20-22, models/mode_disparity.py:11-46, 66-80).
 //
@@ -30,28 +27,16 @@
 
 #include "bn_internal.h"
 #include "conv3d_internal.h"
+#include "split_arith.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace mode::split;
 
 #ifndef MODE_SPLIT_NT
 #define MODE_SPLIT_NT 256  // (512: two waves per SIMD, two rows each -- measured in round 5)
 #endif
 constexpr int NT = MODE_SPLIT_NT;
-// Two arithmetics (template parameter F16 of the kernels below):
-//   false  three bf16 pieces per fp32 value, six MFMAs per product (the product arithmetic: 24 mantissa bits for every element);
-//   true   two fp16 pieces (v_cvt_pk_f16_f32, round to nearest even; the remainder a - a1 is exact in fp32), three MFMAs per product
-//          (a1b1, a1b2, a2b1: 2^-22 per product).  fp16's range is narrow: both operands are multiplied by a power of two that brings
-//          their tensor's largest magnitude (a device scalar the caller provides: mode_abs_max) to [2^14, 2^15), and the accumulators by
-//          the inverse -- all exact.  Elements more than ~2^17 below their tensor's maximum lose relative precision.
-template <bool F16> struct Arith {
-  static constexpr int NP = F16 ? 2 : 3;     // pieces per fp32 value
-  static constexpr int NTERM = F16 ? 3 : 6;  // MFMAs per product
-};
 constexpr int TD = 2, ID = TD + 2, IW = 34;
 // Tile geometry for TH output rows per depth plane: 8 (every instantiation of rounds 2-5) or 16 (round 6, the fp16 plain-store
 // instantiation at volumes with enough tiles: twice the MFMAs per chunk for 1.8 x the staged positions and the same 28 weight
@@ -80,41 +65,15 @@ struct SDims {
   int o0;  // first output channel of this launch (a layer with 33..64 output channels runs as two launches of 32)
 };
 
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// (a, b) -> the packed pieces of the pair; the remainders are exact in fp32
+// (a, b) -> the packed pieces of the pair in this file's two forms (split_arith.h says why these)
 template <bool F16>
 __device__ __forceinline__ void split2(float a, float b, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
   if constexpr (F16) {
-    const f32x2 v = {a, b};
-    const f16x2 h1 = __builtin_convertvector(v, f16x2);
-    p1 = __builtin_bit_cast(uint32_t, h1);
-    const f32x2 r = {a - (float)h1[0], __builtin_fmaf(-1.f, (float)h1[1], b)};
-    p2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
+    split2_f16_subfma(a, b, p1, p2);
     p3 = 0;
   } else {
-    // (the subtractions of a pair stay scalar: packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed fp32
-    // instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
-    p1 = pack2(a, b);
-    float ra = a - __builtin_bit_cast(float, p1 << 16), rb = b - __builtin_bit_cast(float, p1 & 0xffff0000u);
-    asm("" : "+v"(ra), "+v"(rb));
-    p2 = pack2(ra, rb);
-    float sa = ra - __builtin_bit_cast(float, p2 << 16), sb = rb - __builtin_bit_cast(float, p2 & 0xffff0000u);
-    asm("" : "+v"(sa), "+v"(sb));
-    p3 = pack2(sa, sb);
+    split3_bf16_pinned(a, b, p1, p2, p3);
   }
-}
-
-// 2^(14 - floor(log2 m)) for the largest magnitude m of a tensor (m * scale in [2^14, 2^15)); 1 for m = 0; magnitudes below 2^-63 are
-// treated as 2^-63 (the tensor is zero for every purpose); Inf / NaN maxima give a finite scale and propagate through the products
-__device__ __forceinline__ float f16_scale_of(float m) {
-  const unsigned e = min(max((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu, 64u), 254u);
-  return m == 0.f ? 1.f : __builtin_bit_cast(float, (268u - e) << 23);
 }
 
 // wp[(((m * NCHUNK + ch) * NPAIR + pair) * 3 + piece) * 64 + lane] = 8 bf16: piece of Wsrc(o = m*32 + (lane & 31), c = ch*8 + j,
@@ -159,18 +118,6 @@ __global__ void pack_w3d_split(const float* __restrict__ w, uint4* __restrict__ 
     dst[64] = make_uint4(q2[0], q2[1], q2[2], q2[3]);
     if (NP == 3) dst[128] = make_uint4(q3[0], q3[1], q3[2], q3[3]);
   }
-}
-
-// Workgroup barrier that orders LDS accesses only: __syncthreads() also drains the vector-memory counter, i.e. waits for the weight
-// fragments already requested for the next chunk and for the output stores of a finished tile.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma_split(uint4 a, uint4 b, f32x16 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 __host__ __device__ constexpr int tap_off(int tap, int IH) {  // LDS position offset of a tap inside the haloed tile

@@ -1,6 +1,7 @@
 // ConvTranspose3d k3 s2 p1 op1 (hourglass conv5 / conv6, models/mode_disparity.py:23-25) -- and with it the input gradient of the
 // stride-2 convolutions conv1 / conv3 (:17-19), which is the same operator on the same weight layout -- on the bf16 matrix pipe with
-// fp32 operands split exactly into three bf16 pieces: the arithmetic and the structure of conv3d_split.hip (read that file first).
+// fp32 operands split exactly into three bf16 pieces: the arithmetic of split_arith.h and the structure of
+// conv3d_split.hip (read that file first).
 //
 //   y[o][2 q + p] = sum_c sum_{taps of parity class p} w[c][o][k] * x[c][q + s(k)]        (q: low-resolution voxel, p in {0,1}^3)
 // Per axis an even output index takes kernel index 1 from input q, an odd one kernel index 0 from input q + 1 and kernel index 2
@@ -22,13 +23,11 @@
 
 #include "bn_internal.h"
 #include "conv3d_internal.h"
+#include "split_arith.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace mode::split;
 
 constexpr int NT = 256;
 constexpr int IW = 33;
@@ -55,25 +54,6 @@ struct DcDims {
   int nWt, nHt, NCHUNK, ntiles;
 };
 
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split2(float a, float b, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  // (the subtractions of a pair stay scalar: packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed fp32
-  // instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
-  p1 = pack2(a, b);
-  float ra = a - __builtin_bit_cast(float, p1 << 16), rb = b - __builtin_bit_cast(float, p1 & 0xffff0000u);
-  asm("" : "+v"(ra), "+v"(rb));
-  p2 = pack2(ra, rb);
-  float sa = ra - __builtin_bit_cast(float, p2 << 16), sb = rb - __builtin_bit_cast(float, p2 & 0xffff0000u);
-  asm("" : "+v"(sa), "+v"(sb));
-  p3 = pack2(sa, sb);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ f32x16 mfma_bf16(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // wp[(((m * NCHUNK + ch) * NPAIR + pair) * 3 + piece) * 64 + lane] = 8 bf16: piece of W[c = ch*8 + j][o = m*32 + (lane & 31)]
 // [tap = pair_tap(pair, lane >> 5)], j = 0..7, from the (K, Co, 27) weight of the transposed convolution; zero for the empty tap, o >= Co, c >= K
@@ -103,7 +83,7 @@ __global__ void pack_w3d_deconv_split(const float* __restrict__ w, uint4* __rest
     }
     uint32_t q1[4], q2[4], q3[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) split2(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
+    for (int j = 0; j < 4; ++j) split3_bf16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
     uint4* dst = wp + (idx - lane) * 3 + lane;
     dst[0] = make_uint4(q1[0], q1[1], q1[2], q1[3]);
     dst[64] = make_uint4(q2[0], q2[1], q2[2], q2[3]);
@@ -218,7 +198,7 @@ __global__ __launch_bounds__(NT, 1) void deconv3d_split_kernel(const float* __re
   uint32_t sq[3][4];
   auto stage_commit = [&](int buf, int k, int h) {
 #pragma unroll
-    for (int j = 2 * h; j < 2 * h + 2; ++j) split2(raw[k][2 * j], raw[k][2 * j + 1], sq[0][j], sq[1][j], sq[2][j]);
+    for (int j = 2 * h; j < 2 * h + 2; ++j) split3_bf16_pinned(raw[k][2 * j], raw[k][2 * j + 1], sq[0][j], sq[1][j], sq[2][j]);
     if (h == 1) {
       uint4* dst = sm + buf * BUF + tid + k * NT;
 #pragma unroll

@@ -1,4 +1,4 @@
-// Weight gradient of the stride-1 3x3x3 convolution on the bf16 matrix pipe with exactly split fp32 operands (see conv3d_split.hip
+// Weight gradient of the stride-1 3x3x3 convolution on the bf16 matrix pipe with exactly split fp32 operands (see split_arith.h
 // for the arithmetic: three bf16 pieces per fp32 value, six MFMAs per product, fp32 accumulation -- fp32 accuracy).
 //
 //     gW[o][c][tap] = sum_{b, voxel} gy[b, o, voxel] * x[b, c, voxel + tap - 1]          D[i = o][j = c] per tap, GEMM-K = voxels
@@ -23,13 +23,11 @@
 
 #include "bn_internal.h"
 #include "conv3d_internal.h"
+#include "split_arith.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace mode::split;
 
 constexpr int NT = 256;
 constexpr int WTH = 2, XR = WTH + 2;
@@ -46,54 +44,23 @@ constexpr size_t LDS_BYTES = (size_t)(XALL + 2 * GBUF) * 2;  // 148 992
 constexpr int XIT = (32 * XR * 17 + NT - 1) / NT;   // 9 element pairs of an x plane per thread
 constexpr int GIT = 32 * WTH * 16 / NT;             // 4 element pairs of the gy rows per thread
 
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// F16: two fp16 pieces (round to nearest even), three MFMAs per product -- the experimental arithmetic of conv3d_split.hip (its header);
-// the operands arrive scaled by a power of two, the sums leave scaled back.
+// F16: two fp16 pieces (round to nearest even), three MFMAs per product (split_arith.h has both arithmetics and says why this file
+// has these two forms of the split); the operands arrive scaled by a power of two, the sums leave scaled back.
 template <bool F16>
 __device__ __forceinline__ void split2(float a, float b, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
   if constexpr (F16) {
-    const f32x2 v = {a, b};
-    const f16x2 h1 = __builtin_convertvector(v, f16x2);
-    p1 = __builtin_bit_cast(uint32_t, h1);
-    const f32x2 r = {a - (float)h1[0], __builtin_fmaf(-1.f, (float)h1[1], b)};
-    p2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
+    split2_f16_subfma(a, b, p1, p2);
     p3 = 0;
   } else {
-    // (the subtractions of a pair stay scalar: packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed fp32
-    // instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
-    // One of the pair as a subtraction, the other as fma(-1, piece, value) (the same exact difference): two different operations are not
-    // packed, and no empty asm statement is needed to keep them apart -- the scheduler's group pattern places plain VALU instructions
-    // under the MFMAs, an inline-asm node in a chain it left (with everything behind it) for the end of the K-step.
-    p1 = pack2(a, b);
-    const float ra = a - __builtin_bit_cast(float, p1 << 16), rb = __builtin_fmaf(-1.f, __builtin_bit_cast(float, p1 & 0xffff0000u), b);
-    p2 = pack2(ra, rb);
-    const float sa = ra - __builtin_bit_cast(float, p2 << 16), sb = __builtin_fmaf(-1.f, __builtin_bit_cast(float, p2 & 0xffff0000u), rb);
-    p3 = pack2(sa, sb);
+    split3_bf16_subfma(a, b, p1, p2, p3);
   }
 }
-__device__ __forceinline__ float f16_scale_of(float m) {  // as in conv3d_split.hip: m * scale in [2^14, 2^15)
-  const unsigned e = min(max((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu, 64u), 254u);
-  return m == 0.f ? 1.f : __builtin_bit_cast(float, (268u - e) << 23);
-}
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma_split(uint4 a, uint4 b, f32x16 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <bool F16>
 __global__ __launch_bounds__(NT) void conv3d_bww_split_kernel(const float* __restrict__ gy, const float* __restrict__ x,
                                                               float* __restrict__ part, mode::WgradSplitDims d,
                                                               const float* __restrict__ amax_g, const float* __restrict__ amax_x) {
-  constexpr int NP = F16 ? 2 : 3;  // pieces (the LDS layout keeps room for three)
+  constexpr int NP = Arith<F16>::NP;  // pieces (the LDS layout keeps room for three)
   // (F16) amax_g / amax_x = max |gy| / max |x|: both operands scaled when staged, the sums scaled back when written
   const float sg = F16 ? f16_scale_of(mode::absmax_load(amax_g)) : 1.f, sx = F16 ? f16_scale_of(mode::absmax_load(amax_x)) : 1.f;
   const float unscale = F16 ? (1.f / sg) * (1.f / sx) : 1.f;

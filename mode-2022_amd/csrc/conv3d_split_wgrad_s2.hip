@@ -1,5 +1,5 @@
 // Weight gradient of the STRIDE-2 3x3x3 convolution (and, with the operands exchanged, of ConvTranspose3d k3 s2 p1 op1) on the bf16
-// matrix pipe with exactly split fp32 operands (conv3d_split.hip has the arithmetic: three bf16 pieces per fp32 value, six MFMAs per
+// matrix pipe with exactly split fp32 operands (split_arith.h has the arithmetic: three bf16 pieces per fp32 value, six MFMAs per
 // product, fp32 accumulation).
 //
 //     gW[o][c][tap] = sum_{b, q} gy[b, o, q] * x[b, c, 2 q + tap - 1]        D[i = o][j = c] per tap, GEMM-K = output voxels q
@@ -25,13 +25,11 @@
 #include "common.h"
 
 #include "conv3d_internal.h"
+#include "split_arith.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace mode::split;
 
 constexpr int NT = 256;
 constexpr int XROW = 40;               // bf16 per staged x row
@@ -45,25 +43,6 @@ constexpr int GCS = 3 * GPIECE + 8;    // 56 elements = 28 dwords (= 4 * 7) per 
 constexpr int GBUF = 64 * GCS;
 constexpr size_t LDS_BYTES = (size_t)(XALL + 2 * GBUF) * 2;  // 129 536
 
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split2(float a, float b, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  // (the subtractions of a pair stay scalar: packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed fp32
-  // instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
-  p1 = pack2(a, b);
-  float ra = a - __builtin_bit_cast(float, p1 << 16), rb = b - __builtin_bit_cast(float, p1 & 0xffff0000u);
-  asm("" : "+v"(ra), "+v"(rb));
-  p2 = pack2(ra, rb);
-  float sa = ra - __builtin_bit_cast(float, p2 << 16), sb = rb - __builtin_bit_cast(float, p2 & 0xffff0000u);
-  asm("" : "+v"(sa), "+v"(sb));
-  p3 = pack2(sa, sb);
-}
-__device__ __forceinline__ f32x16 mfma_bf16(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ int ring5(int z) { return (z + 10) % 5; }  // z >= -4
 
 // one register set of a phase's staging: six float4 of x (2 planes x 3 rows), the halo element, a float4 of gy
@@ -144,8 +123,8 @@ __global__ __launch_bounds__(NT) void conv3d_bww_s2_split_kernel(const float* __
     const bool ok = ((unsigned)z < (unsigned)d.D) && ((xm >> (k % 3)) & 1u);
     const float4 v = st.xr[k];
     uint32_t e1, e2, e3, o1, o2, o3;
-    split2(ok ? v.x : 0.f, ok ? v.z : 0.f, e1, e2, e3);
-    split2(ok ? v.y : 0.f, ok ? v.w : 0.f, o1, o2, o3);
+    split3_bf16_pinned(ok ? v.x : 0.f, ok ? v.z : 0.f, e1, e2, e3);
+    split3_bf16_pinned(ok ? v.y : 0.f, ok ? v.w : 0.f, o1, o2, o3);
     uint32_t* dst = reinterpret_cast<uint32_t*>(xl + xdst + ring5(z) * XSLOT + (k % 3) * XROW);
     dst[0] = e1;
     dst[XPIECE / 2] = e2;
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(NT) void conv3d_bww_s2_split_kernel(const float* __
       const int z = 2 * q + hpz;
       const float v = (hm && (unsigned)z < (unsigned)d.D) ? st.hr : 0.f;
       uint32_t p1, p2, p3;
-      split2(v, 0.f, p1, p2, p3);
+      split3_bf16_pinned(v, 0.f, p1, p2, p3);
       uint16_t* dst = xl + hdst + ring5(z) * XSLOT;
       dst[0] = (uint16_t)p1;
       dst[XPIECE] = (uint16_t)p2;
@@ -169,8 +148,8 @@ __global__ __launch_bounds__(NT) void conv3d_bww_s2_split_kernel(const float* __
       const bool ok = gm && (unsigned)q < (unsigned)d.Do;
       const float4 v = st.gr;
       uint32_t a1, a2, a3, b1, b2, b3;
-      split2(ok ? v.x : 0.f, ok ? v.y : 0.f, a1, a2, a3);
-      split2(ok ? v.z : 0.f, ok ? v.w : 0.f, b1, b2, b3);
+      split3_bf16_pinned(ok ? v.x : 0.f, ok ? v.y : 0.f, a1, a2, a3);
+      split3_bf16_pinned(ok ? v.z : 0.f, ok ? v.w : 0.f, b1, b2, b3);
       uint2* dst = reinterpret_cast<uint2*>(gl + (q & 1) * GBUF + gdst);
       dst[0] = make_uint2(a1, b1);
       dst[GPIECE / 4] = make_uint2(a2, b2);

@@ -8,8 +8,9 @@
 // longitude axis).  These kernels stage that window of the input ONCE per channel chunk in LDS with plain row loads and
 // build the MFMA B operand on the fly from it: 4 LDS reads + 4 FMAs per sample, no column buffer at all.
 //
-// Nothing is assumed about the table: the host plans every tile from the actual table values (mode_sphere_plan_build,
-// same record arithmetic as the kernel, sphere_tap.h) and classifies it by the window it needs.  A table whose tiles do not
+// Nothing is assumed about the table: the host plans every tile from the actual table values (mode_sphere_plan_build in
+// sphere_plan.hip: same record arithmetic as the kernel, sphere_tap.h, same tile and window sizes, sphere_win_geometry.h) and
+// classifies it by the window it needs.  A table whose tiles do not
 // fit any window class is reported as such and the caller uses the general kernels.
 //
 // Tile = 32 rows x 4 columns of output pixels (stride 1): wave v owns column w0 + v and the 32 rows h0 .. h0+31 as the N
@@ -19,30 +20,22 @@
 //
 // Reference: sphere_conv_cuda_kernel.cu:83-113, 195-262 (im2col gather) + sphere_conv_cuda.cpp:177-205 (addmm_).
 #include <algorithm>
-#include <cstring>
-#include <vector>
 
 #include "common.h"
 #include "bn_internal.h"
 #include "sphere_internal.h"
 #include "sphere_tap.h"
+#include "sphere_win_geometry.h"
+#include "split_arith.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace mode::split;
+using namespace mode::sphere_win;  // TH, TW, WC, CCH, KT, NTHREADS, the window classes: what the planners share with the kernels
+
 typedef float f32x32 __attribute__((ext_vector_type(32)));
 
-constexpr int RB = 2;      // MFMA N-tiles (32 rows) per tile column
-constexpr int TH = 32 * RB;  // tile rows
-constexpr int TW = 4;      // tile columns
-constexpr int WC = 8;      // window columns
-constexpr int CCH = 8;     // input channels per chunk
-constexpr int KT = 9;      // taps (3x3 kernels)
 constexpr int MTW = 4;     // M-tiles (32 output channels each) per wave
-constexpr int NTHREADS = 64 * TW * RB;  // one wave per (column, 32-row block)
-constexpr int SROWS = NTHREADS / WC;    // window rows staged per pass
-constexpr int WR_SMALL = TH + 17, WR_MID = TH + 81;  // window rows of the two compact classes (odd: conflict-free column pitch)
-constexpr int WR_PIPE_MAX = 5 * SROWS;  // tallest window whose next chunk still fits in registers while the current one computes
 
 struct WinDims {
   int B, Ci, H, W, Co, G;
@@ -54,11 +47,6 @@ struct WinDims {
   int sh, sw;     // element strides of h and w in the activation tensors: (W, 1) = NCHW; (1, H) = planes stored transposed
   int accumulate;
 };
-
-__host__ __device__ constexpr int chan_pitch(int wr) {
-  // 8 columns of wr rows, padded so that consecutive channels are 32 banks apart (the two half-waves of a B read)
-  return WC * wr + ((32 - (WC * wr) % 64) + 64) % 64;
-}
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -364,8 +352,6 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_win_tall_kernel(const flo
 // Everything the next column needs (gy, records; the x window before a new item) is fetched into registers before the MFMAs
 // of the current column and written to the other LDS buffer after them.
 constexpr int BW_CG = 32;
-constexpr int BW_TH = 32;                  // rows per work item
-constexpr int BW_WR = BW_TH + 17;          // its window rows (49)
 constexpr int BW_CP = WC * BW_WR + 1;      // odd channel pitch of the x window
 constexpr int BW_GP = BW_TH + 1;           // gy row pitch
 constexpr int BW_SLOTS = KT;                // one partial per tap (the waves' shares of tap 8 are summed in the kernel)
@@ -373,7 +359,6 @@ constexpr int BW_XW = BW_CG * BW_CP + BW_WR + 8;  // + slack: zero-weight corner
 constexpr int BW_COLBUF = 128 * BW_GP;  // gy column
 constexpr int BW_LDS_FLOATS = 2 * BW_XW + 2 * BW_COLBUF;  // x window and gy column, both double-buffered
 constexpr int BW_NXW = BW_CG / TW;  // x-window words per thread and column step: the next item's window arrives in 4 parts
-constexpr int BW_NREC = KT * BW_TH;                                      // records per column (288)
 
 // The 72 MFMAs of one column (32 pixels) of a work item for this wave: own tap (all 32 pixels, software-pipelined: while the
 // MFMAs of pixel px run, the B value of pixel px+1 is combined and the LDS words of pixel px+2 are requested), then this wave's
@@ -622,12 +607,9 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_win_kernel(const float* _
 // one per tap: [32 ch][9 taps][2 columns][34 rows] (78 KB).  Everything of an item is staged in place (no cross-item prefetch:
 // these items are 12.5 % of the pixels), then the k-loop of the compact-window kernel runs unchanged on it.
 // pitems[i] = (h0, w, rbase[9], cbase[9]); records [item][tap][32] hold offsets into the per-tap layout.
-constexpr int BP_WR = BW_TH + 2;         // rows per tap window
-constexpr int BP_TAPW = 2 * BP_WR;       // floats per tap window: [2 cols][34 rows]
 constexpr int BP_CP = KT * BP_TAPW + 1;  // odd channel pitch (613)
 constexpr int BP_XW = BW_CG * BP_CP + BP_WR + 8;
 constexpr int BP_LDS_FLOATS = BP_XW + BW_COLBUF;
-constexpr int BP_ITEM_INTS = 2 + 2 * KT;
 
 __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_kernel(const float* __restrict__ gy, const float* __restrict__ x,
                                                                      float* __restrict__ part, WinDims d, const int* __restrict__ pitems,
@@ -746,27 +728,6 @@ __global__ void reduce_gw_win(const float* __restrict__ part, float* __restrict_
   }
 }
 
-// Class 0 also promises the weight-gradient kernel that each 32-row half of the tile fits a 49-row window starting at
-// rbase (+32 for the second half): true for shift-invariant tables, checked for all.
-bool halves_fit(const float* pos_host, int H, int W, int KK, int h0, int w0, int rbase, int cbase) {
-  const long long HW = (long long)H * W;
-  for (int hf = 0; hf < 2; ++hf) {
-    const int rb = (rbase + hf * BW_TH) % H;
-    for (int k = 0; k < KK; ++k)
-      for (int h = h0 + hf * BW_TH; h < std::min(h0 + (hf + 1) * BW_TH, H); ++h)
-        for (int w = w0; w < std::min(w0 + TW, W); ++w) {
-          int r0, c0;
-          float4 wt;
-          const long long idx = (long long)h * W + w;
-          if (!mode::tap_record_fixed(pos_host[(2 * k) * HW + idx], pos_host[(2 * k + 1) * HW + idx], H, W, r0, c0, wt)) continue;
-          if (wt.x == 0.f && wt.y == 0.f && wt.z == 0.f && wt.w == 0.f) continue;
-          const int lr = ((r0 - rb) % H + H) % H;
-          if (lr + 1 >= BW_WR || c0 - cbase < 0 || c0 - cbase + 1 >= WC) return false;
-        }
-  }
-  return true;
-}
-
 int bww_win_splits(const WinDims& d, int ntiles) {
   const int T = ntiles * 2 * d.B;
   const int wgs_per_slice = mode::cdiv(d.Cig, BW_CG) * d.G * d.MG;
@@ -776,7 +737,7 @@ int bww_win_splits(const WinDims& d, int ntiles) {
 
 
 // =====================================================================================================================
-// Forward on the small-window tiles with the split-bf16 arithmetic of conv3d_split.hip: fp32 operands split exactly
+// Forward on the small-window tiles with the split-bf16 arithmetic of split_arith.h: fp32 operands split exactly
 // into three bf16 pieces, six v_mfma_f32_32x32x16_bf16 per product, fp32 accumulation.
 //
 // Same tile (64 rows x 4 columns), window (81 rows x 8 columns per channel, fp32, double-buffered) and sampling records as
@@ -799,67 +760,17 @@ constexpr size_t SP_LDS_BYTES = (size_t)SP_WIN_FLOATS * sizeof(float) + 2 * (siz
 constexpr size_t SP3_LDS_BYTES = SP_LDS_BYTES + (size_t)SP_OP * sizeof(uint4);  // the forward keeps three operand buffers
 static_assert(SP3_LDS_BYTES <= 160 * 1024, "windows + three operand buffers must fit the 160 KB of a CU");
 
-typedef __bf16 sp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sp_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float sp_f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t sp_pack2(float a, float b) {
-  const sp_f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, sp_bf16x2));
-}
-__device__ __forceinline__ void sp_split2(float a, float b, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  // (the two subtractions of a pair must stay scalar: SLP-packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed
-  // fp32 instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
-  p1 = sp_pack2(a, b);
-  float ra = a - __builtin_bit_cast(float, p1 << 16), rb = b - __builtin_bit_cast(float, p1 & 0xffff0000u);
-  asm("" : "+v"(ra), "+v"(rb));
-  p2 = sp_pack2(ra, rb);
-  float sa = ra - __builtin_bit_cast(float, p2 << 16), sb = rb - __builtin_bit_cast(float, p2 & 0xffff0000u);
-  asm("" : "+v"(sa), "+v"(sb));
-  p3 = sp_pack2(sa, sb);
-}
-__device__ __forceinline__ f32x16 sp_mfma(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sp_bf16x8, a), __builtin_bit_cast(sp_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void sp_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// ---- the two-piece fp16 arithmetic of conv3d_split.hip for the small-window tiles of the TRAINING forward: two fp16 pieces
-// per value (v_cvt_pk_f16_f32, round to nearest even; the remainder is exact in fp32), three v_mfma_f32_32x32x16_f16 per product
-// (lo x hi, hi x hi, hi x lo).  Both operands are multiplied by a power of two that brings their tensor's largest finite magnitude (a
-// device scalar from the caller) to [2^14, 2^15); the sampled operand gets it through its four bilinear weights, once per tile.
-typedef _Float16 sp_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 sp_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float sp_f16_scale_of(float m) {  // as in conv3d_split.hip: m * scale in [2^14, 2^15)
-  const unsigned e = min(max((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu, 64u), 254u);
-  return m == 0.f ? 1.f : __builtin_bit_cast(float, (268u - e) << 23);
-}
-__device__ __forceinline__ void sp_split2_f16(float a, float b, uint32_t& p1, uint32_t& p2) {
-  const sp_f32x2 v = {a, b};
-  const sp_f16x2 h1 = __builtin_convertvector(v, sp_f16x2);
-  p1 = __builtin_bit_cast(uint32_t, h1);
-  // (round 6) the remainders a - (float)h as ONE instruction each: v_fma_mix_f32 reads the fp16 half in place (1.0 * a - h, the same
-  // exact difference).  Written as `a - (float)h` it is a v_cvt_f32_f16 + a v_sub_f32 per value -- 40 / 72 / 104 of the 445 / 970 / 1 637
-  // vector instructions of the forward / input-gradient / weight-gradient loops -- and fma(-1, h, a) is folded back to that; the asm
-  // statement also does what the empty one before it did: it keeps the pair's two chains scalar (see sp_split2).
-  float ra, rb;
-  asm("v_fma_mix_f32 %0, 1.0, %3, -%2 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mix_f32 %1, 1.0, %4, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-      : "=&v"(ra), "=&v"(rb)
-      : "v"(p1), "v"(a), "v"(b));
-  const sp_f32x2 r = {ra, rb};
-  p2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, sp_f16x2));
-}
-__device__ __forceinline__ f32x16 sp_mfma_f16(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(sp_f16x8, a), __builtin_bit_cast(sp_f16x8, b), c, 0, 0, 0);
-}
-
+// F16 of the kernels below: the two-piece fp16 arithmetic (split_arith.h) for the small-window tiles of the TRAINING forward:
+// two fp16 pieces per value, three v_mfma_f32_32x32x16_f16 per product (lo x hi, hi x hi, hi x lo).  Both operands are multiplied by
+// their tensor's power-of-two scale (f16_scale_of of its largest finite magnitude, a device scalar from the caller); the sampled
+// operand gets it through its four bilinear weights, once per tile.  This file splits with split3_bf16_pinned and split2_f16_mix.
 // wps[(((((g*MG + mg)*NCH16 + ch)*KT + tap)*MTW + m)*3 + piece)*64 + lane] = 8 bf16: piece of W[g*Cog + mg*128 + m*32 + (lane&31)]
 // [ch*16 + 8*(lane>>5) + j][tap], j = 0..7 (scaled by the folded BatchNorm scale when fold != 0; the shifts are the ones pack_w_win wrote)
 // F16: two fp16 pieces of w * (the weight tensor's power-of-two scale, from amax_w[0]) in the places of pieces 0 and 1 (no fold)
 template <bool F16>
 __global__ void pack_w_win_split(const float* __restrict__ w, uint4* __restrict__ wps, WinDims d, int NCH16, int fold, mode_bn_epilogue bn,
                                  const float* __restrict__ amax_w) {
-  const float sw = F16 ? sp_f16_scale_of(mode::absmax_load(amax_w)) : 1.f;
+  const float sw = F16 ? f16_scale_of(mode::absmax_load(amax_w)) : 1.f;
   const long long total = (long long)d.G * d.MG * NCH16 * KT * MTW * 64;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
     const int lane = (int)(idx & 63);
@@ -888,10 +799,10 @@ __global__ void pack_w_win_split(const float* __restrict__ w, uint4* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if constexpr (F16) {
-        sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
+        split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
         q3[j] = 0u;
       } else {
-        sp_split2(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
+        split3_bf16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
       }
     }
     uint4* dst = wps + (idx - lane) * 3 + lane;
@@ -917,7 +828,7 @@ constexpr int TP = 5;  // tap pairs of a 3 x 3 kernel
 template <bool F16>
 __global__ void pack_w_win_split_tall(const float* __restrict__ w, uint4* __restrict__ wpt, WinDims d, int fold, mode_bn_epilogue bn,
                                       const float* __restrict__ amax_w) {
-  const float sw = F16 ? sp_f16_scale_of(mode::absmax_load(amax_w)) : 1.f;
+  const float sw = F16 ? f16_scale_of(mode::absmax_load(amax_w)) : 1.f;
   const long long total = (long long)d.G * d.MG * d.NCH * TP * MTW * 64;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
     const int lane = (int)(idx & 63);
@@ -947,10 +858,10 @@ __global__ void pack_w_win_split_tall(const float* __restrict__ w, uint4* __rest
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if constexpr (F16) {
-        sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
+        split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
         q3[j] = 0u;
       } else {
-        sp_split2(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
+        split3_bf16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
       }
     }
     uint4* dst = wpt + (idx - lane) * 3 + lane;
@@ -1103,19 +1014,13 @@ __device__ __forceinline__ void fwd_tile_split(const float* __restrict__ x, cons
     asm("" : "+v"(v[c]));
   };
   auto split_a = [&](int j) {
-    q1[j] = sp_pack2(v[2 * j], v[2 * j + 1]);
-    ra[j] = v[2 * j] - __builtin_bit_cast(float, q1[j] << 16);
-    rb[j] = v[2 * j + 1] - __builtin_bit_cast(float, q1[j] & 0xffff0000u);
-    asm("" : "+v"(ra[j]), "+v"(rb[j]));
+    ra[j] = v[2 * j];
+    rb[j] = v[2 * j + 1];
+    q1[j] = split_step_bf16_pinned(ra[j], rb[j]);
   };
-  auto split_b = [&](int j) {
-    q2[j] = sp_pack2(ra[j], rb[j]);
-    ra[j] = ra[j] - __builtin_bit_cast(float, q2[j] << 16);
-    rb[j] = rb[j] - __builtin_bit_cast(float, q2[j] & 0xffff0000u);
-    asm("" : "+v"(ra[j]), "+v"(rb[j]));
-  };
-  auto split_c = [&](int j) { q3[j] = sp_pack2(ra[j], rb[j]); };
-  auto hsplit = [&](int j) { sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]); };
+  auto split_b = [&](int j) { q2[j] = split_step_bf16_pinned(ra[j], rb[j]); };
+  auto split_c = [&](int j) { q3[j] = pack2(ra[j], rb[j]); };
+  auto hsplit = [&](int j) { split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]); };
 
 #pragma unroll
   for (int ph = 0; ph < NPH; ++ph) {
@@ -1157,8 +1062,8 @@ __device__ __forceinline__ void fwd_tile_split(const float* __restrict__ x, cons
   load_half(smem, 1, 0);  // first half batch of the fragment built under step 0
   MODE_STAMP(1)
 #define MODE_SB __builtin_amdgcn_sched_barrier(0);
-#define MODE_TMF(PA, PB, m, t) acc[t] = sp_mfma(a_cur[m][PA], bq[PB], acc[t]);
-#define MODE_TMFH(PA, PB, m, t) acc[t] = sp_mfma_f16(a_cur[m][PA], bq[PB], acc[t]); asm volatile("" :: "v"(acc[t]));  // (pinned: see the small tiles)
+#define MODE_TMF(PA, PB, m, t) acc[t] = mfma_bf16(a_cur[m][PA], bq[PB], acc[t]);
+#define MODE_TMFH(PA, PB, m, t) acc[t] = mfma_f16(a_cur[m][PA], bq[PB], acc[t]); asm volatile("" :: "v"(acc[t]));  // (pinned: see the small tiles)
 #ifdef MODE_TAPTIME
   unsigned long long tt_top = 0, tt_pre = 0, tt_post = __builtin_readcyclecounter(), ts_a = 0, ts_b = 0, ts_c = 0;
 #endif
@@ -1222,7 +1127,7 @@ __device__ __forceinline__ void fwd_tile_split(const float* __restrict__ x, cons
 #ifdef MODE_TAPTIME
       tt_pre = __builtin_readcyclecounter();
 #endif
-      sp_lds_barrier();  // the weights of step + 1 are in LDS
+      lds_barrier();  // the weights of step + 1 are in LDS
 #ifdef MODE_TAPTIME
       ts_c += tt_top - tt_post;  // second half of the previous step
       tt_post = __builtin_readcyclecounter();
@@ -1398,9 +1303,9 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
   const int cls = t.w >> 16;
   if (cls == 1) {
     if constexpr (F16) {
-      const float sx_ = sp_f16_scale_of(mode::absmax_load(amax_x));
+      const float sx_ = f16_scale_of(mode::absmax_load(amax_x));
       fwd_tile_split<WR_MID, true, (WR_MID + SROWS - 1) / SROWS, 2, EPI, true>(x, pos, wpt, y, d, t.x, t.y, t.z, cbase, smem, epi, sx_,
-                                                                              (1.f / sx_) * (1.f / sp_f16_scale_of(mode::absmax_load(amax_w))));
+                                                                              (1.f / sx_) * (1.f / f16_scale_of(mode::absmax_load(amax_w))));
     } else {
       fwd_tile_split<WR_MID, true, (WR_MID + SROWS - 1) / SROWS, 2, EPI>(x, pos, wpt, y, d, t.x, t.y, t.z, cbase, smem, epi);
     }
@@ -1408,9 +1313,9 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
   }
   if (cls != 0) {
     if constexpr (F16) {
-      const float sx_ = sp_f16_scale_of(mode::absmax_load(amax_x));
+      const float sx_ = f16_scale_of(mode::absmax_load(amax_x));
       fwd_tile_split<0, true, WR_PIPE_MAX / SROWS, 4, EPI, true>(x, pos, wpt, y, d, t.x, t.y, t.z, cbase, smem, epi, sx_,
-                                                                 (1.f / sx_) * (1.f / sp_f16_scale_of(mode::absmax_load(amax_w))));
+                                                                 (1.f / sx_) * (1.f / f16_scale_of(mode::absmax_load(amax_w))));
     } else {
       fwd_tile_split<0, true, WR_PIPE_MAX / SROWS, 4, EPI>(x, pos, wpt, y, d, t.x, t.y, t.z, cbase, smem, epi);
     }
@@ -1425,8 +1330,8 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
   const long long HW = (long long)d.H * d.W;
   float sx = 1.f, unscale = 1.f;
   if (F16) {
-    sx = sp_f16_scale_of(mode::absmax_load(amax_x));
-    unscale = (1.f / sx) * (1.f / sp_f16_scale_of(mode::absmax_load(amax_w)));
+    sx = f16_scale_of(mode::absmax_load(amax_x));
+    unscale = (1.f / sx) * (1.f / f16_scale_of(mode::absmax_load(amax_w)));
   }
 
   int roff[KT];
@@ -1518,10 +1423,10 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
     uint4* dst = op + (wave * 3) * 64 + lane;
     if constexpr (F16) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
+      for (int j = 0; j < 4; ++j) split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sp_split2(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
+      for (int j = 0; j < 4; ++j) split3_bf16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
       dst[128] = make_uint4(q3[0], q3[1], q3[2], q3[3]);
     }
     dst[0] = make_uint4(q1[0], q1[1], q1[2], q1[3]);
@@ -1542,7 +1447,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
   const int m = wave % TW, gset = (wave / TW) * 4;  // output tile and first pixel group of the MATRIX role
   const uint4* wpa = wps + ((long long)(g * d.MG + mg) * NCH16) * KT * MTW * 192 + m * 192;  // uniform; + p * 64 + lane per fragment
   const int nsteps = NCH16 * KT;
-  constexpr int NPC = F16 ? 2 : 3;  // pieces per value
+  constexpr int NPC = Arith<F16>::NP;  // pieces per value
   uint4 acur[3], anxt[3];  // weight fragments of this tap and of the next one (requested at the top of a tap, one tap ahead)
 #pragma unroll
   for (int p = 0; p < NPC; ++p) acur[p] = wpa[(unsigned)(p * 64 + lane)];
@@ -1580,7 +1485,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
   // 2 750 cycles per tap as it was, ~2 100 in this form, 1 500 for the MFMAs alone.
   sample(smem, 0, opbuf);
   sample(smem, 1, opbuf + SP_OP);
-  sp_lds_barrier();
+  lds_barrier();
   uint4 b0[4], b0n[4], b1[4], b2[4];
   const uint4* fragbase = opbuf + gset * 192 + lane;  // + buffer * SP_OP + (gi * 3 + piece) * 64
 #pragma unroll
@@ -1604,7 +1509,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
     // ---- 12 slots: lo x hi (piece 1 of the weights against piece 0 of the operand), hi x hi, hi x lo.  The second half batch of window
     // words has registers of its own (the third piece's are free) and is requested at the top of the tap; the next tap's first half batch
     // and its piece-0 fragments in slot 8, when the combines have consumed this tap's.
-#define MODE_MFH(PA, B, gi) acc[gi] = sp_mfma_f16(acur[PA], B[gi], acc[gi]); asm volatile("" :: "v"(acc[gi]));
+#define MODE_MFH(PA, B, gi) acc[gi] = mfma_f16(acur[PA], B[gi], acc[gi]); asm volatile("" :: "v"(acc[gi]));
     float raw2[4][4];
     for (int ch = 0; ch < NCH16; ++ch) {
       float* cur = smem + (ch & 1) * SP_WIN;
@@ -1622,11 +1527,11 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
         const float4 tw = rw[ks];
         const float* wp_ = wsrc + half * 8 * CP + roff[ks];
         const float* wpn_ = (k + 3 < KT ? cur : nxt) + half * 8 * CP + roff[(k + 3) % KT];
-        auto combine = [&](int c, float (&rr)[4][4]) {  // (one fma chain per value, kept scalar: see sp_split2)
+        auto combine = [&](int c, float (&rr)[4][4]) {  // (one fma chain per value, kept scalar: see split3_bf16_pinned)
           v[c] = __builtin_fmaf(tw.w, rr[c & 3][3], __builtin_fmaf(tw.z, rr[c & 3][2], __builtin_fmaf(tw.y, rr[c & 3][1], tw.x * rr[c & 3][0])));
           asm("" : "+v"(v[c]));
         };
-        auto hsplit = [&](int j) { sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]); };
+        auto hsplit = [&](int j) { split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]); };
 #pragma unroll
         for (int p = 0; p < 2; ++p) anxt[p] = (wpa + (long long)nstep * MTW * 192)[(unsigned)(p * 64 + lane)];
 #pragma unroll
@@ -1678,12 +1583,12 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
         for (int p = 0; p < 2; ++p) acur[p] = anxt[p];
 #pragma unroll
         for (int gi = 0; gi < 4; ++gi) b0[gi] = b0n[gi];
-        sp_lds_barrier();
+        lds_barrier();
       }
     }
 #undef MODE_MFH
   } else {
-#define MODE_MF(PA, B, gi) acc[gi] = sp_mfma(acur[PA], B[gi], acc[gi]);
+#define MODE_MF(PA, B, gi) acc[gi] = mfma_bf16(acur[PA], B[gi], acc[gi]);
 
   for (int ch = 0; ch < NCH16; ++ch) {
     float* cur = smem + (ch & 1) * SP_WIN;
@@ -1713,23 +1618,17 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
           raw[c][3] = q[WRP + 1];
         }
       };
-      auto combine = [&](int c) {  // (one fma chain per value, kept scalar: see sp_split2)
+      auto combine = [&](int c) {  // (one fma chain per value, kept scalar: see split3_bf16_pinned)
         v[c] = __builtin_fmaf(tw.w, raw[c & 3][3], __builtin_fmaf(tw.z, raw[c & 3][2], __builtin_fmaf(tw.y, raw[c & 3][1], tw.x * raw[c & 3][0])));
         asm("" : "+v"(v[c]));
       };
       auto split_a = [&](int j) {
-        q1[j] = sp_pack2(v[2 * j], v[2 * j + 1]);
-        ra[j] = v[2 * j] - __builtin_bit_cast(float, q1[j] << 16);
-        rb[j] = v[2 * j + 1] - __builtin_bit_cast(float, q1[j] & 0xffff0000u);
-        asm("" : "+v"(ra[j]), "+v"(rb[j]));
+        ra[j] = v[2 * j];
+        rb[j] = v[2 * j + 1];
+        q1[j] = split_step_bf16_pinned(ra[j], rb[j]);
       };
-      auto split_b = [&](int j) {
-        q2[j] = sp_pack2(ra[j], rb[j]);
-        ra[j] = ra[j] - __builtin_bit_cast(float, q2[j] << 16);
-        rb[j] = rb[j] - __builtin_bit_cast(float, q2[j] & 0xffff0000u);
-        asm("" : "+v"(ra[j]), "+v"(rb[j]));
-      };
-      auto split_c = [&](int j) { q3[j] = sp_pack2(ra[j], rb[j]); };
+      auto split_b = [&](int j) { q2[j] = split_step_bf16_pinned(ra[j], rb[j]); };
+      auto split_c = [&](int j) { q3[j] = pack2(ra[j], rb[j]); };
 
       // top of the tap: weight fragments of the next tap (global), the first half batch of window words
 #pragma unroll
@@ -1789,7 +1688,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_fwd_split_kernel(const float*
       for (int p = 0; p < 3; ++p) acur[p] = anxt[p];
 #pragma unroll
       for (int gi = 0; gi < 4; ++gi) b0[gi] = b0n[gi];
-      sp_lds_barrier();
+      lds_barrier();
     }
   }
 #undef MODE_MF
@@ -1886,11 +1785,11 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_split_kernel(const float*
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float sg = 1.f, sx = 1.f, unscale = 1.f;
   if (F16) {
-    sg = sp_f16_scale_of(mode::absmax_load(amax_g));
-    sx = sp_f16_scale_of(mode::absmax_load(amax_x));
+    sg = f16_scale_of(mode::absmax_load(amax_g));
+    sx = f16_scale_of(mode::absmax_load(amax_x));
     unscale = (1.f / sg) * (1.f / sx);
   }
-  constexpr int NPC = F16 ? 2 : 3;  // pieces per value
+  constexpr int NPC = Arith<F16>::NP;  // pieces per value
   uint32_t* gyb = reinterpret_cast<uint32_t*>(smem + BS_X2);  // [3][128][BS_GP]
   constexpr int WRP = BW_WR, CP = BW_CP;
   const int s = blockIdx.x, cg = blockIdx.y;
@@ -2009,9 +1908,9 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_split_kernel(const float*
       uint32_t p1, p2, p3;
       uint32_t* dst = gyb + (go0 + 32 * u) * BS_GP + gpp;
       if constexpr (F16) {
-        sp_split2_f16(a * sg, b2 * sg, p1, p2);
+        split2_f16_mix(a * sg, b2 * sg, p1, p2);
       } else {
-        sp_split2(a, b2, p1, p2, p3);
+        split3_bf16_pinned(a, b2, p1, p2, p3);
         dst[2 * 128 * BS_GP] = p3;
       }
       dst[0] = p1;
@@ -2052,10 +1951,10 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_split_kernel(const float*
     uint32_t q1[4], q2[4], q3[4];
     if constexpr (F16) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) sp_split2_f16(t8[2 * i], t8[2 * i + 1], q1[i], q2[i]);
+      for (int i = 0; i < 4; ++i) split2_f16_mix(t8[2 * i], t8[2 * i + 1], q1[i], q2[i]);
     } else {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) sp_split2(t8[2 * i], t8[2 * i + 1], q1[i], q2[i], q3[i]);
+      for (int i = 0; i < 4; ++i) split3_bf16_pinned(t8[2 * i], t8[2 * i + 1], q1[i], q2[i], q3[i]);
       bf[2] = make_uint4(q3[0], q3[1], q3[2], q3[3]);
     }
     bf[0] = make_uint4(q1[0], q1[1], q1[2], q1[3]);
@@ -2073,13 +1972,13 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_split_kernel(const float*
   // the 24 (F16: 12) MFMAs of one K-step of this wave's tap: smallest terms first, consecutive MFMAs on different accumulators
   auto mma24 = [&](const uint4 (&a)[4][3], const uint4 (&bf)[3]) {
     if constexpr (F16) {
-#define MODE_BS_TERM(PA, PB) _Pragma("unroll") for (int m = 0; m < 4; ++m) acc[m] = sp_mfma_f16(a[m][PA], bf[PB], acc[m]);
+#define MODE_BS_TERM(PA, PB) _Pragma("unroll") for (int m = 0; m < 4; ++m) acc[m] = mfma_f16(a[m][PA], bf[PB], acc[m]);
       MODE_BS_TERM(1, 0)
       MODE_BS_TERM(0, 1)
       MODE_BS_TERM(0, 0)
 #undef MODE_BS_TERM
     } else {
-#define MODE_BS_TERM(PA, PB) _Pragma("unroll") for (int m = 0; m < 4; ++m) acc[m] = sp_mfma(a[m][PA], bf[PB], acc[m]);
+#define MODE_BS_TERM(PA, PB) _Pragma("unroll") for (int m = 0; m < 4; ++m) acc[m] = mfma_bf16(a[m][PA], bf[PB], acc[m]);
       MODE_BS_TERM(2, 0)
       MODE_BS_TERM(0, 2)
       MODE_BS_TERM(1, 1)
@@ -2149,17 +2048,17 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_split_kernel(const float*
         const uint4* ga = reinterpret_cast<const uint4*>(gyb + (m8 * 32 + j) * BS_GP + 8 * ks8 + 4 * half);
         const uint4 a1 = ga[0], a2 = ga[128 * BS_GP / 4];
         if constexpr (F16) {
-          acc8 = sp_mfma_f16(a2, b8[0], acc8);
-          acc8 = sp_mfma_f16(a1, b8[1], acc8);
-          acc8 = sp_mfma_f16(a1, b8[0], acc8);
+          acc8 = mfma_f16(a2, b8[0], acc8);
+          acc8 = mfma_f16(a1, b8[1], acc8);
+          acc8 = mfma_f16(a1, b8[0], acc8);
         } else {
           const uint4 a3 = ga[2 * (128 * BS_GP / 4)];
-          acc8 = sp_mfma(a3, b8[0], acc8);
-          acc8 = sp_mfma(a1, b8[2], acc8);
-          acc8 = sp_mfma(a2, b8[1], acc8);
-          acc8 = sp_mfma(a2, b8[0], acc8);
-          acc8 = sp_mfma(a1, b8[1], acc8);
-          acc8 = sp_mfma(a1, b8[0], acc8);
+          acc8 = mfma_bf16(a3, b8[0], acc8);
+          acc8 = mfma_bf16(a1, b8[2], acc8);
+          acc8 = mfma_bf16(a2, b8[1], acc8);
+          acc8 = mfma_bf16(a2, b8[0], acc8);
+          acc8 = mfma_bf16(a1, b8[1], acc8);
+          acc8 = mfma_bf16(a1, b8[0], acc8);
         }
       }
       if (more_items) commit_xw(smem + (xbuf ^ 1) * BW_XW, wc);  // the other window buffer: nobody reads it now
@@ -2259,7 +2158,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_split_kernel(const 
     for (int i = 0; i < 8; ++i) t8[i] = sr[i];
     uint32_t q1[4], q2[4], q3[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) sp_split2(t8[2 * i], t8[2 * i + 1], q1[i], q2[i], q3[i]);
+    for (int i = 0; i < 4; ++i) split3_bf16_pinned(t8[2 * i], t8[2 * i + 1], q1[i], q2[i], q3[i]);
     bf[0] = make_uint4(q1[0], q1[1], q1[2], q1[3]);
     bf[1] = make_uint4(q2[0], q2[1], q2[2], q2[3]);
     bf[2] = make_uint4(q3[0], q3[1], q3[2], q3[3]);
@@ -2273,7 +2172,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_split_kernel(const 
     }
   };
   auto mma24 = [&](const uint4 (&a)[4][3], const uint4 (&bf)[3]) {
-#define MODE_BS_TERM(PA, PB) _Pragma("unroll") for (int m = 0; m < 4; ++m) acc[m] = sp_mfma(a[m][PA], bf[PB], acc[m]);
+#define MODE_BS_TERM(PA, PB) _Pragma("unroll") for (int m = 0; m < 4; ++m) acc[m] = mfma_bf16(a[m][PA], bf[PB], acc[m]);
     MODE_BS_TERM(2, 0)
     MODE_BS_TERM(0, 2)
     MODE_BS_TERM(1, 1)
@@ -2352,7 +2251,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_split_kernel(const 
     for (int u = 0; u < 4; ++u) {
       const bool oo = go0 + 32 * u < omx;
       uint32_t p1, p2, p3;
-      sp_split2((gok0 && oo) ? gv0[u] : 0.f, (gok1 && oo) ? gv1[u] : 0.f, p1, p2, p3);
+      split3_bf16_pinned((gok0 && oo) ? gv0[u] : 0.f, (gok1 && oo) ? gv1[u] : 0.f, p1, p2, p3);
       uint32_t* dst = gyb + (go0 + 32 * u) * BS_GP + gpp;
       dst[0] = p1;
       dst[128 * BS_GP] = p2;
@@ -2370,12 +2269,12 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_split_kernel(const 
     {
       const uint4* ga = reinterpret_cast<const uint4*>(gyb + (m8 * 32 + j) * BS_GP + 8 * ks8 + 4 * half);
       const uint4 a1 = ga[0], a2 = ga[128 * BS_GP / 4], a3 = ga[2 * (128 * BS_GP / 4)];
-      acc8 = sp_mfma(a3, b8[0], acc8);
-      acc8 = sp_mfma(a1, b8[2], acc8);
-      acc8 = sp_mfma(a2, b8[1], acc8);
-      acc8 = sp_mfma(a2, b8[0], acc8);
-      acc8 = sp_mfma(a1, b8[1], acc8);
-      acc8 = sp_mfma(a1, b8[0], acc8);
+      acc8 = mfma_bf16(a3, b8[0], acc8);
+      acc8 = mfma_bf16(a1, b8[2], acc8);
+      acc8 = mfma_bf16(a2, b8[1], acc8);
+      acc8 = mfma_bf16(a2, b8[0], acc8);
+      acc8 = mfma_bf16(a1, b8[1], acc8);
+      acc8 = mfma_bf16(a1, b8[0], acc8);
     }
   }
   __syncthreads();
@@ -2401,11 +2300,9 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bww_polar_split_kernel(const 
   for (int i = tid; i < 128 * BW_CG; i += NTHREADS) pb[(long long)8 * 128 * BW_CG + i] = red[i];
 }
 
-size_t win_lds_bytes(int wr, bool pipe) { return ((size_t)(pipe ? 2 : 1) * CCH * chan_pitch(wr) + wr + 8) * sizeof(float); }
 // the tall tiles of the split forward keep two pair steps of weight fragments (2 x 12 KB) behind their windows
 constexpr size_t TALL_W_BYTES = 2 * (size_t)MTW * 3 * 64 * sizeof(uint4);
 size_t tall_split_lds_bytes(int wr) { return ((win_lds_bytes(wr, true) + 15) / 16) * 16 + TALL_W_BYTES; }
-bool wrap_is_pipelined(int H) { return H + 1 <= WR_PIPE_MAX && win_lds_bytes(H + 1, true) <= 160 * 1024; }
 
 // out[p][w][h] = in[p][h][w] for P planes of H x W: 32x32 tiles through LDS, both sides coalesced
 __global__ __launch_bounds__(256) void transpose_planes_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W) {
@@ -2446,80 +2343,6 @@ int make_win_dims(WinDims& d, int B, int Ci, int H, int W, int Co, int Kh, int K
 
 
 }  // namespace
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Host-side tile plan.  tiles_host[4*i .. 4*i+3] = (h0, w0, rbase, cbase) ordered by class; counts[c] = tiles of class c:
-//   0: window of 81 rows   1: 145 rows   2: all H rows + 1 (wraps around)   3: does not fit (caller must use the general path)
-// and the class is also stored in bits 16.. of the 4th word (cbase | class << 16).
-// Inside a class the tiles are ordered so that, with the round-robin workgroup -> XCD assignment, the tiles that share rows of
-// the output (and cache lines of the input window) run on the same XCD and meet in its L2.
-extern "C" size_t mode_sphere_plan_max_tiles(int H, int W) {
-  if (H <= 0 || W <= 0) return 0;
-  return (size_t)mode::cdiv(H, TH) * mode::cdiv(W, TW);
-}
-
-extern "C" int mode_sphere_plan_build(const float* pos_host, int H, int W, int Kh, int Kw, int32_t* tiles_host, int32_t* counts) {
-  MODE_REQUIRE(pos_host && tiles_host && counts, MODE_ERR_BAD_ARG, "mode_sphere_plan_build: null pointer");
-  MODE_REQUIRE(H > 0 && W > 0 && Kh > 0 && Kw > 0, MODE_ERR_BAD_ARG, "mode_sphere_plan_build: non-positive size");
-  const int KK = Kh * Kw;
-  const long long HW = (long long)H * W;
-  const int nth = mode::cdiv(H, TH), ntw = mode::cdiv(W, TW);
-  std::vector<int32_t> cls[4];
-  // order: groups of 8 row-blocks; inside a group all column blocks; inside a column block the 8 row-blocks -> index % 8
-  // (the XCD) is the row-block, for every column block
-  for (int hg = 0; hg < nth; hg += kNumXCD)
-    for (int tw = 0; tw < ntw; ++tw)
-      for (int hs = 0; hs < kNumXCD && hg + hs < nth; ++hs) {
-        const int h0 = (hg + hs) * TH, w0 = tw * TW;
-        int dmin = 1 << 30, dmax = -(1 << 30), cmin = 1 << 30, cmax = -(1 << 30);
-        bool any = false;
-        for (int k = 0; k < KK; ++k)
-          for (int h = h0; h < std::min(h0 + TH, H); ++h)
-            for (int w = w0; w < std::min(w0 + TW, W); ++w) {
-              int r0, c0;
-              float4 wt;
-              const long long idx = (long long)h * W + w;
-              if (!mode::tap_record_fixed(pos_host[(2 * k) * HW + idx], pos_host[(2 * k + 1) * HW + idx], H, W, r0, c0, wt)) continue;
-              if (wt.x == 0.f && wt.y == 0.f && wt.z == 0.f && wt.w == 0.f) continue;
-              int dr = r0 - h0;  // wrapped into (-H/2, H/2]
-              dr %= H;
-              if (dr > H / 2) dr -= H;
-              if (dr <= -(H + 1) / 2) dr += H;
-              dmin = std::min(dmin, dr);
-              dmax = std::max(dmax, dr);
-              cmin = std::min(cmin, c0);
-              cmax = std::max(cmax, c0);
-              any = true;
-            }
-        int c = 0, rbase = h0, cbase = std::min(w0, std::max(W - WC, 0));
-        if (any) {
-          const int rows = dmax - dmin + 2;  // + the second corner row
-          const int cols = cmax - cmin + 2;
-          cbase = cmin;
-          rbase = ((h0 + dmin) % H + H) % H;
-          if (cols > WC) {
-            c = 3;
-          } else if (rows <= WR_SMALL && halves_fit(pos_host, H, W, KK, h0, w0, rbase, cbase)) {
-            c = 0;
-          } else if (rows <= WR_MID) {
-            c = 1;
-          } else {
-            c = 2;  // whole axis: any start works, take 0 so that no row index wraps twice
-            rbase = 0;
-            if (win_lds_bytes(H + 1, false) > 160 * 1024) c = 3;
-          }
-        }
-        if (cbase >= (1 << 16)) c = 3;
-        cls[c].insert(cls[c].end(), {h0, w0, rbase, cbase | (c << 16)});
-      }
-  size_t o = 0;
-  for (int c = 0; c < 4; ++c) counts[c] = (int32_t)(cls[c].size() / 4);
-  for (int c : {2, 1, 0, 3}) {  // tall windows first: they are the slowest tiles of the launch
-    if (!cls[c].empty()) std::memcpy(tiles_host + o, cls[c].data(), cls[c].size() * sizeof(int32_t));
-    o += cls[c].size();
-  }
-  return MODE_OK;
-}
 
 extern "C" size_t mode_sphere_conv_win_wpack_bytes(int Ci, int Co, int Kh, int Kw, int groups) {
   if (Ci <= 0 || Co <= 0 || groups <= 0 || Kh * Kw != KT || Ci % groups || Co % groups) return 0;
@@ -2691,144 +2514,6 @@ extern "C" int mode_sphere_conv_fwd_win_bn(const float* x, const float* pos, con
   int rc = mode::check_bn(bn, "mode_sphere_conv_fwd_win_bn");
   if (rc != MODE_OK) return rc;
   return sphere_conv_fwd_win_impl(x, pos, w, y, wpack, tiles, n_small, n_mid, n_wrap, B, Ci, H, W, Co, Kh, Kw, groups, transposed, stream, bn);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Pixels of the tiles that are NOT of the small-window class, sorted by linear index (they go to the general kernels).
-extern "C" int mode_sphere_plan_rest_pixels(const int32_t* tiles_host, const int32_t* counts, int H, int W, int32_t* pix_host,
-                                            int32_t* n_pix) {
-  MODE_REQUIRE(tiles_host && counts && pix_host && n_pix, MODE_ERR_BAD_ARG, "mode_sphere_plan_rest_pixels: null pointer");
-  const int n = counts[0] + counts[1] + counts[2] + counts[3];
-  std::vector<int32_t> v;
-  for (int i = 0; i < n; ++i) {
-    const int32_t* t = tiles_host + 4 * i;
-    if ((t[3] >> 16) == 0) continue;
-    for (int h = t[0]; h < std::min(t[0] + TH, H); ++h)
-      for (int w = t[1]; w < std::min(t[1] + TW, W); ++w) v.push_back(h * W + w);
-  }
-  std::sort(v.begin(), v.end());
-  if (!v.empty()) std::memcpy(pix_host, v.data(), v.size() * sizeof(int32_t));
-  *n_pix = (int32_t)v.size();
-  return MODE_OK;
-}
-
-// Sampling records of the small-window tiles for the weight-gradient kernel, in tile-list order:
-//   index (((ti*2 + half)*4 + column)*9 + tap)*32 + row -> window offset (rec_off) and the 4 corner weights (rec_w, 4 floats)
-extern "C" size_t mode_sphere_plan_records_count(int n_small) { return n_small > 0 ? (size_t)n_small * 2 * TW * BW_NREC : 0; }
-
-extern "C" int mode_sphere_plan_records(const float* pos_host, const int32_t* tiles_host, const int32_t* counts, int H, int W,
-                                        float* rec_w_host, int32_t* rec_off_host) {
-  MODE_REQUIRE(pos_host && tiles_host && counts && rec_w_host && rec_off_host, MODE_ERR_BAD_ARG, "mode_sphere_plan_records: null pointer");
-  const long long HW = (long long)H * W;
-  const int32_t* small = tiles_host + 4 * (size_t)(counts[2] + counts[1]);  // list order: wrap-around, mid, small
-  for (int ti = 0; ti < counts[0]; ++ti) {
-    const int h0 = small[4 * ti], w0 = small[4 * ti + 1], rbase = small[4 * ti + 2], cbase = small[4 * ti + 3] & 0xffff;
-    for (int hf = 0; hf < 2; ++hf) {
-      const int rb = (rbase + hf * BW_TH) % H;
-      for (int wc = 0; wc < TW; ++wc)
-        for (int k = 0; k < KT; ++k)
-          for (int px = 0; px < BW_TH; ++px) {
-            const size_t o = ((((size_t)ti * 2 + hf) * TW + wc) * KT + k) * BW_TH + px;
-            const int h = h0 + hf * BW_TH + px, w = w0 + wc;
-            int r0 = 0, c0 = 0;
-            float4 wt = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool live = false;
-            if (h < H && w < W) {
-              const long long idx = (long long)h * W + w;
-              live = mode::tap_record_fixed(pos_host[(2 * k) * HW + idx], pos_host[(2 * k + 1) * HW + idx], H, W, r0, c0, wt);
-            }
-            live = live && !(wt.x == 0.f && wt.y == 0.f && wt.z == 0.f && wt.w == 0.f);
-            rec_off_host[o] = live ? (c0 - cbase) * BW_WR + ((r0 - rb) % H + H) % H : 0;
-            rec_w_host[4 * o + 0] = live ? wt.x : 0.f;
-            rec_w_host[4 * o + 1] = live ? wt.y : 0.f;
-            rec_w_host[4 * o + 2] = live ? wt.z : 0.f;
-            rec_w_host[4 * o + 3] = live ? wt.w : 0.f;
-          }
-    }
-  }
-  return MODE_OK;
-}
-
-// Work items of the polar weight-gradient kernel: every tile that is NOT of the small-window class, split into 2 halves x 4
-// columns.  pitems_host[20 * i ..] = (h0, w, rbase[9], cbase[9]); rec_w_host[4 * (i*288 + tap*32 + row)], rec_off_host[...] = the
-// sampling records in the per-tap window layout.  Returns the number of items, or -1 (in *n_items) if some column does not fit
-// its per-tap windows (34 rows x 2 columns per tap) -- the caller then keeps those pixels on the general kernel.
-extern "C" size_t mode_sphere_plan_polar_max_items(const int32_t* counts) {
-  return counts ? (size_t)(counts[1] + counts[2]) * 2 * TW : 0;
-}
-
-extern "C" int mode_sphere_plan_polar(const float* pos_host, const int32_t* tiles_host, const int32_t* counts, int H, int W,
-                                      int32_t* pitems_host, float* rec_w_host, int32_t* rec_off_host, int32_t* n_items) {
-  MODE_REQUIRE(pos_host && tiles_host && counts && pitems_host && rec_w_host && rec_off_host && n_items, MODE_ERR_BAD_ARG,
-               "mode_sphere_plan_polar: null pointer");
-  const long long HW = (long long)H * W;
-  const int ntall = counts[2] + counts[1];  // list order: wrap-around, mid, small
-  int ni = 0;
-  for (int ti = 0; ti < ntall; ++ti) {
-    const int th0 = tiles_host[4 * ti], tw0 = tiles_host[4 * ti + 1];
-    for (int hf = 0; hf < 2; ++hf)
-      for (int wc = 0; wc < TW; ++wc) {
-        const int h0 = th0 + hf * BW_TH, w = tw0 + wc;
-        if (h0 >= H || w >= W) continue;
-        int32_t* pi = pitems_host + (size_t)ni * BP_ITEM_INTS;
-        pi[0] = h0;
-        pi[1] = w;
-        for (int k = 0; k < KT; ++k) {
-          // row SHIFT of every live pixel, n = r0 - (h0 + px) modulo H, taken relative to the first one so that a shift of about
-          // half the axis (the far side of the sphere) does not straddle the wrap-around cut
-          int nfirst = 0, nmin = 1 << 30, nmax = -(1 << 30), cmin = 1 << 30, cmax = -(1 << 30);
-          bool have = false;
-          for (int px = 0; px < BW_TH && h0 + px < H; ++px) {
-            int r0, c0;
-            float4 wt;
-            const long long idx = (long long)(h0 + px) * W + w;
-            if (!mode::tap_record_fixed(pos_host[(2 * k) * HW + idx], pos_host[(2 * k + 1) * HW + idx], H, W, r0, c0, wt)) continue;
-            if (wt.x == 0.f && wt.y == 0.f && wt.z == 0.f && wt.w == 0.f) continue;
-            int n = ((r0 - h0 - px) % H + H) % H;
-            if (!have) {
-              nfirst = n;
-              have = true;
-            }
-            n = ((n - nfirst + H / 2) % H + H) % H - H / 2 + nfirst;  // within H/2 of the first shift
-            nmin = std::min(nmin, n);
-            nmax = std::max(nmax, n);
-            cmin = std::min(cmin, c0);
-            cmax = std::max(cmax, c0);
-          }
-          int rb = 0, cbs = 0;
-          if (have) {
-            // rows h0 + nmin .. h0 + 31 + nmax (+1 for the second corner) must fit the 34-row window, the columns its 2
-            if (BW_TH - 1 + (nmax - nmin) + 2 > BP_WR || cmax - cmin + 2 > 2) {
-              *n_items = -1;
-              return MODE_OK;
-            }
-            rb = ((h0 + nmin) % H + H) % H;
-            cbs = cmin;
-          }
-          pi[2 + k] = rb;
-          pi[2 + KT + k] = cbs;
-          for (int px = 0; px < BW_TH; ++px) {
-            const size_t o = ((size_t)ni * KT + k) * BW_TH + px;
-            int r0 = 0, c0 = 0;
-            float4 wt = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool live = false;
-            if (h0 + px < H) {
-              const long long idx = (long long)(h0 + px) * W + w;
-              live = mode::tap_record_fixed(pos_host[(2 * k) * HW + idx], pos_host[(2 * k + 1) * HW + idx], H, W, r0, c0, wt);
-            }
-            live = live && !(wt.x == 0.f && wt.y == 0.f && wt.z == 0.f && wt.w == 0.f);
-            rec_off_host[o] = live ? k * BP_TAPW + (c0 - cbs) * BP_WR + ((r0 - rb) % H + H) % H : 0;
-            rec_w_host[4 * o + 0] = live ? wt.x : 0.f;
-            rec_w_host[4 * o + 1] = live ? wt.y : 0.f;
-            rec_w_host[4 * o + 2] = live ? wt.z : 0.f;
-            rec_w_host[4 * o + 3] = live ? wt.w : 0.f;
-          }
-        }
-        ++ni;
-      }
-  }
-  *n_items = ni;
-  return MODE_OK;
 }
 
 int bww_polar_splits(const WinDims& d, int n_items) {
@@ -3011,7 +2696,6 @@ extern "C" int mode_transpose_planes(const float* in, float* out, long long plan
 // sphere_conv.hip, restricted to a tile list (mode_sphere_conv_bwd_data_adj_list).
 namespace {
 
-constexpr int AJ_PIX = TH * TW;  // 256 pixels per tile = 8 waves x 32 lanes
 
 // NS = 4: every adjoint list of the tile has at most four entries; NS = 6: up to six (the columns around the equator, where the
 // sampling positions of neighbouring output columns straddle a pixel boundary): slots 4 and 5 come from a second record array, read
@@ -3141,10 +2825,10 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
     uint4* dst = op + (wave * 3) * 64 + lane;
     if constexpr (F16) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
+      for (int j = 0; j < 4; ++j) split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sp_split2(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
+      for (int j = 0; j < 4; ++j) split3_bf16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
       dst[128] = make_uint4(q3[0], q3[1], q3[2], q3[3]);
     }
     dst[0] = make_uint4(q1[0], q1[1], q1[2], q1[3]);
@@ -3159,7 +2843,7 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
   const int m = wave % TW, gset = (wave / TW) * 4;
   const uint4* wpa = wps + ((long long)(g * d.MG + mg) * NCH16) * KT * MTW * 192 + m * 192;
   const int nsteps = NCH16 * KT;
-  constexpr int NPC = F16 ? 2 : 3;  // pieces per value
+  constexpr int NPC = Arith<F16>::NP;  // pieces per value
   uint4 acur[3], anxt[3];  // weight fragments of this tap and of the next one
 #pragma unroll
   for (int p = 0; p < NPC; ++p) acur[p] = wpa[(unsigned)(p * 64 + lane)];
@@ -3173,7 +2857,7 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
   // refilled in place, window words in two half batches of 4 channels); here a sample has NS sources at arbitrary window offsets
   sample(smem, o_p0, w_p0, o2_p0, w2_p0, opbuf);
   sample(smem, o_p1, w_p1, o2_p1, w2_p1, opbuf + SP_OP);
-  sp_lds_barrier();
+  lds_barrier();
   uint4 b0[4], b0n[4], b1[4], b2[4];
   const uint4* fragbase = opbuf + gset * 192 + lane;
 #pragma unroll
@@ -3202,7 +2886,7 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
     // ---- 12 slots, as in sphere_fwd_split_kernel<false, true>: hi x hi, lo x hi, hi x lo; the second half batch of window words in
     // registers of its own, requested at the top of the tap.  (The empty asm behind each MFMA pins it to its slot: without a consumer in
     // the slot the compiler sinks the first eight below all their sched_barriers, to where their operands' registers are assembled.)
-#define MODE_MFH(PA, B, gi) acc[gi] = sp_mfma_f16(acur[PA], B[gi], acc[gi]); asm volatile("" :: "v"(acc[gi]));
+#define MODE_MFH(PA, B, gi) acc[gi] = mfma_f16(acur[PA], B[gi], acc[gi]); asm volatile("" :: "v"(acc[gi]));
     float raw2[4][NS];
     // Three record sets, the record of sampled tap s in set s % 3, requested FOUR taps ahead (at the top of tap s - 6 ... i.e. under tap
     // k the record of tap k + 4 is requested and the one of tap k + 3 becomes current in slot 8): requested one tap ahead as in the
@@ -3235,7 +2919,7 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
           v[c] = t;
           asm("" : "+v"(v[c]));
         };
-        auto hsplit = [&](int j) { sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]); };
+        auto hsplit = [&](int j) { split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]); };
 #pragma unroll
         for (int p = 0; p < 2; ++p) anxt[p] = (wpa + (long long)nstep * MTW * 192)[(unsigned)(p * 64 + lane)];
         record((k + 4) % KT, ro[sl], rwt[sl], ro2[sl], rwt2[sl]);
@@ -3290,12 +2974,12 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
         for (int p = 0; p < 2; ++p) acur[p] = anxt[p];
 #pragma unroll
         for (int gi = 0; gi < 4; ++gi) b0[gi] = b0n[gi];
-        sp_lds_barrier();
+        lds_barrier();
       }
     }
 #undef MODE_MFH
   } else {
-#define MODE_MF(PA, B, gi) acc[gi] = sp_mfma(acur[PA], B[gi], acc[gi]);
+#define MODE_MF(PA, B, gi) acc[gi] = mfma_bf16(acur[PA], B[gi], acc[gi]);
 
   for (int ch = 0; ch < NCH16; ++ch) {
     float* cur = smem + (ch & 1) * SP_WIN;
@@ -3314,21 +2998,15 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
         float t = __builtin_fmaf(w_use.w, raw[c & 3][3], __builtin_fmaf(w_use.z, raw[c & 3][2], __builtin_fmaf(w_use.y, raw[c & 3][1], w_use.x * raw[c & 3][0])));
         if (NS == 6) t = __builtin_fmaf(w2_use.y, raw[c & 3][NS - 1], __builtin_fmaf(w2_use.x, raw[c & 3][NS - 2], t));
         v[c] = t;
-        asm("" : "+v"(v[c]));  // (scalar chains: see sp_split2)
+        asm("" : "+v"(v[c]));  // (scalar chains: see split3_bf16_pinned)
       };
       auto split_a = [&](int j) {
-        q1[j] = sp_pack2(v[2 * j], v[2 * j + 1]);
-        ra[j] = v[2 * j] - __builtin_bit_cast(float, q1[j] << 16);
-        rb[j] = v[2 * j + 1] - __builtin_bit_cast(float, q1[j] & 0xffff0000u);
-        asm("" : "+v"(ra[j]), "+v"(rb[j]));
+        ra[j] = v[2 * j];
+        rb[j] = v[2 * j + 1];
+        q1[j] = split_step_bf16_pinned(ra[j], rb[j]);
       };
-      auto split_b = [&](int j) {
-        q2[j] = sp_pack2(ra[j], rb[j]);
-        ra[j] = ra[j] - __builtin_bit_cast(float, q2[j] << 16);
-        rb[j] = rb[j] - __builtin_bit_cast(float, q2[j] & 0xffff0000u);
-        asm("" : "+v"(ra[j]), "+v"(rb[j]));
-      };
-      auto split_c = [&](int j) { q3[j] = sp_pack2(ra[j], rb[j]); };
+      auto split_b = [&](int j) { q2[j] = split_step_bf16_pinned(ra[j], rb[j]); };
+      auto split_c = [&](int j) { q3[j] = pack2(ra[j], rb[j]); };
 
 #pragma unroll
       for (int p = 0; p < 3; ++p) anxt[p] = (wpa + (long long)nstep * MTW * 192)[(unsigned)(p * 64 + lane)];
@@ -3391,7 +3069,7 @@ __device__ __forceinline__ void bwd_data_tile(const float* __restrict__ gy, cons
       for (int p = 0; p < 3; ++p) acur[p] = anxt[p];
 #pragma unroll
       for (int gi = 0; gi < 4; ++gi) b0[gi] = b0n[gi];
-      sp_lds_barrier();
+      lds_barrier();
     }
   }
 #undef MODE_MF
@@ -3425,8 +3103,8 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_split_kernel(const f
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float sx = 1.f, unscale = 1.f;
   if (F16) {
-    sx = sp_f16_scale_of(mode::absmax_load(amax_g));
-    unscale = (1.f / sx) * (1.f / sp_f16_scale_of(mode::absmax_load(amax_w)));
+    sx = f16_scale_of(mode::absmax_load(amax_g));
+    unscale = (1.f / sx) * (1.f / f16_scale_of(mode::absmax_load(amax_w)));
   }
   const int4 t = tiles[blockIdx.x];
   if ((t.w >> 16) == 0)
@@ -3440,7 +3118,7 @@ __global__ __launch_bounds__(NTHREADS) void sphere_bwd_data_split_kernel(const f
 // runs over the output channels o.  `d` carries the swapped roles (d.Cog = input channels per group, d.Cig = output channels per group).
 template <bool F16>
 __global__ void pack_w_win_split_t(const float* __restrict__ w, uint4* __restrict__ wps, WinDims d, int NCH16, const float* __restrict__ amax_w) {
-  const float sw = F16 ? sp_f16_scale_of(mode::absmax_load(amax_w)) : 1.f;
+  const float sw = F16 ? f16_scale_of(mode::absmax_load(amax_w)) : 1.f;
   const long long total = (long long)d.G * d.MG * NCH16 * KT * MTW * 64;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
     const int lane = (int)(idx & 63);
@@ -3465,10 +3143,10 @@ __global__ void pack_w_win_split_t(const float* __restrict__ w, uint4* __restric
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if constexpr (F16) {
-        sp_split2_f16(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
+        split2_f16_mix(v[2 * j], v[2 * j + 1], q1[j], q2[j]);
         q3[j] = 0u;
       } else {
-        sp_split2(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
+        split3_bf16_pinned(v[2 * j], v[2 * j + 1], q1[j], q2[j], q3[j]);
       }
     }
     uint4* dst = wps + (idx - lane) * 3 + lane;
@@ -3479,149 +3157,6 @@ __global__ void pack_w_win_split_t(const float* __restrict__ w, uint4* __restric
 }
 
 }  // namespace
-
-// Host-side plan of the adjoint windows (stride 1, output grid = input grid).  For every 64 x 4 tile of INPUT pixels q (same tiling as
-// mode_sphere_plan_build) it collects L(k, q) for all nine taps and all pixels of the tile.  A tile is "good" when every list has at
-// most 4 entries and all their source pixels lie in one window of WR_SMALL rows x WC columns:
-//   good_tiles[4 i ..] = (h0, w0, rbase, cbase | six << 16), six = 1 when some list of the tile has 5 or 6 entries (slots 4, 5 in
-//   rec_off2 / rec_w2 [((i * 9 + tap) * 256 + pixel) * 2 + slot - 4]; lists longer than 6 make a tile bad);
-//   rec_off / rec_w [((i * 9 + tap) * 256 + pixel) * 4 + slot], pixel =
-//   ((rowblock * 4 + column) * 32 + row) -- the lane order of the kernel; offset = (source column - cbase) * WR_SMALL + (source row -
-//   rbase) mod H, unused slots (0, 0.0f); slots in ascending source-pixel order (the gather kernel's summation order).
-//   bad_tiles[2 j ..] = (h0, w0) of the others.  counts = (good, bad).
-extern "C" int mode_sphere_adjplan_build(const float* pos_host, int H, int W, int Kh, int Kw, int32_t* good_tiles, int32_t* bad_tiles,
-                                         int32_t* counts, int32_t* rec_off_host, float* rec_w_host, int32_t* rec_off2_host,
-                                         float* rec_w2_host) {
-  MODE_REQUIRE(pos_host && good_tiles && bad_tiles && counts && rec_off_host && rec_w_host && rec_off2_host && rec_w2_host,
-               MODE_ERR_BAD_ARG, "mode_sphere_adjplan_build: null pointer");
-  MODE_REQUIRE(H > 0 && W > 0 && Kh * Kw == KT, MODE_ERR_BAD_ARG, "mode_sphere_adjplan_build: needs a positive size and %d taps", KT);
-  const long long HW = (long long)H * W;
-  MODE_REQUIRE((long long)KT * HW * 4 < (1ll << 31), MODE_ERR_UNSUPPORTED, "mode_sphere_adjplan_build: table too large");
-  // adjoint lists in CSR form, rows (tap, q), filled in ascending p (the order of mode_sphere_adjoint_build)
-  std::vector<int32_t> rowptr((size_t)KT * HW + 1, 0);
-  auto corners = [&](int k, long long p, int qs[4], float ws[4]) -> int {
-    const float h = pos_host[(long long)(2 * k) * HW + p], w = pos_host[(long long)(2 * k + 1) * HW + p];
-    if (!(h > -1.f && w > -1.f && h < (float)H && w < (float)W)) return 0;
-    const float hf = floorf(h), wf = floorf(w);
-    const int hl = (int)hf, wl = (int)wf, hh = hl + 1, wh = wl + 1;
-    const float lh = h - hf, lw = w - wf, uh = 1.f - lh, uw = 1.f - lw;
-    const float wt[4] = {uh * uw, uh * lw, lh * uw, lh * lw};
-    const int hc[4] = {hl, hl, hh, hh}, wc[4] = {wl, wh, wl, wh};
-    int n = 0;
-    for (int i = 0; i < 4; ++i)
-      if (hc[i] >= 0 && hc[i] <= H - 1 && wc[i] >= 0 && wc[i] <= W - 1 && wt[i] != 0.f) {
-        qs[n] = hc[i] * W + wc[i];
-        ws[n] = wt[i];
-        ++n;
-      }
-    return n;
-  };
-  int qs[4];
-  float ws[4];
-  for (int k = 0; k < KT; ++k)
-    for (long long p = 0; p < HW; ++p) {
-      const int n = corners(k, p, qs, ws);
-      for (int i = 0; i < n; ++i) rowptr[(size_t)k * HW + qs[i] + 1]++;
-    }
-  for (size_t i = 0; i < (size_t)KT * HW; ++i) rowptr[i + 1] += rowptr[i];
-  std::vector<int32_t> ep(rowptr.back());
-  std::vector<float> ew(rowptr.back());
-  {
-    std::vector<int32_t> cur(rowptr.begin(), rowptr.end() - 1);
-    for (int k = 0; k < KT; ++k)
-      for (long long p = 0; p < HW; ++p) {
-        const int n = corners(k, p, qs, ws);
-        for (int i = 0; i < n; ++i) {
-          const int32_t at = cur[(size_t)k * HW + qs[i]]++;
-          ep[at] = (int32_t)p;
-          ew[at] = ws[i];
-        }
-      }
-  }
-  const int nth = mode::cdiv(H, TH), ntw = mode::cdiv(W, TW);
-  int ngood = 0, nbad = 0;
-  struct GoodTile {
-    int h0, w0, rbase, cbase, six;
-  };
-  std::vector<GoodTile> good;
-  for (int hg = 0; hg < nth; hg += kNumXCD)  // tile order as in mode_sphere_plan_build (tiles sharing rows meet on one XCD)
-    for (int tw = 0; tw < ntw; ++tw)
-      for (int hs = 0; hs < kNumXCD && hg + hs < nth; ++hs) {
-        const int h0 = (hg + hs) * TH, w0 = tw * TW;
-        bool ok = h0 + TH <= H && w0 + TW <= W;  // whole tiles only: ragged edges stay on the gather kernel
-        bool six = false;                        // some list has 5 or 6 entries: the 6-slot class
-        int dmin = 1 << 30, dmax = -(1 << 30), cmin = 1 << 30, cmax = -(1 << 30);
-        for (int k = 0; k < KT && ok; ++k)
-          for (int h = h0; h < h0 + TH && ok; ++h)
-            for (int w = w0; w < w0 + TW; ++w) {
-              const size_t row = (size_t)k * HW + (size_t)h * W + w;
-              const int nent = rowptr[row + 1] - rowptr[row];
-              if (nent > 6) {
-                ok = false;
-                break;
-              }
-              if (nent > 4) six = true;
-              for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) {
-                const int hp = ep[e] / W, wp = ep[e] % W;
-                int dr = (hp - h0) % H;
-                if (dr > H / 2) dr -= H;
-                if (dr <= -(H + 1) / 2) dr += H;
-                dmin = std::min(dmin, dr);
-                dmax = std::max(dmax, dr);
-                cmin = std::min(cmin, wp);
-                cmax = std::max(cmax, wp);
-              }
-            }
-        int rbase = h0, cbase = std::min(w0, std::max(W - WC, 0));
-        if (ok && dmax >= dmin) {
-          if (dmax - dmin + 1 > WR_SMALL || cmax - cmin + 1 > WC || cmin >= (1 << 16)) ok = false;
-          rbase = ((h0 + dmin) % H + H) % H;
-          cbase = cmin;
-        }
-        if (!ok) {
-          bad_tiles[2 * nbad] = h0;
-          bad_tiles[2 * nbad + 1] = w0;
-          ++nbad;
-          continue;
-        }
-        good.push_back({h0, w0, rbase, cbase, six ? 1 : 0});
-      }
-  // the 6-slot tiles first: they are the slowest workgroups of the launch, and started first they end inside its last round
-  std::stable_sort(good.begin(), good.end(), [](const GoodTile& a, const GoodTile& b2) { return a.six > b2.six; });
-  for (const GoodTile& gt : good) {
-    const int h0 = gt.h0, w0 = gt.w0, rbase = gt.rbase, cbase = gt.cbase;
-    int32_t* tl = good_tiles + 4 * (size_t)ngood;
-    tl[0] = h0; tl[1] = w0; tl[2] = rbase; tl[3] = cbase | (gt.six << 16);
-    for (int k = 0; k < KT; ++k)
-      for (int pix = 0; pix < AJ_PIX; ++pix) {
-        const int wv = pix >> 5, h = h0 + (wv / TW) * 32 + (pix & 31), w = w0 + (wv % TW);
-        const size_t row = (size_t)k * HW + (size_t)h * W + w;
-        const size_t o = (((size_t)ngood * KT + k) * AJ_PIX + pix) * 4, o2 = o / 2;
-        for (int s = 0; s < 4; ++s) {
-          rec_off_host[o + s] = 0;
-          rec_w_host[o + s] = 0.f;
-        }
-        rec_off2_host[o2] = rec_off2_host[o2 + 1] = 0;
-        rec_w2_host[o2] = rec_w2_host[o2 + 1] = 0.f;
-        int s = 0;
-        for (int e = rowptr[row]; e < rowptr[row + 1]; ++e, ++s) {
-          const int hp = ep[e] / W, wp = ep[e] % W;
-          const int off = (wp - cbase) * WR_SMALL + ((hp - rbase) % H + H) % H;
-          if (s < 4) {
-            rec_off_host[o + s] = off;
-            rec_w_host[o + s] = ew[e];
-          } else {
-            rec_off2_host[o2 + s - 4] = off;
-            rec_w2_host[o2 + s - 4] = ew[e];
-          }
-        }
-      }
-    ++ngood;
-  }
-  counts[0] = ngood;
-  counts[1] = nbad;
-  return MODE_OK;
-}
 
 extern "C" size_t mode_sphere_conv_bwd_data_win_wpack_bytes(int Ci, int Co, int Kh, int Kw, int groups) {
   if (Ci <= 0 || Co <= 0 || groups <= 0 || Kh * Kw != KT || Ci % groups || Co % groups) return 0;

@@ -1401,11 +1401,14 @@ def _tag3(name, ci, co, stride, d, h, w):
 # The stride-1 3-D layers of a TRAINING step run on TWO fp16 pieces and three MFMAs per product (mode_conv3d_*_split_f16; the
 # product default since round 5, `bench.py --no-conv3d-f16` is the A/B): each operand scaled by a power of two taken from its tensor's
 # largest finite magnitude -- left by the BatchNorm pass that wrote the tensor (the `_amax` entries), or by mode_abs_max.
-# Precision contract (include/mode_hip.h): an element keeps 22 significant bits down to ~2^-17 of its tensor's maximum, fewer below,
-# none below ~2^-39 of it; three bf16 pieces (CONV3D_S1_F16 = False, and every inference call) keep 24 bits for every element.
+# Precision contract (stated once in csrc/split_arith.h; include/mode_hip.h for the entries): on two fp16 pieces an element keeps 22
+# significant bits down to ~2^-17 of its tensor's maximum, fewer below, none below ~2^-39 of it; on three bf16 pieces (the switch set to
+# False) it keeps 24 bits whatever its size.
 CONV3D_S1_F16 = True
 # ... and of an INFERENCE forward (conv3d_bn_eval: the folded-BatchNorm epilogues on the same arithmetic, the activations' maxima out of the
-# kernels' epilogues; mode_conv3d_fwd_split_f16_bn)
+# kernels' epilogues; mode_conv3d_fwd_split_f16_bn).  On BY DEFAULT: an inference call's stride-1 3-D and 3 x 3 layers run on two fp16 pieces
+# too, under the same 22-bit contract.  To keep inference on three bf16 pieces (24 bits for every element) set both module globals below
+# to False before the forward; `bench.py --no-eval-f16` does exactly that.
 CONV3D_EVAL_F16 = True
 CONV2D_EVAL_F16 = True  # (the extractor's stride-1 3 x 3 layers of an inference forward: mode_conv2d_fwd_split_f16_bn)
 
