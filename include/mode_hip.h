@@ -997,6 +997,61 @@ int mode_spp_concat_fwd(const float* raw, const float* skip, const float* b8, co
 int mode_spp_concat_bwd(const float* gcat, float* graw, float* gb8, float* gb16, float* gb32, float* gb64, int N, int Cr, int Cs, int Cb,
                         int H, int W, mode_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The optimizer of the training step (train_disparity.py:293: optim.Adam(params, lr, betas=(0.9, 0.999))).  csrc/optim.hip:
+ * one update rule for all parameter tensors and all parameter groups in THREE launches, none of which depends on a host value
+ * that changes from step to step (capturable), with a guard against non-finite gradients and the global gradient norm as a by-product.
+ * No atomics, a summation order that depends on n alone: bit-repeatable on any stream.
+ *
+ * Data (all device memory of the caller):
+ *   grad, exp_avg, exp_avg_sq: three flat fp32 buffers of n elements in ONE layout: segment after segment, no padding.
+ *   segments[n_seg] (mode_adam_segment): one per parameter tensor: its address, its first element in the flat layout, its size and
+ *     its group.  chunks[n_chunks] (mode_adam_chunk): at most MODE_ADAM_CHUNK elements each, every chunk inside ONE segment (off is
+ *     the chunk's first element in the flat layout), together covering every element exactly once; built once by the caller.
+ *   block: mode_adam_block_bytes(n_groups) bytes, 8-byte aligned, zeroed by the caller before the first step:
+ *     doubles [0, MODE_ADAM_STATE_DOUBLES): the state (MODE_ADAM_STEP .. below), written by mode_adam_prepare only;
+ *     doubles [8 + 8 g, 8 + 8 g + 8), g < n_groups: the group's hyper-parameters lr, beta1, beta2, eps, weight_decay, max_grad_norm
+ *       (<= 0: no clipping) and two unused, written by the caller (and only by the caller);
+ *     then 8 + 8 n_groups floats that mode_adam_prepare derives for mode_adam_update (word 0: the decision, 1 = skip).
+ * mode_adam_prepare: sum of squares of grad in fp64 (the square of an fp32 value is exact there) and the count of non-finite
+ *   elements, in the scheme of mode_masked_metrics (two launches).  The second launch decides: with skip_nonfinite != 0 and a non-finite
+ *   element the step is SKIPPED (MODE_ADAM_SKIPPED + 1, MODE_ADAM_STEP unchanged); otherwise MODE_ADAM_STEP + 1 and per group
+ *   step_size = lr / (1 - beta1^step), sqrt(1 - beta2^step) and clip = min(1, max_grad_norm / (norm + 1e-6)), formed in fp64 and rounded
+ *   to fp32 (torch.optim.Adam's single-tensor path; torch.nn.utils.clip_grad_norm_).  MODE_ADAM_GRAD_NORM, MODE_ADAM_FOUND_INF (0 / 1)
+ *   and MODE_ADAM_NONFINITE (the count) are written by every call.  workspace: 8-byte aligned, >= mode_adam_workspace_bytes(n).
+ * mode_adam_update (one launch): nothing at all when the decision is "skip"; otherwise per element, in fp32, unfused, in torch's order
+ *     g = grad * clip;  g = g + weight_decay * p (weight_decay != 0);  m = m + (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g g;
+ *     p = p - step_size * (m / (sqrt(v) / sqrt(1 - beta2^step) + eps))
+ *   grad itself is left as it was.  16-byte accesses wherever the chunk's addresses in all four buffers share their alignment.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, n <= 0, n_seg / n_chunks / n_groups <= 0 and a
+ * misaligned block; MODE_ERR_WORKSPACE for a missing, misaligned or small workspace.  The tables live in device memory and are trusted. */
+#define MODE_ADAM_CHUNK 2048
+#define MODE_ADAM_STATE_DOUBLES 8
+#define MODE_ADAM_STEP 0
+#define MODE_ADAM_SKIPPED 1
+#define MODE_ADAM_GRAD_NORM 2
+#define MODE_ADAM_FOUND_INF 3
+#define MODE_ADAM_NONFINITE 4
+#define MODE_ADAM_GROUP_DOUBLES 8
+typedef struct mode_adam_segment {
+  float* param;    /* the parameter tensor (contiguous fp32) */
+  long long first; /* its first element in the flat layout */
+  long long numel;
+  int group;
+  int unused;
+} mode_adam_segment;
+typedef struct mode_adam_chunk {
+  long long off; /* first element in the flat layout */
+  int seg;
+  int count; /* 1 .. MODE_ADAM_CHUNK */
+} mode_adam_chunk;
+size_t mode_adam_workspace_bytes(long long n);
+size_t mode_adam_block_bytes(int n_groups);
+int mode_adam_prepare(const float* grad, long long n, void* workspace, size_t workspace_bytes, void* block, int n_groups,
+                      int skip_nonfinite, mode_stream_t stream);
+int mode_adam_update(const mode_adam_segment* segments, int n_seg, const mode_adam_chunk* chunks, int n_chunks, const float* grad,
+                     float* exp_avg, float* exp_avg_sq, void* block, int n_groups, mode_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,11 @@ SIGNATURES = {
     'mode_spp_pool_bwd': (_c_int, [_c_ptr] + [_c_int] * 2 + [_c_ptr] * 5 + [_c_int] * 4 + [_c_ptr]),
     'mode_spp_concat_fwd': (_c_int, [_c_ptr] * 7 + [_c_int] * 6 + [_c_ptr]),
     'mode_spp_concat_bwd': (_c_int, [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr]),
+    # the optimizer of the training step (csrc/optim.hip; reference train_disparity.py:293)
+    'mode_adam_workspace_bytes': (_c_size, [ctypes.c_longlong]),
+    'mode_adam_block_bytes': (_c_size, [_c_int]),
+    'mode_adam_prepare': (_c_int, [_c_ptr, ctypes.c_longlong, _c_ptr, _c_size, _c_ptr, _c_int, _c_int, _c_ptr]),
+    'mode_adam_update': (_c_int, [_c_ptr, _c_int, _c_ptr, _c_int] + [_c_ptr] * 4 + [_c_int, _c_ptr]),
 }
 
 ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against

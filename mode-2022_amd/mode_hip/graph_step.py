@@ -6,8 +6,11 @@ are constants of the geometry, the loss mask is applied arithmetically), so it i
 into the flat gradient buffer -- and replayed with a single launch.  The native library only ever enqueues on the stream it
 is handed and never allocates, so capture needs nothing special from it.
 
-The gradient exchange and the optimizer stay outside the graph: the exchange because a collective is only capturable with
-RCCL (not with the gloo backend the CPU tests use), the optimizer so that its hyper-parameters stay ordinary Python state.
+The gradient exchange stays outside the graph: a collective is only capturable with RCCL (not with the gloo backend the CPU tests
+use).  torch's optimizers stay outside too -- their hyper-parameters are Python values that a capture would bake in.  mode_hip.optim.Adam
+need not: its step() is three launches that read their hyper-parameters and step counter from a device block, so on one GPU fn() may end in
+opt.step() and the whole step -- zero-grad, forward, loss, backward, update -- is one graph launch (change e.g. the learning rate in
+param_groups and call opt.sync_hyperparameters() between replays; replay() moves the parameters' version counters, see `written` below).
 
   gs = GraphedStep(fn, static_inputs)      # fn() reads the static input tensors and returns a tensor / tuple of tensors
   gs.load(left, right, gt, count)          # copy_ new data into the static inputs (optional)
