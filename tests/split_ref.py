@@ -1,0 +1,504 @@
+"""Float64 emulation of the split-operand arithmetic of the MFMA kernels (csrc/split_arith.h), a componentwise error metric, and the
+case lists that tests/test_split_ref_host.py (CPU tier) and tests/test_gpu_split_precision.py (GPU tier) share.  Plain torch, no
+mode_hip: what is restated here is the CONTRACT of split_arith.h, not its code.
+
+Pieces.  Three bf16 pieces are a1 = rne(a), a2 = rne(a - a1), a3 = rne(a - a1 - a2), every remainder an exact fp32 difference; two fp16
+pieces are h1 = rne(s a), h2 = rne(s a - h1) with s = f16_scale_of(max |tensor|) = 2^(14 - floor(log2 max)).
+
+Emulation.  Every operator here is bilinear in its two MFMA operands, so the value a kernel computes, apart from the rounding of its
+fp32 accumulator, is the float64 operator summed over the partial products the header lists: (1,1) (1,2) (2,1) (2,2) (1,3) (3,1) on
+bf16 pieces, (1,1) (1,2) (2,1) on fp16 pieces.  `emulate` evaluates that sum, or a MUTANT of it:
+  ('drop', i, j)   the partial product a_i b_j left out;
+  ('trunc',)       the last piece of both operands truncated toward zero instead of rounded;
+  ('scale', k)     fp16 only: operand a scaled 2^k below f16_scale_of (what a stale or foreign maximum does).
+Two facts about the truncation mutant, both asserted by the host tier: on bf16 pieces it is the IDENTITY (the third piece is the exact
+remainder -- 8 + 8 + 8 bits hold an fp32 mantissa -- so there is nothing to round), and on fp16 pieces it stays within twice the
+faithful error (an error in [0, 1) ulp of the second piece against [-1/2, 1/2]; measured 0.040 against 0.041 of 2^-22 at 8 -> 8: the
+left-out a2 b2 dominates both), which no threshold a third of the way can separate.  It therefore enters no threshold; the thresholds
+come from the dropped pairs and, where it is judged, the scale mutant.
+
+Metric.  u = |got - want| / den in units of 2^-24 (three pieces) or 2^-22 (two), `want` the float64 result and `den` the same operator
+applied to |a| and |b| (plus |acc| where a gradient is added in the store: that sum is rounded once more; for the sphere the sampling
+applied to |x|, not the magnitude of the sampled x).  Reported: the rms of u over
+the whole tensor, and the worst rms over slices along EVERY axis of the output, consecutive indices grouped until a slice holds at least
+256 elements.  Where den == 0 the output must be exactly 0; nothing else is excluded.
+
+Threshold.  T = (smallest whole-tensor rms among the case's mutants, pure emulation) / 3, from the case's own inputs, never from a
+kernel's output.  A kernel passes when its whole-tensor rms and its worst slice are both <= T.
+
+The fp16 contract holds down to ~2^-17 of the tensor's maximum: on the 'six decades along a row' data the two-piece cases are judged over
+the first five sixths of the row (contract_columns); the columns beyond are reported only."""
+import collections
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+BF16_PAIRS = ((1, 1), (1, 2), (2, 1), (2, 2), (1, 3), (3, 1))
+F16_PAIRS = ((1, 1), (1, 2), (2, 1))
+PAIRS = {'bf16x6': BF16_PAIRS, 'f16x3': F16_PAIRS}
+UNIT = {'bf16x6': 2.0**-24, 'f16x3': 2.0**-22}
+# the mutants a threshold is taken from (module docstring: the truncation mutant enters none)
+DROPS = {'bf16x6': (('drop', 2, 2), ('drop', 1, 3), ('drop', 3, 1)), 'f16x3': (('drop', 1, 2), ('drop', 2, 1))}
+SCALE_MUTANT = ('scale', 4)
+MIN_SLICE = 256
+
+
+# ------------------------------------------------------------------------------------------------ pieces
+def _f32(t):
+  assert t.dtype == torch.float32
+  return t.contiguous()
+
+
+def _trunc_bf16(r):
+  return (r.view(torch.int32) & -65536).view(torch.float32)
+
+
+def pieces_bf16(a, trunc_last=False):
+  """(a1, a2, a3) as fp32 tensors holding bf16 values; a1 + a2 + a3 == a exactly."""
+  a = _f32(a)
+  p1 = a.to(torch.bfloat16).float()
+  r1 = a - p1
+  p2 = r1.to(torch.bfloat16).float()
+  r2 = r1 - p2
+  p3 = _trunc_bf16(r2) if trunc_last else r2.to(torch.bfloat16).float()
+  return p1, p2, p3
+
+
+def f16_scale_of(m):
+  """2^(14 - floor(log2 m)) for the largest magnitude m of a tensor (m * scale in [2^14, 2^15)); 1 for m = 0; magnitudes below 2^-63
+  are treated as 2^-63."""
+  m = float(m)
+  if m == 0.0:
+    return 1.0
+  e = min(max(math.frexp(m)[1] - 1 + 127, 64), 254)  # the biased exponent of m, clamped as the header clamps it
+  return 2.0**(141 - e)
+
+
+def _trunc_f16(r):
+  h = r.to(torch.float16)
+  over = h.float().abs() > r.abs()  # rounded away from zero: one step back (sign-magnitude: the magnitude bits minus one)
+  bits = h.view(torch.int16)
+  return torch.where(over, bits - 1, bits).view(torch.float16).float()
+
+
+def pieces_f16(a, scale, trunc_last=False):
+  """(h1, h2) as fp32 tensors holding fp16 values of a * scale (a power of two: the product is exact)."""
+  s = _f32(a) * scale
+  h1 = s.to(torch.float16).float()
+  r = s - h1
+  h2 = _trunc_f16(r) if trunc_last else r.to(torch.float16).float()
+  return h1, h2
+
+
+# ------------------------------------------------------------------------------------------------ emulation
+def _pieces(a, b, arith, mutant):
+  trunc = mutant == ('trunc',)
+  if arith == 'bf16x6':
+    return pieces_bf16(a, trunc), pieces_bf16(b, trunc), 1.0
+  sa, sb = f16_scale_of(a.abs().max()), f16_scale_of(b.abs().max())
+  if mutant is not None and mutant[0] == 'scale':
+    sa = sa / 2.0**mutant[1]
+  return pieces_f16(a, sa, trunc), pieces_f16(b, sb, trunc), sa * sb
+
+
+def emulate(op, a, b, arith, mutant=None):
+  """The float64 value of operator `op` (a callable of two float64 tensors, bilinear) on the split arithmetic `arith` ('bf16x6' |
+  'f16x3') for fp32 operands a and b, or of a mutant of that arithmetic (module docstring)."""
+  if mutant is not None and mutant[0] == 'scale':
+    assert arith == 'f16x3'
+  pa, pb, s = _pieces(a, b, arith, mutant)
+  pairs = [p for p in PAIRS[arith] if not (mutant is not None and mutant[0] == 'drop' and p == tuple(mutant[1:]))]
+  out = None
+  for i in sorted({p[0] for p in pairs}):  # bilinear: sum over j first (exact in float64: the pieces of one value do not overlap)
+    bsum = sum(pb[j - 1].double() for (ii, j) in pairs if ii == i)
+    term = op(pa[i - 1].double(), bsum)
+    out = term if out is None else out + term
+  return out / s
+
+
+def emulations(op, a, b, arith, mutants):
+  """{None: faithful, mutant: value, ...}; a dropped pair is the faithful value minus that pair's product (one evaluation, not three)."""
+  out = {None: emulate(op, a, b, arith)}
+  pa, pb, s = _pieces(a, b, arith, None)
+  for m in mutants:
+    if m[0] == 'drop':
+      out[m] = out[None] - op(pa[m[1] - 1].double(), pb[m[2] - 1].double()) / s
+    else:
+      out[m] = emulate(op, a, b, arith, m)
+  return out
+
+
+# ------------------------------------------------------------------------------------------------ metric
+def units(got, want, den, arith):
+  """u = |got - want| / den in units of the arithmetic; exactly zero output demanded where den == 0."""
+  got, want, den = got.detach().cpu().double(), want.double(), den.double()
+  zero = den == 0
+  assert bool((got[zero] == 0).all()), 'a non-zero output where every product is zero'
+  return torch.where(zero, torch.zeros_like(den), (got - want).abs() / den.masked_fill(zero, 1.0)) / UNIT[arith]
+
+
+def rms(u):
+  return float(u.pow(2).mean().sqrt())
+
+
+Worst = collections.namedtuple('Worst', 'rms axis index')
+
+
+def worst_slice(u):
+  """The largest rms over slices along every axis: consecutive indices grouped until a slice holds >= MIN_SLICE elements (a short tail
+  joins the group before it), so that every element is in one slice per axis."""
+  worst = Worst(-1.0, -1, -1)
+  sq = u.pow(2)
+  for ax in range(u.dim()):
+    n = u.shape[ax]
+    per = sq.mean([d for d in range(u.dim()) if d != ax]) if u.dim() > 1 else sq
+    g = max(1, -(-MIN_SLICE // max(u.numel() // n, 1)))
+    starts = list(range(0, n, g))
+    if len(starts) > 1 and n - starts[-1] < g:
+      starts.pop()
+    for k, s0 in enumerate(starts):
+      s1 = starts[k + 1] if k + 1 < len(starts) else n
+      r = float(per[s0:s1].mean().sqrt())
+      if r > worst.rms:
+        worst = Worst(r, ax, s0)
+  return worst
+
+
+# ------------------------------------------------------------------------------------------------ data
+def _randn(shape, seed, scale=1.0):
+  return torch.from_numpy((np.random.RandomState(seed).standard_normal(shape) * scale).astype(np.float32))
+
+
+KINDS = ('unit variance', 'six decades along a row', 'gradient-sized')
+
+
+def column_factor(W):
+  return torch.logspace(0, -6, W, dtype=torch.float64).float()
+
+
+def data(shape, seed, kind, gradient=False):
+  """An activation (gradient=False) or an output gradient (True) of the given kind; 'gradient-sized' scales gradients alone."""
+  t = _randn(shape, seed)
+  if kind == 'six decades along a row':
+    t = torch.relu(t) * column_factor(shape[-1])
+  elif kind == 'gradient-sized' and gradient:
+    t = t * 1e-7
+  return t.contiguous()
+
+
+def contract_columns(W):
+  """The number of leading columns of six-decades data a two-piece case is judged over: the first five sixths of the row (factor >=
+  1e-5).  Values of order one there are 2^-16.6 x 2^-2 of a maximum of ~4: the last of them are already past the contract's '22 bits down
+  to ~2^-17 of the maximum' by a bit or two, which the emulation knows -- T comes from the emulated mutants on the same columns -- and it
+  is there that a mis-scaled operand shows first.  (Cutting at a factor of 2^-15 instead leaves the scale mutant with k = 4 within 4 x the
+  noise of a plain fp32 sum, which a threshold at a third cannot separate: measured 0.35 against 0.09 at 32 -> 32, 6 x 10 x 40.)"""
+  return (5 * W) // 6
+
+
+# ------------------------------------------------------------------------------------------------ operators (float64 or float32)
+def conv3d_fwd(x, w, stride):
+  return F.conv3d(x, w, None, stride, 1)
+
+
+def conv3d_bwd_data(gy, w, in_shape, stride):
+  return torch.nn.grad.conv3d_input(in_shape, w, gy, stride, 1)
+
+
+def conv3d_bwd_weight(gy, x, co_ci, stride):
+  return torch.nn.grad.conv3d_weight(x, tuple(co_ci) + (3, 3, 3), gy, stride, 1)
+
+
+def deconv3d_fwd(x, w):
+  return F.conv_transpose3d(x, w, None, 2, 1, 1)
+
+
+def conv2d_fwd(x, w, dil):
+  return F.conv2d(x, w, None, 1, dil, dil)
+
+
+def conv2d_bwd_data(gy, w, in_shape, dil):
+  return torch.nn.grad.conv2d_input(in_shape, w, gy, 1, dil, dil)
+
+
+def conv2d_bwd_weight(gy, x, co_ci, dil):
+  return torch.nn.grad.conv2d_weight(x, tuple(co_ci) + (3, 3), gy, 1, dil, dil)
+
+
+# ------------------------------------------------------------------------------------------------ cases
+# A case is one operator family at one shape on one kind of data in one arithmetic; its ROLES (forward, input gradient, input gradient
+# added to one that is there, weight gradient) share the inputs.  role.a / role.b are the fp32 MFMA operands, role.op the bilinear
+# float64 operator on them, role.plain32() a plain fp32 evaluation, role.acc the gradient already there (or None).
+Case = collections.namedtuple('Case', 'family shape kind arith seed')
+Role = collections.namedtuple('Role', 'name a b op plain32 acc chan_axis col_axis cols exact den_ab')
+# exact: a callable giving the float64 result where it is not op(a, b) (the sphere: an unrounded column); den_ab: the float64 operands of
+# the denominator where they are not |a|, |b| (the sphere: the sampling applied to |x|, not the magnitude of the sampled x)
+Role.__new__.__defaults__ = (None, None)
+
+CONV3D_S1 = [(2, 8, 8, 8, 8, 8), (1, 32, 32, 6, 10, 40), (2, 16, 20, 5, 7, 33), (1, 32, 32, 3, 17, 130), (1, 64, 32, 4, 8, 32)]
+CONV3D_S2 = [(2, 32, 64, 8, 12, 32), (1, 64, 64, 6, 8, 24), (3, 64, 128, 2, 4, 8)]
+DECONV3D = [(2, 64, 32, 4, 6, 16), (2, 64, 64, 3, 4, 8)]  # (B, cin, cout, D, H, W) of the layer's input
+CONV2D = [(2, 32, 32, 16, 64, 1), (2, 16, 40, 7, 33, 1), (1, 64, 64, 12, 32, 2), (1, 32, 96, 18, 70, 2)]
+# (ih, iw, B, ci, co, groups), Cassini tables.  Two things differ from the convolutions.  The plain fp32 evaluation of the input gradient is
+# the fp32 product of w and the adjoint-sampled gradient (sampled in float64), as in the emulation: the oracle's own fp32 adjoint forms
+# its bilinear weights from rounded sums of coordinates (a + 1 - h at a ~ 64: 2^-18 of a weight), the oracle's arithmetic and no kernel's.
+# And the six-decades kind has a weight-gradient role on the smallest table only (16 x 32: 512 pixels): the reduction is the table's pixel
+# count, which no trimming of the operands shortens, and on non-negative data torch's fp32 sum over it is at T already on the larger tables
+# (worst slice / T: 1.92 / 1.54 at 64 x 128, 1.93 / 2.66 at 33 x 66) -- a weight gradient has no row axis for that kind to test.
+# Which roles reach a split kernel (tests/test_gpu_split_precision.py asserts them): the windowed forward and weight gradient need compact
+# tiles in the table's plan (64 x 128, 33 x 66, 16 x 32 have them, 32 x 64 has none), the forward also 16 input channels per group (12 -> 40
+# with groups 2 runs on the fp32 window kernel INSIDE the split entry); the windowed adjoint needs an adjoint plan (32 x 64 alone here).
+# Only the roles that reach a split kernel are built (the others would be judged nowhere, and the float64 adjoint of 128 channels is slow).
+SPHERE_ROLES = {
+    (64, 128, 1, 16, 32, 1): ('forward', 'weight gradient'),
+    (33, 66, 1, 12, 40, 2): ('weight gradient',),
+    (32, 64, 1, 128, 128, 1): ('input gradient',),
+    (33, 66, 1, 32, 64, 2): ('forward', 'weight gradient'),
+    (32, 64, 1, 64, 64, 1): ('input gradient',),
+    (64, 128, 1, 128, 128, 1): ('forward', 'weight gradient'),
+    (16, 32, 1, 16, 32, 1): ('forward', 'weight gradient'),
+}
+SPHERE = list(SPHERE_ROLES)
+SPHERE_WGRAD_DECADES_MAX_PIXELS = 512
+
+
+# The weight gradients whose reduction is shortened so that the host tier's condition holds (a plain fp32 evaluation's worst slice
+# <= T / 1.5): the operands' leading rows only.  The noise of an fp32 sum grows with the number of additions and the mutants' signal falls
+# with the number of terms, both as the square root, so their ratio goes with the row count.  Non-negative data (six decades: relu) is
+# the hard case -- every partial sum is as large as the result.  Figures before the trim (worst slice of torch's fp32 operator / T) beside
+# each entry; tests/test_split_ref_host.py holds the trimmed cases to the condition.
+WGRAD_ROWS = {
+    ('conv3d_s1', (1, 32, 32, 3, 17, 130), 'six decades along a row'): 12,  # 1.66 / 2.37
+    ('conv2d', (2, 32, 32, 16, 64, 1), 'unit variance'): 8,                 # 0.37 / 0.48
+    ('conv2d', (2, 32, 32, 16, 64, 1), 'gradient-sized'): 8,                # 0.37 / 0.48
+    ('conv2d', (2, 32, 32, 16, 64, 1), 'six decades along a row'): 6,       # 3.76 / 3.31
+    ('conv2d', (1, 32, 96, 18, 70, 2), 'unit variance'): 10,                # 0.56 / 0.64
+    ('conv2d', (1, 32, 96, 18, 70, 2), 'gradient-sized'): 10,               # 0.59 / 0.64
+    ('conv2d', (1, 32, 96, 18, 70, 2), 'six decades along a row'): 6,       # 5.26 / 4.25
+}
+
+
+def _rows(case, t, stride=1):
+  h = WGRAD_ROWS.get((case.family, case.shape, case.kind))
+  return t if h is None else t.narrow(-2, 0, h * stride).contiguous()
+
+
+# 12 -> 40 with groups 2 reaches a split kernel with its weight gradient alone (6 input channels per group: the forward runs on the fp32
+# window kernel), and the spherical six-decades kind has no weight gradient at 33 x 66: nothing of that combination could be judged.
+NO_CASE = {('sphere', (33, 66, 1, 12, 40, 2), 'six decades along a row')}
+
+
+def _cases():
+  out = []
+  seed = 9000
+  for fam, shapes, ariths in (('conv3d_s1', CONV3D_S1, ('bf16x6', 'f16x3')), ('conv3d_s2', CONV3D_S2, ('bf16x6',)),
+                              ('deconv3d', DECONV3D, ('bf16x6',)), ('conv2d', CONV2D, ('bf16x6', 'f16x3')), ('sphere', SPHERE, ('bf16x6',))):
+    for shape in shapes:
+      seed += 10
+      for arith in ariths:
+        for kind in KINDS:
+          if (fam, shape, kind) in NO_CASE:
+            continue
+          out.append(Case(fam, shape, kind, arith, seed))
+  return out
+
+
+CASES = _cases()
+
+
+def case_id(c):
+  return '%s-%s-%s-%s' % (c.family, 'x'.join(str(v) for v in c.shape), c.arith, c.kind.replace(' ', '_'))
+
+
+def _acc_for(want, kind, seed):
+  """A gradient that is already there: a tenth of the new one's rms, with the same column structure."""
+  acc = _randn(tuple(want.shape), seed) * (0.1 * float(want.pow(2).mean().sqrt()))
+  if kind == 'six decades along a row':
+    acc = acc * column_factor(want.shape[-1])
+  return acc.float().contiguous()
+
+
+def _cols(case, W):
+  """The leading columns a two-piece case on six-decades data is judged over (all of them otherwise)."""
+  return contract_columns(W) if (case.arith == 'f16x3' and case.kind == 'six decades along a row') else W
+
+
+def roles(case):
+  """(roles, tensors): the roles of a case, in the order forward, input gradient, input gradient + acc, weight gradient, and its fp32
+  inputs by name (x, w, gy, acc, pos).  The 'gradient-sized' kind has no forward (a forward reads no gradient)."""
+  fam, kind, s = case.family, case.kind, case.seed
+  grad_only = kind == 'gradient-sized'
+  out = []
+  if fam in ('conv3d_s1', 'conv3d_s2', 'conv2d'):
+    three_d = fam != 'conv2d'
+    if three_d:
+      B, Ci, Co, D, H, W = case.shape
+      stride = 1 if fam == 'conv3d_s1' else 2
+      xs = (B, Ci, D, H, W)
+      ys = (B, Co) + tuple((n - 1) // stride + 1 for n in (D, H, W))
+      ws = (Co, Ci, 3, 3, 3)
+      fwd = lambda x, w: conv3d_fwd(x, w, stride)
+      bwd = lambda gy, w: conv3d_bwd_data(gy, w, xs, stride)
+      wgr = lambda gy, x: conv3d_bwd_weight(gy, x, (Co, Ci), stride)
+    else:
+      B, Ci, Co, H, W, dil = case.shape
+      xs, ys, ws = (B, Ci, H, W), (B, Co, H, W), (Co, Ci, 3, 3)
+      fwd = lambda x, w: conv2d_fwd(x, w, dil)
+      bwd = lambda gy, w: conv2d_bwd_data(gy, w, xs, dil)
+      wgr = lambda gy, x: conv2d_bwd_weight(gy, x, (Co, Ci), dil)
+    taps = 27 if three_d else 9
+    x = data(xs, s + 1, kind)
+    w = _randn(ws, s + 2, (2.0 / (taps * Co))**0.5)
+    gy = data(ys, s + 3, kind, gradient=True)
+    last = len(xs) - 1
+    if not grad_only:
+      out.append(Role('forward', x, w, fwd, lambda: fwd(x, w), None, 1, last, _cols(case, ys[-1])))
+    out.append(Role('input gradient', gy, w, bwd, lambda: bwd(gy, w), None, 1, last, _cols(case, xs[-1])))
+    tensors = {'x': x, 'w': w, 'gy': gy}
+    if fam != 'conv3d_s2':  # (the entries with a gradient added in the store: the stride-1 3-D and the 3 x 3 layers)
+      acc = tensors['acc'] = _acc_for(bwd(gy.double(), w.double()), kind, s + 4)
+      out.append(Role('input gradient + acc', gy, w, bwd, lambda: bwd(gy, w) + acc, acc, 1, last, _cols(case, xs[-1])))
+    gyw, xw = _rows(case, gy), _rows(case, x, stride if three_d else 1)
+    out.append(Role('weight gradient', gyw, xw, wgr, lambda: wgr(gyw, xw), None, 0, None, None))
+  elif fam == 'deconv3d':
+    B, cin, cout, D, H, W = case.shape
+    xs, ys, ws = (B, cin, D, H, W), (B, cout, 2 * D, 2 * H, 2 * W), (cin, cout, 3, 3, 3)
+    x = data(xs, s + 1, kind)
+    w = _randn(ws, s + 2, (2.0 / (27 * cin))**0.5 * 2)
+    gy = data(ys, s + 3, kind, gradient=True)
+    bwd = lambda g, w_: conv3d_fwd(g, w_, 2)  # the input gradient of the transposed layer is the stride-2 convolution
+    wgr = lambda x_, g: conv3d_bwd_weight(x_, g, (cin, cout), 2)  # ... and its weight gradient that kernel with the operands exchanged
+    if not grad_only:
+      out.append(Role('forward', x, w, deconv3d_fwd, lambda: deconv3d_fwd(x, w), None, 1, 4, _cols(case, ys[-1])))
+    out.append(Role('input gradient', gy, w, bwd, lambda: bwd(gy, w), None, 1, 4, _cols(case, xs[-1])))
+    out.append(Role('weight gradient', x, gy, wgr, lambda: wgr(x, gy), None, 0, None, None))
+    tensors = {'x': x, 'w': w, 'gy': gy}
+  elif fam == 'sphere':
+    return _sphere_roles(case)
+  else:
+    raise ValueError(fam)
+  return out, tensors
+
+
+# ------------------------------------------------------------------------------------------------ the spherical convolution
+_pos_cache = {}
+
+
+def sphere_table(ih, iw):
+  from oracle import mode_ref
+  if (ih, iw) not in _pos_cache:
+    _pos_cache[(ih, iw)] = mode_ref.sphere_position(ih, iw, 'Cassini').contiguous()
+  return _pos_cache[(ih, iw)]
+
+
+def _sphere_roles(case):
+  """The split operand of the forward and of the weight gradient is the SAMPLED column (oracle/sphere_conv_ref.im2col in float64,
+  rounded to fp32); that of the input gradient is the ADJOINT-sampled output gradient (oracle/sphere_conv_ref.col2im_scatter in float64,
+  rounded to fp32), which is what the windowed kernel splits: its MFMA operands are W and G_k, not W and gy."""
+  from oracle import sphere_conv_ref as R
+  ih, iw, B, ci, co, g = case.shape
+  pos = sphere_table(ih, iw)
+  H, W = pos.shape[2:]
+  kind, s = case.kind, case.seed
+  cig, cog, N = ci // g, co // g, H * W
+  x = data((B, ci, H, W), s + 1, kind)
+  w = _randn((co, cig, 3, 3), s + 2, (2.0 / (9 * cig))**0.5)
+  gy = data((B, co, H, W), s + 3, kind, gradient=True)
+  pos64 = pos.double()
+  build = SPHERE_ROLES[case.shape]
+  tensors = {'x': x, 'w': w, 'gy': gy, 'pos': pos}
+  out = []
+  if 'forward' in build or 'weight gradient' in build:
+    col = R.im2col(x.double(), pos64, 3, 3, 1, 1, H, W).float().contiguous()  # (B, ci, 9, H, W)
+    col_abs = R.im2col(x.double().abs(), pos64, 3, 3, 1, 1, H, W)
+
+  def fwd(c, w_):
+    return torch.einsum('gok,bgkn->bgon', w_.reshape(g, cog, cig * 9), c.reshape(B, g, cig * 9, N)).reshape(B, co, H, W)
+
+  def wgr(gy_, c):
+    return torch.einsum('bgon,bgkn->gok', gy_.reshape(B, g, cog, N), c.reshape(B, g, cig * 9, N)).reshape(co, cig, 3, 3)
+
+  # the adjoint-sampled gradient G_k[o][q] = sum over the output pixels p whose tap k touches q of wt * gy[o][p] (the kernel's header:
+  # csrc/sphere_conv_win.hip, "Input gradient on the split-bf16 matrix path"), tap by tap: the scatter of a one-tap problem
+  def adjoint(g_):
+    return torch.stack([R.col2im_scatter(g_[:, :, None], pos64[:, 2 * k:2 * k + 2], H, W, 1, 1, 1, 1) for k in range(9)], 2)
+
+  def bwd(G_, w_):
+    return torch.einsum('gock,bgokn->bgcn', w_.reshape(g, cog, cig, 9), G_.reshape(B, g, cog, 9, N)).reshape(B, ci, H, W)
+
+  if 'forward' in build and kind != 'gradient-sized':
+    out.append(Role('forward', col, w, fwd, lambda: R.forward(x, pos, w, (1, 1), (1, 1), (1, 1), g), None, 1, 3, W,
+                    lambda: sphere_exact(case, 'forward', tensors), (col_abs, w.double().abs())))
+  if 'input gradient' in build:
+    G, G_abs = adjoint(gy.double()).float().contiguous(), adjoint(gy.double().abs())
+    out.append(Role('input gradient', G, w, bwd, lambda: bwd(G, w), None, 1, 3, W, lambda: sphere_exact(case, 'input gradient', tensors),
+                    (G_abs, w.double().abs())))
+  if 'weight gradient' in build and (kind != 'six decades along a row' or N <= SPHERE_WGRAD_DECADES_MAX_PIXELS):  # (see SPHERE above)
+    out.append(Role('weight gradient', gy, col, wgr, lambda: R.backward(x, pos, torch.zeros_like(w), gy, (1, 1), (1, 1), (1, 1), g)[1], None, 0, None,
+                    None, lambda: sphere_exact(case, 'weight gradient', tensors), (gy.double().abs(), col_abs)))
+  return out, tensors
+
+
+def sphere_exact(case, role_name, tensors):
+  """The float64 result of a spherical role from the UNROUNDED column (the emulation rounds it to fp32, as the kernels do)."""
+  from oracle import sphere_conv_ref as R
+  g = case.shape[5]
+  x, w, gy, pos = (tensors[k].double() for k in ('x', 'w', 'gy', 'pos'))
+  if role_name == 'forward':
+    return R.forward(x, pos, w, (1, 1), (1, 1), (1, 1), g)
+  gx, gw = R.backward(x, pos, w, gy, (1, 1), (1, 1), (1, 1), g)
+  return gx if role_name == 'input gradient' else gw
+
+
+# ------------------------------------------------------------------------------------------------ a role's reference, den, T
+Ref = collections.namedtuple('Ref', 'want den T emu mutants')
+
+
+def mutants_of(case, role):
+  m = list(DROPS[case.arith])
+  # judged where the output has the row axis (a weight gradient sums over it) and the row samples the six decades finely enough for a
+  # column to sit within a factor of two of the judged region's edge (10^(6 / (W - 1)) <= 2: W >= 21; at W = 8 the nearest is 7 x inside)
+  if case.arith == 'f16x3' and case.kind == 'six decades along a row' and role.col_axis is not None and role.a.shape[-1] >= 21:
+    m.append(SCALE_MUTANT)
+  return m
+
+
+def judged(role, t):
+  """The part of an output the case is judged over (the in-contract columns of a two-piece case on six-decades data)."""
+  if role.col_axis is None or role.cols == t.shape[role.col_axis]:
+    return t
+  return t.narrow(role.col_axis, 0, role.cols)
+
+
+def reference(case, role):
+  """want, den, T and the emulations {None: faithful, mutant: ...} of a role; all float64 on the CPU."""
+  a, b = role.a, role.b
+  want = role.exact() if role.exact is not None else role.op(a.double(), b.double())
+  den = role.op(*role.den_ab) if role.den_ab is not None else role.op(a.double().abs(), b.double().abs())
+  muts = mutants_of(case, role)
+  emu = emulations(role.op, a, b, case.arith, muts)
+  if role.acc is not None:
+    want = want + role.acc.double()
+    den = den + role.acc.double().abs()
+    emu = {k: v + role.acc.double() for k, v in emu.items()}
+  T = min(mutant_size(case, role, m, emu[m], want, den) for m in muts) / 3.0
+  return Ref(want, den, T, emu, muts)
+
+
+def mutant_size(case, role, m, value, want, den):
+  """What a mutant contributes to T: its whole-tensor rms -- except the scale mutant, whose damage is LOCAL by nature (the few columns next
+  to the contract's edge lose 2^k; the rest lose nothing, so its whole-tensor rms sits at the accumulator's noise): it is sized by its
+  worst slice, and it is the slice condition that has to catch it."""
+  u = judged(role, units(value, want, den, case.arith))
+  return worst_slice(u).rms if m[0] == 'scale' else rms(u)
+
+
+def measure(case, role, ref, got):
+  """(whole-tensor rms, worst slice) of `got` over the judged part, and the whole-tensor rms of the rest (None when there is none)."""
+  u = units(got, ref.want, ref.den, case.arith)
+  j = judged(role, u)
+  rest = None
+  if j.shape != u.shape:
+    rest = rms(u.narrow(role.col_axis, role.cols, u.shape[role.col_axis] - role.cols))
+  return rms(j), worst_slice(j), rest

@@ -1,10 +1,19 @@
-"""GPU (-m gpu): the stride-1 3x3x3 layers on the split-bf16 matrix path (csrc/conv3d_split.hip, functional.CONV_ARITH = 'bf16x6').
+"""GPU (-m gpu): the 3x3x3 / 3x3 / spherical layers on the split-operand matrix path (csrc/conv3d_split.hip and its siblings,
+functional.CONV_ARITH = 'bf16x6').
 
 The claim under test is that this path computes an fp32 convolution: every check uses the SAME bound as the fp32 MFMA kernels'
 tests (2^-22 * sqrt(terms) * 8 relative to the largest exact output, tests/test_gpu_fullsize.py), against float64 references
 (torch's conv3d on the CPU for the small shapes, oracle/conv_ref.py at the benchmark size), and the error is printed next to the
 fp32 kernel's on the same inputs.  Whole-model parity with the reference in this mode: tests/test_gpu_parity.py (parametrised
-over both arithmetics)."""
+over both arithmetics).
+
+Which arithmetic runs when.  'bf16x6' selects the split path; WITHIN it the stride-1 3-D layers (all three roles) run on two fp16
+pieces while functional.CONV3D_S1_F16 is True, and the 3 x 3 layers' input and weight gradients (and a training forward, f16=True) while
+functional.CONV2D_F16 is True -- both the default -- and on three bf16 pieces otherwise.  The stride-2 and transposed 3-D layers, an
+inference 3 x 3 forward and the eval epilogues' opt-out always run on three bf16 pieces.  The stride-1 3-D tests and the 3 x 3 gradient
+tests below therefore run under BOTH settings of the switch and assert the entry that launched (mode_*_split_f16 | mode_*_split); their
+bounds are the same for both.  The componentwise contract of either arithmetic (which these max-norm bounds cannot see):
+tests/test_gpu_split_precision.py."""
 import numpy as np
 import pytest
 import torch
@@ -15,6 +24,7 @@ from oracle import conv_ref
 import cpu_threads
 import mode_hip
 from mode_hip import functional as HF
+from test_gpu_size_contracts import _ran, recorder  # noqa: F401  (the entries that launch, by name)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -28,9 +38,11 @@ def _need_gpu():
 
 @pytest.fixture
 def split_arith():
+  keep = (HF.CONV3D_S1_F16, HF.CONV2D_F16)
   HF.set_conv_arith('bf16x6')
   yield
   HF.set_conv_arith('bf16x6')
+  HF.CONV3D_S1_F16, HF.CONV2D_F16 = keep
 
 
 def _rand(shape, seed, scale=1.0):
@@ -57,7 +69,7 @@ CASES = [
 
 
 @pytest.mark.parametrize('B,Ci,Co,D,H,W', CASES)
-def test_split_forward_and_input_gradient_are_fp32_convolutions(B, Ci, Co, D, H, W, split_arith):
+def test_split_forward_and_input_gradient_are_fp32_convolutions(B, Ci, Co, D, H, W, split_arith, recorder):
   assert mode_hip.lib().mode_conv3d_split_supported(Ci, Co, 1, 0) == 1
   x = _rand((B, Ci, D, H, W), 141)
   w = _rand((Co, Ci, 3, 3, 3), 142, (2.0 / (27 * Co))**0.5)
@@ -66,19 +78,26 @@ def test_split_forward_and_input_gradient_are_fp32_convolutions(B, Ci, Co, D, H,
   want = F.conv3d(xa, w.double(), None, 1, 1)
   want.backward(gy.double())
   xd, wd, gd = x.to(DEV), w.to(DEV), gy.to(DEV)
-  y = HF.conv3d_fwd(xd, wd, 1)
-  e_split, tol = _err(y, want.detach()), _tol(Ci * 27, want.detach())
   HF.set_conv_arith('f32')
   e_f32 = _err(HF.conv3d_fwd(xd, wd, 1), want.detach())
   HF.set_conv_arith('bf16x6')
-  print('fwd %s: split %.3e, fp32 MFMA %.3e, bound %.3e' % ((B, Ci, Co, D, H, W), e_split, e_f32, tol))
-  assert e_split <= tol
-  assert torch.equal(y, HF.conv3d_fwd(xd, wd, 1)), 'not deterministic'
-  if mode_hip.lib().mode_conv3d_split_supported(Ci, Co, 1, 1) == 1:
-    gx = HF.conv3d_bwd_data(gd, wd, x.shape, 1)
-    e_split, tol = _err(gx, xa.grad), _tol(Co * 27, xa.grad)
-    print('bwd_data: split %.3e, bound %.3e' % (e_split, tol))
+  for f16 in (True, False):  # two fp16 pieces (the default of a training step) | three bf16 pieces
+    HF.CONV3D_S1_F16 = f16
+    sfx = '_f16' if f16 else ''
+    del recorder.names[:]
+    y = HF.conv3d_fwd(xd, wd, 1)
+    assert _ran(recorder, 'mode_conv3d_fwd') == ['mode_conv3d_fwd_split' + sfx]
+    e_split, tol = _err(y, want.detach()), _tol(Ci * 27, want.detach())
+    print('fwd %s [%s]: split %.3e, fp32 MFMA %.3e, bound %.3e' % ((B, Ci, Co, D, H, W), 'f16' if f16 else 'bf16', e_split, e_f32, tol))
     assert e_split <= tol
+    assert torch.equal(y, HF.conv3d_fwd(xd, wd, 1)), 'not deterministic'
+    if mode_hip.lib().mode_conv3d_split_supported(Ci, Co, 1, 1) == 1:
+      del recorder.names[:]
+      gx = HF.conv3d_bwd_data(gd, wd, x.shape, 1)
+      assert _ran(recorder, 'mode_conv3d_bwd_data') == ['mode_conv3d_bwd_data_split' + sfx]
+      e_split, tol = _err(gx, xa.grad), _tol(Co * 27, xa.grad)
+      print('bwd_data [%s]: split %.3e, bound %.3e' % ('f16' if f16 else 'bf16', e_split, tol))
+      assert e_split <= tol
 
 
 WGRAD_CASES = [
@@ -93,7 +112,7 @@ WGRAD_CASES = [
 
 
 @pytest.mark.parametrize('B,Ci,Co,D,H,W', WGRAD_CASES)
-def test_split_weight_gradient_is_an_fp32_weight_gradient(B, Ci, Co, D, H, W, split_arith):
+def test_split_weight_gradient_is_an_fp32_weight_gradient(B, Ci, Co, D, H, W, split_arith, recorder):
   assert mode_hip.lib().mode_conv3d_split_supported(Ci, Co, 1, 2) == 1
   x = _rand((B, Ci, D, H, W), 171)
   gy = _rand((B, Co, D, H, W), 172)
@@ -101,18 +120,22 @@ def test_split_weight_gradient_is_an_fp32_weight_gradient(B, Ci, Co, D, H, W, sp
   F.conv3d(x.double(), wa, None, 1, 1).backward(gy.double())
   want = wa.grad
   xd, gd = x.to(DEV), gy.to(DEV)
-  got = HF.conv3d_bwd_weight(gd, xd, 1)
   HF.set_conv_arith('f32')
   got32 = HF.conv3d_bwd_weight(gd, xd, 1)
   HF.set_conv_arith('bf16x6')
   scale = max(1.0, float(want.abs().max()))
-  e, e32 = _err(got, want), _err(got32, want)
-  print('bwd_weight %s: split %.3e, fp32 MFMA %.3e (scale %.3g)' % ((B, Ci, Co, D, H, W), e, e32, scale))
-  assert e <= 2e-5 * scale  # the bound of the fp32 kernels' test (tests/test_gpu_kernels.py::test_conv3d_fwd_bwd)
-  assert torch.equal(got, HF.conv3d_bwd_weight(gd, xd, 1)), 'not deterministic'
-  acc = torch.ones_like(got)
-  HF.conv3d_bwd_weight(gd, xd, 1, into=acc)
-  assert torch.allclose(acc, got + 1.0, rtol=0, atol=1e-5 * scale), 'accumulating form'
+  for f16 in (True, False):  # two fp16 pieces (the default of a training step) | three bf16 pieces
+    HF.CONV3D_S1_F16 = f16
+    del recorder.names[:]
+    got = HF.conv3d_bwd_weight(gd, xd, 1)
+    assert _ran(recorder, 'mode_conv3d_bwd_weight') == ['mode_conv3d_bwd_weight_split' + ('_f16' if f16 else '')]
+    e, e32 = _err(got, want), _err(got32, want)
+    print('bwd_weight %s [%s]: split %.3e, fp32 MFMA %.3e (scale %.3g)' % ((B, Ci, Co, D, H, W), 'f16' if f16 else 'bf16', e, e32, scale))
+    assert e <= 2e-5 * scale  # the bound of the fp32 kernels' test (tests/test_gpu_kernels.py::test_conv3d_fwd_bwd)
+    assert torch.equal(got, HF.conv3d_bwd_weight(gd, xd, 1)), 'not deterministic'
+    acc = torch.ones_like(got)
+    HF.conv3d_bwd_weight(gd, xd, 1, into=acc)
+    assert torch.allclose(acc, got + 1.0, rtol=0, atol=1e-5 * scale), 'accumulating form'
 
 
 S2_WGRAD_CASES = [
@@ -262,7 +285,7 @@ CONV2D_CASES = [
 
 
 @pytest.mark.parametrize('B,Ci,Co,H,W,dil', CONV2D_CASES)
-def test_split_conv2d_forward_and_input_gradient(B, Ci, Co, H, W, dil, split_arith):
+def test_split_conv2d_forward_and_input_gradient(B, Ci, Co, H, W, dil, split_arith, recorder):
   lib = mode_hip.lib()
   assert lib.mode_conv2d_split_supported(Ci, Co, dil, 0) == 1
   x = _rand((B, Ci, H, W), 181)
@@ -272,7 +295,9 @@ def test_split_conv2d_forward_and_input_gradient(B, Ci, Co, H, W, dil, split_ari
   want = F.conv2d(xa, w.double(), None, 1, dil, dil)
   want.backward(gy.double())
   xd, wd, gd = x.to(DEV), w.to(DEV), gy.to(DEV)
+  del recorder.names[:]
   y = HF.conv2d_fwd(xd, wd, dil)
+  assert _ran(recorder, 'mode_conv2d_fwd') == ['mode_conv2d_fwd_split']  # (an inference forward: three bf16 pieces whatever CONV2D_F16 says)
   HF.set_conv_arith('f32')
   y32 = HF.conv2d_fwd(xd, wd, dil)
   HF.set_conv_arith('bf16x6')
@@ -281,10 +306,14 @@ def test_split_conv2d_forward_and_input_gradient(B, Ci, Co, H, W, dil, split_ari
   assert e <= tol
   assert torch.equal(y, HF.conv2d_fwd(xd, wd, dil)), 'not deterministic'
   if lib.mode_conv2d_split_supported(Ci, Co, dil, 1) == 1:
-    gx = HF.conv2d_bwd_data(gd, wd, dil)
-    e, tol = _err(gx, xa.grad), _tol(Co * 9, xa.grad)
-    print('conv2d bwd_data: split %.3e, bound %.3e' % (e, tol))
-    assert e <= tol
+    for f16 in (True, False):  # two fp16 pieces (a backward pass is a training step) | three bf16 pieces
+      HF.CONV2D_F16 = f16
+      del recorder.names[:]
+      gx = HF.conv2d_bwd_data(gd, wd, dil)
+      assert _ran(recorder, 'mode_conv2d_bwd_data') == ['mode_conv2d_bwd_data_split' + ('_f16' if f16 else '')]
+      e, tol = _err(gx, xa.grad), _tol(Co * 9, xa.grad)
+      print('conv2d bwd_data [%s]: split %.3e, bound %.3e' % ('f16' if f16 else 'bf16', e, tol))
+      assert e <= tol
 
 
 @pytest.mark.parametrize('relu,with_add', [(True, False), (False, True), (True, True), (False, False)])
@@ -330,25 +359,30 @@ def test_split_conv2d_at_the_extractor_sizes_against_float64(split_arith):
 
 
 @pytest.mark.parametrize('B,Ci,Co,H,W,dil', CONV2D_CASES + [(2, 20, 40, 7, 33, 1), (1, 8, 8, 3, 5, 2), (3, 32, 32, 64, 96, 1)])
-def test_split_conv2d_weight_gradient(B, Ci, Co, H, W, dil, split_arith):
+def test_split_conv2d_weight_gradient(B, Ci, Co, H, W, dil, split_arith, recorder):
   x = _rand((B, Ci, H, W), 211)
   gy = _rand((B, Co, H, W), 212)
   wa = torch.zeros((Co, Ci, 3, 3), dtype=torch.float64, requires_grad=True)
   F.conv2d(x.double(), wa, None, 1, dil, dil).backward(gy.double())
   want = wa.grad
   xd, gd = x.to(DEV), gy.to(DEV)
-  got = HF.conv2d_bwd_weight(gd, xd, dil)
   HF.set_conv_arith('f32')
   got32 = HF.conv2d_bwd_weight(gd, xd, dil)
   HF.set_conv_arith('bf16x6')
   scale = max(1.0, float(want.abs().max()))
-  e, e32 = _err(got, want), _err(got32, want)
-  print('conv2d bwd_weight %s: split %.3e, fp32 MFMA %.3e (scale %.3g)' % ((B, Ci, Co, H, W, dil), e, e32, scale))
-  assert e <= 2e-5 * scale
-  assert torch.equal(got, HF.conv2d_bwd_weight(gd, xd, dil)), 'not deterministic'
-  acc = torch.ones_like(got)
-  HF.conv2d_bwd_weight(gd, xd, dil, into=acc)
-  assert torch.allclose(acc, got + 1.0, rtol=0, atol=1e-5 * scale), 'accumulating form'
+  assert mode_hip.lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dil, 2) == 1
+  for f16 in (True, False):  # two fp16 pieces (a weight gradient is a training step) | three bf16 pieces
+    HF.CONV2D_F16 = f16
+    del recorder.names[:]
+    got = HF.conv2d_bwd_weight(gd, xd, dil)
+    assert _ran(recorder, 'mode_conv2d_bwd_weight') == ['mode_conv2d_bwd_weight_split' + ('_f16' if f16 else '')]
+    e, e32 = _err(got, want), _err(got32, want)
+    print('conv2d bwd_weight %s [%s]: split %.3e, fp32 MFMA %.3e (scale %.3g)' % ((B, Ci, Co, H, W, dil), 'f16' if f16 else 'bf16', e, e32, scale))
+    assert e <= 2e-5 * scale
+    assert torch.equal(got, HF.conv2d_bwd_weight(gd, xd, dil)), 'not deterministic'
+    acc = torch.ones_like(got)
+    HF.conv2d_bwd_weight(gd, xd, dil, into=acc)
+    assert torch.allclose(acc, got + 1.0, rtol=0, atol=1e-5 * scale), 'accumulating form'
 
 
 def test_split_kernels_on_random_small_shapes(split_arith):

@@ -1,0 +1,157 @@
+"""CPU tier: the emulation of tests/split_ref.py separates a faithful split-operand kernel from a subtly wrong one on every case the
+GPU tier (tests/test_gpu_split_precision.py) runs, and the bounds the older tests use do not.
+
+For every shared case and role, from the case's own inputs:
+  * the faithful emulation plus the error of a plain fp32 evaluation (torch's CPU operator on the fp32 tensors; the oracle on fp32
+    tensors for the sphere) has a worst slice <= T / 1.5: a kernel that keeps the contract and accumulates like an fp32 sum passes
+    with room to spare;
+  * every mutant is >= 3 T by construction of T;
+  * the same mutant confined to one output channel (one slice of channels where a channel is smaller than a slice), or to the last
+    partial column tile, has a worst slice > T: a fault in one place is seen although the whole-tensor figure barely moves.
+Pieces and the scale are checked bit for bit against their definitions in csrc/split_arith.h."""
+import numpy as np
+import pytest
+import torch
+
+import split_ref as S
+
+
+def _localised(case, role, ref, m, where):
+  """The faithful value everywhere but in one output channel / the last partial column tile, where it is the mutant's.  Where a channel
+  holds fewer than the 256 elements of a slice (the smallest outputs: 24 at 3 x 128 x 1 x 2 x 4), the fault takes the consecutive channels
+  that make one slice -- the finest thing the metric resolves."""
+  got = ref.emu[None].clone()
+  bad = ref.emu[m]
+  if where == 'channel':
+    C = got.shape[role.chan_axis]
+    g = min(C, -(-S.MIN_SLICE // (got.numel() // C)))
+    got.narrow(role.chan_axis, 0, g).copy_(bad.narrow(role.chan_axis, 0, g))
+  else:
+    n = role.cols  # (the judged columns: a two-piece case on six-decades data ends before the row does)
+    k = n % 32 or 8
+    got.narrow(role.col_axis, n - k, k).copy_(bad.narrow(role.col_axis, n - k, k))
+  return got
+
+
+@pytest.mark.parametrize('case', S.CASES, ids=S.case_id)
+def test_faithful_passes_and_every_mutant_fails(case):
+  roles, _ = S.roles(case)
+  assert roles
+  for role in roles:
+    ref = S.reference(case, role)
+    tag = (S.case_id(case), role.name)
+    assert ref.T > 0, tag
+    plain = role.plain32().double()
+    whole, worst, rest = S.measure(case, role, ref, ref.emu[None] + (plain - ref.want))
+    line = '%-64s %-22s T %.3f | faithful + fp32: rms %.3f worst slice %.3f (axis %d @ %d)' % (tag + (ref.T, whole, worst.rms, worst.axis, worst.index))
+    assert worst.rms <= ref.T / 1.5 and whole <= ref.T / 1.5, line
+    for m in ref.mutants:
+      size = S.mutant_size(case, role, m, ref.emu[m], ref.want, ref.den)
+      assert size >= 3 * ref.T * (1 - 1e-12), (tag, m)
+      if m[0] == 'scale':
+        continue  # (local by nature, and sized by its worst slice: mutant_size)
+      for where in ('channel', 'columns'):
+        if where == 'columns' and role.col_axis is None:
+          continue
+        w = S.measure(case, role, ref, _localised(case, role, ref, m, where))[1]
+        line += ' | %s in one %s: %.2f' % ('x'.join(str(v) for v in m), where, w.rms)
+        assert w.rms > ref.T, (tag, m, where, w, ref.T)
+    print(line + ('' if rest is None else ' | columns past the contract (not judged): rms %.2f' % rest))
+
+
+def test_pieces_sum_to_the_value_bit_for_bit():
+  r = np.random.RandomState(7)
+  a = torch.from_numpy((r.standard_normal(200000) * np.exp(r.uniform(-30, 30, 200000))).astype(np.float32))
+  a[:3] = torch.tensor([0.0, -0.0, 1.0])  # (magnitudes e^-30 .. e^30: every remainder a normal fp32 number, no piece rounds to infinity)
+  p1, p2, p3 = S.pieces_bf16(a)
+  for p in (p1, p2, p3):
+    assert torch.equal(p, p.to(torch.bfloat16).float())  # each piece IS a bf16 value
+  assert torch.equal(p1.double() + p2.double() + p3.double(), a.double())
+  assert torch.equal((p1 + p2) + p3, a)
+  # the third piece is the exact remainder: truncating it instead of rounding changes nothing (why that mutant enters no threshold)
+  assert all(torch.equal(x, y) for x, y in zip(S.pieces_bf16(a, trunc_last=True), (p1, p2, p3)))
+  # two fp16 pieces of the scaled value: the leading 22 bits, the remainder exact in fp32
+  b = torch.from_numpy(r.standard_normal(200000).astype(np.float32))
+  s = S.f16_scale_of(b.abs().max())
+  h1, h2 = S.pieces_f16(b, s)
+  big = b.abs() * s >= 2.0**-3  # (both pieces normal fp16 numbers)
+  err = ((h1.double() + h2.double()) / s - b.double()).abs()
+  assert bool((err[big] <= 2.0**-22 * b.double().abs()[big]).all())
+  t1, t2 = S.pieces_f16(b, s, trunc_last=True)
+  assert torch.equal(t1, h1) and bool((t2.abs() <= h2.abs()).all()) and not torch.equal(t2, h2)
+  rem = (b * s - h1).double()
+  assert bool(((rem - t2.double()).abs() <= (rem - h2.double()).abs() * 2 + 2.0**-24).all()) and bool((t2.double().abs() <= rem.abs()).all())
+
+
+def test_f16_scale_of_as_its_comment_states_it():
+  for m in (1.0, 1.5, 0.75, 3.9e4, 6.1e-5, 1e-7, 2.0**-60, 1e30):
+    s = S.f16_scale_of(m)
+    assert 2.0**14 <= m * s < 2.0**15 and s == 2.0**round(np.log2(s)), m
+  assert S.f16_scale_of(0.0) == 1.0
+  assert S.f16_scale_of(2.0**-70) == S.f16_scale_of(2.0**-63) == 2.0**77  # magnitudes below 2^-63 are treated as 2^-63
+  assert np.isfinite(S.f16_scale_of(float('inf'))) and np.isfinite(S.f16_scale_of(float('nan')))
+
+
+def test_emulate_with_every_pair_is_the_product_of_the_kept_bits():
+  """Six bf16 pairs leave out a2 b3 + a3 b2 + a3 b3 <= 3 * 2^-24 |a||b|; three fp16 pairs a2 b2 <= 2^-22 |a||b|: the faithful emulation
+  is within that of the float64 operator, componentwise; and `emulations` (a dropped pair as one subtraction) agrees with `emulate`."""
+  case = next(c for c in S.CASES if c.family == 'conv3d_s1' and c.shape == (2, 8, 8, 8, 8, 8) and c.kind == 'unit variance')
+  for arith in ('bf16x6', 'f16x3'):
+    role = S.roles(case._replace(arith=arith))[0][0]
+    want = role.op(role.a.double(), role.b.double())
+    den = role.op(role.a.double().abs(), role.b.double().abs())
+    u = S.units(S.emulate(role.op, role.a, role.b, arith), want, den, arith)
+    assert float(u.max()) <= (3.0 if arith == 'bf16x6' else 1.0)
+    both = S.emulations(role.op, role.a, role.b, arith, S.DROPS[arith])
+    for m in S.DROPS[arith]:
+      direct = S.emulate(role.op, role.a, role.b, arith, m)
+      assert float(((both[m] - direct).abs() / den).max()) <= 2.0**-45, m
+    # the truncation mutant: the identity on three bf16 pieces, within twice the faithful error on two fp16 pieces -- it enters no T
+    faithful, trunc = both[None], S.emulate(role.op, role.a, role.b, arith, ('trunc',))
+    if arith == 'bf16x6':
+      assert torch.equal(trunc, faithful)
+    else:
+      r_f, r_t = S.rms(S.units(faithful, want, den, arith)), S.rms(S.units(trunc, want, den, arith))
+      print('fp16 pieces, last piece truncated: rms %.3f against %.3f faithful' % (r_t, r_f))
+      assert not torch.equal(trunc, faithful) and r_t <= 2 * r_f
+
+
+def test_worst_slice_groups_short_axes_and_skips_nothing():
+  shape = (3, 5, 7, 11)  # elements per index: 385, 231, 165, 105 -> groups of 1, 2, 2, 3 indices; the short tails join the group before
+  want_sizes = {0: 385, 1: 3 * 231, 2: 3 * 165, 3: 5 * 105}
+  for ax in range(4):
+    v = torch.zeros(shape, dtype=torch.float64)
+    v.select(ax, shape[ax] - 1).fill_(1.0)  # the last index of the axis: in a tail group
+    got = S.worst_slice(v)
+    # the slice along `ax` that holds the ones is the worst: the fraction of ones in it is the last index's share of its group
+    share = (v.numel() // shape[ax]) / float(want_sizes[ax])
+    assert got.axis == ax and abs(got.rms - share**0.5) < 1e-12, (ax, got, share)
+  with pytest.raises(AssertionError):
+    S.units(torch.ones(4), torch.zeros(4), torch.tensor([1.0, 0.0, 1.0, 1.0]), 'bf16x6')  # non-zero where every product is zero
+
+
+# ------------------------------------------------------------------------------------------------ why this file exists
+def _old_bounds_admit(case, role_name, bound_of):
+  role = next(r for r in S.roles(case)[0] if r.name == role_name)
+  ref = S.reference(case, role)
+  plain = role.plain32().double()
+  bound = bound_of(role, ref.want)
+  out = []
+  for m in [None] + list(ref.mutants):
+    got = ref.emu[m] + (plain - ref.want)  # the arithmetic (or a mutant of it) plus an fp32 accumulator's rounding
+    e = float((got - ref.want).abs().max())
+    out.append((m, e, bound, S.measure(case, role, ref, got)[0], ref.T))
+  return out
+
+
+def test_the_bounds_of_the_older_tests_admit_every_single_pair_mutant():
+  """tests/test_gpu_split.py holds a forward to 2^-22 sqrt(terms) 8 max|y| and a weight gradient to 2e-5 max|gw|.  At 32 -> 32, 6 x 10 x 40
+  a kernel that lost ANY one of a2 b2, a1 b3, a3 b1 stays below both by a wide margin -- and exceeds T by the factor of three T is made of."""
+  case = next(c for c in S.CASES if c.family == 'conv3d_s1' and c.shape == (1, 32, 32, 6, 10, 40) and c.kind == 'unit variance' and c.arith == 'bf16x6')
+  fwd = _old_bounds_admit(case, 'forward', lambda role, want: 2.0**-22 * np.sqrt(32 * 27) * 8 * max(1.0, float(want.abs().max())))
+  wgr = _old_bounds_admit(case, 'weight gradient', lambda role, want: 2e-5 * max(1.0, float(want.abs().max())))
+  for name, rows in (('forward', fwd), ('weight gradient', wgr)):
+    for m, e, bound, whole, T in rows:
+      print('%-16s %-14s max error %.2e, old bound %.2e (x %.0f) | componentwise rms %.2f, T %.2f' % (name, m, e, bound, bound / e, whole, T))
+      assert e <= bound / 4, (name, m)  # admitted, faithful and mutant alike
+      assert (whole <= T / 1.5) if m is None else (whole >= 2.5 * T), (name, m, whole, T)
