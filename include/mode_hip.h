@@ -928,6 +928,46 @@ int mode_rgb_half_pil(const uint8_t* frames_u8, const int32_t* tab_w, const int3
 int mode_decimate2(const float* in, float* out, long long planes, int H, int W, mode_stream_t stream);
 int mode_decimate2_bwd(const float* gout, float* gin, long long planes, int H, int W, mode_stream_t stream);
 
+/* Colour augmentation on the 8-bit ingest (csrc/augment.hip): the reference's inception_color_preproccess
+ * (dataloader/preprocess.py:33-46: ToTensor, ColorJitter(0.4, 0.4, 0.4), Lighting(0.1, eigval, eigvec), Normalize; Lighting is
+ * preprocess.py:78-95) on N images, fused with the planar split.  The random draws are the host's; the kernels read them from two
+ * device tables.  Per image, in fp32, every operation rounded once to nearest, in this order, nothing contracted:
+ *     x = (float)v / 255.0f                                           (IEEE division)
+ *     grey(x) = (0.2989f * r + 0.587f * g) + 0.114f * b
+ *     blend(a, b, k) = clamp(rho_k * a + sigma_k * b, 0, 1)           rho_k the factor, sigma_k = (float)(1.0 - factor) formed by
+ *                                                                     the host in double: the kernel never computes 1 - rho
+ *     up to three operations in the image's own order:
+ *       brightness  x = blend(x, 0, b)
+ *       contrast    x = blend(x, m, c), m = the mean of grey(x) over the H W pixels as x stands when the step is reached
+ *       saturation  x = blend(x, grey(x), s)                          per pixel
+ *     x[c] += shift[c]                                                (Lighting: no clamp)
+ *     (x[c] - mean[c]) / std[c]                                       (fp32 ImageNet statistics, IEEE division)
+ *   m: the fp32 grey values are summed in fp64 in a fixed order (a thread walks its quads in ascending order, a fixed butterfly over
+ *   the lanes, the waves in index order, one partial per block; the partials folded in index order), divided by H W and rounded once
+ *   to fp32.  No atomics; the number of partials depends on H W alone: the same images and tables give the same bits on any
+ *   stream and any device.
+ * mode_images_u8_augment:
+ *   images_u8 (N, H, W, 3) bytes, each image as np.asarray(PIL RGB image) lays it out; 4-byte aligned.
+ *   ops (N, 3) int32, device: the image's operations in order -- 0 brightness, 1 contrast, 2 saturation, anything else: no operation.
+ *     A code only selects a branch; a row should name an operation at most once (a second contrast step would blend with the mean
+ *     of the first).
+ *   coef (N, 9) fp32, device: rho_b, sigma_b, rho_c, sigma_c, rho_s, sigma_s, shift_r, shift_g, shift_b (indexed by operation, not by
+ *     position in the order).
+ *   dst (N, ndst) int32, device, or NULL; ndst = 1 or 2: image n is written to out[dst[n][j]] for every j; NULL means one slot,
+ *     dst[n] = n (whatever ndst says, which must still be 1 or 2).  A slot outside [0, slots) is skipped (-1: "no second copy"; an image with no valid slot
+ *     is not written).  Two images with the same slot: undefined which one stays.  ndst = 2 is what lets one call write the left /
+ *     right stacks of a frame AND the second copy of the four panoramas the fusion stage takes.
+ *   out (slots, 3, H, W) fp32, 16-byte aligned; slots that no image names keep their content.
+ *   means (N,) fp32 or NULL: the contrast mean m used for image n, 0 for an image without a contrast step.
+ *   workspace: device, 8-byte aligned, workspace_bytes >= mode_images_u8_augment_workspace_bytes(N, H, W); it needs no initialisation.
+ *   Two launches: the grey sums (of the images that have a contrast step, after the operations that precede it), then the whole chain.
+ *   One thread handles four pixels: three dwords in, one 16-byte store per colour plane out.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, misaligned buffers, H, W <= 0, N or slots < 0,
+ * ndst not 1 or 2, H W % 4 != 0, element counts (3 N H W, 3 slots H W) >= 2^31 and a workspace that is too small.  N = 0 is a no-op. */
+size_t mode_images_u8_augment_workspace_bytes(int N, int H, int W);
+int mode_images_u8_augment(const uint8_t* images_u8, const int32_t* ops, const float* coef, const int32_t* dst, int ndst, int N, int H,
+                           int W, int slots, float* out, float* means, void* workspace, size_t workspace_bytes, mode_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * 3D60 ingest (csrc/erp_ingest.hip): what the reference's Dataset3D60Disparity.__getitem__ (dataloader/dataset3D60Loader.py:123-248)
  * does on the host per sample between the decoded equirectangular (ERP) files and ModeDisparity, for a batch of N pairs.

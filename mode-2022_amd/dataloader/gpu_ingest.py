@@ -9,6 +9,11 @@
                   and normalised, the depth turned into the disparity ground truth, for the pair and its mirrored twin
                   (mode_erp_pairs_u8_cassini, mode_erp_depth_disp)
 
+  augment_u8_gpu  preprocess.get_transform_stage1(augment=True) of the reference (dataloader/preprocess.py:33-46, 78-95): ColorJitter(0.4,
+                  0.4, 0.4) and the PCA Lighting(0.1) between ToTensor and Normalize, on (N, H, W, 3) uint8 images, with the random
+                  draws made on the host (draw_colour_params -> ColourParams) and everything per pixel on the device
+                  (mode_images_u8_augment); frames_u8_gpu(augment=) and erp_pairs_gpu(augment=) run their images through it
+
 The first two are bit for bit what the host computes, and so are the images of the third (its disparities differ from numpy's by the
 last bits of asin): the normalisation is a lookup in the table the host transform produces for the 256 byte
 values (preprocess.norm_table), the resize Pillow's own fixed-point arithmetic on the coefficients of preprocess.pil_half_table.
@@ -26,6 +31,7 @@ from . import preprocess
 _lut_cache = _HF._LRU(8)    # device -> (256, 3) float32 normalisation table (graph-pinned while captured)
 _half_cache = _HF._LRU(8)   # (H, W, device) -> (tab_w (W/2, 10), tab_h (H/2, 10)) int32 tables of mode_rgb_half_pil
 _erp_cache = _HF._LRU(16)   # (pair, H, W, device) -> grid (1, H, W, 2); ('cols', W, device) -> cols (3, W): the 3D60 ingest's tables
+_dst_cache = _HF._LRU(8)    # (F, want_rgb, device) -> (12 F, 2) int32: the slots of every panorama of F frames in cat(left, right, rgb)
 _lock = threading.Lock()
 
 
@@ -55,11 +61,160 @@ def _half_tables(H, W, device):
     return hit
 
 
-def frames_u8_gpu(frames_u8, want_rgb=True):
+def frames_u8_gpu(frames_u8, want_rgb=True, augment=None):
   """(F, 12, H, W, 3) uint8 device frames -- the 12 panoramas of a frame in sorted file order, each as np.asarray(PIL image) lays
-  it out -> (left (6F, 3, H, W), right (6F, 3, H, W), rgb (F, 12, H, W) or None): split_frames of the ImageNet-normalised panoramas."""
+  it out -> (left (6F, 3, H, W), right (6F, 3, H, W), rgb (F, 12, H, W) or None): split_frames of the ImageNet-normalised panoramas.
+  augment: ColourParams for the 12 F panoramas (row 12 f + k: panorama k of frame f) -> the same three tensors of the colour-augmented
+  panoramas (augment_u8_gpu): left, right and rgb are three parts of one buffer that mode_images_u8_augment writes through its slot
+  table in one call (panoramas 0, 1, 10, 11 have two slots each: their pair and the fusion RGB)."""
   _HF.require_u8_frames(frames_u8, 'frames_u8_gpu')
-  return _HF.frames_u8_ingest(frames_u8, _norm_lut(frames_u8.device), want_rgb)
+  if augment is None:
+    return _HF.frames_u8_ingest(frames_u8, _norm_lut(frames_u8.device), want_rgb)
+  F, _, H, W, _ = frames_u8.shape
+  _require_params(augment, 12 * F, frames_u8.device, 'frames_u8_gpu')
+  all3 = torch.empty(((16 if want_rgb else 12) * F, 3, H, W), dtype=torch.float32, device=frames_u8.device)
+  if F:
+    _HF.images_u8_augment(frames_u8.view(12 * F, H, W, 3), augment.ops, augment.coef, dst=_frame_slots(F, want_rgb, frames_u8.device),
+                          out=all3)
+  return all3[:6 * F], all3[6 * F:12 * F], (all3[12 * F:].view(F, 12, H, W) if want_rgb else None)
+
+
+def _frame_slots(F, want_rgb, device):
+  """(12 F, 2) int32 on the device: where panorama k of frame f goes in cat(left, right, rgb viewed as (4 F, 3, H, W)) -- left[6 f + k / 2]
+  for even k, right[...] for odd, and for k = 0, 1, 10, 11 with want_rgb also slot 4 f + (0, 1, 2, 3) of the fusion RGB; -1: no second slot."""
+  key = (F, bool(want_rgb), str(device))
+  with _lock:
+    hit = _dst_cache.get(key)
+    if hit is None:
+      f, k = np.divmod(np.arange(12 * F), 12)
+      second = np.where((k < 2) | (k >= 10), 12 * F + 4 * f + np.where(k < 2, k, k - 8), -1) if want_rgb else np.full(12 * F, -1)
+      hit = torch.from_numpy(np.stack([(k & 1) * 6 * F + 6 * f + k // 2, second], 1).astype(np.int32)).to(device)
+      _dst_cache[key] = hit
+    return hit
+
+
+# ------------------------------------------------------------------------------------ colour augmentation
+# The reference's __imagenet_pca (dataloader/preprocess.py:10-25), float32 as torch.Tensor([...]) rounds them.
+PCA_EIGVAL = torch.tensor([0.2175, 0.0188, 0.0045], dtype=torch.float32)
+PCA_EIGVEC = torch.tensor([[-0.5675, 0.7192, 0.4009], [-0.5808, -0.0045, -0.8140], [-0.5836, -0.6948, 0.4203]], dtype=torch.float32)
+OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE, OP_NONE = 0, 1, 2, 3, -1
+
+
+def lighting_shift(alpha, eigval=PCA_EIGVAL, eigvec=PCA_EIGVEC):
+  """Lighting's per-channel shift (reference preprocess.py:90-93) with its float32 torch operations in its order:
+  shift[c] = sum_j (eigvec[c][j] * alpha[j]) * eigval[j]."""
+  alpha = torch.as_tensor(alpha, dtype=torch.float32)
+  return ((eigvec * alpha.view(1, 3)) * eigval.view(1, 3)).sum(1)
+
+
+class ColourParams(object):
+  """The device tables of mode_images_u8_augment for n images, built from host values:
+    order    n rows of up to three operation codes in the order they are applied (OP_BRIGHTNESS 0, OP_CONTRAST 1, OP_SATURATION 2;
+             OP_NONE -1 or a shorter row: fewer operations).  An operation appears at most once in a row; OP_HUE is refused (the
+             reference's ColorJitter call has no hue).
+    factors  (n, 3): brightness, contrast and saturation factor of every image, >= 0 (1 = identity; read only where the row names
+             the operation).
+    shifts   (n, 3) float32: Lighting's per-channel shift (lighting_shift), or None = zero.
+  ops (n, 3) int32 and coef (n, 9) float32 are the device tensors; ops_host / coef_host the same values on the host.  coef holds per
+  operation rho = float32(factor) and sigma = float32(1.0 - factor), the difference formed in double as torch forms it for a Python
+  scalar.  copy_from(other) refills the device tensors in place, so that a captured graph can be replayed with new draws."""
+
+  def __init__(self, order, factors, shifts=None, device='cuda'):
+    self.ops_host, self.coef_host = self._tables(order, factors, shifts)
+    self.n = self.ops_host.shape[0]
+    self.device = torch.device(device)
+    self.ops = self.ops_host.to(self.device)
+    self.coef = self.coef_host.to(self.device)
+
+  @staticmethod
+  def _tables(order, factors, shifts):
+    order = [list(int(c) for c in row) for row in order]
+    n = len(order)
+    factors = np.asarray(factors, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    shifts = torch.zeros(n, 3) if shifts is None else torch.as_tensor(shifts, dtype=torch.float32).reshape(-1, 3)
+    if factors.shape[0] != n or shifts.shape[0] != n:
+      raise ValueError('ColourParams: %d orders, %d factor rows, %d shift rows' % (n, factors.shape[0], shifts.shape[0]))
+    if not np.isfinite(factors).all() or (factors < 0).any():
+      raise ValueError('ColourParams: factors must be finite and >= 0')
+    if not bool(torch.isfinite(shifts).all()):
+      raise ValueError('ColourParams: shifts must be finite')
+    ops = np.full((n, 3), OP_NONE, dtype=np.int32)
+    for i, row in enumerate(order):
+      row = [c for c in row if c != OP_NONE]
+      if OP_HUE in row:
+        raise ValueError('ColourParams: image %d asks for hue, which the reference\'s ColorJitter(0.4, 0.4, 0.4) does not apply' % i)
+      if any(c not in (OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION) for c in row):
+        raise ValueError('ColourParams: image %d has an unknown operation code in %s' % (i, row))
+      if len(set(row)) != len(row):
+        raise ValueError('ColourParams: image %d repeats an operation: %s' % (i, row))
+      ops[i, :len(row)] = row
+    coef = np.empty((n, 9), dtype=np.float32)
+    coef[:, 0:6:2] = factors.astype(np.float32)
+    coef[:, 1:6:2] = (1.0 - factors).astype(np.float32)  # (factors is float64 here)
+    coef[:, 6:] = shifts.numpy()
+    return torch.from_numpy(ops), torch.from_numpy(coef)
+
+  def copy_from(self, other):
+    """Refill the device (and host) tables from another ColourParams of the same n, in place."""
+    if not isinstance(other, ColourParams) or other.n != self.n:
+      raise ValueError('ColourParams.copy_from: needs ColourParams for %d images' % self.n)
+    self.ops_host.copy_(other.ops_host)
+    self.coef_host.copy_(other.coef_host)
+    self.ops.copy_(other.ops)
+    self.coef.copy_(other.coef)
+    return self
+
+
+def _require_params(params, n, device, who):
+  if not isinstance(params, ColourParams):
+    raise TypeError('%s: augment must be ColourParams (draw_colour_params), got %s' % (who, type(params)))
+  if params.n != n:
+    raise ValueError('%s: ColourParams for %d images, %d images given' % (who, params.n, n))
+  if params.ops.device != device:
+    raise ValueError('%s: ColourParams on %s, images on %s' % (who, params.ops.device, device))
+
+
+def draw_colour_params(n, device, generator=None, brightness=0.4, contrast=0.4, saturation=0.4, alphastd=0.1, share=1):
+  """Draw the colour augmentation of n images on the host and upload it: -> ColourParams.
+
+  Per draw, in this order (what torchvision >= 0.8's ColorJitter.get_params / forward and then the reference's Lighting.__call__ consume):
+    torch.randperm(4)                                      the order of brightness 0, contrast 1, saturation 2, hue 3; hue is dropped
+    torch.empty(1).uniform_(max(0, 1 - v), 1 + v)          once each for brightness, contrast, saturation, in that order; a factor
+                                                           given as None draws nothing and disables the operation
+    torch.empty(3).normal_(0, alphastd)                    Lighting's alphas; alphastd == 0 draws nothing and gives zero shifts
+  and shift = lighting_shift(alpha).  With `generator` the draws come from it, otherwise from torch's global generator.
+  share = k gives k consecutive images one draw (2: both images of a pair, 12: a whole Deep360 frame); 1, every image on its own, is
+  what the reference's loaders do, which transform image by image.
+  torchvision is not a dependency of this package: the draw order above restates its documented behaviour and is not pinned by a run
+  of the library."""
+  if n < 0 or share < 1:
+    raise ValueError('draw_colour_params: n = %r, share = %r' % (n, share))
+  ranges = []
+  for v in (brightness, contrast, saturation):
+    if v is not None and v < 0:
+      raise ValueError('draw_colour_params: a jitter value must be None or >= 0')
+    ranges.append(None if v is None else (max(0.0, 1.0 - v), 1.0 + v))
+  order, factors, shifts = [], [], []
+  for _ in range(-(-n // share)):
+    perm = torch.randperm(4, generator=generator).tolist()
+    f = [1.0 if r is None else float(torch.empty(1).uniform_(r[0], r[1], generator=generator)) for r in ranges]
+    alpha = torch.empty(3).normal_(0, alphastd, generator=generator) if alphastd != 0 else torch.zeros(3)
+    order.append([c for c in perm if c != OP_HUE and ranges[c] is not None])
+    factors.append(f)
+    shifts.append(lighting_shift(alpha) if alphastd != 0 else torch.zeros(3))
+  rows = [i // share for i in range(n)]
+  return ColourParams([order[i] for i in rows], [factors[i] for i in rows], torch.stack([shifts[i] for i in rows]) if n else None, device)
+
+
+def augment_u8_gpu(images_u8, params, return_means=False):
+  """(N, H, W, 3) uint8 device images and ColourParams for N images -> (N, 3, H, W) float32: the reference's
+  get_transform_stage1(augment=True) of every image with the draws of `params`, on mode_images_u8_augment (two launches, no host
+  synchronisation).  With return_means also the (N,) contrast means the kernel used (0 where an image has no contrast step)."""
+  if not torch.is_tensor(images_u8) or images_u8.dim() != 4:
+    raise ValueError('augment_u8_gpu: images must be a (N, H, W, 3) uint8 tensor')
+  _HF.require_gpu(images_u8)
+  _require_params(params, images_u8.shape[0], images_u8.device, 'augment_u8_gpu')
+  return _HF.images_u8_augment(images_u8, params.ops, params.coef, return_means=return_means)
 
 
 def rgb_half_gpu(frames_u8, return_u8=False):
@@ -94,14 +249,17 @@ def _erp_tables(pairs, H, W, device):
 
 
 def erp_pairs_gpu(pairs_u8, depth_left=None, depth_right=None, pair='lr', shape=(512, 256), max_depth=20.0, baseline=0.26, flip=True,
-                  return_u8=False):
+                  return_u8=False, augment=None):
   """(N, 2, He, We, 3) uint8 device tensor -- the left and right ERP panorama of N 3D60 samples, each as np.asarray(PIL RGB image) lays
   it out -- and optionally the (N, He, We) float32 ERP depth of the left and of the right view -> the reference loader's dict of device
   tensors: 'leftImg', 'rightImg' (N, 3, H, W), 'dispMap' (N, 1, H, W, NaN where the depth is invalid), and with `flip` the mirrored twin
   'leftImg_flip', 'rightImg_flip', 'dispMap_flip'.  'dispMap' needs depth_left, 'dispMap_flip' depth_right; without them the key is absent.
   pair: 'lr', 'ud', 'ur', or a sequence of N of them (what a batch of Dataset3D60Disparity(device_ingest=True) items carries).  shape:
   the Cassini (H, W).  With return_u8 also 'cassini_u8' (N, 2, H, W, 3), the 8-bit Cassini images.  Two or three launches, no host
-  synchronisation; the grids and the column table are cached per (pair, shape, device)."""
+  synchronisation; the grids and the column table are cached per (pair, shape, device).
+  augment: ColourParams for the 2 N images (row 2 n: left, row 2 n + 1: right) -> 'leftImg' and 'rightImg' are augment_u8_gpu of the
+  8-bit Cassini images, and the twin is the mirror of the augmented pair (leftImg_flip = rightImg mirrored, rightImg_flip = leftImg
+  mirrored); the disparities are untouched."""
   N = pairs_u8.shape[0] if torch.is_tensor(pairs_u8) and pairs_u8.dim() == 5 else 0
   pairs = (pair,) * max(N, 1) if isinstance(pair, str) else (tuple(pair) or ('lr',))  # (an empty batch still gets a grid of the right shape)
   if N and len(pairs) != N:
@@ -111,7 +269,18 @@ def erp_pairs_gpu(pairs_u8, depth_left=None, depth_right=None, pair='lr', shape=
     raise ValueError('erp_pairs_gpu: Cassini shape %s needs a positive height and a width that is a positive multiple of 4' % (tuple(shape),))
   _HF.require_gpu(pairs_u8)
   grid, cols = _erp_tables(pairs, H, W, pairs_u8.device)
-  left, right, left_f, right_f, u8 = _HF.erp_pairs_u8_cassini(pairs_u8, grid, _norm_lut(pairs_u8.device), flip, return_u8)
+  if augment is None:
+    left, right, left_f, right_f, u8 = _HF.erp_pairs_u8_cassini(pairs_u8, grid, _norm_lut(pairs_u8.device), flip, return_u8)
+  else:
+    _require_params(augment, 2 * N, pairs_u8.device, 'erp_pairs_gpu')
+    u8 = _HF.erp_pairs_u8_cassini(pairs_u8, grid, _norm_lut(pairs_u8.device), False, True)[4]
+    both = torch.empty((2 * N, 3, H, W), dtype=torch.float32, device=pairs_u8.device)
+    if N:
+      slots = torch.arange(2 * N, dtype=torch.int32, device=pairs_u8.device)
+      slots = (slots & 1) * N + (slots >> 1)  # image 2 n + s -> slot s N + n: the left images first, then the right ones
+      _HF.images_u8_augment(u8.view(2 * N, H, W, 3), augment.ops, augment.coef, dst=slots.to(torch.int32), out=both)
+    left, right = both[:N], both[N:]
+    left_f, right_f = (torch.flip(right, (3,)), torch.flip(left, (3,))) if flip else (None, None)
   out = {'leftImg': left, 'rightImg': right}
   if depth_left is not None:
     out['dispMap'] = _HF.erp_depth_disp(depth_left, grid, cols, baseline, max_depth)

@@ -1,8 +1,9 @@
 """Input normalisation (reference dataloader/preprocess.py:8, 49-76): ToTensor + Normalize, without torchvision.
 
-Only the non-augmented transforms are on the path (Deep360DatasetDisparity / Deep360DatasetFusion build them with
-augment=False, deep360_loader.py:77, 157, 161); the colour-jitter + PCA-lighting augmentation of preprocess.py:33-46 is not
-provided and asking for it raises."""
+Only the non-augmented transforms exist as host transforms (Deep360DatasetDisparity / Deep360DatasetFusion build them with
+augment=False, deep360_loader.py:77, 157, 161).  The colour-jitter + PCA-lighting augmentation of preprocess.py:33-46 is a device
+call on 8-bit images -- dataloader.gpu_ingest.draw_colour_params + augment_u8_gpu, or frames_u8_gpu / erp_pairs_gpu with augment=
+ -- and the package has no CPU path, so asking for it here still raises."""
 import numpy as np
 import torch
 
@@ -42,7 +43,8 @@ def depth_normalize(normalize=deep360_stats):
 def get_transform_stage1(name='imagenet', normalize=None, augment=True):
   """RGB transform (preprocess.py:64-69); `normalize` is ignored there too (always the ImageNet statistics)."""
   if augment:
-    raise NotImplementedError('the colour augmentation of preprocess.py:33-46 is not part of this build')
+    raise NotImplementedError('the colour augmentation of preprocess.py:33-46 has no host transform here: it runs on the GPU, on 8-bit '
+                              'images (dataloader.gpu_ingest.draw_colour_params and augment_u8_gpu / frames_u8_gpu(augment=...))')
   return color_normalize(imagenet_stats)
 
 

@@ -185,6 +185,9 @@ SIGNATURES = {
     'mode_rgb_half_pil': (_c_int, [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr] * 3),
     'mode_decimate2': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
     'mode_decimate2_bwd': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
+    # colour augmentation on the 8-bit ingest (csrc/augment.hip; reference dataloader/preprocess.py:33-46, 78-95)
+    'mode_images_u8_augment_workspace_bytes': (_c_size, [_c_int] * 3),
+    'mode_images_u8_augment': (_c_int, [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr] * 3 + [_c_size, _c_ptr]),
     # 3D60 ingest: ERP pairs and depth to rectified Cassini (csrc/erp_ingest.hip; reference dataloader/dataset3D60Loader.py:123-270)
     'mode_erp_pairs_u8_cassini': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr] * 6),
     'mode_erp_depth_disp': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 3),

@@ -2029,6 +2029,52 @@ def frames_u8_ingest(frames_u8, lut, want_rgb=True):
   return left, right, rgb
 
 
+def images_u8_augment(images_u8, ops, coef, dst=None, out=None, return_means=False):
+  """(N, H, W, 3) uint8 images -> the colour-augmented, ImageNet-normalised planes (N, 3, H, W) on mode_images_u8_augment (the reference's
+  inception_color_preproccess, dataloader/preprocess.py:33-46, 78-95; the contract is in include/mode_hip.h).  ops (N, 3) int32: the
+  operations of every image in order (0 brightness, 1 contrast, 2 saturation, anything else none); coef (N, 9) float32: rho and sigma of
+  the three operations and the three lighting shifts (dataloader.gpu_ingest.ColourParams builds both).  dst (N,) or (N, 2) int32: image n goes to
+  out[dst[n]] (to both slots of its row; a slot outside `out`, e.g. -1, is skipped) of `out` (slots, 3, H, W), which must be given with
+  it; slots that no image names keep their content.  With return_means
+  also the (N,) contrast means the kernel used."""
+  who = 'images_u8_augment'
+  if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8:
+    raise TypeError('%s: images must be a uint8 tensor (got %s)' % (who, getattr(images_u8, 'dtype', type(images_u8))))
+  require_gpu(images_u8, ops, coef, dst, out)
+  if images_u8.dim() != 4 or images_u8.shape[3] != 3:
+    raise ValueError('%s: images must be (N, H, W, 3), got %s' % (who, tuple(images_u8.shape)))
+  N, H, W, _ = images_u8.shape
+  if (H * W) % 4 or H * W == 0:
+    raise ValueError('%s: H W = %d x %d must be a positive multiple of 4' % (who, H, W))
+  for t, dt, shape, name in ((ops, torch.int32, (N, 3), 'ops'), (coef, torch.float32, (N, 9), 'coef'), (dst, torch.int32, (N,), 'dst')):
+    if name == 'dst' and torch.is_tensor(t) and t.dim() == 2:
+      shape = (N, 2)
+    if (t is not None or name != 'dst') and (not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape):
+      raise ValueError('%s: %s must be %s %s, got %s %s' % (who, name, str(dt).replace('torch.', ''), shape, getattr(t, 'dtype', type(t)),
+                                                            tuple(getattr(t, 'shape', ()))))
+  dev = images_u8.device
+  if (dst is None) != (out is None):
+    raise ValueError('%s: dst and out are given together' % who)
+  if out is None:
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
+  else:
+    require_f32c(out)
+    if out.dim() != 4 or tuple(out.shape[1:]) != (3, H, W):
+      raise ValueError('%s: out must be (slots, 3, %d, %d), got %s' % (who, H, W, tuple(out.shape)))
+  for t, name in ((images_u8, 'images'), (ops, 'ops'), (coef, 'coef'), (dst, 'dst'), (out, 'out')):
+    if t is not None and (not t.is_contiguous() or t.device != dev):
+      raise TypeError('%s: %s must be contiguous and on %s' % (who, name, dev))
+  means = torch.empty((N,), dtype=torch.float32, device=dev) if return_means else None
+  nws = lib().mode_images_u8_augment_workspace_bytes(N, H, W)
+  ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=dev)
+  with torch.cuda.device_of(images_u8), profiling.region('images_u8_augment', images_u8.numel() * 2 + 12 * N * H * W, 0, dev):
+    check(lib().mode_images_u8_augment(ptr(images_u8), ptr(ops), ptr(coef), None if dst is None else ptr(dst),
+                                       2 if dst is not None and dst.dim() == 2 else 1, N, H, W, out.shape[0],
+                                       ptr(out), None if means is None else ptr(means), ptr(ws), nws, stream_of(images_u8)),
+          'mode_images_u8_augment')
+  return (out, means) if return_means else out
+
+
 def rgb_half_pil(frames_u8, tab_w, tab_h, lut, return_u8=False):
   """Panoramas 0, 1, 10, 11 of (F, 12, H, W, 3) uint8 frames halved as PIL.Image.resize((W / 2, H / 2)) halves them and normalised ->
   (F, 12, H/2, W/2) float32 (with return_u8: and the 8-bit result (F, 4, H/2, W/2, 3)) on mode_rgb_half_pil.  tab_w (W/2, 10), tab_h
