@@ -944,6 +944,7 @@ def test_folded_batchnorm_conv3d(relu, with_add, arith):
       want = F.conv3d(x.cpu().double(), w.cpu().double(), None, stride, 1).to(DEV)
       add = _rand(tuple(want.shape), 94).to(DEV) if with_add else None
       got = HF.conv3d_bn_eval(x, w, bn, stride, add, relu)
+      # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
       assert (got.double() - _unfused(bn, want, add, relu)).abs().max() < 1e-4, (ci, co, stride)
     for (cin, cout) in ((24, 40), (64, 32), (64, 64), (12, 40)):  # two output tiles (fp32 kernel), hourglass conv6 and conv5 (in bf16x6 mode the
       # split kernel's own epilogue, mode_deconv3d_fwd_split_bn), channels off the split kernel's grid
@@ -951,6 +952,7 @@ def test_folded_batchnorm_conv3d(relu, with_add, arith):
       bn = _eval_bn(cout, 97)
       want = F.conv_transpose3d(x.cpu().double(), w.cpu().double(), None, 2, 1, 1).to(DEV)
       add = _rand(tuple(want.shape), 98).to(DEV) if with_add else None
+      # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
       assert (HF.deconv3d_bn_eval(x, w, bn, add, relu).double() - _unfused(bn, want, add, relu)).abs().max() < 1e-4, (cin, cout)
 
 
@@ -1053,6 +1055,7 @@ def test_folded_batchnorm_conv2d_3x3(dil, relu, with_add, arith):
     bn = _eval_bn(40, 101, 2)
     want = F.conv2d(x.cpu().double(), w.cpu().double(), None, 1, dil, dil).to(DEV)
     add = _rand(tuple(want.shape), 102).to(DEV) if with_add else None
+    # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
     assert (HF.conv2d_bn_eval(x, w, bn, dil, add, relu).double() - _unfused(bn, want, add, relu)).abs().max() < 1e-4
 
 
@@ -1073,6 +1076,7 @@ def test_folded_batchnorm_other_conv2d_layers(ci, co, k, s, p, relu, with_add):
     seq = nn.Sequential(conv, bn).eval()
     got = stage3d.conv_bn(seq, x, relu, add)
     assert tuple(got.shape) == tuple(want.shape)
+    # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
     assert (got.double() - _unfused(bn, want, add, relu)).abs().max() < 1e-4
 
 
@@ -1091,10 +1095,12 @@ def test_folded_batchnorm_sphere_conv(ih, iw, B, relu, with_add):
     want = sphere_conv_ref.forward(x.cpu().double(), m.position, m.weight.detach().cpu().double(), (1, 1), (1, 1), (1, 1), 1).to(DEV)
     add = _rand(tuple(want.shape), 108).to(DEV) if with_add else None
     ref = _unfused(bn, want, add, relu)
+    # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
     assert (m.forward_bn(x, bn, add, relu).double() - ref).abs().max() < 1e-4
     if m.supports_transposed_io(B, x.device):
       with sc.transposed_io():
         got_t = m.forward_bn(HF.transpose_planes(x), bn, HF.transpose_planes(add) if add is not None else None, relu)
+      # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
       assert (HF.transpose_planes(got_t).double() - ref).abs().max() < 1e-4
     else:
       assert (ih, iw) == (16, 32)
@@ -1108,6 +1114,7 @@ def test_folded_batchnorm_cost_conv(relu):
     w = _rand((12, 16, 3, 3, 3), 111, 0.1).to(DEV)
     bn = _eval_bn(12, 112)
     want = F.conv3d(mode_ref.cost_volume(fr.cpu().double(), ft.cpu().double(), 5), w.cpu().double(), None, 1, 1).to(DEV)
+    # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
     assert (HF.cost_conv_bn_eval(fr, ft, w, 5, bn, relu).double() - _unfused(bn, want, None, relu)).abs().max() < 1e-4
 
 
@@ -1190,6 +1197,7 @@ def test_conv1x1_kernels(B, Ci, Co, H, W, s):
     bn = _eval_bn(Co, 124, 2)
     add = _rand(tuple(y_ref.shape), 125).to(DEV)
     got = stage3d.conv_bn(nn.Sequential(conv, bn).eval(), x.to(DEV), True, add)
+    # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
     assert (got.double() - _unfused(bn, y_ref.detach().to(DEV), add, True)).abs().max() < 1e-4
 
 
@@ -1225,6 +1233,7 @@ def test_conv_stem_kernels(B, Co, H, W):
   with torch.no_grad():
     bn = _eval_bn(Co, 134, 2)
     got = stage3d.conv_bn(nn.Sequential(conv, bn).eval(), xd, True, None)
+    # (an absolute 1e-4, ~100 x fp32 round-off: tests/test_gpu_eval_precision.py holds this entry to the componentwise contract)
     assert (got.double() - _unfused(bn, y_ref.detach().to(DEV), None, True)).abs().max() < 1e-4
 
 
