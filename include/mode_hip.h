@@ -133,7 +133,7 @@ int mode_sphere_conv_bwd_data_adj_list(const float* gy, const float* w, float* g
                                        int Ho, int Wo, int groups, int accumulate, const int32_t* tile_list, int n_list,
                                        mode_stream_t stream);
 
-/* Windowed input gradient on the split-bf16 matrix path (csrc/sphere_conv_win.hip; replaces the col2im scatter of
+/* Windowed input gradient on the split-bf16 matrix path (csrc/sphere_win_bwd_data.hip; replaces the col2im scatter of
  * sphere_conv_cuda_kernel.cu:293-356 + the GEMM of sphere_conv_cuda.cpp:275-315 for stride 1, 3x3 taps, output grid = input grid).
  * Host planning, once per table: mode_sphere_adjplan_build(pos_host, H, W, Kh, Kw, good_tiles[4 n], bad_tiles[2 n], counts[2],
  *   rec_off_host[n * 9 * 256 * 4], rec_w_host[same], rec_off2_host[n * 9 * 256 * 2], rec_w2_host[same]) with n =
@@ -162,7 +162,7 @@ int mode_sphere_conv_bwd_data_win_split_f16(const float* gy, const float* w, con
                                             const int32_t* rec_off2, const float* rec_w2, int B, int Ci, int H, int W, int Co, int Kh,
                                             int Kw, int groups, int transposed, mode_stream_t stream);
 
-/* Windowed forward (csrc/sphere_conv_win.hip): same result as mode_sphere_conv_fwd for stride 1 and 3x3 taps, ~2x faster on
+/* Windowed forward (csrc/sphere_win_fwd.hip): same result as mode_sphere_conv_fwd for stride 1 and 3x3 taps, ~2x faster on
  * tables whose samples are spatially compact (the gnomonic tables of the network).  The caller plans the table once on the HOST
  * (the mode_sphere_*plan* entries: csrc/sphere_plan.hip, host code only):
  *   mode_sphere_plan_build(pos_host, ...) fills tiles_host[4 * mode_sphere_plan_max_tiles(H, W)] with (h0, w0, rbase, cbase)

@@ -955,7 +955,7 @@ extern "C" size_t mode_sphere_conv_bwd_weight_workspace_bytes(int B, int Ci, int
 namespace mode {
 // General (gather) weight-gradient kernels over all output pixels (pixmap == nullptr) or over the listed ones only; ADDS the
 // result to gw.  Used by mode_sphere_conv_bwd_weight and, for the tiles the windowed kernel leaves out, by
-// mode_sphere_conv_bwd_weight_win (sphere_conv_win.hip).
+// mode_sphere_conv_bwd_weight_win (sphere_win_bww.hip).
 size_t sphere_bwd_weight_general_workspace(int B, int Ci, int Co, int Kh, int Kw, int Ho, int Wo, int groups, int nsel) {
   Dims d;
   if (make_dims(d, B, Ci, 1 << 14, 1 << 14, Co, Kh, Kw, 1, 1, Ho, Wo, groups, "mode_sphere_conv_bwd_weight_workspace_bytes") != MODE_OK)

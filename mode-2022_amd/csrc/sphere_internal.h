@@ -1,4 +1,4 @@
-// Internal links between sphere_conv.hip (general gather kernels) and sphere_conv_win.hip (windowed kernels).
+// Internal links between sphere_conv.hip (general gather kernels) and sphere_win_*.hip (windowed kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// Host-side planners of the windowed spherical kernels (sphere_conv_win.hip): they cut a sampling table into the tiles, windows and
+// Host-side planners of the windowed spherical kernels (sphere_win_*.hip): they cut a sampling table into the tiles, windows and
 // sampling records those kernels run on.  No kernel in here -- plain host code on host memory, with the record arithmetic the kernels use
 // (sphere_tap.h) and their geometry (sphere_win_geometry.h).
 #include <algorithm>

@@ -1,4 +1,4 @@
-// Tile and window geometry of the windowed spherical kernels, shared by the kernels (sphere_conv_win.hip) and the host-side planners
+// Tile and window geometry of the windowed spherical kernels, shared by the kernels (sphere_win_*.hip) and the host-side planners
 // that cut a sampling table into their tiles (sphere_plan.hip): both sides must agree on every number here.
 #pragma once
 #include <cstddef>

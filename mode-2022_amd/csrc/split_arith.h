@@ -54,7 +54,7 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
 // (the subtractions of a pair stay scalar: packed into v_pk_add_f32 each costs ~9 cycles of the MATRIX pipe -- packed fp32
 // instructions do not overlap with MFMAs on gfx950, plain ones do; tools/experiments/mfma_op_cost.hip)
 // Users: conv3d_split, conv2d_split, conv2d_split_wgrad (compiled with -fno-slp-vectorize) and conv3d_split_s2, conv3d_split_deconv,
-// conv3d_split_wgrad_s2, sphere_conv_win (no per-file flag: there the asm statement alone keeps the pair apart).
+// conv3d_split_wgrad_s2, sphere_win_* (no per-file flag: there the asm statement alone keeps the pair apart).
 // One step of it: returns the pair's next piece and leaves the pair's exact remainders in (a, b).  The spherical kernels call the steps
 // one by one, spread over the MFMAs of a tap (their split_a / split_b / split_c).
 __device__ __forceinline__ uint32_t split_step_bf16_pinned(float& a, float& b) {
@@ -114,7 +114,7 @@ __device__ __forceinline__ void split2_f16_pinned(float a, float b, uint32_t& p1
 // vector instructions of the spherical forward / input-gradient / weight-gradient loops -- and fma(-1, h, a) is folded back to that
 // in a file compiled without -fno-slp-vectorize; the asm statement also does what the empty one of split2_f16_pinned does: it keeps
 // the pair's two chains scalar.
-// User: sphere_conv_win (no per-file flag).
+// User: sphere_win_* (no per-file flag).
 __device__ __forceinline__ void split2_f16_mix(float a, float b, uint32_t& p1, uint32_t& p2) {
   const f32x2 v = {a, b};
   const f16x2 h1 = __builtin_convertvector(v, f16x2);

@@ -424,7 +424,7 @@ def _sphere_roles(case):
     return torch.einsum('bgon,bgkn->gok', gy_.reshape(B, g, cog, N), c.reshape(B, g, cig * 9, N)).reshape(co, cig, 3, 3)
 
   # the adjoint-sampled gradient G_k[o][q] = sum over the output pixels p whose tap k touches q of wt * gy[o][p] (the kernel's header:
-  # csrc/sphere_conv_win.hip, "Input gradient on the split-bf16 matrix path"), tap by tap: the scatter of a one-tap problem
+  # csrc/sphere_win_bwd_data.hip, "Input gradient on the split-bf16 matrix path"), tap by tap: the scatter of a one-tap problem
   def adjoint(g_):
     return torch.stack([R.col2im_scatter(g_[:, :, None], pos64[:, 2 * k:2 * k + 2], H, W, 1, 1, 1, 1) for k in range(9)], 2)
 

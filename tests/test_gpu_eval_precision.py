@@ -30,7 +30,7 @@ The eval instantiations, read from the launch code of csrc/*, and the case that 
                           (mode_deconv3d_fwd_split_bn_amax)                                           deconv3d * route split
   conv2d_split.hip      the 3 x 3 kernel, dilation 1 | 2, epilogue forms on three bf16 pieces (mode_conv2d_fwd_split) and on two fp16
                           pieces with the maximum (mode_conv2d_fwd_split_f16_bn)                      conv2d * route split | f16
-  sphere_conv_win.hip   the windowed split kernel with the epilogue, NCHW caller (plane-transposed copies) and transposed storage
+  sphere_win_fwd.hip    the windowed split kernel with the epilogue, NCHW caller (plane-transposed copies) and transposed storage
                           (mode_sphere_conv_fwd_win_split)                                            sphere * route split
   conv3d.hip            the fp32 MFMA kernels' folded forms: stride 1, stride 2 (mode_conv3d_fwd_bn), transposed with one and two
                           output tiles (mode_deconv3d_fwd_bn)                                         conv3d_s1 | conv3d_s2 | deconv3d * route f32

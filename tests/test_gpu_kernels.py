@@ -217,7 +217,7 @@ def test_sphere_conv_fwd_bwd(typ, ih, iw, B, ci, co, stride, groups):
 @pytest.mark.parametrize('ih,iw,B,ci,co,groups', [(64, 128, 1, 16, 32, 1), (128, 256, 1, 8, 32, 1), (10, 20, 2, 5, 7, 1), (33, 66, 1, 12, 40, 2),
                                                    (16, 32, 1, 40, 160, 1)])
 def test_sphere_conv_window_kernels_match_gather_kernels(ih, iw, B, ci, co, groups, monkeypatch):
-  """The LDS-window forward (csrc/sphere_conv_win.hip) against the general gather forward on Cassini tables: all three
+  """The LDS-window forward (csrc/sphere_win_fwd.hip) against the general gather forward on Cassini tables: all three
   window classes (equator, near-pole, wrap-around) appear at 128x256; ragged tiles (H % 32, W % 4 != 0), groups and
   Co > 128.  Same products, different summation order: fp32 round-off only."""
   pos = mode_ref.sphere_position(ih, iw, 'Cassini').to(DEV)

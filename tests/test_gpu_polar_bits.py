@@ -1,7 +1,7 @@
 """GPU (-m gpu): the two polar kernels of the spherical gradients compute what they computed before they were rescheduled, bit for bit.
 
 sphere_bwd_data_adj9_kernel (csrc/sphere_conv.hip) went from 4 to 8 waves per 64-pixel tile and sphere_bww_polar_split_kernel
-(csrc/sphere_conv_win.hip) issues an item's loads in one batch ahead of its barrier; neither change touches the sequence of operations
+(csrc/sphere_win_bww.hip) issues an item's loads in one batch ahead of its barrier; neither change touches the sequence of operations
 behind an output element.  tests/golden/polar_parent_bits.json holds the SHA-256 of the operators' outputs at the commit before
 (tests/golden/make_golden_polar_bits.py, run once on the MI355X there): the outputs are recomputed here on the same seeded inputs and
 their hashes compared, and each call is repeated once and compared with torch.equal."""

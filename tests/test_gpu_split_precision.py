@@ -197,7 +197,7 @@ def _launch(case, role, t):
   H, W = pos.shape[2:]
   plan = HF.sphere_plan(pos, 3, 3)
   if name == 'forward':
-    # (csrc/sphere_conv_win.hip, sphere_conv_fwd_win_impl: the split kernel takes 16 input channels of a group per chunk; with fewer the
+    # (csrc/sphere_win_fwd.hip, sphere_conv_fwd_win_impl: the split kernel takes 16 input channels of a group per chunk; with fewer the
     # SAME entry runs the fp32 window kernels, so the entry's name proves nothing there and the role is not judged)
     ok = HF._plan_usable(plan) and (ci // g) % 16 == 0
     return ('mode_sphere_conv_fwd_win_split',

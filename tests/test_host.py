@@ -408,3 +408,44 @@ def test_isa_loops_reads_a_listing(tmp_path, monkeypatch, capsys):
   assert '(1, (10, 0, 1, 1))' in capsys.readouterr().out
   mod.chains('kernel')
   assert '[(2, 2)]' in capsys.readouterr().out
+
+
+def test_isa_same_tells_a_moved_kernel_from_a_changed_one(tmp_path, capsys):
+  """tools/isa_same.py on two hand-written listings: a kernel that moved to another place in its file (other .LBB index, other comments)
+  is SAME, one changed opcode is DIFF with the opcode named, a changed register count in the descriptor is DIFF, a kernel that went
+  missing is reported, and the exit status follows."""
+  import importlib.util
+  spec = importlib.util.spec_from_file_location('isa_same', os.path.join(os.path.dirname(__file__), '..', 'tools', 'isa_same.py'))
+  mod = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(mod)
+
+  def listing(name, idx, op='v_add_f32_e32', vgpr=12, note='old'):
+    return '\n'.join(['\t.type\t%s,@function' % name, '%s:                            ; @%s (%s)' % (name, name, note),
+                      '\ts_load_dwordx2 s[0:1], s[4:5], 0x0', '.LBB%d_1:                 ; =>This Inner Loop Header: Depth=1 %s' % (idx, note),
+                      '\tglobal_load_dword v1, v0, s[0:1]', '\t%s v3, v3, v1' % op, '\ts_cbranch_scc1 .LBB%d_1' % idx, '\ts_endpgm',
+                      '.Lfunc_end%d:' % idx, '\t.amdhsa_kernel %s' % name, '\t\t.amdhsa_next_free_vgpr %d' % vgpr, '\t\t.amdhsa_next_free_sgpr 16',
+                      '\t\t.amdhsa_private_segment_fixed_size 0', '\t.end_amdhsa_kernel', ''])
+
+  old, new = tmp_path / 'old', tmp_path / 'new'
+  old.mkdir()
+  new.mkdir()
+  (old / 'all.s').write_text(listing('_Z1aPf', 0) + listing('_Z1bPf', 1))
+  (new / 'a.s').write_text(listing('_Z1aPf', 0, note='new'))
+  (new / 'b.s').write_text(listing('_Z1bPf', 0, note='new'))  # the second kernel of the old file is the first of its new one
+  assert mod.main([str(old), str(new)]) == 0
+  out = capsys.readouterr().out
+  assert 'SAME _Z1aPf  lines 6/6  vgpr 12/12 sgpr 16/16 scratch 0/0' in out and 'SAME _Z1bPf' in out and 'DIFF' not in out
+  (new / 'b.s').write_text(listing('_Z1bPf', 0, op='v_mul_f32_e32'))
+  assert mod.main([str(old), str(new)]) == 1
+  out = capsys.readouterr().out
+  assert 'SAME _Z1aPf' in out and 'DIFF _Z1bPf' in out and 'v_add_f32_e32 -1, v_mul_f32_e32 +1' in out
+  assert mod.main([str(old), str(new), '--allow-diff']) == 0
+  assert mod.main([str(old), str(new), '_Z1a']) == 0  # only the kernels asked for
+  capsys.readouterr()
+  (new / 'b.s').write_text(listing('_Z1bPf', 0, vgpr=13))
+  assert mod.main([str(old / 'all.s'), str(new)]) == 1
+  assert 'DIFF _Z1bPf  lines 6/6  vgpr 12/13' in capsys.readouterr().out
+  (new / 'b.s').write_text(listing('_Z1cPf', 0))
+  assert mod.main([str(old), str(new)]) == 1
+  out = capsys.readouterr().out
+  assert 'ONLY old  _Z1bPf' in out and 'ONLY new  _Z1cPf' in out

@@ -1,0 +1,43 @@
+"""Host: the table of tests/test_gpu_sphere_win_bits.py reaches every class of windowed kernel, so that no case of it passes vacuously.
+
+The planners run on the host (csrc/sphere_plan.hip), so this needs no GPU: the forward / weight-gradient plan of the table has compact,
+mid and wrap tiles and polar items, its adjoint plan has good tiles of the six-source class, and every input-gradient case has
+channel counts the windowed kernel takes.  The small table of the two extra input-gradient cases is all good adjoint tiles."""
+import make_golden_sphere_win_bits as G
+from mode_hip import functional as HF
+from oracle import mode_ref
+
+
+def test_the_table_has_every_tile_class():
+  pos = mode_ref.sphere_position(*G.TABLE, 'Cassini').contiguous()
+  plan = HF.sphere_plan(pos, 3, 3)
+  assert plan is not None and HF._plan_usable(plan)
+  n_small, n_mid, n_wrap = plan[1]
+  assert n_small > 0 and n_mid > 0 and n_wrap > 0, plan[1]
+  assert plan[6] is not None and plan[6][3] > 0  # polar items
+  aplan = HF.sphere_adjplan(pos, 3, 3)
+  assert aplan is not None and aplan[1] > 0
+  six = (aplan[0].view(-1, 4)[:, 3] >> 16) & 1
+  assert 0 < int(six.sum()) < aplan[1]  # both the four- and the six-source class
+  assert aplan[5] > 0  # and tiles left to the gather kernel's list form
+
+
+def test_the_small_table_is_all_windowed_input_gradient():
+  pos = mode_ref.sphere_position(*G.SMALL_TABLE, 'Cassini').contiguous()
+  assert tuple(pos.shape[2:]) == (64, 32)
+  aplan = HF.sphere_adjplan(pos, 3, 3)
+  assert aplan is not None and aplan[1] == 8 and aplan[4] is None and aplan[5] == 0  # every tile good: nothing for the gather kernel
+  six = (aplan[0].view(-1, 4)[:, 3] >> 16) & 1
+  assert 0 < int(six.sum()) < aplan[1]
+  assert not HF._plan_usable(HF.sphere_plan(pos, 3, 3))  # no compact tile: the model keeps it off the other two windowed passes
+
+
+def test_every_case_reaches_its_kernel():
+  for case in G.FWD + G.EVAL + G.BWD_WEIGHT:
+    assert tuple(case[:2]) == G.TABLE
+  for case in G.FWD + G.EVAL + G.BWD_DATA + G.BWD_WEIGHT:
+    assert case[2] <= 2 and max(case[3], case[4]) <= 64
+  for case in G.BWD_DATA:
+    assert tuple(case[:2]) in (G.TABLE, G.SMALL_TABLE)
+    assert HF.lib().mode_sphere_conv_bwd_data_win_supported(case[3], case[4], case[5]) == 1
+  assert {tuple(case[:2]) for case in G.BWD_DATA} == {G.TABLE, G.SMALL_TABLE}
