@@ -968,6 +968,48 @@ size_t mode_images_u8_augment_workspace_bytes(int N, int H, int W);
 int mode_images_u8_augment(const uint8_t* images_u8, const int32_t* ops, const float* coef, const int32_t* dst, int ndst, int N, int H,
                            int W, int slots, float* out, float* means, void* workspace, size_t workspace_bytes, mode_stream_t stream);
 
+/* Stereo pairs at any working size (csrc/resize.hip): what the reference's Deep360DatasetDisparity does on the host when a
+ * pair is stored at another width than the working one (dataloader/deep360_loader.py:92-106), on the decoded data.
+ *
+ * mode_images_u8_resize_pil: N images (N, Hs, Ws, 3) bytes, each as np.asarray(PIL RGB image) lays it out (no alignment asked for:
+ *   bytes are read one at a time), resized to (H, W) exactly as Pillow's Image.resize((W, H)) resizes an RGB image -- Resample.c,
+ *   the default bicubic filter (a = -0.5), 8 bits per channel: the horizontal pass, its result stored in 8 bits, the vertical pass; per
+ *   pass clip((2^21 + sum_j px_j kk_j) >> 22, 0, 255) in 32-bit integers; a pass whose size does not change is skipped (with both
+ *   skipped the entry copies).
+ *   MODE_RESIZE_MAX_SCALE: along either axis the sizes may differ by a factor of 4 at most, in either direction (Hs <= 4 H, H <= 4 Hs,
+ *   likewise the widths; any ratio inside that, different ones per axis).  Anything beyond returns MODE_ERR_UNSUPPORTED before a
+ *   pointer is looked at.
+ *   tab_w (W, 2 + ksize_w), tab_h (H, 2 + ksize_h) int32, device: per output index the first source index, the number of taps
+ *     (<= ksize) and ksize fixed-point coefficients kk = int(k 2^22 +/- 0.5), built on the host in double
+ *     (dataloader.preprocess.pil_resize_table); 1 <= ksize <= 17.  The table of a skipped pass is not read and may be NULL.
+ *   lut: the (256, 3) table of the other ingest entries; needed with `out`.
+ *   windows (ceil(N / per_window), 2) int32, device, or NULL: (top, left) of the (h_win, w_win) window of the resized (H, W) image that
+ *     is computed and stored for images n with n / per_window = the row (per_window = 2: both images of a pair share a window).
+ *     NULL: (0, 0) for every image; the whole image is h_win = H, w_win = W.  A window is moved inside the image where the table would
+ *     put it outside.  Nothing outside the window is computed, and the full resized image is not stored anywhere.
+ *   out_u8 (N, h_win, w_win, 3) bytes and / or out (N, 3, h_win, w_win) fp32 = the table lookup of those bytes; either may be NULL, not
+ *     both.  split = 1 (N a multiple of per_window): image n goes to slot (n % per_window) * (N / per_window) + n / per_window of
+ *     both outputs -- the left images of N / 2 pairs first, then the right ones; split = 0: slot n.
+ *   workspace: device, mode_images_u8_resize_pil_workspace_bytes(...) bytes -- the 8-bit result of the horizontal pass,
+ *     (N, Hs, w_win, 3), of which only the rows the window's vertical taps reach are written and read; 0 bytes (workspace may be NULL)
+ *     when at most one pass runs.  It needs no initialisation.
+ *   One launch per pass that runs; a thread per output pixel of the pass and a plain loop over the taps.
+ * mode_disp_resize_nearest: out[n, y, x] = disp[n, rows[top + y], cols[left + x]] * ratio for N fp32 maps (N, Hs, Ws) -> (N, h_win, w_win):
+ *   cv2.resize(..., (W, H), INTER_NEAREST) * (W / Ws) and the same window.  rows (H,), cols (W,) int32, device: the source index
+ *   min(floor(i * (src / dst)), src - 1) formed in double on the host (clamped to the map here); ratio: one fp32 multiply, NaN stays
+ *   NaN.  windows (N, 2) or NULL as above with one row per map.  Any sizes.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, misaligned tables, non-positive sizes, N < 0, a window
+ * that does not fit into (H, W), ksize outside 1 .. 17, per_window < 1 and element counts (3 N Hs max(Ws, W), 3 N H W; N Hs Ws, N H W
+ * for the maps) >= 2^31; MODE_ERR_WORKSPACE for a missing or small workspace.  N = 0 is a no-op. */
+#define MODE_RESIZE_MAX_SCALE 4
+size_t mode_images_u8_resize_pil_workspace_bytes(int N, int Hs, int Ws, int H, int W, int h_win, int w_win);
+int mode_images_u8_resize_pil(const uint8_t* images_u8, const int32_t* tab_w, int ksize_w, const int32_t* tab_h, int ksize_h,
+                              const float* lut, const int32_t* windows, int per_window, int split, int N, int Hs, int Ws, int H, int W,
+                              int h_win, int w_win, uint8_t* out_u8, float* out, void* workspace, size_t workspace_bytes,
+                              mode_stream_t stream);
+int mode_disp_resize_nearest(const float* disp, const int32_t* rows, const int32_t* cols, const int32_t* windows, int N, int Hs, int Ws,
+                             int H, int W, int h_win, int w_win, float ratio, float* out, mode_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * 3D60 ingest (csrc/erp_ingest.hip): what the reference's Dataset3D60Disparity.__getitem__ (dataloader/dataset3D60Loader.py:123-248)
  * does on the host per sample between the decoded equirectangular (ERP) files and ModeDisparity, for a batch of N pairs.

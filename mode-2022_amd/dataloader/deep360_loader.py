@@ -60,13 +60,24 @@ class Deep360DatasetDisparity(Dataset):
 
   Pairs stored at another width than `shape` are resized (images with PIL, the disparity map by nearest neighbour and multiplied
   by the width ratio, deep360_loader.py:96-99).  crop=True cuts the same random 512 x 256 window out of all three; the
-  reference's own crop branch (:101-108) uses names it never defined and raises."""
+  reference's own crop branch (:101-108) uses names it never defined and raises.
 
-  def __init__(self, leftImgs, rightImgs, disps, shape=(1024, 512), crop=False, disploader=disparity_loader, rgbloader=default_loader):
+  device_ingest=True returns what the GPU path starts from instead: {'pair_u8': (2, Hs, Ws, 3) uint8 -- the left and the right
+  panorama as they decode, at their stored size --, 'disp': (Hs, Ws) float32, 'dispNames': path}; the training loop makes one call per
+  batch, dataloader.gpu_ingest.pairs_u8_gpu(batch['pair_u8'].cuda(), batch['disp'].cuda(), shape=shape).  A random window per item is
+  drawn by the loop there (gpu_ingest.draw_crop_windows and pairs_u8_gpu's crop= / windows=), so crop=True is refused with it."""
+
+  def __init__(self, leftImgs, rightImgs, disps, shape=(1024, 512), crop=False, disploader=disparity_loader, rgbloader=default_loader,
+               device_ingest=False):
     super(Deep360DatasetDisparity, self).__init__()
+    if device_ingest and crop:
+      raise ValueError('Deep360DatasetDisparity: crop=True draws its window on the host path; with device_ingest=True draw the windows '
+                       'of a batch with dataloader.gpu_ingest.draw_crop_windows and pass them to pairs_u8_gpu(crop=(%d, %d), windows=...)'
+                       % (CROP_H, CROP_W))
     self.leftImgs, self.rightImgs, self.disps = leftImgs, rightImgs, disps
     self.height, self.width = shape
     self.crop = crop
+    self.device_ingest = device_ingest
     self.disp_loader, self.rgb_loader = disploader, rgbloader
     self.processed = preprocess.get_transform_stage1(augment=False)
 
@@ -91,6 +102,10 @@ class Deep360DatasetDisparity(Dataset):
   def __getitem__(self, index):
     name = self.disps[index]
     views = [self.rgb_loader(self.leftImgs[index]), self.rgb_loader(self.rightImgs[index])]
+    if self.device_ingest:
+      pair = torch.from_numpy(np.stack([np.asarray(v, dtype=np.uint8) for v in views]))
+      disp = torch.from_numpy(np.ascontiguousarray(self.disp_loader(name), dtype=np.float32))
+      return {'pair_u8': pair, 'disp': disp, 'dispNames': name}
     views, disp = self._fit(views, self.disp_loader(name))
     if self.crop:
       views, disp = self._window(views, disp)

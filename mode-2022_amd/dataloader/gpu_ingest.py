@@ -14,9 +14,15 @@
                   draws made on the host (draw_colour_params -> ColourParams) and everything per pixel on the device
                   (mode_images_u8_augment); frames_u8_gpu(augment=) and erp_pairs_gpu(augment=) run their images through it
 
+  pairs_u8_gpu    Deep360DatasetDisparity(shape=...) for a batch of decoded pairs stored at another size (reference
+                  dataloader/deep360_loader.py:92-109): PIL.Image.resize of both panoramas between any two sizes, the nearest-neighbour
+                  resize of the disparity times the width ratio, the training crop (draw_crop_windows), the transform or the colour
+                  augmentation (mode_images_u8_resize_pil, mode_disp_resize_nearest); resize_u8_gpu is its 8-bit resize alone
+
 The first two are bit for bit what the host computes, and so are the images of the third (its disparities differ from numpy's by the
-last bits of asin): the normalisation is a lookup in the table the host transform produces for the 256 byte
-values (preprocess.norm_table), the resize Pillow's own fixed-point arithmetic on the coefficients of preprocess.pil_half_table.
+last bits of asin) and everything pairs_u8_gpu returns: the normalisation is a lookup in the table the host transform produces
+for the 256 byte values (preprocess.norm_table), the resize Pillow's own fixed-point arithmetic on the coefficients of
+preprocess.pil_half_table / pil_resize_table.
 Tables are built and uploaded once per device / per (H, W, device) and cached, so the calls can be captured into a graph after a
 first eager call.  Importing this module does not load the native library; there is no CPU path."""
 import threading
@@ -27,11 +33,13 @@ import torch
 from mode_hip import functional as _HF
 
 from . import preprocess
+from .deep360_loader import CROP_H, CROP_W
 
 _lut_cache = _HF._LRU(8)    # device -> (256, 3) float32 normalisation table (graph-pinned while captured)
 _half_cache = _HF._LRU(8)   # (H, W, device) -> (tab_w (W/2, 10), tab_h (H/2, 10)) int32 tables of mode_rgb_half_pil
 _erp_cache = _HF._LRU(16)   # (pair, H, W, device) -> grid (1, H, W, 2); ('cols', W, device) -> cols (3, W): the 3D60 ingest's tables
 _dst_cache = _HF._LRU(8)    # (F, want_rgb, device) -> (12 F, 2) int32: the slots of every panorama of F frames in cat(left, right, rgb)
+_resize_cache = _HF._LRU(16)  # ('pil' | 'nearest', n, out, device) -> one axis' table of mode_images_u8_resize_pil / mode_disp_resize_nearest
 _lock = threading.Lock()
 
 
@@ -224,6 +232,152 @@ def rgb_half_gpu(frames_u8, return_u8=False):
   H, W = frames_u8.shape[2:4]
   tab_w, tab_h = _half_tables(H, W, frames_u8.device)
   return _HF.rgb_half_pil(frames_u8, tab_w, tab_h, _norm_lut(frames_u8.device), return_u8)
+
+
+# ------------------------------------------------------------------------------------ any working size
+def resize_table_rows(n, out):
+  """pil_resize_table(n, out) packed as the kernel reads it: (out, 2 + ksize) int32 rows [xmin, count, kk[0 .. ksize - 1]]."""
+  xmin, count, kk = preprocess.pil_resize_table(n, out)
+  return torch.from_numpy(np.ascontiguousarray(np.concatenate([xmin[:, None], count[:, None], kk], axis=1), dtype=np.int32))
+
+
+def _axis_table(kind, n, out, device):
+  """The device table of one axis, cached per (n, out, device): kind 'pil' -> resize_table_rows, 'nearest' -> nearest_index_table."""
+  key = (kind, n, out, str(device))
+  with _lock:
+    hit = _resize_cache.get(key)
+    if hit is None:
+      hit = (resize_table_rows(n, out) if kind == 'pil' else torch.from_numpy(preprocess.nearest_index_table(n, out))).to(device)
+      _resize_cache[key] = hit
+    return hit
+
+
+def _pil_tables(Hs, Ws, H, W, device):
+  """(tab_w, tab_h) of mode_images_u8_resize_pil; None for an axis whose size does not change (Pillow skips that pass)."""
+  if max(Hs, H) > _HF.RESIZE_MAX_SCALE * min(Hs, H) or max(Ws, W) > _HF.RESIZE_MAX_SCALE * min(Ws, W):
+    raise ValueError('resize: %d x %d -> %d x %d is beyond a factor of %d along an axis' % (Hs, Ws, H, W, _HF.RESIZE_MAX_SCALE))
+  return (None if Ws == W else _axis_table('pil', Ws, W, device)), (None if Hs == H else _axis_table('pil', Hs, H, device))
+
+
+def _device_windows(windows, n, shape, crop, device, who):
+  """windows (n, 2) (top, left), on the host (checked against the image, then uploaded: not inside a capture) or already on the device
+  (trusted: the kernels move a window inside the image) -> contiguous int32 on the device."""
+  if crop is None:
+    raise ValueError('%s: windows need crop=(h, w)' % who)
+  w = torch.as_tensor(windows)
+  if w.dim() != 2 or tuple(w.shape) != (n, 2) or w.dtype not in (torch.int32, torch.int64):
+    raise ValueError('%s: windows must be an integer (%d, 2) tensor of (top, left), got %s %s' % (who, n, w.dtype, tuple(w.shape)))
+  if not w.is_cuda:
+    if n and (int(w.min()) < 0 or int(w[:, 0].max()) > shape[0] - crop[0] or int(w[:, 1].max()) > shape[1] - crop[1]):
+      raise ValueError('%s: a %d x %d window lies outside the %d x %d image' % (who, crop[0], crop[1], shape[0], shape[1]))
+    w = w.to(torch.int32).to(device)
+  return w.to(torch.int32).contiguous()
+
+
+def draw_crop_windows(n, shape, crop=(CROP_H, CROP_W), generator=None):
+  """(n, 2) int32 (top, left) on the host: n training windows of crop = (h, w) -- default the disparity loader's 512 x 256 -- inside a
+  shape = (H, W) image, each coordinate uniform over its valid range [0, H - h] / [0, W - w] as the host loader's random.randint is
+  (Deep360DatasetDisparity._window).  Per window the top is drawn first, then the left; with `generator` the draws come from it,
+  otherwise from torch's global generator."""
+  h, w = crop
+  H, W = shape
+  if n < 0 or not (0 < h <= H and 0 < w <= W):
+    raise ValueError('draw_crop_windows: n = %r, a %r x %r window in a %r x %r image' % (n, h, w, H, W))
+  u = torch.rand((n, 2), generator=generator, dtype=torch.float64)
+  span = torch.tensor([H - h + 1, W - w + 1], dtype=torch.float64)
+  return torch.minimum((u * span).floor(), span - 1).to(torch.int32)
+
+
+def resize_u8_gpu(images_u8, shape, windows=None, crop=None, out=None):
+  """(..., Hs, Ws, 3) uint8 device images -> (..., h, w, 3) uint8: every image resized to shape = (H, W) as PIL.Image.resize((W, H))
+  resizes it (bicubic, 8 bits per channel, bit for bit; up to a factor of 4 along an axis, either way), on mode_images_u8_resize_pil.
+  windows: (n, 2) (top, left) for the n = prod(...) images with crop = (h, w): only that window of every resized image is computed.
+  out: a uint8 tensor of the result's shape to write into.  Equal sizes and no window return the input itself.
+  Frames stored at another size than the networks' reach ModeMultiView / frames_u8_gpu this way: resize the (F, 12, Hs, Ws, 3) frames first."""
+  if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() < 3 or images_u8.shape[-1] != 3:
+    raise ValueError('resize_u8_gpu: images must be a (..., H, W, 3) uint8 tensor')
+  _HF.require_gpu(images_u8)
+  lead, (Hs, Ws) = tuple(images_u8.shape[:-3]), images_u8.shape[-3:-1]
+  H, W = shape
+  if (Hs, Ws) == (H, W) and windows is None and crop is None:
+    return images_u8 if out is None else out.copy_(images_u8)
+  flat = images_u8.contiguous().view(-1, Hs, Ws, 3)
+  tab_w, tab_h = _pil_tables(Hs, Ws, H, W, flat.device)
+  if windows is not None:
+    windows = _device_windows(windows, flat.shape[0], (H, W), crop, flat.device, 'resize_u8_gpu')
+  hw = (H, W) if crop is None else tuple(crop)
+  if out is not None:
+    if tuple(out.shape) != lead + hw + (3,) or not out.is_contiguous():
+      raise ValueError('resize_u8_gpu: out must be a contiguous %s tensor' % (lead + hw + (3,),))
+    out = out.view((-1,) + hw + (3,))
+  u8 = _HF.images_u8_resize_pil(flat, (H, W), tab_w, tab_h, windows=windows, crop=crop, out_u8=out)[0]
+  return u8.view(lead + hw + (3,))
+
+
+def _pair_slots(N, device):
+  """(2 N,) int32 on the device: image 2 n + s of N pairs -> slot s N + n (the left images first, then the right ones)."""
+  key = ('pairs', N, str(device))
+  with _lock:
+    hit = _dst_cache.get(key)
+    if hit is None:
+      i = np.arange(2 * N)
+      hit = torch.from_numpy(((i & 1) * N + (i >> 1)).astype(np.int32)).to(device)
+      _dst_cache[key] = hit
+    return hit
+
+
+def pairs_u8_gpu(pairs_u8, disp=None, shape=(1024, 512), crop=None, windows=None, augment=None):
+  """(N, 2, Hs, Ws, 3) uint8 device tensor -- the left and right panorama of N Deep360 pairs at their stored size, each as
+  np.asarray(PIL RGB image) lays it out -- and optionally their (N, Hs, Ws) float32 disparity maps -> the host loader's dict of device
+  tensors {'leftImg', 'rightImg': (N, 3, h, w) float32, 'dispMap': (N, 1, h, w)} ('dispMap' only with disp): what
+  Deep360DatasetDisparity(shape=shape) makes of the pair (reference dataloader/deep360_loader.py:92-109).  shape = (H, W).
+  As the loader's _fit, a pair is resized only when its stored WIDTH differs from W: both images as PIL.Image.resize((W, H)), the
+  disparity by nearest neighbour times float32(W / Ws).  With equal widths the heights must agree too (ValueError otherwise).
+  crop = (h, w) with windows (N, 2) (top, left; draw_crop_windows): the training crop -- the same window of the left image, the right
+  image and the disparity of a sample; only the window is computed.  Host windows are checked and uploaded; pass a device tensor
+  (refilled in place between replays) to capture the call into a graph.
+  augment: ColourParams for the 2 N images (row 2 n: left, row 2 n + 1: right): the resize writes 8-bit images and augment_u8_gpu's
+  kernels follow -- the reference's order: resize, crop, then the transform.  Without it the normalisation is a lookup in the resize's
+  store.  Bit for bit the host loader's images; two to five launches, no host synchronisation, and nothing is uploaded after the first
+  call per size (the tables are cached per (n, out, device))."""
+  who = 'pairs_u8_gpu'
+  if not torch.is_tensor(pairs_u8) or pairs_u8.dtype != torch.uint8 or pairs_u8.dim() != 5 or pairs_u8.shape[1] != 2 or pairs_u8.shape[4] != 3:
+    raise ValueError('%s: pairs must be a (N, 2, H, W, 3) uint8 tensor' % who)
+  _HF.require_gpu(pairs_u8, disp)
+  N, _, Hs, Ws, _ = pairs_u8.shape
+  H, W = shape
+  dev = pairs_u8.device
+  if Ws == W:
+    if Hs != H:
+      raise ValueError('%s: pairs stored at %d x %d have the working width but not the working height of %d x %d (the loader resizes '
+                       'only when the widths differ)' % (who, Hs, Ws, H, W))
+  if disp is not None and (not torch.is_tensor(disp) or tuple(disp.shape) != (N, Hs, Ws) or disp.dtype != torch.float32):
+    raise ValueError('%s: disp must be a (%d, %d, %d) float32 tensor' % (who, N, Hs, Ws))
+  if (crop is None) != (windows is None):
+    raise ValueError('%s: crop=(h, w) and windows (draw_crop_windows) are given together' % who)
+  if windows is not None:
+    windows = _device_windows(windows, N, (H, W), crop, dev, who)
+  hw = (H, W) if crop is None else (int(crop[0]), int(crop[1]))
+  tab_w, tab_h = _pil_tables(Hs, Ws, H, W, dev)
+  flat = pairs_u8.contiguous().view(2 * N, Hs, Ws, 3)
+  if augment is None:
+    both = _HF.images_u8_resize_pil(flat, (H, W), tab_w, tab_h, lut=_norm_lut(dev), windows=windows, per_window=2, crop=crop, split=True,
+                                    want_u8=False, want_f32=True)[1]
+  else:
+    _require_params(augment, 2 * N, dev, who)
+    u8 = flat if (Ws == W and crop is None) else _HF.images_u8_resize_pil(flat, (H, W), tab_w, tab_h, windows=windows, per_window=2, crop=crop)[0]
+    both = torch.empty((2 * N,) + (3,) + hw, dtype=torch.float32, device=dev)
+    if N:
+      _HF.images_u8_augment(u8, augment.ops, augment.coef, dst=_pair_slots(N, dev), out=both)
+  out = {'leftImg': both[:N], 'rightImg': both[N:]}
+  if disp is not None:
+    if Ws == W and crop is None:
+      out['dispMap'] = disp.unsqueeze(1)
+    else:
+      rows, cols = _axis_table('nearest', Hs, H, dev), _axis_table('nearest', Ws, W, dev)
+      ratio = 1.0 if Ws == W else W / Ws
+      out['dispMap'] = _HF.disp_resize_nearest(disp.contiguous(), (H, W), rows, cols, ratio, windows=windows, crop=crop).unsqueeze(1)
+  return out
 
 
 def _erp_tables(pairs, H, W, device):

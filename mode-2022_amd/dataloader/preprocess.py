@@ -98,3 +98,44 @@ def pil_half_table(n):
     xmin[i], count[i] = lo, hi - lo
     kk[i, :hi - lo] = [int(-0.5 + v * (1 << PIL_PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PIL_PRECISION_BITS)) for v in k]
   return xmin, count, kk
+
+
+def pil_resize_table(n, out):
+  """The coefficients of one pass of PIL.Image.resize from n to out along an axis, for any pair of sizes (the disparity loader's resize
+  to the working size, reference dataloader/deep360_loader.py:92-97), as Pillow's Resample.c builds them for 8-bit images
+  (precompute_coeffs with the default bicubic filter, then normalize_coeffs_8bpc):
+  -> (xmin (out,) int32, count (out,) int32, kk (out, ksize) int32), ksize = 2 ceil(2 max(n / out, 1)) + 1.
+  Output i is clip((2^21 + sum_{j < count[i]} px[xmin[i] + j] * kk[i, j]) >> 22, 0, 255).  pil_half_table's arithmetic in its order,
+  with Pillow's general scale: the filter argument is multiplied by 1 / max(n / out, 1), the sum and the normalisation are in double,
+  the fixed point is rounded away from zero; entries past count are zero.  pil_resize_table(n, n // 2) is pil_half_table(n) with a ninth,
+  zero column.  Pillow runs the horizontal pass first, stores it in 8 bits, and skips a pass whose size does not change."""
+  if n < 1 or out < 1:
+    raise ValueError('pil_resize_table: sizes must be positive, got %r -> %r' % (n, out))
+  scale = n / out
+  filterscale = max(scale, 1.0)
+  support = 2.0 * filterscale
+  ksize = 2 * int(np.ceil(support)) + 1
+  ss = 1.0 / filterscale
+  xmin = np.zeros(out, dtype=np.int32)
+  count = np.zeros(out, dtype=np.int32)
+  kk = np.zeros((out, ksize), dtype=np.int32)
+  for i in range(out):
+    center = (i + 0.5) * scale
+    lo = max(0, int(center - support + 0.5))
+    hi = min(n, int(center + support + 0.5))
+    k = [_pil_bicubic((j + lo - center + 0.5) * ss) for j in range(hi - lo)]
+    ww = 0.0
+    for v in k:
+      ww += v
+    k = [v / ww for v in k] if ww != 0.0 else k
+    xmin[i], count[i] = lo, hi - lo
+    kk[i, :hi - lo] = [int(-0.5 + v * (1 << PIL_PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PIL_PRECISION_BITS)) for v in k]
+  return xmin, count, kk
+
+
+def nearest_index_table(src, dst):
+  """(dst,) int32: the source index that cv2.resize(..., INTER_NEAREST) copies into destination index i along an axis,
+  min(floor(i * (src / dst)), src - 1) in double -- deep360_loader.resize_nearest's indices."""
+  if src < 1 or dst < 1:
+    raise ValueError('nearest_index_table: sizes must be positive, got %r -> %r' % (src, dst))
+  return np.minimum(np.floor(np.arange(dst) * (src / dst)).astype(np.int64), src - 1).astype(np.int32)

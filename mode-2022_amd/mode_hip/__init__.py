@@ -188,6 +188,11 @@ SIGNATURES = {
     # colour augmentation on the 8-bit ingest (csrc/augment.hip; reference dataloader/preprocess.py:33-46, 78-95)
     'mode_images_u8_augment_workspace_bytes': (_c_size, [_c_int] * 3),
     'mode_images_u8_augment': (_c_int, [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr] * 3 + [_c_size, _c_ptr]),
+    # stereo pairs at any working size (csrc/resize.hip; reference dataloader/deep360_loader.py:92-106)
+    'mode_images_u8_resize_pil_workspace_bytes': (_c_size, [_c_int] * 7),
+    'mode_images_u8_resize_pil': (_c_int, [_c_ptr, _c_ptr, _c_int, _c_ptr, _c_int, _c_ptr, _c_ptr] + [_c_int] * 9 + [_c_ptr] * 3 +
+                                  [_c_size, _c_ptr]),
+    'mode_disp_resize_nearest': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [ctypes.c_float] + [_c_ptr] * 2),
     # 3D60 ingest: ERP pairs and depth to rectified Cassini (csrc/erp_ingest.hip; reference dataloader/dataset3D60Loader.py:123-270)
     'mode_erp_pairs_u8_cassini': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr] * 6),
     'mode_erp_depth_disp': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 3),

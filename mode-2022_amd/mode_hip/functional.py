@@ -2099,6 +2099,107 @@ def rgb_half_pil(frames_u8, tab_w, tab_h, lut, return_u8=False):
   return (out, u8) if return_u8 else out
 
 
+RESIZE_MAX_SCALE = 4  # MODE_RESIZE_MAX_SCALE of include/mode_hip.h
+RESIZE_MAX_TAPS = 17
+
+
+def _require_windows(windows, rows, crop, shape, dev, who):
+  """-> (h_win, w_win) for a window table (rows, 2) int32 on `dev` (or None: the whole image, or the crop at the top left corner)."""
+  H, W = shape
+  h_win, w_win = (H, W) if crop is None else (int(crop[0]), int(crop[1]))
+  if not (0 < h_win <= H and 0 < w_win <= W):
+    raise ValueError('%s: a window of %d x %d does not lie inside the %d x %d image' % (who, h_win, w_win, H, W))
+  if windows is not None:
+    if (not torch.is_tensor(windows) or windows.dtype != torch.int32 or tuple(windows.shape) != (rows, 2) or not windows.is_contiguous() or
+        windows.device != dev):
+      raise ValueError('%s: windows must be a contiguous int32 (%d, 2) tensor of (top, left) on %s, got %s %s' %
+                       (who, rows, dev, getattr(windows, 'dtype', type(windows)), tuple(getattr(windows, 'shape', ()))))
+  return h_win, w_win
+
+
+def images_u8_resize_pil(images_u8, shape, tab_w, tab_h, lut=None, windows=None, per_window=1, crop=None, split=False, want_u8=True,
+                         want_f32=False, out_u8=None):
+  """(N, Hs, Ws, 3) uint8 images resized to shape = (H, W) as PIL.Image.resize((W, H)) resizes them, on mode_images_u8_resize_pil
+  (the contract is in include/mode_hip.h) -> (u8 (N, h, w, 3) or None, f32 (N, 3, h, w) or None): the bytes and / or their lookup in
+  lut, the (256, 3) normalisation table.  tab_w (W, 2 + ksize), tab_h (H, 2 + ksize): int32 device tables of
+  dataloader.gpu_ingest.resize_table_rows (None for an axis whose size does not change).  windows (ceil(N / per_window), 2) int32
+  device (top, left) with crop = (h, w): only that window of every resized image is computed and returned; crop alone: the window at
+  (0, 0).  split: the images of a group of per_window go to slots member * (N / per_window) + group (left images first, then right ones)."""
+  who = 'images_u8_resize_pil'
+  if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8:
+    raise TypeError('%s: images must be a uint8 tensor (got %s)' % (who, getattr(images_u8, 'dtype', type(images_u8))))
+  require_gpu(images_u8, tab_w, tab_h, lut, windows, out_u8)
+  if images_u8.dim() != 4 or images_u8.shape[3] != 3 or not images_u8.is_contiguous():
+    raise ValueError('%s: images must be contiguous (N, H, W, 3), got %s' % (who, tuple(images_u8.shape)))
+  N, Hs, Ws, _ = images_u8.shape
+  H, W = int(shape[0]), int(shape[1])
+  if min(Hs, Ws, H, W) <= 0:
+    raise ValueError('%s: %d x %d -> %d x %d' % (who, Hs, Ws, H, W))
+  dev = images_u8.device
+  per_window = int(per_window)
+  if per_window < 1 or (split and N % per_window):
+    raise ValueError('%s: %d images in groups of %d' % (who, N, per_window))
+  h_win, w_win = _require_windows(windows, -(-N // per_window), crop, (H, W), dev, who)
+  ksize = []
+  for t, n, out, name in ((tab_w, Ws, W, 'tab_w'), (tab_h, Hs, H, 'tab_h')):
+    if n == out:
+      ksize.append(0)
+      continue
+    if (not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != out or not 3 <= t.shape[1] <= 2 + RESIZE_MAX_TAPS or
+        not t.is_contiguous() or t.device != dev):
+      raise ValueError('%s: %s must be a contiguous int32 (%d, 2 + ksize) tensor on %s, got %s %s' %
+                       (who, name, out, dev, getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+    ksize.append(t.shape[1] - 2)
+  if not (want_u8 or want_f32 or out_u8 is not None):
+    raise ValueError('%s: no output asked for' % who)
+  if want_f32:
+    if lut is None:
+      raise ValueError('%s: the float output needs lut' % who)
+    require_f32c(lut)
+    if tuple(lut.shape) != (256, 3) or lut.device != dev:
+      raise ValueError('%s: lut %s must be (256, 3) on %s' % (who, tuple(lut.shape), dev))
+  if out_u8 is not None:
+    if out_u8.dtype != torch.uint8 or tuple(out_u8.shape) != (N, h_win, w_win, 3) or not out_u8.is_contiguous() or out_u8.device != dev:
+      raise ValueError('%s: out_u8 must be a contiguous uint8 %s tensor on %s' % (who, (N, h_win, w_win, 3), dev))
+    u8 = out_u8
+  else:
+    u8 = torch.empty((N, h_win, w_win, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+  f32 = torch.empty((N, 3, h_win, w_win), dtype=torch.float32, device=dev) if want_f32 else None
+  nws = lib().mode_images_u8_resize_pil_workspace_bytes(N, Hs, Ws, H, W, h_win, w_win)
+  ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+  nbytes = images_u8.numel() + 2 * nws + N * h_win * w_win * ((3 if u8 is not None else 0) + (12 if f32 is not None else 0))
+  opt = lambda t: None if t is None else ptr(t)
+  with torch.cuda.device_of(images_u8), profiling.region('images_u8_resize_pil', nbytes, 0, dev):
+    check(lib().mode_images_u8_resize_pil(ptr(images_u8), opt(tab_w) if ksize[0] else None, ksize[0], opt(tab_h) if ksize[1] else None,
+                                          ksize[1], opt(lut) if want_f32 else None, opt(windows), per_window, 1 if split else 0, N, Hs, Ws,
+                                          H, W, h_win, w_win, opt(u8), opt(f32), opt(ws), nws, stream_of(images_u8)),
+          'mode_images_u8_resize_pil')
+  return u8, f32
+
+
+def disp_resize_nearest(disp, shape, rows, cols, ratio, windows=None, crop=None):
+  """(N, Hs, Ws) float32 maps -> (N, h, w): disp[n, rows[top + y], cols[left + x]] * float32(ratio) on mode_disp_resize_nearest --
+  cv2.resize(..., (W, H), INTER_NEAREST) * ratio for shape = (H, W) and, with windows (N, 2) int32 (top, left) and crop = (h, w), that
+  window of it.  rows (H,), cols (W,): int32 device tables of dataloader.preprocess.nearest_index_table."""
+  who = 'disp_resize_nearest'
+  require_gpu(disp, rows, cols, windows)
+  require_f32c(disp)
+  if disp.dim() != 3 or 0 in disp.shape[1:]:
+    raise ValueError('%s: maps must be (N, H, W), got %s' % (who, tuple(disp.shape)))
+  N, Hs, Ws = disp.shape
+  H, W = int(shape[0]), int(shape[1])
+  dev = disp.device
+  for t, n, name in ((rows, H, 'rows'), (cols, W, 'cols')):
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != dev:
+      raise ValueError('%s: %s must be a contiguous int32 (%d,) tensor on %s' % (who, name, n, dev))
+  h_win, w_win = _require_windows(windows, N, crop, (H, W), dev, who)
+  out = torch.empty((N, h_win, w_win), dtype=torch.float32, device=dev)
+  with torch.cuda.device_of(disp), profiling.region('disp_resize_nearest', 8 * out.numel(), out.numel(), dev):
+    check(lib().mode_disp_resize_nearest(ptr(disp), ptr(rows), ptr(cols), None if windows is None else ptr(windows), N, Hs, Ws, H, W, h_win,
+                                         w_win, float(ratio), ptr(out), stream_of(disp)), 'mode_disp_resize_nearest')
+  return out
+
+
 def _decimate2_fwd(x):
   H, W = x.shape[-2:]
   y = torch.empty(tuple(x.shape[:-2]) + ((H + 1) // 2, (W + 1) // 2), dtype=x.dtype, device=x.device)
