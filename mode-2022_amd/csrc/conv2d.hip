@@ -3,7 +3,7 @@
 // the step's 4 images: 90-130 TFLOP/s here against 80-112 for the vendor library (Winograd / NHWC implicit GEMM between layout
 // transposes for the dilated layers); the host picks per layer (functional._conv2d_own).
 //
-// Same structure as conv3d.hip, one dimension down: implicit GEMM on v_mfma_f32_32x32x2_f32, D[i = o][j = 32 pixels along w];
+// Same structure as conv3d_f32_fwd.hip, one dimension down: implicit GEMM on v_mfma_f32_32x32x2_f32, D[i = o][j = 32 pixels along w];
 // haloed input tile [8 channels][TH + 2 dil][32 + 2 dil] in LDS, input channels streamed in chunks of 8 with the next chunk
 // travelling global -> registers under the MFMAs (half-wave = channel, item = tile row; unconditional loads from clamped
 // addresses, masks at the LDS store); weights pre-packed in fragment order and requested one tap ahead.  The input gradient is the

@@ -7,7 +7,7 @@
 //   D[i = o][j = c] per tap on v_mfma_f32_32x32x2_f32;  A[i = o][k = pixel] = gy tile, B[k = pixel][j = c] = x tile shifted by
 //   the tap, both in LDS with odd channel strides (conflict-free fragments).  A workgroup owns a 32 x 32 (o, c) block and a
 //   slice of the 4 x 32 pixel tiles; wave v takes row v of the tile (16 k-steps) for ALL nine taps (9 accumulators), so one A
-//   fragment feeds 9 MFMAs.  The next tile travels global -> registers under the MFMAs (same pipeline as conv3d.hip: loads
+//   fragment feeds 9 MFMAs.  The next tile travels global -> registers under the MFMAs (same pipeline as conv3d_f32_wgrad.hip: loads
 //   unconditional from clamped addresses, masks at the LDS store, operands of k-step n+1 read before the MFMAs of step n).
 //   The four waves' sums are combined through LDS at the end; split-K partials are reduced in a fixed order: deterministic.
 #include "common.h"

@@ -1,6 +1,6 @@
 // Single-output-channel 3x3x3 convolution: the last layer of classif1-3, Conv3d(32 -> 1) (models/mode_disparity.py:76-80).
 //
-// With one output channel the implicit-GEMM tile of conv3d.hip is 31/32 padding (1.47 ms forward, 1.71 ms weight gradient at
+// With one output channel the implicit-GEMM tile of conv3d_f32_fwd.hip is 31/32 padding (1.47 ms forward, 1.71 ms weight gradient at
 // the benchmark volume).  The layer is really a memory-bound stencil: 201 MB of input per sample for 6.3 MB of output.
 //   forward        : vector-ALU stencil; a thread owns 4 outputs along h so that one LDS read feeds up to 3 FMAs
 //   weight gradient: gW[c][tap] = sum_q x[c,q] * gy[q + 1 - k]  as an MFMA GEMM with  D[i = c][j = tap]  (27 of 32 columns

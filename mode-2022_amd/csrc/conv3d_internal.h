@@ -5,6 +5,53 @@
 
 namespace mode {
 
+// Host: one launch of a kernel with dynamic LDS -- the opt-in above 64 KiB, the launch, the launch check (launch_win of
+// sphere_win_internal.h with the block size as an argument).
+template <typename... P, typename... A>
+int launch_lds(const char* who, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  int rc = allow_lds(kernel, lds, who);
+  if (rc != MODE_OK) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return check_launch(who);
+}
+
+#pragma GCC visibility push(hidden)  // (what moved out of conv3d.hip's anonymous namespace stays out of the library's dynamic symbols)
+// conv3d_f32_fwd.hip: the 3x3x3 layers on the fp32 MFMA.  rows = output channels of THIS GEMM (Co for forward, Ci for backward-data),
+// K = its reduction channels; flip selects how `w` is indexed (pack_w3d: 0 forward, 1 backward-data); bn: the folded-BatchNorm
+// epilogue of an eval-mode layer.  wpack >= conv3d_f32_pack_floats(K, rows) + 32 * cdiv(rows, 32) floats (the folded shifts).
+size_t conv3d_f32_pack_floats(int K, int rows);
+int conv3d_s1(const float* x, const float* w, float* y, float* wpack, int B, int K, int rows, int D, int H, int W, int flip,
+              hipStream_t st, const char* who, const mode_bn_epilogue* bn = nullptr);
+// Stride-2 forward (also the backward-data of ConvTranspose3d k3 s2 p1 op1): output = ((X - 1) / 2 + 1).
+int conv3d_s2(const float* x, const float* w, float* y, float* wpack, int B, int K, int rows, int D, int H, int W, hipStream_t st,
+              const char* who, const mode_bn_epilogue* bn = nullptr);
+// x (B,K,D,H,W) -> y (B,rows,2D,2H,2W) with w indexed [k][row][tap]: ConvTranspose3d weights (Cin,Cout,27), and the backward-data of a
+// stride-2 Conv3d whose weight is (Co,Ci,27) with K = Co, rows = Ci.
+int deconv3d(const float* x, const float* w, float* y, float* wpack, int B, int K, int rows, int D, int H, int W, hipStream_t st,
+             const char* who, const mode_bn_epilogue* bn = nullptr);
+
+// conv3d_f32_wgrad.hip: the weight gradient as split-K partials part[s][o / 32][c / 32][tap][o % 32][c % 32] and their reduction.
+// The grid of x (B, Ci, D, H, W) against gy (B, Co, Do, Ho, Wo): tiles of 2 (stride 1) or 1 (stride 2) rows x 32 output voxels, 32 x 32
+// channel blocks, and S = the split-K slices the workspace is sized for -- a launcher may write fewer slices, never more.
+struct WgradGrid {
+  int Do, Ho, Wo, nWt, nHt, MTo, MTc, S;
+  size_t part_floats() const { return (size_t)S * MTo * MTc * 27 * 1024; }
+};
+WgradGrid conv3d_wgrad_grid(int B, int Ci, int D, int H, int W, int Co, int stride);
+// The fp32 kernel for this shape writes its partials; *S = the slices it wrote.
+int conv3d_f32_wgrad_partials(const float* gy, const float* x, float* part, int B, int Ci, int D, int H, int W, int Co, int stride,
+                              hipStream_t st, const char* who, int* S);
+// gw[o][c][tap] (+)= the sum of the S slices, in a fixed order.
+int conv3d_wgrad_reduce(const float* part, float* gw, int Ci, int Co, int S, int accumulate, hipStream_t st, const char* who);
+#pragma GCC visibility pop
+// Depths per work unit of a rolling-window weight-gradient kernel: a unit starts with un-pipelined stagings, so as deep as the volume
+// allows (halved while above `floor`) while each of the S workgroups still gets >= 2 of the columns * cdiv(depth, result) units.
+inline int ring_depths(int depth, long long columns, int S, int floor) {
+  int dc = depth;
+  while (dc > floor && columns * cdiv(depth, dc) < 2ll * S) dc = cdiv(dc, 2);
+  return dc;
+}
+
 // 3x3x3, pad 1, stride 1 convolution with a SINGLE output channel (the classifier heads, mode_disparity.py:76-80).
 // The MFMA tile would be 31/32 padding for Co = 1; these use the vector ALU (forward) and an MFMA formulation with the 27
 // taps as the GEMM-N dimension (weight gradient) or the GEMM-K dimension (input gradient).
@@ -22,7 +69,7 @@ int conv3d_co1_bwd_weight(const float* gy, const float* x, float* gw, float* wor
                           int accumulate, hipStream_t st, const char* who);
 
 // conv3d_split.hip: stride-1 3x3x3 convolution on the bf16 matrix pipe with three-way split fp32 operands (fp32 accuracy).  Same
-// argument meaning as conv3d_s1 in conv3d.hip (rows = output channels of the GEMM, K = its reduction channels, flip 0 forward /
+// argument meaning as conv3d_s1 above (rows = output channels of the GEMM, K = its reduction channels, flip 0 forward /
 // 1 backward-data); wpack >= conv3d_split_wpack_floats(K, rows) floats.
 bool conv3d_split_supported(int K, int rows);
 size_t conv3d_split_wpack_floats(int K, int rows);
@@ -60,7 +107,7 @@ int deconv3d_split(const float* x, const float* w, float* y, float* wpack, int B
 // acc_in (whole 32-channel output tiles, not with bn)
 
 // conv3d_split_wgrad.hip: split-K partials of the stride-1 weight gradient on the split-bf16 matrix path, written in the layout of
-// conv3d.hip's weight-gradient kernels (part[s][o / 32][c / 32][tap][o % 32][c % 32]); the caller reduces them.
+// conv3d_f32_wgrad.hip's kernels (part[s][o / 32][c / 32][tap][o % 32][c % 32]); the caller reduces them (conv3d_wgrad_reduce).
 struct WgradSplitDims {
   int Ci, Co, D, H, W;
   int nWt, nHt, nDc, ring_dc, units;  // units = B * nHt * nWt * nDc work units of ring_dc depths x 2 rows x 32 voxels

@@ -3,9 +3,9 @@
 // into two fp16 pieces and three v_mfma_f32_32x32x16_f16.  split_arith.h states both arithmetics, their error and their precision
 // contract, and defines their primitives; this comment is about the kernel.
 //
-// Reference: the same nn.Conv3d layers as conv3d.hip (models/submodule.py:20-22, models/mode_disparity.py:11-46, 66-80).
+// Reference: the same nn.Conv3d layers as conv3d_f32_fwd.hip (models/submodule.py:20-22, models/mode_disparity.py:11-46, 66-80).
 //
-// Layout.  D[i = o][j = 32 consecutive w] as in conv3d.hip, NCDHW kept.  GEMM-K of one MFMA = 16 = 8 input channels x 2 taps
+// Layout.  D[i = o][j = 32 consecutive w] as in conv3d_f32_fwd.hip, NCDHW kept.  GEMM-K of one MFMA = 16 = 8 input channels x 2 taps
 // (lanes 0..31 carry tap 2p, lanes 32..63 tap 2p+1 of tap pair p; 27 taps = 13 pairs + 1 half-empty pair), so an LDS chunk is 8
 // channels deep: [3 pieces][4 x 10 haloed rows x 34 w, padded to 1 536] of uint4 (= 8 channels of bf16), 73 728 B for a 2 x 8-row
 // output tile, double-buffered (147 KB: one workgroup of 4 waves per CU, one wave per SIMD, 256 VGPRs + 130 AGPRs).
@@ -77,7 +77,7 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t& p1, uint32_t&
 }
 
 // wp[(((m * NCHUNK + ch) * NPAIR + pair) * 3 + piece) * 64 + lane] = 8 bf16: piece of Wsrc(o = m*32 + (lane & 31), c = ch*8 + j,
-// tap = 2 * pair + (lane >> 5)), j = 0..7; zero for tap 27, o >= rows, c >= K.  flip / fold as pack_w3d (conv3d.hip): flip 0 forward
+// tap = 2 * pair + (lane >> 5)), j = 0..7; zero for tap 27, o >= rows, c >= K.  flip / fold as pack_w3d (conv3d_f32_fwd.hip): flip 0 forward
 // (w is (rows, K, 27)), flip 1 backward-data (w is (K, rows, 27), taps mirrored); fold: row o scaled by the folded BatchNorm scale
 // and the shifts written to the floats at wp + total.
 // F16: the values are multiplied by the weight tensor's power-of-two scale (amax_w[0] = its largest magnitude) before the split.

@@ -5,7 +5,7 @@
 //
 // Reference: the weight gradients cuDNN computes for the nn.Conv3d layers of convbn_3d (models/submodule.py:20-22).
 //
-// Same decomposition as conv3d_bwd_weight_ring_kernel (conv3d.hip): a workgroup owns a 32 x 32 (o, c) block and walks work units
+// Same decomposition as conv3d_bwd_weight_ring_kernel (conv3d_f32_wgrad.hip): a workgroup owns a 32 x 32 (o, c) block and walks work units
 // = (sample, 2-row x 32-voxel column, run of depths) with the x planes d-1, d, d+1 in an LDS ring; split-K partials go to the same
 // workspace layout and are reduced by the same fixed-order kernel.  What differs:
 //   * one MFMA (v_mfma_f32_32x32x16_bf16) reduces 16 voxels: lanes 0..31 carry 8 consecutive voxels of a row, lanes 32..63 the next

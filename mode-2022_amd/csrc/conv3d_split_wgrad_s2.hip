@@ -20,7 +20,7 @@
 // each, so every x value is loaded and split once per unit; gy has two buffers.  The 27 taps are dealt to the waves as whole
 // (kd, kh) groups (wave w: groups w and w + 4, the ninth group one tap each to waves 0..2), 14 accumulators of 16 registers per wave.
 // A phase = one output depth = 84 MFMAs per wave; the loads of phase q + 3 are issued at the head of phase q and split + stored during
-// phase q + 2 (three register sets), one LDS-only barrier per phase.  Split-K partials in the layout of conv3d.hip's weight-gradient
+// phase q + 2 (three register sets), one LDS-only barrier per phase.  Split-K partials in the layout of conv3d_f32_wgrad.hip's weight-gradient
 // kernels, reduced by its fixed-order kernel.
 #include "common.h"
 

@@ -1360,7 +1360,7 @@ def _wpack3d(ci, co, device):
 #            the rounding of an fp32 convolution -- measured against float64 they are at least as close as the fp32 MFMA kernels' on
 #            the same inputs (tests/test_gpu_split.py) -- at 1.5-2 x their speed.  Layers the split kernels do not cover (stride 2,
 #            transposed, single-channel heads, channel counts off their grid) run on the fp32 kernels.
-#   'f32'    v_mfma_f32_32x32x2_f32 everywhere (csrc/conv3d.hip, conv2d.hip).
+#   'f32'    v_mfma_f32_32x32x2_f32 everywhere (csrc/conv3d_f32_fwd.hip, conv3d_f32_wgrad.hip, conv2d.hip).
 # Process-wide, read at call time (bench.py --conv-arith; the parity tests run under both).
 CONV_ARITH = 'bf16x6'
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / LDS / scratch use of every kernel in one csrc/*.hip file (compile-only, no GPU needed).
-# usage: bash tools/kernel_resources.sh mode-2022_amd/csrc/conv3d.hip [filter-regex]
+# usage: bash tools/kernel_resources.sh mode-2022_amd/csrc/conv3d_f32_fwd.hip [filter-regex]
 R=$(cd "$(dirname "$0")/.." && pwd)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -I$R/include -I$R/mode-2022_amd/csrc \
   -Rpass-analysis=kernel-resource-usage -c "$1" -o /dev/null 2>&1 | python3 -c '

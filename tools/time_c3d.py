@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times the stride-1 3-D convolution kernels of the regulariser in isolation (benchmark shapes, B = 2), 20 launches each after
-warm-up, torch events on the current stream (HF launches on it): ms per launch.  For A/B runs of one kernel change on one box."""
+warm-up, torch events on the current stream (HF launches on it): ms per launch.  For A/B runs of one kernel change on one box.
+`--conv-arith f32` times the fp32 MFMA kernels instead of the default split arithmetic."""
 import os
 import sys
 
@@ -12,6 +13,8 @@ import torch  # noqa: E402
 from mode_hip import functional as HF  # noqa: E402
 
 dev = torch.device('cuda', 0)
+if '--conv-arith' in sys.argv:
+  HF.set_conv_arith(sys.argv[sys.argv.index('--conv-arith') + 1])
 
 
 def t_ms(fn, n=20):
