@@ -9,6 +9,12 @@ import torch
 from . import METRICS_COUNT, METRICS_MAX_THRESHOLDS, BnEpilogue, MetricsParams, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of
 
 
+def _call(entry, *args):
+  """Run the C entry `entry` and raise on its error code.  `check` and `lib` are this module's globals, looked up at call time: tests
+  replace either to see which entries run."""
+  check(getattr(lib(), entry)(*args), entry)
+
+
 def _stream_capturing():
   """True while the calling thread's current stream is being captured into a hipGraph."""
   return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
@@ -93,7 +99,7 @@ def cost_volume_fwd(ref, tgt, d4):
   cost = torch.empty((B, 2 * C, d4, H, W), dtype=ref.dtype, device=ref.device)
   nbytes = 4 * (2 * ref.numel() + cost.numel())
   with torch.cuda.device_of(ref), profiling.region('cost_volume_fwd', nbytes, 0, ref.device):
-    check(lib().mode_cost_volume_fwd(ptr(ref), ptr(tgt), ptr(cost), B, C, d4, H, W, stream_of(ref)), 'mode_cost_volume_fwd')
+    _call('mode_cost_volume_fwd', ptr(ref), ptr(tgt), ptr(cost), B, C, d4, H, W, stream_of(ref))
   return cost
 
 
@@ -106,8 +112,7 @@ def cost_volume_bwd(gcost, C):
   g_tgt = torch.empty_like(g_ref)
   nbytes = 4 * (gcost.numel() + 2 * g_ref.numel())
   with torch.cuda.device_of(gcost), profiling.region('cost_volume_bwd', nbytes, 0, gcost.device):
-    check(lib().mode_cost_volume_bwd(ptr(gcost), ptr(g_ref), ptr(g_tgt), B, C, D4, H, W, stream_of(gcost)),
-          'mode_cost_volume_bwd')
+    _call('mode_cost_volume_bwd', ptr(gcost), ptr(g_ref), ptr(g_tgt), B, C, D4, H, W, stream_of(gcost))
   return g_ref, g_tgt
 
 
@@ -130,6 +135,30 @@ def cost_volume(ref, tgt, d4):
 
 # ------------------------------------------------------------------------------------ sphere conv
 # ------------------------------------------------------------------------------------ regular 3x3 Conv2d: own weight gradient
+CONV2D_F16 = True  # forward and input gradient of the 3 x 3 layers of a TRAINING step on two fp16 pieces / three MFMAs per product
+
+
+def _conv2d_f16(f16):
+  return bool(f16) and CONV2D_F16 and CONV_ARITH == 'bf16x6'
+
+
+def _conv2d_route(ci, co, H, W, dilation, which, f16):
+  """The kernel family of the stride-1 3 x 3 layer ci -> co on H x W images -- which: 0 forward, 1 input gradient, 2 weight gradient:
+  'split' (three bf16 pieces) where CONV_ARITH says so and the split kernel is right at this size (mode_conv2d_split_shape_supported: the
+  channel grid and every 32-bit contract; the weight gradient takes any channel counts, an image beyond the offsets -- 2048 x 4096 at up
+  to 32 channels is the first -- does not fit), 'split_f16' (two fp16 pieces) when the caller also passes f16, else 'f32'.
+  f16 is the one argument in which the sites differ: a training call passes _conv2d_f16(its own flag) (CONV2D_F16), the inference
+  wrapper CONV2D_EVAL_F16."""
+  if not (CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(ci, co, H, W, dilation, which) == 1):
+    return 'f32'
+  return 'split_f16' if f16 else 'split'
+
+
+def _tag2d(name, ci, co, dilation, h, w):
+  """Profiling label of a 3 x 3 layer, e.g. conv2d_fwd[32->32 d1 256x128]."""
+  return '%s[%d->%d d%d %dx%d]' % (name, ci, co, dilation, h, w) if profiling.ENABLED else name
+
+
 def conv2d_bwd_weight(gy, x, dilation=1, into=None):
   """Weight gradient (Co, Ci, 3, 3) of a stride-1 3x3 convolution with padding = dilation (1 or 2): mode_conv2d_bwd_weight.
   `into`: add to this tensor (a gradient sink) instead of returning a new one."""
@@ -141,19 +170,14 @@ def conv2d_bwd_weight(gy, x, dilation=1, into=None):
   gw = into if into is not None else torch.empty((Co, Ci, 3, 3), dtype=x.dtype, device=x.device)
   flops = 2 * gy.numel() * Ci * 9
   nbytes = 4 * (gy.numel() + x.numel() + gw.numel())
-  with torch.cuda.device_of(x), profiling.region('conv2d_bwd_weight[%d->%d d%d %dx%d]' % (Ci, Co, dilation, H, W) if profiling.ENABLED
-                                                 else 'conv2d_bwd_weight', nbytes, flops, x.device):
+  with torch.cuda.device_of(x), profiling.region(_tag2d('conv2d_bwd_weight', Ci, Co, dilation, H, W), nbytes, flops, x.device):
     ws = torch.empty(max(lib().mode_conv2d_bwd_weight_workspace_bytes(B, Ci, H, W, Co) // 4, 1), dtype=torch.float32, device=x.device)
-    # (any channel counts: masked blocks; an image beyond the split kernel's 32-bit offsets -- 2048 x 4096 at up to 32 channels is the
-    # first -- runs on the fp32 kernel)
-    split = CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 2) == 1
-    entry = 'mode_conv2d_bwd_weight_split' if split else 'mode_conv2d_bwd_weight'
-    am = ()
-    if split and _conv2d_f16(True):  # (a weight gradient is a training step: the two-piece fp16 arithmetic)
-      entry, am = entry + '_f16', (ptr(_tagged_abs_max(gy)), ptr(_tagged_abs_max(x)))
-    check(getattr(lib(), entry)(ptr(gy), ptr(x), *am, ptr(gw), ptr(ws), B, Ci, H, W, Co, dilation, 1 if into is not None else 0, stream_of(x)),
-          entry)
+    route = _conv2d_route(Ci, Co, H, W, dilation, 2, _conv2d_f16(True))  # (a weight gradient is a training step)
+    entry = {'f32': 'mode_conv2d_bwd_weight', 'split': 'mode_conv2d_bwd_weight_split', 'split_f16': 'mode_conv2d_bwd_weight_split_f16'}[route]
+    am = (ptr(_tagged_abs_max(gy)), ptr(_tagged_abs_max(x))) if route == 'split_f16' else ()
+    _call(entry, ptr(gy), ptr(x), *am, ptr(gw), ptr(ws), B, Ci, H, W, Co, dilation, 1 if into is not None else 0, stream_of(x))
   return gw
+
 
 
 CONV2D_OWN_MAX_PIXELS = 1024 * 512  # own forward / input gradient up to this H*W
@@ -174,85 +198,67 @@ def _conv2d_own(x, w):
 
 def conv2d_wgrad_supported(x, w, dilation=1):
   """Whether conv2d_bwd_weight has a kernel that is right at this size: the split kernel inside its 32-bit contracts
-  (mode_conv2d_split_shape_supported, which 2), else the fp32 kernel, which addresses a sample with 32-bit lane offsets
+  (_conv2d_route, which 2), else the fp32 kernel, which addresses a sample with 32-bit lane offsets
   (csrc/conv2d_wgrad.hip: max(Ci, Co) * H * W < 2^29)."""
   co, ci, H, W = int(w.shape[0]), int(w.shape[1]), int(x.shape[2]), int(x.shape[3])
-  if CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(ci, co, H, W, dilation, 2) == 1:
-    return True
-  return max(co, ci) * H * W < 2**29
+  return _conv2d_route(ci, co, H, W, dilation, 2, False) != 'f32' or max(co, ci) * H * W < 2**29
 
 
-CONV2D_F16 = True  # forward and input gradient of the 3 x 3 layers of a TRAINING step on two fp16 pieces / three MFMAs per product (DESIGN 3v)
-
-
-def _conv2d_f16(f16):
-  return bool(f16) and CONV2D_F16 and CONV_ARITH == 'bf16x6'
-
-
-def _conv2d_run(entry, name, src, w, out_channels, dilation, f16=False, w_amax=None, amax_out=None):
+def _conv2d_run(which, src, w, dilation, f16=False, w_amax=None, amax_out=None):
+  """Forward (which 0: src = x) or input gradient (which 1: src = gy) of the 3 x 3 layer with weight w."""
+  name = 'conv2d_bwd_data' if which else 'conv2d_fwd'
   require_gpu(src, w)
   require_f32c(src, w)
   B, _, H, W = src.shape
   Co, Ci = w.shape[:2]
-  out = torch.empty((B, out_channels, H, W), dtype=src.dtype, device=src.device)
+  out = torch.empty((B, Ci if which else Co, H, W), dtype=src.dtype, device=src.device)
   flops = 2 * B * H * W * Ci * Co * 9
   nbytes = 4 * (src.numel() + out.numel() + w.numel())
-  with torch.cuda.device_of(src), profiling.region('%s[%d->%d d%d %dx%d]' % (name, Ci, Co, dilation, H, W) if profiling.ENABLED else name,
-                                                   nbytes, flops, src.device):
+  with torch.cuda.device_of(src), profiling.region(_tag2d(name, Ci, Co, dilation, H, W), nbytes, flops, src.device):
     wp = torch.empty(lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, dtype=torch.float32, device=src.device)
-    which = int(entry == 'mode_conv2d_bwd_data')
-    if CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, which) == 1:
-      if _conv2d_f16(f16):
-        aw = _weight_abs_max(w, w_amax)
-        if amax_out is not None:
-          amax_out.append(aw)
-        am = (ptr(_tagged_abs_max(src)), ptr(aw))
-        if which:
-          check(lib().mode_conv2d_bwd_data_split_f16(ptr(src), ptr(w), am[0], am[1], None, ptr(out), ptr(wp), B, Ci, H, W, Co, dilation,
-                                                     stream_of(src)), 'mode_conv2d_bwd_data_split_f16')
-        else:
-          check(lib().mode_conv2d_fwd_split_f16(ptr(src), ptr(w), am[0], am[1], ptr(out), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(src)),
-                'mode_conv2d_fwd_split_f16')
-      elif which:
-        check(lib().mode_conv2d_bwd_data_split(ptr(src), ptr(w), ptr(out), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(src)),
-              'mode_conv2d_bwd_data_split')
-      else:
-        check(lib().mode_conv2d_fwd_split(ptr(src), ptr(w), None, ptr(out), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(src)),
-              'mode_conv2d_fwd_split')
+    route = _conv2d_route(Ci, Co, H, W, dilation, which, _conv2d_f16(f16))
+    tail = (ptr(out), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(src))
+    if route == 'split_f16':
+      aw = _weight_abs_max(w, w_amax)
+      if amax_out is not None:
+        amax_out.append(aw)
+      am = (ptr(_tagged_abs_max(src)), ptr(aw))
+      _call('mode_conv2d_bwd_data_split_f16' if which else 'mode_conv2d_fwd_split_f16', ptr(src), ptr(w), *am, *((None,) if which else ()), *tail)
+    elif route == 'split' and not which:
+      _call('mode_conv2d_fwd_split', ptr(src), ptr(w), None, *tail)  # (None: no folded-BatchNorm epilogue)
     else:
-      check(getattr(lib(), entry)(ptr(src), ptr(w), ptr(out), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(src)), entry)
+      _call('mode_' + name + ('_split' if route == 'split' else ''), ptr(src), ptr(w), *tail)
   return out
 
 
 def conv2d_fwd(x, w, dilation=1, f16=False, amax_out=None):
   """f16: the caller is a training step (Conv2d3x3Function with gradients being recorded): the split kernel may use the fp16 arithmetic;
   amax_out: a list that receives the weight's maximum buffer when it did (for the layer's backward)."""
-  return _conv2d_run('mode_conv2d_fwd', 'conv2d_fwd', x, w, w.shape[0], dilation, f16, amax_out=amax_out)
+  return _conv2d_run(0, x, w, dilation, f16, amax_out=amax_out)
 
 
 def conv2d_bwd_data(gy, w, dilation=1, acc=None, f16=True, w_amax=None):
   """acc: a gradient of the same tensor that is already there; the sum is returned (added in the split kernel's store where it runs).
   (A backward pass is a training step: the fp16 arithmetic where CONV2D_F16 says so; w_amax: the weight's maximum from the forward.)"""
   if acc is None:
-    return _conv2d_run('mode_conv2d_bwd_data', 'conv2d_bwd_data', gy, w, w.shape[1], dilation, f16, w_amax=w_amax)
+    return _conv2d_run(1, gy, w, dilation, f16, w_amax=w_amax)
   require_gpu(gy, w, acc)
   acc = acc.contiguous()
   require_f32c(gy, w, acc)
   B, _, H, W = gy.shape
   Co, Ci = w.shape[:2]
-  if not (CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 1) == 1 and
-          tuple(acc.shape) == (B, Ci, H, W)):
-    return _conv2d_run('mode_conv2d_bwd_data', 'conv2d_bwd_data', gy, w, Ci, dilation, f16, w_amax=w_amax).add_(acc)
+  route = _conv2d_route(Ci, Co, H, W, dilation, 1, _conv2d_f16(f16))
+  if route == 'f32' or tuple(acc.shape) != (B, Ci, H, W):
+    return _conv2d_run(1, gy, w, dilation, f16, w_amax=w_amax).add_(acc)
   gx = torch.empty((B, Ci, H, W), dtype=gy.dtype, device=gy.device)
-  with torch.cuda.device_of(gy), profiling.region('conv2d_bwd_data[%d->%d d%d %dx%d]' % (Ci, Co, dilation, H, W) if profiling.ENABLED else 'conv2d_bwd_data',
+  with torch.cuda.device_of(gy), profiling.region(_tag2d('conv2d_bwd_data', Ci, Co, dilation, H, W),
                                                   4 * (gy.numel() + 2 * gx.numel() + w.numel()), 2 * B * H * W * Ci * Co * 9, gy.device):
     wp = torch.empty(lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, dtype=torch.float32, device=gy.device)
-    if _conv2d_f16(f16):
-      check(lib().mode_conv2d_bwd_data_split_f16(ptr(gy), ptr(w), ptr(_tagged_abs_max(gy)), ptr(_weight_abs_max(w, w_amax)), ptr(acc), ptr(gx), ptr(wp),
-                                                 B, Ci, H, W, Co, dilation, stream_of(gy)), 'mode_conv2d_bwd_data_split_f16')
+    if route == 'split_f16':
+      _call('mode_conv2d_bwd_data_split_f16', ptr(gy), ptr(w), ptr(_tagged_abs_max(gy)), ptr(_weight_abs_max(w, w_amax)), ptr(acc), ptr(gx), ptr(wp),
+            B, Ci, H, W, Co, dilation, stream_of(gy))
     else:
-      check(lib().mode_conv2d_bwd_data_split_acc(ptr(gy), ptr(w), ptr(acc), ptr(gx), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(gy)),
-            'mode_conv2d_bwd_data_split_acc')
+      _call('mode_conv2d_bwd_data_split_acc', ptr(gy), ptr(w), ptr(acc), ptr(gx), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(gy))
   return gx
 
 
@@ -321,7 +327,7 @@ class CostConvAssemble(torch.autograd.Function):
     out = torch.empty((B, Co, D, H, W), dtype=R.dtype, device=R.device)
     nbytes = 4 * (R.numel() + T.numel() + out.numel())
     with torch.cuda.device_of(R), profiling.region('cost_conv_assemble_fwd', nbytes, 0, R.device):
-      check(lib().mode_cost_conv_assemble_fwd(ptr(R), ptr(T), ptr(out), B, Co, D, H, W, stream_of(R)), 'mode_cost_conv_assemble_fwd')
+      _call('mode_cost_conv_assemble_fwd', ptr(R), ptr(T), ptr(out), B, Co, D, H, W, stream_of(R))
     ctx.D = D
     return out
 
@@ -334,7 +340,7 @@ class CostConvAssemble(torch.autograd.Function):
     gT = torch.empty_like(gR)
     nbytes = 4 * (gR.numel() + gT.numel() + gout.numel())
     with torch.cuda.device_of(gout), profiling.region('cost_conv_assemble_bwd', nbytes, 0, gout.device):
-      check(lib().mode_cost_conv_assemble_bwd(ptr(gout), ptr(gR), ptr(gT), B, Co, D, H, W, stream_of(gout)), 'mode_cost_conv_assemble_bwd')
+      _call('mode_cost_conv_assemble_bwd', ptr(gout), ptr(gR), ptr(gT), B, Co, D, H, W, stream_of(gout))
     return gR, gT, None
 
 
@@ -408,7 +414,7 @@ def transpose_planes(t, out=None):
   if out is None:
     out = torch.empty((B, C, W, H), dtype=t.dtype, device=t.device)
   with torch.cuda.device_of(t):
-    check(lib().mode_transpose_planes(ptr(t), ptr(out), B * C, H, W, stream_of(t)), 'mode_transpose_planes')
+    _call('mode_transpose_planes', ptr(t), ptr(out), B * C, H, W, stream_of(t))
   return out
 
 
@@ -426,19 +432,19 @@ def sphere_plan(pos, kh, kw):
     n = lib().mode_sphere_plan_max_tiles(H, W)
     tiles = torch.empty(4 * n, dtype=torch.int32)
     counts = torch.zeros(4, dtype=torch.int32)
-    check(lib().mode_sphere_plan_build(ptr(host), H, W, kh, kw, ptr(tiles), ptr(counts)), 'mode_sphere_plan_build')
+    _call('mode_sphere_plan_build', ptr(host), H, W, kh, kw, ptr(tiles), ptr(counts))
     c = [int(v) for v in counts]
     plan = None
     if not c[3]:
       rest = torch.empty(H * W, dtype=torch.int32)
       nrest = torch.zeros(1, dtype=torch.int32)
-      check(lib().mode_sphere_plan_rest_pixels(ptr(tiles), ptr(counts), H, W, ptr(rest), ptr(nrest)), 'mode_sphere_plan_rest_pixels')
+      _call('mode_sphere_plan_rest_pixels', ptr(tiles), ptr(counts), H, W, ptr(rest), ptr(nrest))
       nrest = int(nrest)
       nrec = max(lib().mode_sphere_plan_records_count(c[0]), 1)
       rec_w = torch.zeros(4 * nrec, dtype=torch.float32)
       rec_off = torch.zeros(nrec, dtype=torch.int32)
       if c[0]:
-        check(lib().mode_sphere_plan_records(ptr(host), ptr(tiles), ptr(counts), H, W, ptr(rec_w), ptr(rec_off)), 'mode_sphere_plan_records')
+        _call('mode_sphere_plan_records', ptr(host), ptr(tiles), ptr(counts), H, W, ptr(rec_w), ptr(rec_off))
       polar = None
       npmax = lib().mode_sphere_plan_polar_max_items(ptr(counts))
       if npmax and c[0]:
@@ -446,8 +452,7 @@ def sphere_plan(pos, kh, kw):
         prw = torch.zeros(4 * 288 * npmax, dtype=torch.float32)
         pro = torch.zeros(288 * npmax, dtype=torch.int32)
         npol = torch.zeros(1, dtype=torch.int32)
-        check(lib().mode_sphere_plan_polar(ptr(host), ptr(tiles), ptr(counts), H, W, ptr(pitems), ptr(prw), ptr(pro), ptr(npol)),
-              'mode_sphere_plan_polar')
+        _call('mode_sphere_plan_polar', ptr(host), ptr(tiles), ptr(counts), H, W, ptr(pitems), ptr(prw), ptr(pro), ptr(npol))
         if int(npol) > 0:
           n = int(npol)
           polar = (pitems[:20 * n].contiguous().to(pos.device), prw[:4 * 288 * n].contiguous().to(pos.device),
@@ -470,7 +475,7 @@ def _tagged_abs_max(t):
   am = known_abs_max(t)
   if am is None:
     am = abs_max(t)
-    t._mode_amax = (am, t._version, t.data_ptr())
+    _tag_amax(t, am)
   return am
 
 
@@ -519,7 +524,7 @@ class weight_maxima(object):
       m.__dict__['_mode_wmax_cache'] = cache
     out = torch.empty((len(ws), BN_ABSMAX_FLOATS), dtype=torch.float32, device=ws[0].device)
     with torch.cuda.device_of(out), profiling.region('abs_max_batch', 4 * sum(p.numel() for p in ws), 0, out.device):
-      check(lib().mode_abs_max_batch(ptr(cache[1]), ptr(cache[2]), len(ws), ptr(out), stream_of(out)), 'mode_abs_max_batch')
+      _call('mode_abs_max_batch', ptr(cache[1]), ptr(cache[2]), len(ws), ptr(out), stream_of(out))
     _wmax_tls.table = {p.data_ptr(): (out[i], p._version, p.numel()) for i, p in enumerate(ws)}
     return self
 
@@ -535,6 +540,32 @@ def _sphere_f16_maxima(x, w, f16):
   return (_tagged_abs_max(x), _weight_abs_max(w))
 
 
+def _sphere_fwd_route(pos, w, B, groups, stride, same_size, honour_switch, native_t=True):
+  """Which kernel runs the spherical forward of weight w on table pos at batch B:
+    ('window', plan)    the LDS-window kernels on the tile plan of pos (on plane-transposed copies where SPHERE_LAYOUT says so);
+    ('native_t', post)  an ERP-like table: the `_t` operator on the NCHW tensors themselves, with the transposed table post;
+    ('gather', None)    the general gather-and-MAC kernel.
+  The rule, written once: stride 1, 3 x 3 taps and an output of the input's size (same_size) can be planned; a plan of fewer than
+  SPHERE_FWD_MIN_WG workgroups is dropped (one workgroup per 64x4 tile, sample and 128-channel slice: below ~one workgroup per CU the
+  general kernel's 64-pixel tiles fill the chip better -- measured at B = 1, 256x128: 22.9 vs 20.3 ms for the whole eval forward); a plan
+  that is not usable as a whole (_plan_usable) gives way to the transposed table where that one is.
+  Where the sites differ:
+    honour_switch  whether SPHERE_FWD = 'gather' turns the windowed kernels off: the training operator (sphere_conv_fwd) and
+                   sphere_t_supported pass True, the inference wrapper (sphere_conv_bn_eval) passes False -- it never read the switch;
+    native_t       False for sphere_t_supported, which asks about the table it was given only."""
+  Kh, Kw = w.shape[2:]
+  if (honour_switch and SPHERE_FWD != 'window') or tuple(stride) != (1, 1) or Kh * Kw != 9 or not same_size:
+    return 'gather', None
+  plan = sphere_plan(pos, Kh, Kw)
+  if plan is not None and sum(plan[1]) * B * groups * (-(-(w.shape[0] // groups) // 128)) < SPHERE_FWD_MIN_WG:
+    plan = None
+  if native_t and not _plan_usable(plan):
+    post = sphere_native_t(pos, Kh, Kw)
+    if post is not None and sphere_t_supported(post, w, B, groups):
+      return 'native_t', post
+  return ('window', plan) if plan is not None else ('gather', None)
+
+
 def sphere_conv_fwd(x, pos, w, out, stride, groups, return_transposed=False, f16=False):
   """Writes `out` (B,Co,Ho,Wo) in place.  Replaces sphere_conv_forward_cuda (sphere_conv_cuda.cpp:129-210).
   return_transposed: return the plane-transposed copy of x the windowed kernel used (None if it did not run) instead of out.
@@ -545,26 +576,16 @@ def sphere_conv_fwd(x, pos, w, out, stride, groups, return_transposed=False, f16
   dims = _sc_dims(x.shape, w.shape, out.shape[2:], stride, groups)
   flops = 2 * out.numel() * w[0].numel()
   nbytes = 4 * (x.numel() + out.numel() + pos.numel() + w.numel())
-  plan = None
-  if SPHERE_FWD == 'window' and tuple(stride) == (1, 1) and w.shape[2] * w.shape[3] == 9 and tuple(out.shape[2:]) == tuple(x.shape[2:]):
-    plan = sphere_plan(pos, w.shape[2], w.shape[3])
-    if plan is not None:
-      # one workgroup per 64x4 tile, sample and 128-channel slice: below ~one workgroup per CU the general kernel (64-pixel
-      # tiles) fills the chip better (measured at B = 1, 256x128: 22.9 vs 20.3 ms for the whole eval forward)
-      n_wg = sum(plan[1]) * x.shape[0] * groups * (-(-(w.shape[0] // groups) // 128))
-      if n_wg < SPHERE_FWD_MIN_WG:
-        plan = None
-    if not _plan_usable(plan):
-      post = sphere_native_t(pos, w.shape[2], w.shape[3])  # ERP-like table: the `_t` operator on the NCHW tensors themselves
-      if post is not None and sphere_t_supported(post, w, x.shape[0], groups):
-        sphere_conv_fwd_t(x, post, w, out, groups, f16=f16)
-        return None if return_transposed else out
+  route, plan = _sphere_fwd_route(pos, w, x.shape[0], groups, stride, tuple(out.shape[2:]) == tuple(x.shape[2:]), honour_switch=True)
+  if route == 'native_t':
+    sphere_conv_fwd_t(x, plan, w, out, groups, f16=f16)
+    return None if return_transposed else out
+  xt = None
   with torch.cuda.device_of(x), profiling.region(_tag2('sphere_conv_fwd', w, x), nbytes, flops, x.device):
-    if plan is not None:
+    if route == 'window':
       B, Ci, H, W, Co, Kh, Kw = dims[:7]
       tiles, (n0, n1, n2) = plan[:2]
       wp = torch.empty(lib().mode_sphere_conv_win_wpack_bytes(Ci, Co, Kh, Kw, groups) // 4, dtype=torch.float32, device=w.device)
-      xt = None
       amax = _sphere_f16_maxima(x, w, f16)
       if SPHERE_LAYOUT == 'transposed':
         xt, yt = transpose_planes(x), torch.empty((B, Co, W, H), dtype=x.dtype, device=x.device)
@@ -573,9 +594,8 @@ def sphere_conv_fwd(x, pos, w, out, stride, groups, return_transposed=False, f16
       else:
         _sphere_fwd_win(ptr(x), pos, w, None, ptr(out), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 0, stream_of(x), amax)
     else:
-      xt = None
       wp = _wpack(w, groups)
-      check(lib().mode_sphere_conv_fwd(ptr(x), ptr(pos), ptr(w), ptr(out), ptr(wp), *dims, stream_of(x)), 'mode_sphere_conv_fwd')
+      _call('mode_sphere_conv_fwd', ptr(x), ptr(pos), ptr(w), ptr(out), ptr(wp), *dims, stream_of(x))
   return xt if return_transposed else out
 
 
@@ -584,17 +604,16 @@ def _sphere_fwd_win(xp, pos, w, e, yp, wp, tiles, n0, n1, n2, B, Ci, H, W, Co, K
   CONV_ARITH says so (the library falls back to the fp32 kernels by itself when the channel count does not fit).
   amax = (max |x|, max |w|) device scalars: the fp16 arithmetic (_sphere_f16_maxima; no epilogue)."""
   if amax is not None and e is None and CONV_ARITH == 'bf16x6':
-    check(lib().mode_sphere_conv_fwd_win_split_f16(xp, ptr(pos), ptr(w), ptr(amax[0]), ptr(amax[1]), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H,
-                                                   W, Co, Kh, Kw, groups, transposed, stream), 'mode_sphere_conv_fwd_win_split_f16')
+    _call('mode_sphere_conv_fwd_win_split_f16', xp, ptr(pos), ptr(w), ptr(amax[0]), ptr(amax[1]), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co,
+          Kh, Kw, groups, transposed, stream)
   elif CONV_ARITH == 'bf16x6':
-    check(lib().mode_sphere_conv_fwd_win_split(xp, ptr(pos), ptr(w), ctypes.byref(e) if e is not None else None, yp, ptr(wp), ptr(tiles), n0, n1,
-                                               n2, B, Ci, H, W, Co, Kh, Kw, groups, transposed, stream), 'mode_sphere_conv_fwd_win_split')
+    _call('mode_sphere_conv_fwd_win_split', xp, ptr(pos), ptr(w), ctypes.byref(e) if e is not None else None, yp, ptr(wp), ptr(tiles), n0, n1, n2, B,
+          Ci, H, W, Co, Kh, Kw, groups, transposed, stream)
   elif e is not None:
-    check(lib().mode_sphere_conv_fwd_win_bn(xp, ptr(pos), ptr(w), ctypes.byref(e), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co, Kh, Kw,
-                                            groups, transposed, stream), 'mode_sphere_conv_fwd_win_bn')
+    _call('mode_sphere_conv_fwd_win_bn', xp, ptr(pos), ptr(w), ctypes.byref(e), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups,
+          transposed, stream)
   else:
-    check(lib().mode_sphere_conv_fwd_win(xp, ptr(pos), ptr(w), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups,
-                                         transposed, stream), 'mode_sphere_conv_fwd_win')
+    _call('mode_sphere_conv_fwd_win', xp, ptr(pos), ptr(w), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, transposed, stream)
 
 
 _adjoint_cache = _LRU(TABLE_CACHE_ENTRIES)
@@ -617,8 +636,8 @@ def sphere_adjoint(pos, kh, kw, stride, out_hw):
     rowptr = torch.empty(kh * kw * H * W + 1, dtype=torch.int32)
     entries = torch.empty(2 * nmax, dtype=torch.int32)
     n = ctypes.c_int64(0)
-    check(lib().mode_sphere_adjoint_build(ptr(host), H, W, kh, kw, stride[0], stride[1], out_hw[0], out_hw[1], ptr(rowptr),
-                                          ptr(entries), ctypes.cast(ctypes.pointer(n), ctypes.c_void_p)), 'mode_sphere_adjoint_build')
+    _call('mode_sphere_adjoint_build', ptr(host), H, W, kh, kw, stride[0], stride[1], out_hw[0], out_hw[1], ptr(rowptr), ptr(entries),
+          ctypes.cast(ctypes.pointer(n), ctypes.c_void_p))
     hit = (rowptr.to(pos.device), entries[:2 * max(n.value, 1)].contiguous().to(pos.device), pos)  # keep `pos` alive: key uses its address
     _adjoint_cache[key] = hit
     return hit
@@ -696,15 +715,14 @@ def sphere_conv_bwd_data(gy, pos, w, gx, stride, groups, overwrite=False, gy_tra
     with torch.cuda.device_of(gy), profiling.region(_tag2('sphere_conv_bwd_data', w, gx), nbytes, flops, gy.device):
       wp = _wpack(w, groups)
       rowptr, entries, _ = sphere_adjoint(pos, Kh, Kw, stride, gy.shape[2:])
-      check(lib().mode_sphere_conv_bwd_data_adj(ptr(gy), ptr(w), ptr(gx), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, H, W, Co, Kh,
-                                                Kw, Ho, Wo, G, 0 if overwrite else 1, stream_of(gy)), 'mode_sphere_conv_bwd_data_adj')
+      _call('mode_sphere_conv_bwd_data_adj', ptr(gy), ptr(w), ptr(gx), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, H, W, Co, Kh, Kw, Ho, Wo, G,
+            0 if overwrite else 1, stream_of(gy))
     return gx
   if overwrite:
     gx.zero_()  # the scatter form adds with atomics
   with torch.cuda.device_of(gy), profiling.region(_tag2('sphere_conv_bwd_data', w, gx), nbytes, flops, gy.device):
     wp = _wpack(w, groups)
-    check(lib().mode_sphere_conv_bwd_data(ptr(gy), ptr(pos), ptr(w), ptr(gx), ptr(wp), *dims, stream_of(gy)),
-          'mode_sphere_conv_bwd_data')
+    _call('mode_sphere_conv_bwd_data', ptr(gy), ptr(pos), ptr(w), ptr(gx), ptr(wp), *dims, stream_of(gy))
   return gx
 
 
@@ -730,6 +748,29 @@ def _bww_f16_maxima(gy, x, gy_src=None, x_src=None):
 SPHERE_BWD_WEIGHT = 'window'  # 'window' (where the table allows) | 'gather'
 
 
+def _sphere_bww_win(gy, x, gyt, xt, pos, gw, plan, use_polar, B, Ci, H, W, Co, groups):
+  """The launch of the windowed weight gradient, for both storages: gy, x are the NCHW operands (None on plane-transposed storage),
+  gyt, xt their plane-transposed copies (None under SPHERE_LAYOUT 'nchw').  use_polar: the tall-window tiles on the polar kernel
+  instead of the pixel list, where the plan has polar items."""
+  Kh, Kw = gw.shape[2:]
+  tiles, (n0, n1, n2), rest, nrest, rec_w, rec_off, polar = plan
+  if polar is not None and use_polar:
+    pitems, prw, pro, npol = polar
+    nrest = 0
+  else:
+    pitems = prw = pro = None
+    npol = 0
+  first = gy if gy is not None else gyt
+  n = lib().mode_sphere_conv_bwd_weight_win_workspace_bytes(B, Ci, H, W, Co, Kh, Kw, groups, n0, nrest, npol)
+  ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=first.device)
+  entry = _bww_win_entry()
+  amax = _bww_f16_maxima(gyt if gyt is not None else gy, xt if xt is not None else x, gy, x)
+  if amax is not None:
+    entry, amax = entry + '_f16', (ptr(amax[0]), ptr(amax[1]))
+  _call(entry, _optr(gy), ptr(pos), _optr(x), *(amax or ()), ptr(gw), ptr(ws), ptr(tiles), n0, n1, n2, ptr(rec_w), ptr(rec_off), ptr(rest), nrest,
+        _optr(pitems), _optr(prw), _optr(pro), npol, B, Ci, H, W, Co, Kh, Kw, groups, _optr(gyt), _optr(xt), stream_of(first))
+
+
 def sphere_conv_bwd_weight(gy, pos, x, gw, stride, groups, x_transposed=None, gy_transposed=None):
   """Accumulates into `gw` (Co,Ci/g,Kh,Kw) (caller zero-fills, sphere_conv.py:63).  x_transposed: the plane-transposed copy
   of x kept from the forward, if any (saves rebuilding it for the windowed kernel); gy_transposed: the same for gy."""
@@ -750,33 +791,15 @@ def sphere_conv_bwd_weight(gy, pos, x, gw, stride, groups, x_transposed=None, gy
         return sphere_conv_bwd_weight_t(gy, post, x, gw, groups)
   with torch.cuda.device_of(gy), profiling.region(_tag2('sphere_conv_bwd_weight', gw, x), nbytes, flops, gy.device):
     if plan is not None:
-      tiles, (n0, n1, n2), rest, nrest, rec_w, rec_off, polar = plan
-      if polar is not None and SPHERE_POLAR:  # the tall-window tiles on the polar kernel instead of the pixel list
-        pitems, prw, pro, npol = polar
-        nrest = 0
-      else:
-        pitems = prw = pro = None
-        npol = 0
-      n = lib().mode_sphere_conv_bwd_weight_win_workspace_bytes(B, Ci, H, W, Co, Kh, Kw, G, n0, nrest, npol)
-      ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=gy.device)
       gyt = xt = None
       if SPHERE_LAYOUT == 'transposed':
         gyt = gy_transposed if gy_transposed is not None and tuple(gy_transposed.shape) == (B, Co, Wo, Ho) else transpose_planes(gy)
         xt = x_transposed if x_transposed is not None and tuple(x_transposed.shape) == (B, Ci, W, H) else transpose_planes(x)
-      entry = _bww_win_entry()
-      amax = _bww_f16_maxima(gyt if gyt is not None else gy, xt if xt is not None else x, gy, x)
-      if amax is not None:
-        entry, amax = entry + '_f16', (ptr(amax[0]), ptr(amax[1]))
-      check(getattr(lib(), entry)(ptr(gy), ptr(pos), ptr(x), *(amax or ()), ptr(gw), ptr(ws), ptr(tiles), n0, n1, n2, ptr(rec_w),
-                                  ptr(rec_off), ptr(rest), nrest, ptr(pitems) if npol else None, ptr(prw) if npol else None,
-                                  ptr(pro) if npol else None, npol, B, Ci, H, W, Co, Kh, Kw, G,
-                                  ptr(gyt) if gyt is not None else None, ptr(xt) if xt is not None else None,
-                                  stream_of(gy)), entry)
+      _sphere_bww_win(gy, x, gyt, xt, pos, gw, plan, SPHERE_POLAR, B, Ci, H, W, Co, G)
     else:
       n = lib().mode_sphere_conv_bwd_weight_workspace_bytes(B, Ci, Co, Kh, Kw, Ho, Wo, G)
       ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=gy.device)
-      check(lib().mode_sphere_conv_bwd_weight(ptr(gy), ptr(pos), ptr(x), ptr(gw), ptr(ws), *dims, stream_of(gy)),
-            'mode_sphere_conv_bwd_weight')
+      _call('mode_sphere_conv_bwd_weight', ptr(gy), ptr(pos), ptr(x), ptr(gw), ptr(ws), *dims, stream_of(gy))
   return gw
 
 
@@ -786,14 +809,10 @@ def sphere_conv_bwd_weight(gy, pos, x, gw, stride, groups, x_transposed=None, gy
 # windowed kernels work on: the three functions below are the operator on that storage, without any transpose.
 def sphere_t_supported(pos, w, B, groups):
   """True when the windowed forward would run for this table / weight / batch (else callers use the NCHW operator)."""
-  if SPHERE_LAYOUT != 'transposed' or SPHERE_FWD != 'window' or SPHERE_BWD_WEIGHT != 'window' or SPHERE_BWD_DATA != 'gather':
+  if SPHERE_LAYOUT != 'transposed' or SPHERE_BWD_WEIGHT != 'window' or SPHERE_BWD_DATA != 'gather':
     return False
-  if w.shape[2] * w.shape[3] != 9:
-    return False
-  plan = sphere_plan(pos, w.shape[2], w.shape[3])
-  if not _plan_usable(plan):
-    return False
-  return sum(plan[1]) * B * groups * (-(-(w.shape[0] // groups) // 128)) >= SPHERE_FWD_MIN_WG
+  route, plan = _sphere_fwd_route(pos, w, B, groups, (1, 1), True, honour_switch=True, native_t=False)
+  return route == 'window' and _plan_usable(plan)
 
 
 def sphere_conv_fwd_t(xt, pos, w, yt, groups, f16=False, amax_out=None):
@@ -842,8 +861,8 @@ def sphere_adjplan(pos, kh, kw):
       rec_w = torch.zeros(n * 9 * 256 * 4, dtype=torch.float32)
       rec_off2 = torch.zeros(n * 9 * 256 * 2, dtype=torch.int32)
       rec_w2 = torch.zeros(n * 9 * 256 * 2, dtype=torch.float32)
-      check(lib().mode_sphere_adjplan_build(ptr(host), H, W, kh, kw, ptr(good), ptr(bad), ptr(counts), ptr(rec_off), ptr(rec_w), ptr(rec_off2),
-                                            ptr(rec_w2)), 'mode_sphere_adjplan_build')
+      _call('mode_sphere_adjplan_build', ptr(host), H, W, kh, kw, ptr(good), ptr(bad), ptr(counts), ptr(rec_off), ptr(rec_w), ptr(rec_off2),
+            ptr(rec_w2))
       ng, nb = int(counts[0]), int(counts[1])
       if ng > 0:
         # a bad tile (h0, w0) = the 64-pixel runs h0 .. h0 + 63 of the stored rows w0 .. w0 + 3 of the (W, H) planes
@@ -879,20 +898,17 @@ def sphere_conv_bwd_data_t(gyt, pos, w, gxt, groups, w_amax=None):
       tiles, ng, rec_off, rec_w, bad_ids, nbad, rec_off2, rec_w2 = aplan
       wps = torch.empty(lib().mode_sphere_conv_bwd_data_win_wpack_bytes(Ci, Co, Kh, Kw, groups) // 4, dtype=torch.float32, device=w.device)
       if SPHERE_BWD_F16:  # (a backward pass is a training step: the two-piece fp16 arithmetic)
-        check(lib().mode_sphere_conv_bwd_data_win_split_f16(ptr(gyt), ptr(w), ptr(_tagged_abs_max(gyt)), ptr(_weight_abs_max(w, w_amax)), ptr(gxt),
-                                                            ptr(wps), ptr(tiles), ng, ptr(rec_off), ptr(rec_w), ptr(rec_off2), ptr(rec_w2), B, Ci,
-                                                            H, W, Co, Kh, Kw, groups, 1, stream_of(gyt)), 'mode_sphere_conv_bwd_data_win_split_f16')
+        _call('mode_sphere_conv_bwd_data_win_split_f16', ptr(gyt), ptr(w), ptr(_tagged_abs_max(gyt)), ptr(_weight_abs_max(w, w_amax)), ptr(gxt),
+              ptr(wps), ptr(tiles), ng, ptr(rec_off), ptr(rec_w), ptr(rec_off2), ptr(rec_w2), B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(gyt))
       else:
-        check(lib().mode_sphere_conv_bwd_data_win_split(ptr(gyt), ptr(w), ptr(gxt), ptr(wps), ptr(tiles), ng, ptr(rec_off), ptr(rec_w),
-                                                        ptr(rec_off2), ptr(rec_w2), B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(gyt)),
-              'mode_sphere_conv_bwd_data_win_split')
+        _call('mode_sphere_conv_bwd_data_win_split', ptr(gyt), ptr(w), ptr(gxt), ptr(wps), ptr(tiles), ng, ptr(rec_off), ptr(rec_w), ptr(rec_off2),
+              ptr(rec_w2), B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(gyt))
       if nbad:  # the tiles next to the poles and the few columns with more than four sources per tap: gather kernel on a tile list
-        check(lib().mode_sphere_conv_bwd_data_adj_list(ptr(gyt), ptr(w), ptr(gxt), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, W, H, Co,
-                                                       Kh, Kw, W, H, groups, 0, ptr(bad_ids), nbad, stream_of(gyt)),
-              'mode_sphere_conv_bwd_data_adj_list')
+        _call('mode_sphere_conv_bwd_data_adj_list', ptr(gyt), ptr(w), ptr(gxt), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, W, H, Co, Kh, Kw, W, H,
+              groups, 0, ptr(bad_ids), nbad, stream_of(gyt))
     else:
-      check(lib().mode_sphere_conv_bwd_data_adj(ptr(gyt), ptr(w), ptr(gxt), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, W, H, Co, Kh, Kw,
-                                                W, H, groups, 0, stream_of(gyt)), 'mode_sphere_conv_bwd_data_adj')
+      _call('mode_sphere_conv_bwd_data_adj', ptr(gyt), ptr(w), ptr(gxt), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, W, H, Co, Kh, Kw, W, H, groups, 0,
+            stream_of(gyt))
   return gxt
 
 
@@ -902,23 +918,13 @@ def sphere_conv_bwd_weight_t(gyt, pos, xt, gw, groups):
   require_f32c(gyt, pos, xt, gw)
   B, Co, W, H = gyt.shape
   Ci, Kh, Kw = xt.shape[1], gw.shape[2], gw.shape[3]
-  tiles, (n0, n1, n2), rest, nrest, rec_w, rec_off, polar = sphere_plan(pos, Kh, Kw)
-  if nrest and polar is None:
+  plan = sphere_plan(pos, Kh, Kw)
+  if plan[3] and plan[6] is None:
     raise RuntimeError('sphere_conv_bwd_weight_t: the table needs the pixel-list fallback, which reads NCHW tensors')
-  pitems, prw, pro, npol = polar if polar is not None else (None, None, None, 0)
   flops = 2 * gyt.numel() * gw[0].numel()
   nbytes = 4 * (xt.numel() + gyt.numel() + pos.numel() + gw.numel())
   with torch.cuda.device_of(gyt), profiling.region('sphere_conv_bwd_weight[%d->%d %dx%d]' % (Ci, Co, H, W), nbytes, flops, gyt.device):
-    n = lib().mode_sphere_conv_bwd_weight_win_workspace_bytes(B, Ci, H, W, Co, Kh, Kw, groups, n0, 0, npol)
-    ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=gyt.device)
-    entry = _bww_win_entry()
-    amax = _bww_f16_maxima(gyt, xt)
-    if amax is not None:
-      entry, amax = entry + '_f16', (ptr(amax[0]), ptr(amax[1]))
-    check(getattr(lib(), entry)(None, ptr(pos), None, *(amax or ()), ptr(gw), ptr(ws), ptr(tiles), n0, n1, n2, ptr(rec_w), ptr(rec_off),
-                                ptr(rest), 0, ptr(pitems) if npol else None, ptr(prw) if npol else None,
-                                ptr(pro) if npol else None, npol, B, Ci, H, W, Co, Kh, Kw, groups, ptr(gyt), ptr(xt),
-                                stream_of(gyt)), entry)
+    _sphere_bww_win(None, None, gyt, xt, pos, gw, plan, True, B, Ci, H, W, Co, groups)  # (polar items whatever SPHERE_POLAR says: no pixel list here)
   return gw
 
 
@@ -951,7 +957,7 @@ class Conv2d3x3S2Function(torch.autograd.Function):
     B, Co, Ho, Wo = gy.shape
     up = torch.empty((B, Co, 2 * Ho, 2 * Wo), dtype=gy.dtype, device=gy.device)
     with torch.cuda.device_of(gy):
-      check(lib().mode_zero_insert2(ptr(gy), ptr(up), B * Co, Ho, Wo, stream_of(gy)), 'mode_zero_insert2')
+      _call('mode_zero_insert2', ptr(gy), ptr(up), B * Co, Ho, Wo, stream_of(gy))
     gx = conv2d_bwd_data(up, w, 1) if ctx.needs_input_grad[0] else None
     gw = None
     if ctx.needs_input_grad[1]:
@@ -995,13 +1001,12 @@ def conv1x1_fwd(x, w, stride=1, bn=None, add=None, relu=False):
                                                  flops, x.device):
     if bn is None:
       wp = torch.empty(lib().mode_conv1x1_wpack_bytes(Ci, Co) // 4, dtype=torch.float32, device=x.device)
-      check(lib().mode_conv1x1_fwd(ptr(x), ptr(w), ptr(y), ptr(wp), B, Ci, H, W, Co, stride, stream_of(x)), 'mode_conv1x1_fwd')
+      _call('mode_conv1x1_fwd', ptr(x), ptr(w), ptr(y), ptr(wp), B, Ci, H, W, Co, stride, stream_of(x))
     else:
       e, keep = _epilogue(bn, add, relu, y)
       wp, reuse = _eval_wpack(bn, 'conv1x1_fwd_bn', w, lib().mode_conv1x1_wpack_bytes(Ci, Co) // 4, x.device)
       with reuse:
-        check(lib().mode_conv1x1_fwd_bn(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, stride, stream_of(x)),
-              'mode_conv1x1_fwd_bn')
+        _call('mode_conv1x1_fwd_bn', ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, stride, stream_of(x))
   return y
 
 
@@ -1026,7 +1031,7 @@ class Conv1x1Function(torch.autograd.Function):
       with torch.cuda.device_of(x), profiling.region(_tag1('conv1x1_bwd_data', Ci, Co, s, H, W), 4 * (gx.numel() + gy.numel() + w.numel()),
                                                      2 * gy.numel() * Ci, x.device):
         wp = torch.empty(lib().mode_conv1x1_wpack_bytes(Ci, Co) // 4, dtype=torch.float32, device=x.device)
-        check(lib().mode_conv1x1_bwd_data(ptr(gy), ptr(w), ptr(gx), ptr(wp), B, Ci, H, W, Co, s, stream_of(x)), 'mode_conv1x1_bwd_data')
+        _call('mode_conv1x1_bwd_data', ptr(gy), ptr(w), ptr(gx), ptr(wp), B, Ci, H, W, Co, s, stream_of(x))
     gw = None
     if ctx.needs_input_grad[1]:
       sink = grad_sink(w)
@@ -1034,8 +1039,7 @@ class Conv1x1Function(torch.autograd.Function):
       with torch.cuda.device_of(x), profiling.region(_tag1('conv1x1_bwd_weight', Ci, Co, s, H, W), 4 * (x.numel() // s**2 + gy.numel() + w.numel()),
                                                      2 * gy.numel() * Ci, x.device):
         ws = torch.empty(max(lib().mode_conv1x1_bwd_weight_workspace_bytes(B, Ci, H, W, Co, s) // 4, 1), dtype=torch.float32, device=x.device)
-        check(lib().mode_conv1x1_bwd_weight(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, H, W, Co, s, int(sink is not None), stream_of(x)),
-              'mode_conv1x1_bwd_weight')
+        _call('mode_conv1x1_bwd_weight', ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, H, W, Co, s, int(sink is not None), stream_of(x))
       if sink is not None:
         gw = None
     return gx, gw, None
@@ -1065,13 +1069,12 @@ def conv_stem_fwd(x, w, bn=None, add=None, relu=False):
                                                  2 * y.numel() * Ci * 49, x.device):
     if bn is None:
       wp = torch.empty(lib().mode_conv_stem_wpack_bytes(Ci, Co) // 4, dtype=torch.float32, device=x.device)
-      check(lib().mode_conv_stem_fwd(ptr(x), ptr(w), ptr(y), ptr(wp), B, Ci, H, W, Co, stream_of(x)), 'mode_conv_stem_fwd')
+      _call('mode_conv_stem_fwd', ptr(x), ptr(w), ptr(y), ptr(wp), B, Ci, H, W, Co, stream_of(x))
     else:
       e, keep = _epilogue(bn, add, relu, y)
       wp, reuse = _eval_wpack(bn, 'conv_stem_fwd_bn', w, lib().mode_conv_stem_wpack_bytes(Ci, Co) // 4, x.device)
       with reuse:
-        check(lib().mode_conv_stem_fwd_bn(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, stream_of(x)),
-              'mode_conv_stem_fwd_bn')
+        _call('mode_conv_stem_fwd_bn', ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, stream_of(x))
   return y
 
 
@@ -1098,8 +1101,7 @@ class ConvStemFunction(torch.autograd.Function):
       with torch.cuda.device_of(x), profiling.region(_tag1('conv_stem_bwd_weight', Ci, Co, 2, H, W), 4 * (x.numel() + gy.numel() + w.numel()),
                                                      2 * gy.numel() * Ci * 49, x.device):
         ws = torch.empty(max(lib().mode_conv_stem_bwd_weight_workspace_bytes(B, Ci, H, W, Co) // 4, 1), dtype=torch.float32, device=x.device)
-        check(lib().mode_conv_stem_bwd_weight(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, H, W, Co, int(sink is not None), stream_of(x)),
-              'mode_conv_stem_bwd_weight')
+        _call('mode_conv_stem_bwd_weight', ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, H, W, Co, int(sink is not None), stream_of(x))
       if sink is not None:
         gw = None
     return None, gw
@@ -1259,8 +1261,8 @@ def sum_n(tensors):
     grp, ts = ts[:4], ts[4:]
     out = torch.empty_like(grp[0])
     with torch.cuda.device_of(out), profiling.region('grad_sum%d' % len(grp), 4 * out.numel() * (len(grp) + 1), 0, out.device):
-      check(lib().mode_sum_n(ptr(grp[0]), ptr(grp[1]), ptr(grp[2]) if len(grp) > 2 else None, ptr(grp[3]) if len(grp) > 3 else None, ptr(out),
-                             out.numel(), stream_of(out)), 'mode_sum_n')
+      _call('mode_sum_n', ptr(grp[0]), ptr(grp[1]), ptr(grp[2]) if len(grp) > 2 else None, ptr(grp[3]) if len(grp) > 3 else None, ptr(out),
+            out.numel(), stream_of(out))
     ts = [out] + ts
   return ts[0]
 
@@ -1386,7 +1388,7 @@ def _split3d(ci, co, stride, which, vol=None):
 def _deconv_split3d(cin, cout, vol):
   """The transposed convolution (cin, D, H, W) -> (cout, 2D, 2H, 2W) on the split kernel: it is the input gradient of the stride-2
   convolution cout -> cin over the doubled volume."""
-  return _split3d(cout, cin, 2, 1, (2 * vol[0], 2 * vol[1], 2 * vol[2]))
+  return _conv3d_route(cout, cin, 2, 1, (2 * vol[0], 2 * vol[1], 2 * vol[2]), False) == 's2_split'
 
 
 def _out3(n, stride):
@@ -1398,19 +1400,21 @@ def _tag3(name, ci, co, stride, d, h, w):
   return '%s[%d->%d s%d %dx%dx%d]' % (name, ci, co, stride, d, h, w) if profiling.ENABLED else name
 
 
-# The stride-1 3-D layers of a TRAINING step run on TWO fp16 pieces and three MFMAs per product (mode_conv3d_*_split_f16; the
-# product default since round 5, `bench.py --no-conv3d-f16` is the A/B): each operand scaled by a power of two taken from its tensor's
-# largest finite magnitude -- left by the BatchNorm pass that wrote the tensor (the `_amax` entries), or by mode_abs_max.
+# Two fp16 pieces and three MFMAs per product (mode_conv3d_*_split_f16) for the stride-1 3-D layers that the split kernels
+# cover: each operand scaled by a power of two taken from its tensor's largest finite magnitude -- left by the pass that wrote the tensor
+# (the `_amax` entries), or by mode_abs_max.  One switch per kind of call, each on by default and read at call time; _conv3d_route gets the
+# one that applies as its `f16` argument:
+#   CONV3D_S1_F16    a TRAINING step's forward and both gradients (`bench.py --no-conv3d-f16` is the A/B);
+#   CONV3D_EVAL_F16  an INFERENCE forward (conv3d_bn_eval: the folded-BatchNorm epilogues on the same arithmetic, the activations' maxima
+#                    out of the kernels' epilogues; mode_conv3d_fwd_split_f16_bn), and
+#   CONV2D_EVAL_F16  the extractor's stride-1 3 x 3 layers of an inference forward (mode_conv2d_fwd_split_f16_bn; _conv2d_route).
 # Precision contract (stated once in csrc/split_arith.h; include/mode_hip.h for the entries): on two fp16 pieces an element keeps 22
-# significant bits down to ~2^-17 of its tensor's maximum, fewer below, none below ~2^-39 of it; on three bf16 pieces (the switch set to
-# False) it keeps 24 bits whatever its size.
+# significant bits down to ~2^-17 of its tensor's maximum, fewer below, none below ~2^-39 of it -- in training AND, by default, in
+# inference.  With a switch set to False its calls run on three bf16 pieces, which keep 24 bits of every element whatever its size: set
+# both *_EVAL_F16 globals to False before the forward to keep inference there (`bench.py --no-eval-f16` does exactly that).
 CONV3D_S1_F16 = True
-# ... and of an INFERENCE forward (conv3d_bn_eval: the folded-BatchNorm epilogues on the same arithmetic, the activations' maxima out of the
-# kernels' epilogues; mode_conv3d_fwd_split_f16_bn).  On BY DEFAULT: an inference call's stride-1 3-D and 3 x 3 layers run on two fp16 pieces
-# too, under the same 22-bit contract.  To keep inference on three bf16 pieces (24 bits for every element) set both module globals below
-# to False before the forward; `bench.py --no-eval-f16` does exactly that.
 CONV3D_EVAL_F16 = True
-CONV2D_EVAL_F16 = True  # (the extractor's stride-1 3 x 3 layers of an inference forward: mode_conv2d_fwd_split_f16_bn)
+CONV2D_EVAL_F16 = True
 
 
 BN_ABSMAX_FLOATS = 2064  # MODE_BN_ABSMAX_FLOATS of include/mode_hip.h: the buffer a tensor's maximum lives in
@@ -1421,7 +1425,7 @@ def abs_max(t):
   of BN_ABSMAX_FLOATS floats whose maximum is the value (abs_max_value reads it on the host).  A tensor's maximum is computed once and
   handed to every kernel that reads the tensor (the forward's x again in the weight gradient, gy in both gradients)."""
   out = torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=t.device)
-  check(lib().mode_abs_max(ptr(t), t.numel(), ptr(out), stream_of(t)), 'mode_abs_max')
+  _call('mode_abs_max', ptr(t), t.numel(), ptr(out), stream_of(t))
   return out
 
 
@@ -1430,10 +1434,25 @@ def abs_max_value(buf):
   return float(buf.max())
 
 
+def _conv3d_route(ci, co, stride, which, vol, f16):
+  """The kernel family of the 3x3x3 layer ci -> co (stride 1 | 2) at the input volume vol = (D, H, W) -- which: 0 forward, 1 input
+  gradient, 2 weight gradient:
+    'f32'        the fp32 MFMA kernels: CONV_ARITH 'f32', channel counts off the split kernels' grid, or a volume beyond their 32-bit
+                 contracts (_split3d);
+    's2_split'   stride 2 on three bf16 pieces;
+    'split_f16'  stride 1 on two fp16 pieces -- where f16: a training call passes CONV3D_S1_F16, the inference wrapper CONV3D_EVAL_F16;
+    'split'      stride 1 on three bf16 pieces."""
+  if not _split3d(ci, co, stride, which, vol):
+    return 'f32'
+  if stride == 2:
+    return 's2_split'
+  return 'split_f16' if f16 else 'split'
+
+
 def conv3d_s1_f16(ci, co, which, vol=None):
   """True when the stride-1 layer ci -> co runs its forward (which 0) / input gradient (1) / weight gradient (2) on the fp16 arithmetic
   (vol = (D, H, W): at this size)."""
-  return CONV3D_S1_F16 and _split3d(ci, co, 1, which, vol)
+  return _conv3d_route(ci, co, 1, which, vol, CONV3D_S1_F16) == 'split_f16'
 
 
 def conv3d_fwd(x, w, stride=1, amax=None):
@@ -1451,18 +1470,15 @@ def conv3d_fwd(x, w, stride=1, amax=None):
   with torch.cuda.device_of(x), profiling.region(_tag3('conv3d_fwd', Ci, Co, stride, D, H, W), 4 * (x.numel() + y.numel() + w.numel()),
                                                  flops, x.device):
     wp = _wpack3d(Ci, Co, x.device)
-    split = _split3d(Ci, Co, stride, 0, (D, H, W))
-    if split and stride == 2:
-      check(lib().mode_conv3d_fwd_s2_split(ptr(x), ptr(w), None, ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)),
-            'mode_conv3d_fwd_s2_split')
-    elif split and stride == 1 and CONV3D_S1_F16:
+    route = _conv3d_route(Ci, Co, stride, 0, (D, H, W), CONV3D_S1_F16)
+    tail = (ptr(y), ptr(wp), B, Ci, D, H, W, Co)
+    if route == 'split_f16':
       ax, aw = amax if amax is not None else (abs_max(x), abs_max(w))
-      check(lib().mode_conv3d_fwd_split_f16(ptr(x), ptr(w), ptr(ax), ptr(aw), ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)),
-            'mode_conv3d_fwd_split_f16')
-    elif split and stride == 1:
-      check(lib().mode_conv3d_fwd_split(ptr(x), ptr(w), None, ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)), 'mode_conv3d_fwd_split')
-    else:
-      check(lib().mode_conv3d_fwd(ptr(x), ptr(w), ptr(y), ptr(wp), B, Ci, D, H, W, Co, stride, stream_of(x)), 'mode_conv3d_fwd')
+      _call('mode_conv3d_fwd_split_f16', ptr(x), ptr(w), ptr(ax), ptr(aw), *tail, stream_of(x))
+    elif route == 'f32':
+      _call('mode_conv3d_fwd', ptr(x), ptr(w), *tail, stride, stream_of(x))
+    else:  # (None: no folded-BatchNorm epilogue)
+      _call('mode_conv3d_fwd_s2_split' if route == 's2_split' else 'mode_conv3d_fwd_split', ptr(x), ptr(w), None, *tail, stream_of(x))
   return y
 
 
@@ -1476,40 +1492,26 @@ def conv3d_bwd_data(gy, w, in_shape, stride=1, acc=None, amax=None):
   Co = w.shape[0]
   gx = torch.empty((B, Ci, D, H, W), dtype=gy.dtype, device=gy.device)
   flops = 2 * gy.numel() * Ci * 27
+  route = _conv3d_route(Ci, Co, stride, 1, (D, H, W), CONV3D_S1_F16)
+  in_store = False  # acc is an argument of the chosen entry (one more tensor read in its store); else gx.add_(acc) behind it
   if acc is not None:
     acc = acc.contiguous()
-    if (tuple(acc.shape) == tuple(gx.shape) and acc.dtype == gx.dtype and _split3d(Ci, Co, stride, 1, (D, H, W)) and
-        lib().mode_conv3d_bwd_data_split_acc_supported(Ci, Co, stride) == 1):
-      with torch.cuda.device_of(gy), profiling.region(_tag3('conv3d_bwd_data', Ci, Co, stride, D, H, W),
-                                                      4 * (2 * gx.numel() + gy.numel() + w.numel()), flops, gy.device):
-        wp = _wpack3d(Ci, Co, gy.device)
-        if stride == 1 and CONV3D_S1_F16:
-          ag, aw = amax if amax is not None else (abs_max(gy), abs_max(w))
-          check(lib().mode_conv3d_bwd_data_split_f16(ptr(gy), ptr(w), ptr(ag), ptr(aw), ptr(acc), ptr(gx), ptr(wp), B, Ci, D, H, W, Co,
-                                                     stream_of(gy)), 'mode_conv3d_bwd_data_split_f16')
-        else:
-          check(lib().mode_conv3d_bwd_data_split_acc(ptr(gy), ptr(w), ptr(acc), ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stride, stream_of(gy)),
-                'mode_conv3d_bwd_data_split_acc')
-      return gx
-    return conv3d_bwd_data(gy, w, in_shape, stride, amax=amax).add_(acc)
+    in_store = (tuple(acc.shape) == tuple(gx.shape) and acc.dtype == gx.dtype and route != 'f32' and
+                lib().mode_conv3d_bwd_data_split_acc_supported(Ci, Co, stride) == 1)
   with torch.cuda.device_of(gy), profiling.region(_tag3('conv3d_bwd_data', Ci, Co, stride, D, H, W),
-                                                  4 * (gx.numel() + gy.numel() + w.numel()), flops, gy.device):
+                                                  4 * ((2 if in_store else 1) * gx.numel() + gy.numel() + w.numel()), flops, gy.device):
     wp = _wpack3d(Ci, Co, gy.device)
-    split = _split3d(Ci, Co, stride, 1, (D, H, W))
-    if stride == 2 and split:
-      check(lib().mode_conv3d_bwd_data_s2_split(ptr(gy), ptr(w), ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stream_of(gy)),
-            'mode_conv3d_bwd_data_s2_split')
-    elif stride == 1 and split and CONV3D_S1_F16:
+    tail = (ptr(gx), ptr(wp), B, Ci, D, H, W, Co)
+    if route == 'split_f16':
       ag, aw = amax if amax is not None else (abs_max(gy), abs_max(w))
-      check(lib().mode_conv3d_bwd_data_split_f16(ptr(gy), ptr(w), ptr(ag), ptr(aw), None, ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stream_of(gy)),
-            'mode_conv3d_bwd_data_split_f16')
-    elif stride == 1 and split:
-      check(lib().mode_conv3d_bwd_data_split(ptr(gy), ptr(w), ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stream_of(gy)),
-            'mode_conv3d_bwd_data_split')
+      _call('mode_conv3d_bwd_data_split_f16', ptr(gy), ptr(w), ptr(ag), ptr(aw), ptr(acc) if in_store else None, *tail, stream_of(gy))
+    elif in_store:  # ('split' and 's2_split' alike)
+      _call('mode_conv3d_bwd_data_split_acc', ptr(gy), ptr(w), ptr(acc), *tail, stride, stream_of(gy))
+    elif route == 'f32':
+      _call('mode_conv3d_bwd_data', ptr(gy), ptr(w), *tail, stride, stream_of(gy))
     else:
-      check(lib().mode_conv3d_bwd_data(ptr(gy), ptr(w), ptr(gx), ptr(wp), B, Ci, D, H, W, Co, stride, stream_of(gy)),
-            'mode_conv3d_bwd_data')
-  return gx
+      _call('mode_conv3d_bwd_data_s2_split' if route == 's2_split' else 'mode_conv3d_bwd_data_split', ptr(gy), ptr(w), *tail, stream_of(gy))
+  return gx if acc is None or in_store else gx.add_(acc)
 
 
 def conv3d_bwd_weight(gy, x, stride=1, into=None, amax=None):
@@ -1528,20 +1530,16 @@ def conv3d_bwd_weight(gy, x, stride=1, into=None, amax=None):
                                                   4 * (x.numel() + gy.numel() + gw.numel()), flops, gy.device):
     n = lib().mode_conv3d_bwd_weight_workspace_bytes(B, Ci, D, H, W, Co, stride)
     ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=gy.device)
-    split = _split3d(Ci, Co, stride, 2, (D, H, W))
-    if stride == 2 and split:
-      check(lib().mode_conv3d_bwd_weight_s2_split(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, D, H, W, Co, int(into is not None), stream_of(gy)),
-            'mode_conv3d_bwd_weight_s2_split')
-    elif stride == 1 and split and CONV3D_S1_F16:
+    route = _conv3d_route(Ci, Co, stride, 2, (D, H, W), CONV3D_S1_F16)
+    tail = (ptr(gw), ptr(ws), B, Ci, D, H, W, Co)
+    if route == 'split_f16':
       ag, ax = amax if amax is not None else (abs_max(gy), abs_max(x))
-      check(lib().mode_conv3d_bwd_weight_split_f16(ptr(gy), ptr(x), ptr(ag), ptr(ax), ptr(gw), ptr(ws), B, Ci, D, H, W, Co, int(into is not None),
-                                                   stream_of(gy)), 'mode_conv3d_bwd_weight_split_f16')
-    elif stride == 1 and split:
-      check(lib().mode_conv3d_bwd_weight_split(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, D, H, W, Co, int(into is not None), stream_of(gy)),
-            'mode_conv3d_bwd_weight_split')
+      _call('mode_conv3d_bwd_weight_split_f16', ptr(gy), ptr(x), ptr(ag), ptr(ax), *tail, int(into is not None), stream_of(gy))
+    elif route == 'f32':
+      _call('mode_conv3d_bwd_weight', ptr(gy), ptr(x), *tail, stride, int(into is not None), stream_of(gy))
     else:
-      check(lib().mode_conv3d_bwd_weight(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, Ci, D, H, W, Co, stride, int(into is not None), stream_of(gy)),
-            'mode_conv3d_bwd_weight')
+      _call('mode_conv3d_bwd_weight_s2_split' if route == 's2_split' else 'mode_conv3d_bwd_weight_split', ptr(gy), ptr(x), *tail,
+            int(into is not None), stream_of(gy))
   return gw
 
 
@@ -1558,10 +1556,8 @@ def deconv3d_fwd(x, w):
   flops = 2 * x.numel() * Cout * 27
   with torch.cuda.device_of(x), profiling.region('deconv3d_fwd', 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
     wp = _wpack3d(Cin, Cout, x.device)
-    if _deconv_split3d(Cin, Cout, (D, H, W)):
-      check(lib().mode_deconv3d_fwd_split(ptr(x), ptr(w), ptr(y), ptr(wp), B, Cin, D, H, W, Cout, stream_of(x)), 'mode_deconv3d_fwd_split')
-    else:
-      check(lib().mode_deconv3d_fwd(ptr(x), ptr(w), ptr(y), ptr(wp), B, Cin, D, H, W, Cout, stream_of(x)), 'mode_deconv3d_fwd')
+    _call('mode_deconv3d_fwd_split' if _deconv_split3d(Cin, Cout, (D, H, W)) else 'mode_deconv3d_fwd', ptr(x), ptr(w), ptr(y), ptr(wp), B, Cin,
+          D, H, W, Cout, stream_of(x))
   return y
 
 
@@ -1574,7 +1570,7 @@ class Conv3dFunction(torch.autograd.Function):
     ctx.stride = stride
     ctx.carrier = carrier  # GradCarrier of x (x has one other consumer), or None
     ctx.amax = None
-    if stride == 1 and x.is_cuda and CONV3D_S1_F16 and _split3d(x.shape[1], w.shape[0], 1, 0, x.shape[2:]):
+    if x.is_cuda and _conv3d_route(x.shape[1], w.shape[0], stride, 0, x.shape[2:], CONV3D_S1_F16) == 'split_f16':
       ax = known_abs_max(x)  # left by the BatchNorm pass that wrote x, where there is one
       ctx.amax = (ax if ax is not None else abs_max(x.contiguous()), _weight_abs_max(w.contiguous()))  # the backward reads both tensors again
     return conv3d_fwd(x, w, stride, amax=ctx.amax)
@@ -1645,7 +1641,8 @@ def conv3d_stats_supported(x, w, bn):
   """Training-mode convbn_3d whose stride-1 convolution runs on the split kernel: the BatchNorm batch statistics can be taken in the
   convolution's epilogue (mode_conv3d_fwd_split_stats) instead of by a pass over its output."""
   return (CONV3D_BN_STATS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[0] > 0 and bn.training and
-          bn.momentum is not None and _split3d(x.shape[1], w.shape[0], 1, 0, x.shape[2:]) and x.shape[0] * w.shape[0] < 65536)
+          bn.momentum is not None and _conv3d_route(x.shape[1], w.shape[0], 1, 0, x.shape[2:], False) == 'split' and
+          x.shape[0] * w.shape[0] < 65536)
 
 
 class Conv3dStatsFunction(torch.autograd.Function):
@@ -1665,8 +1662,7 @@ class Conv3dStatsFunction(torch.autograd.Function):
     with torch.cuda.device_of(x), profiling.region(_tag3('conv3d_fwd', Ci, Co, 1, D, H, W), 4 * (x.numel() + y.numel() + w.numel()),
                                                    2 * y.numel() * Ci * 27, x.device):
       wp = _wpack3d(Ci, Co, x.device)
-      check(lib().mode_conv3d_fwd_split_stats(ptr(x), ptr(w), ptr(y), ptr(wp), ptr(ws), B, Ci, D, H, W, Co, stream_of(x)),
-            'mode_conv3d_fwd_split_stats')
+      _call('mode_conv3d_fwd_split_stats', ptr(x), ptr(w), ptr(y), ptr(wp), ptr(ws), B, Ci, D, H, W, Co, stream_of(x))
     ctx.save_for_backward(x, w)
     ctx.stride = 1
     return y
@@ -1713,8 +1709,7 @@ def head_fwd(logits, size, with_confidence=False):
   conf = torch.empty_like(pred) if with_confidence else None
   nbytes = 4 * (logits.numel() + pred.numel() * (2 if with_confidence else 1))
   with torch.cuda.device_of(logits), profiling.region(_tag_head('head_fwd', D4, H, W), nbytes, 0, logits.device):
-    check(lib().mode_head_fwd(ptr(logits), ptr(pred), ptr(conf) if conf is not None else None, B, D4, H4, W4, D, H, W,
-                              stream_of(logits)), 'mode_head_fwd')
+    _call('mode_head_fwd', ptr(logits), ptr(pred), _optr(conf), B, D4, H4, W4, D, H, W, stream_of(logits))
   return (pred, conf) if with_confidence else pred
 
 
@@ -1729,8 +1724,7 @@ def head_bwd(logits, gpred, size):
   with torch.cuda.device_of(logits), profiling.region(_tag_head('head_bwd', D4, H, W), nbytes, 0, logits.device):
     n = lib().mode_head_bwd_workspace_bytes(B, D4, H, W)
     ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=logits.device)
-    check(lib().mode_head_bwd(ptr(logits), ptr(gpred), ptr(gl), ptr(ws), B, D4, H4, W4, D, H, W, stream_of(logits)),
-          'mode_head_bwd')
+    _call('mode_head_bwd', ptr(logits), ptr(gpred), ptr(gl), ptr(ws), B, D4, H4, W4, D, H, W, stream_of(logits))
   return gl
 
 
@@ -1769,8 +1763,7 @@ def head_bwd_conf(logits, pred, conf, gpred, gconf, size):
   with torch.cuda.device_of(logits), profiling.region(_tag_head('head_bwd_conf', D4, H, W), nbytes, 0, logits.device):
     n = lib().mode_head_bwd_workspace_bytes(B, D4, H, W)
     ws = torch.empty(max(n // 4, 1), dtype=torch.float32, device=logits.device)
-    check(lib().mode_head_bwd_conf(ptr(logits), ptr(pred), ptr(conf), ptr(gpred), ptr(gconf), ptr(gl), ptr(ws), B, D4, H4, W4, D, H, W,
-                                   stream_of(logits)), 'mode_head_bwd_conf')
+    _call('mode_head_bwd_conf', ptr(logits), ptr(pred), ptr(conf), ptr(gpred), ptr(gconf), ptr(gl), ptr(ws), B, D4, H4, W4, D, H, W, stream_of(logits))
   return gl
 
 
@@ -1831,8 +1824,8 @@ class HeadLossFunction(torch.autograd.Function):
     loss = torch.empty(1, dtype=torch.float32, device=gt.device)
     with torch.cuda.device_of(gt), profiling.region('smooth_l1_masked', 4 * 4 * n, 0, gt.device):
       ws = torch.empty(max(lib().mode_smooth_l1_workspace_bytes(n) // 4, 1), dtype=torch.float32, device=gt.device)
-      check(lib().mode_smooth_l1_masked(ptr(preds[0]), ptr(preds[1]), ptr(preds[2]), ptr(gt), float(weights[0]), float(weights[1]),
-                                        float(weights[2]), ptr(scale), ptr(loss), ptr(ws), n, stream_of(gt)), 'mode_smooth_l1_masked')
+      _call('mode_smooth_l1_masked', ptr(preds[0]), ptr(preds[1]), ptr(preds[2]), ptr(gt), float(weights[0]), float(weights[1]), float(weights[2]),
+            ptr(scale), ptr(loss), ptr(ws), n, stream_of(gt))
     ctx.save_for_backward(*costs, *preds, gt, scale)
     ctx.weights, ctx.size = tuple(float(w) for w in weights), tuple(size)
     ctx.mark_non_differentiable(*preds)
@@ -1852,8 +1845,7 @@ class HeadLossFunction(torch.autograd.Function):
       gl = torch.empty_like(c)
       with torch.cuda.device_of(c), profiling.region(_tag_head('head_bwd', D4, H, W), 4 * (2 * c.numel() + 2 * p.numel()), 0, c.device):
         ws = torch.empty(max(lib().mode_head_bwd_workspace_bytes(B, D4, H, W) // 4, 1), dtype=torch.float32, device=c.device)
-        check(lib().mode_head_bwd_loss(ptr(c), ptr(p), ptr(gt), wt, ptr(sg), ptr(gl), ptr(ws), B, D4, H4, W4, D, H, W, stream_of(c)),
-              'mode_head_bwd_loss')
+        _call('mode_head_bwd_loss', ptr(c), ptr(p), ptr(gt), wt, ptr(sg), ptr(gl), ptr(ws), B, D4, H4, W4, D, H, W, stream_of(c))
       grads.append(gl)
     return grads[0], grads[1], grads[2], None, None, None, None
 
@@ -1911,8 +1903,7 @@ def masked_metrics(pred, gt, mask=None, px=(), d1=(), ratio=()):
   out = torch.empty(METRICS_COUNT, dtype=torch.float64, device=gt.device)
   with torch.cuda.device_of(gt), profiling.region('masked_metrics', (8 + (1 if mask is not None else 0)) * n, 0, gt.device):
     ws = _metrics_workspace(n, gt.device)
-    check(lib().mode_masked_metrics(ptr(pred), ptr(gt), None if mask is None else ptr(mask), n, ctypes.byref(prm), ptr(ws),
-                                    ws.numel() * 8, ptr(out), stream_of(gt)), 'mode_masked_metrics')
+    _call('mode_masked_metrics', ptr(pred), ptr(gt), _optr(mask), n, ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(out), stream_of(gt))
   return out.cpu().numpy()
 
 
@@ -1928,8 +1919,7 @@ class SilogLossFunction(torch.autograd.Function):
     loss = torch.empty(1, dtype=torch.float32, device=g.device)
     with torch.cuda.device_of(g), profiling.region('silog_loss_fwd', (8 + (1 if m is not None else 0)) * n, 0, g.device):
       ws = _metrics_workspace(n, g.device)
-      check(lib().mode_silog_loss_fwd(ptr(p), ptr(g), None if m is None else ptr(m), n, float(lamda), ptr(ws), ws.numel() * 8, ptr(stats),
-                                      ptr(loss), stream_of(g)), 'mode_silog_loss_fwd')
+      _call('mode_silog_loss_fwd', ptr(p), ptr(g), _optr(m), n, float(lamda), ptr(ws), ws.numel() * 8, ptr(stats), ptr(loss), stream_of(g))
     ctx.save_for_backward(p, g, m if m is not None else torch.empty(0, dtype=torch.uint8, device=g.device), stats)
     ctx.has_mask, ctx.lamda, ctx.shape = m is not None, float(lamda), pred.shape
     return loss.reshape(())
@@ -1941,8 +1931,7 @@ class SilogLossFunction(torch.autograd.Function):
     gl = gloss.reshape(1).to(torch.float32).contiguous()
     gp = torch.empty_like(p)
     with torch.cuda.device_of(g), profiling.region('silog_loss_bwd', (12 + (1 if ctx.has_mask else 0)) * n, 0, g.device):
-      check(lib().mode_silog_loss_bwd(ptr(p), ptr(g), ptr(m) if ctx.has_mask else None, n, ctx.lamda, ptr(stats), ptr(gl), ptr(gp),
-                                      stream_of(g)), 'mode_silog_loss_bwd')
+      _call('mode_silog_loss_bwd', ptr(p), ptr(g), ptr(m) if ctx.has_mask else None, n, ctx.lamda, ptr(stats), ptr(gl), ptr(gp), stream_of(g))
     return gp.view(ctx.shape), None, None, None
 
 
@@ -1977,9 +1966,8 @@ def erp_depth_metrics(pred, gt, grid, maxdepth, ratio=(), px=(), d1=(), return_e
   nbytes = (16 + (8 if return_erp else 0)) * F * H * W
   with torch.cuda.device_of(gt), profiling.region('erp_depth_metrics', nbytes, 0, gt.device):
     ws = torch.empty(max(lib().mode_erp_depth_metrics_workspace_bytes(F, H, W) // 8, 1), dtype=torch.float64, device=gt.device)
-    check(lib().mode_erp_depth_metrics(ptr(pred), ptr(gt), ptr(grid), F, H, W, float(maxdepth), ctypes.byref(prm), ptr(ws), ws.numel() * 8,
-                                       ptr(out), None if pe is None else ptr(pe), None if ge is None else ptr(ge), stream_of(gt)),
-          'mode_erp_depth_metrics')
+    _call('mode_erp_depth_metrics', ptr(pred), ptr(gt), ptr(grid), F, H, W, float(maxdepth), ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(out),
+          _optr(pe), _optr(ge), stream_of(gt))
   return (out, pe, ge) if return_erp else out
 
 
@@ -1993,7 +1981,7 @@ def bicubic_up2(x):
   N, C, H, W = x.shape
   y = torch.empty((N, C, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
   with torch.cuda.device_of(x), profiling.region('bicubic_up2', 4 * 5 * x.numel(), 2 * 20 * y.numel(), x.device):
-    check(lib().mode_bicubic_up2(ptr(x), ptr(y), N, C, H, W, stream_of(x)), 'mode_bicubic_up2')
+    _call('mode_bicubic_up2', ptr(x), ptr(y), N, C, H, W, stream_of(x))
   return y
 
 
@@ -2024,8 +2012,7 @@ def frames_u8_ingest(frames_u8, lut, want_rgb=True):
   rgb = torch.empty((F, 12, H, W), dtype=torch.float32, device=dev) if want_rgb else None
   nbytes = frames_u8.numel() * 5 + (0 if rgb is None else 4 * rgb.numel())
   with torch.cuda.device_of(frames_u8), profiling.region('frames_u8_ingest', nbytes, 0, dev):
-    check(lib().mode_frames_u8_ingest(ptr(frames_u8), ptr(lut), F, H, W, ptr(left), ptr(right), None if rgb is None else ptr(rgb),
-                                      stream_of(frames_u8)), 'mode_frames_u8_ingest')
+    _call('mode_frames_u8_ingest', ptr(frames_u8), ptr(lut), F, H, W, ptr(left), ptr(right), _optr(rgb), stream_of(frames_u8))
   return left, right, rgb
 
 
@@ -2068,10 +2055,8 @@ def images_u8_augment(images_u8, ops, coef, dst=None, out=None, return_means=Fal
   nws = lib().mode_images_u8_augment_workspace_bytes(N, H, W)
   ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=dev)
   with torch.cuda.device_of(images_u8), profiling.region('images_u8_augment', images_u8.numel() * 2 + 12 * N * H * W, 0, dev):
-    check(lib().mode_images_u8_augment(ptr(images_u8), ptr(ops), ptr(coef), None if dst is None else ptr(dst),
-                                       2 if dst is not None and dst.dim() == 2 else 1, N, H, W, out.shape[0],
-                                       ptr(out), None if means is None else ptr(means), ptr(ws), nws, stream_of(images_u8)),
-          'mode_images_u8_augment')
+    _call('mode_images_u8_augment', ptr(images_u8), ptr(ops), ptr(coef), _optr(dst), 2 if dst is not None and dst.dim() == 2 else 1, N, H, W,
+          out.shape[0], ptr(out), _optr(means), ptr(ws), nws, stream_of(images_u8))
   return (out, means) if return_means else out
 
 
@@ -2094,8 +2079,7 @@ def rgb_half_pil(frames_u8, tab_w, tab_h, lut, return_u8=False):
   out = torch.empty((F, 12, H // 2, W // 2), dtype=torch.float32, device=dev)
   u8 = torch.empty((F, 4, H // 2, W // 2, 3), dtype=torch.uint8, device=dev) if return_u8 else None
   with torch.cuda.device_of(frames_u8), profiling.region('rgb_half_pil', F * 4 * H * W * 3 + 4 * out.numel(), 0, dev):
-    check(lib().mode_rgb_half_pil(ptr(frames_u8), ptr(tab_w), ptr(tab_h), ptr(lut), F, H, W, ptr(out), None if u8 is None else ptr(u8),
-                                  stream_of(frames_u8)), 'mode_rgb_half_pil')
+    _call('mode_rgb_half_pil', ptr(frames_u8), ptr(tab_w), ptr(tab_h), ptr(lut), F, H, W, ptr(out), _optr(u8), stream_of(frames_u8))
   return (out, u8) if return_u8 else out
 
 
@@ -2168,12 +2152,10 @@ def images_u8_resize_pil(images_u8, shape, tab_w, tab_h, lut=None, windows=None,
   nws = lib().mode_images_u8_resize_pil_workspace_bytes(N, Hs, Ws, H, W, h_win, w_win)
   ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
   nbytes = images_u8.numel() + 2 * nws + N * h_win * w_win * ((3 if u8 is not None else 0) + (12 if f32 is not None else 0))
-  opt = lambda t: None if t is None else ptr(t)
   with torch.cuda.device_of(images_u8), profiling.region('images_u8_resize_pil', nbytes, 0, dev):
-    check(lib().mode_images_u8_resize_pil(ptr(images_u8), opt(tab_w) if ksize[0] else None, ksize[0], opt(tab_h) if ksize[1] else None,
-                                          ksize[1], opt(lut) if want_f32 else None, opt(windows), per_window, 1 if split else 0, N, Hs, Ws,
-                                          H, W, h_win, w_win, opt(u8), opt(f32), opt(ws), nws, stream_of(images_u8)),
-          'mode_images_u8_resize_pil')
+    _call('mode_images_u8_resize_pil', ptr(images_u8), _optr(tab_w) if ksize[0] else None, ksize[0], _optr(tab_h) if ksize[1] else None, ksize[1],
+          _optr(lut) if want_f32 else None, _optr(windows), per_window, 1 if split else 0, N, Hs, Ws, H, W, h_win, w_win, _optr(u8), _optr(f32), _optr(ws), nws,
+          stream_of(images_u8))
   return u8, f32
 
 
@@ -2195,8 +2177,8 @@ def disp_resize_nearest(disp, shape, rows, cols, ratio, windows=None, crop=None)
   h_win, w_win = _require_windows(windows, N, crop, (H, W), dev, who)
   out = torch.empty((N, h_win, w_win), dtype=torch.float32, device=dev)
   with torch.cuda.device_of(disp), profiling.region('disp_resize_nearest', 8 * out.numel(), out.numel(), dev):
-    check(lib().mode_disp_resize_nearest(ptr(disp), ptr(rows), ptr(cols), None if windows is None else ptr(windows), N, Hs, Ws, H, W, h_win,
-                                         w_win, float(ratio), ptr(out), stream_of(disp)), 'mode_disp_resize_nearest')
+    _call('mode_disp_resize_nearest', ptr(disp), ptr(rows), ptr(cols), _optr(windows), N, Hs, Ws, H, W, h_win, w_win,
+          float(ratio), ptr(out), stream_of(disp))
   return out
 
 
@@ -2204,7 +2186,7 @@ def _decimate2_fwd(x):
   H, W = x.shape[-2:]
   y = torch.empty(tuple(x.shape[:-2]) + ((H + 1) // 2, (W + 1) // 2), dtype=x.dtype, device=x.device)
   with torch.cuda.device_of(x), profiling.region('decimate2', 4 * (x.numel() // 2 + y.numel()), 0, x.device):
-    check(lib().mode_decimate2(ptr(x), ptr(y), x.numel() // (H * W), H, W, stream_of(x)), 'mode_decimate2')
+    _call('mode_decimate2', ptr(x), ptr(y), x.numel() // (H * W), H, W, stream_of(x))
   return y
 
 
@@ -2218,7 +2200,7 @@ def decimate2_bwd(gy, shape):
     raise ValueError('decimate2_bwd: gradient %s does not belong to an input of shape %s' % (tuple(gy.shape), tuple(shape)))
   gx = torch.empty(tuple(shape), dtype=gy.dtype, device=gy.device)
   with torch.cuda.device_of(gy), profiling.region('decimate2_bwd', 4 * (gy.numel() + gx.numel()), 0, gy.device):
-    check(lib().mode_decimate2_bwd(ptr(gy), ptr(gx), gx.numel() // (H * W), H, W, stream_of(gy)), 'mode_decimate2_bwd')
+    _call('mode_decimate2_bwd', ptr(gy), ptr(gx), gx.numel() // (H * W), H, W, stream_of(gy))
   return gx
 
 
@@ -2281,9 +2263,8 @@ def erp_pairs_u8_cassini(pairs_u8, grid, lut, flip=True, return_u8=False):
   u8 = torch.empty((N, 2, H, W, 3), dtype=torch.uint8, device=dev) if return_u8 else None
   nbytes = pairs_u8.numel() + 4 * grid.numel() + sum(4 * o.numel() for o in outs if o is not None) + (0 if u8 is None else u8.numel())
   with torch.cuda.device_of(pairs_u8), profiling.region('erp_pairs_u8_cassini', nbytes, 0, dev):
-    check(lib().mode_erp_pairs_u8_cassini(ptr(pairs_u8), ptr(grid), ptr(lut), N, He, We, H, W, G, ptr(outs[0]), ptr(outs[1]),
-                                          None if outs[2] is None else ptr(outs[2]), None if outs[3] is None else ptr(outs[3]),
-                                          None if u8 is None else ptr(u8), stream_of(pairs_u8)), 'mode_erp_pairs_u8_cassini')
+    _call('mode_erp_pairs_u8_cassini', ptr(pairs_u8), ptr(grid), ptr(lut), N, He, We, H, W, G, ptr(outs[0]), ptr(outs[1]),
+          _optr(outs[2]), _optr(outs[3]), _optr(u8), stream_of(pairs_u8))
   return outs[0], outs[1], outs[2], outs[3], u8
 
 
@@ -2308,9 +2289,8 @@ def erp_depth_disp(depth_erp, grid, cols, baseline, maxdepth, mirror=False, retu
   dc = torch.empty((N, H, W), dtype=torch.float32, device=dev) if return_depth else None
   nbytes = 4 * (depth_erp.numel() + grid.numel() + disp.numel() + (0 if dc is None else dc.numel()))
   with torch.cuda.device_of(depth_erp), profiling.region('erp_depth_disp', nbytes, 0, dev):
-    check(lib().mode_erp_depth_disp(ptr(depth_erp), ptr(grid), ptr(cols), N, He, We, H, W, G, float(baseline), float(maxdepth),
-                                    1 if mirror else 0, ptr(disp), None if dc is None else ptr(dc), stream_of(depth_erp)),
-          'mode_erp_depth_disp')
+    _call('mode_erp_depth_disp', ptr(depth_erp), ptr(grid), ptr(cols), N, He, We, H, W, G, float(baseline), float(maxdepth), 1 if mirror else 0,
+          ptr(disp), _optr(dc), stream_of(depth_erp))
   return (disp, dc) if return_depth else disp
 
 
@@ -2374,6 +2354,29 @@ def known_abs_max(t):
   return tag[0] if tag is not None and tag[1] == t._version and tag[2] == t.data_ptr() else None
 
 
+def _tag_amax(t, am):
+  """Leave the maximum buffer am (or nothing, when None) next to t for known_abs_max: valid until t is written or moves."""
+  if am is not None:
+    t._mode_amax = (am, t._version, t.data_ptr())
+
+
+def _amax_for_consumer(t, training, gradient=False):
+  """The producer's side of the fp16 arithmetic: a buffer for the kernel that writes t to leave t's maximum in, when the layer that
+  reads t next will want it -- else None (the plain call).  A producer knows the tensor, not the consumer's channel counts, so it asks
+  by rank: a 5-D tensor feeds the 3-D stack's stride-1 layers (the `f16` argument of _conv3d_route: CONV3D_S1_F16 in a training step,
+  CONV3D_EVAL_F16 in inference), a 4-D one the extractor's spherical layers (_sphere_f16_maxima's rule: 16 channels per MFMA;
+  SPHERE_FWD_F16 for an activation, SPHERE_BWD_F16 for a gradient; training only).
+  Kept as it was: the 3 x 3 layers' CONV2D_F16 is NOT asked here, though weight_maxima asks it -- with SPHERE_*_F16 off their operands'
+  maxima come from a pass (_tagged_abs_max)."""
+  if CONV_ARITH != 'bf16x6':
+    return None
+  if t.dim() == 5:
+    want = CONV3D_S1_F16 if training else CONV3D_EVAL_F16
+  else:
+    want = training and (SPHERE_BWD_F16 if gradient else SPHERE_FWD_F16) and t.dim() == 4 and t.shape[1] % 16 == 0
+  return torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=t.device) if want else None
+
+
 class BnActFunction(torch.autograd.Function):
   """out = relu?(batch_norm_train(y) [+ add]); running statistics updated in place (torch semantics)."""
 
@@ -2396,25 +2399,19 @@ class BnActFunction(torch.autograd.Function):
     coef = torch.empty((2, groups * C), dtype=torch.float32, device=y.device) if from_y else None
     nbytes = 4 * y.numel() * (3 + (1 if add is not None else 0))
     with torch.cuda.device_of(y), profiling.region(_tag_bn('bn_train_fwd', y), nbytes, 0, y.device):
-      common = (ptr(y), ptr(add) if add is not None else None, ptr(gamma), ptr(beta), ptr(running_mean) if running_mean is not None else None,
-                ptr(running_var) if running_var is not None else None, ptr(num_batches_tracked) if num_batches_tracked is not None else None,
-                float(momentum), float(eps), int(relu), ptr(out), ptr(mean), ptr(invstd), ptr(coef[0]) if from_y else None,
-                ptr(coef[1]) if from_y else None)
-      _bn_tls.out_amax = out_amax = None
-      if CONV_ARITH == 'bf16x6' and ((CONV3D_S1_F16 and y.dim() == 5) or (SPHERE_FWD_F16 and y.dim() == 4 and C % 16 == 0)):
-        # the 3-D stack's activations feed stride-1 convolutions on the fp16 arithmetic, the extractor's the spherical layers: their
-        # maximum comes out of this pass (the `_amax` entries; bn_act tags `out` with the buffer)
-        _bn_tls.out_amax = out_amax = torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=y.device)
+      common = (ptr(y), _optr(add), ptr(gamma), ptr(beta), _optr(running_mean), _optr(running_var), _optr(num_batches_tracked), float(momentum),
+                float(eps), int(relu), ptr(out), ptr(mean), ptr(invstd), ptr(coef[0]) if from_y else None, ptr(coef[1]) if from_y else None)
+      # the 3-D stack's activations feed stride-1 convolutions on the fp16 arithmetic, the extractor's the spherical layers: their
+      # maximum comes out of this pass (the `_amax` entries; bn_act tags `out` with the buffer)
+      _bn_tls.out_amax = out_amax = _amax_for_consumer(y, True)
       if prestats_ws is not None:  # the producing convolution left the statistics in the workspace (conv3d_bn_train): no statistics pass
         if groups != 1:
           raise RuntimeError('BatchNorm with precomputed statistics takes one statistics group')
-        check(lib().mode_bn_train_fwd_prestats_amax(*common, ptr(prestats_ws), lib().mode_conv3d_fwd_split_stats_partials(), B, C, S,
-                                                    ptr(out_amax) if out_amax is not None else None, stream_of(y)),
-              'mode_bn_train_fwd_prestats_amax')
+        _call('mode_bn_train_fwd_prestats_amax', *common, ptr(prestats_ws), lib().mode_conv3d_fwd_split_stats_partials(), B, C, S,
+              _optr(out_amax), stream_of(y))
       else:
         ws = _bn_ws(C * groups, y.device)
-        check(lib().mode_bn_train_fwd_amax(*common, ptr(ws), B, C, S, groups, ptr(out_amax) if out_amax is not None else None, stream_of(y)),
-              'mode_bn_train_fwd_amax')
+        _call('mode_bn_train_fwd_amax', *common, ptr(ws), B, C, S, groups, _optr(out_amax), stream_of(y))
     _written_by_kernel(running_mean, running_var, num_batches_tracked)
     ctx.save_for_backward(y, out if (relu and not from_y) else None, gamma, beta, mean, invstd, coef)
     ctx.relu, ctx.has_add, ctx.groups = bool(relu), add is not None, groups
@@ -2438,19 +2435,14 @@ class BnActFunction(torch.autograd.Function):
       nbytes = 4 * y.numel() * 7
     else:
       nbytes = 4 * y.numel() * (2 * (2 + (1 if out is not None else 0)) + 1 + (1 if need_gadd else 0))
-    gy_amax = None
-    if CONV_ARITH == 'bf16x6' and ((CONV3D_S1_F16 and y.dim() == 5) or (SPHERE_BWD_F16 and y.dim() == 4 and C % 16 == 0)):
-      gy_amax = torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=y.device)  # the convolution in front reads gy in both of its gradients
+    gy_amax = _amax_for_consumer(y, True, gradient=True)  # the convolution in front reads gy in both of its gradients
     with torch.cuda.device_of(y), profiling.region(_tag_bn('bn_train_bwd', y), nbytes, 0, y.device):
       ws = _bn_ws(C * ctx.groups, y.device)
-      check(lib().mode_bn_train_bwd_amax(ptr(gout), ptr(y), ptr(out) if out is not None else None, ptr(gamma), ptr(mean), ptr(invstd),
-                                         ptr(coef[0]) if coef is not None else None, ptr(coef[1]) if coef is not None else None, int(ctx.relu),
-                                         ptr(gy), ptr(gadd) if gadd is not None else None, ptr(ggamma), ptr(gbeta),
-                                         int(fused), ptr(ws), B, C, S, ctx.groups, ptr(gy_amax) if gy_amax is not None else None,
-                                         stream_of(y)), 'mode_bn_train_bwd_amax')
-    if gy_amax is not None:
-      gy._mode_amax = (gy_amax, gy._version, gy.data_ptr())  # (survives the engine's hand-over when the tensor's Python object does;
-    if fused:                                               #  Conv3dFunction.backward computes the maximum itself otherwise)
+      _call('mode_bn_train_bwd_amax', ptr(gout), ptr(y), _optr(out), ptr(gamma), ptr(mean), ptr(invstd), ptr(coef[0]) if coef is not None else None,
+            ptr(coef[1]) if coef is not None else None, int(ctx.relu), ptr(gy), _optr(gadd), ptr(ggamma), ptr(gbeta), int(fused), ptr(ws), B, C, S,
+            ctx.groups, _optr(gy_amax), stream_of(y))
+    _tag_amax(gy, gy_amax)  # (survives the engine's hand-over when the tensor's Python object does; Conv3dFunction.backward computes the
+    if fused:               #  maximum itself otherwise)
       ggamma = gbeta = None
     if ctx.has_add and not ctx.relu:
       gadd = gout  # the add passes the gradient through unchanged
@@ -2472,8 +2464,8 @@ def bn_eval(y, add, gamma, beta, running_mean, running_var, eps, relu):
   out = torch.empty_like(y)
   nbytes = 4 * y.numel() * (2 + (1 if add is not None else 0))
   with torch.cuda.device_of(y), profiling.region('bn_eval_fwd', nbytes, 0, y.device):
-    check(lib().mode_bn_eval_fwd(ptr(y), ptr(add) if add is not None else None, ptr(gamma), ptr(beta), ptr(running_mean),
-                                 ptr(running_var), float(eps), int(relu), ptr(out), B, C, S, stream_of(y)), 'mode_bn_eval_fwd')
+    _call('mode_bn_eval_fwd', ptr(y), _optr(add), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(eps),
+          int(relu), ptr(out), B, C, S, stream_of(y))
   return out
 
 
@@ -2501,7 +2493,7 @@ def bn_act(bn, y, add=None, relu=False, groups=1, add_carrier=None):
     am = getattr(_bn_tls, 'out_amax', None)
     if am is not None:
       _bn_tls.out_amax = None
-      out._mode_amax = (am, out._version, out.data_ptr())  # (a later in-place write to `out` invalidates it: known_abs_max checks)
+      _tag_amax(out, am)  # (a later in-place write to `out` invalidates it: known_abs_max checks)
     return out
   if torch.is_grad_enabled() and (y.requires_grad or bn.weight.requires_grad):
     # eval-mode BN inside a graph that needs gradients: rare (the reference never does it); vendor ops keep autograd correct
@@ -2547,11 +2539,9 @@ class ClassifHeadFunction(torch.autograd.Function):
     with torch.cuda.device_of(y), profiling.region(_tag3('classif_fwd', C, 1, 1, D, H, W), 4 * (2 * y.numel() + cost.numel() * (2 if add is not None else 1)),
                                                    2 * cost.numel() * C * 27, y.device):
       ws = torch.empty(max(lib().mode_classif_workspace_bytes(B, C, D, H, W) // 4, 1), dtype=torch.float32, device=y.device)
-      check(lib().mode_classif_train_fwd(ptr(y), ptr(gamma), ptr(beta), ptr(running_mean) if running_mean is not None else None,
-                                         ptr(running_var) if running_var is not None else None,
-                                         ptr(num_batches_tracked) if num_batches_tracked is not None else None, float(momentum), float(eps),
-                                         ptr(w), ptr(add) if add is not None else None, ptr(cost), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]),
-                                         ptr(saved[3]), ptr(ws), B, C, D, H, W, stream_of(y)), 'mode_classif_train_fwd')
+      _call('mode_classif_train_fwd', ptr(y), ptr(gamma), ptr(beta), _optr(running_mean), _optr(running_var), _optr(num_batches_tracked),
+            float(momentum), float(eps), ptr(w), _optr(add), ptr(cost), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(saved[3]), ptr(ws), B, C, D,
+            H, W, stream_of(y))
     _written_by_kernel(running_mean, running_var, num_batches_tracked)
     ctx.save_for_backward(y, w, gamma, beta, saved)
     ctx.has_add = add is not None
@@ -2572,14 +2562,10 @@ class ClassifHeadFunction(torch.autograd.Function):
     with torch.cuda.device_of(y), profiling.region(_tag3('classif_bwd', C, 1, 1, D, H, W), 4 * (3 * y.numel() + 4 * gcost.numel()),
                                                    2 * 3 * gcost.numel() * C * 27, y.device):
       ws = torch.empty(max(lib().mode_classif_workspace_bytes(B, C, D, H, W) // 4, 1), dtype=torch.float32, device=y.device)
-      gy_amax = None
-      if CONV3D_S1_F16 and CONV_ARITH == 'bf16x6':  # the 32 -> 32 convolution in front reads gy in both of its gradients (BnActFunction.backward)
-        gy_amax = torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=y.device)
-      check(lib().mode_classif_train_bwd_amax(ptr(gcost), ptr(y), ptr(w), ptr(gamma), ptr(beta), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]),
-                                              ptr(saved[3]), ptr(gy), ptr(gw), ptr(ggamma), ptr(gbeta), int(fused), ptr(ws), B, C, D, H, W,
-                                              ptr(gy_amax) if gy_amax is not None else None, stream_of(y)), 'mode_classif_train_bwd_amax')
-      if gy_amax is not None:
-        gy._mode_amax = (gy_amax, gy._version, gy.data_ptr())
+      gy_amax = _amax_for_consumer(y, True, gradient=True)  # the 32 -> 32 convolution in front reads gy in both of its gradients (BnActFunction.backward)
+      _call('mode_classif_train_bwd_amax', ptr(gcost), ptr(y), ptr(w), ptr(gamma), ptr(beta), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]),
+            ptr(saved[3]), ptr(gy), ptr(gw), ptr(ggamma), ptr(gbeta), int(fused), ptr(ws), B, C, D, H, W, _optr(gy_amax), stream_of(y))
+      _tag_amax(gy, gy_amax)
     if fused:
       gw = ggamma = gbeta = None
     return gy, gw, ggamma, gbeta, (gcost if ctx.has_add else None), None, None, None, None, None
@@ -2620,7 +2606,7 @@ class SppPoolFunction(torch.autograd.Function):
     ys = tuple(torch.empty((N, C, H // k, W // k), dtype=skip.dtype, device=skip.device) for k in SPP_KERNELS)
     with torch.cuda.device_of(skip), profiling.region('spp_pool_fwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_pool_fwd',
                                                       4 * (skip.numel() + sum(y.numel() for y in ys)), 0, skip.device):
-      check(lib().mode_spp_pool_fwd(ptr(skip), ptr(ys[0]), ptr(ys[1]), ptr(ys[2]), ptr(ys[3]), N * C, H, W, stream_of(skip)), 'mode_spp_pool_fwd')
+      _call('mode_spp_pool_fwd', ptr(skip), ptr(ys[0]), ptr(ys[1]), ptr(ys[2]), ptr(ys[3]), N * C, H, W, stream_of(skip))
     ctx.shape = tuple(skip.shape)
     ctx.set_materialize_grads(False)
     return ys + (skip,)
@@ -2652,8 +2638,7 @@ class SppPoolFunction(torch.autograd.Function):
     nbytes = 4 * (gskip.numel() * (2 if gslice is not None else 1) + sum(g.numel() for g in gs))
     with torch.cuda.device_of(gskip), profiling.region('spp_pool_bwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_pool_bwd', nbytes, 0,
                                                        gskip.device):
-      check(lib().mode_spp_pool_bwd(ptr(gslice) if gslice is not None else None, Cg, 0, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gskip),
-                                    N, C, H, W, stream_of(gskip)), 'mode_spp_pool_bwd')
+      _call('mode_spp_pool_bwd', _optr(gslice), Cg, 0, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gskip), N, C, H, W, stream_of(gskip))
     return gskip
 
 
@@ -2694,8 +2679,7 @@ class SppConcatFunction(torch.autograd.Function):
     out = torch.empty((N, Cr + Cs + 4 * Cb, H, W), dtype=skip.dtype, device=skip.device)
     with torch.cuda.device_of(skip), profiling.region('spp_concat_fwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_concat_fwd',
                                                       4 * (raw.numel() + skip.numel() + out.numel()), 0, skip.device):
-      check(lib().mode_spp_concat_fwd(ptr(raw), ptr(skip), ptr(b4), ptr(b3), ptr(b2), ptr(b1), ptr(out), N, Cr, Cs, Cb, H, W, stream_of(skip)),
-            'mode_spp_concat_fwd')
+      _call('mode_spp_concat_fwd', ptr(raw), ptr(skip), ptr(b4), ptr(b3), ptr(b2), ptr(b1), ptr(out), N, Cr, Cs, Cb, H, W, stream_of(skip))
     ctx.dims = (N, Cr, Cs, Cb, H, W)
     return out
 
@@ -2711,8 +2695,7 @@ class SppConcatFunction(torch.autograd.Function):
     nbytes = 4 * (2 * graw.numel() + 4 * N * Cb * H * W + sum(g.numel() for g in gbs))
     with torch.cuda.device_of(gcat), profiling.region('spp_concat_bwd[%dx%d]' % (H, W) if profiling.ENABLED else 'spp_concat_bwd', nbytes, 0,
                                                       gcat.device):
-      check(lib().mode_spp_concat_bwd(ptr(gcat), ptr(graw), ptr(gbs[0]), ptr(gbs[1]), ptr(gbs[2]), ptr(gbs[3]), N, Cr, Cs, Cb, H, W,
-                                      stream_of(gcat)), 'mode_spp_concat_bwd')
+      _call('mode_spp_concat_bwd', ptr(gcat), ptr(graw), ptr(gbs[0]), ptr(gbs[1]), ptr(gbs[2]), ptr(gbs[3]), N, Cr, Cs, Cb, H, W, stream_of(gcat))
     return (graw, gcat[:, Cr:Cr + Cs]) + tuple(gbs)
 
 
@@ -2734,7 +2717,7 @@ class MaxPool2x2Function(torch.autograd.Function):
     B, C, H, W = x.shape
     y = torch.empty((B, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
     with torch.cuda.device_of(x), profiling.region('maxpool2x2_fwd', 4 * (x.numel() + y.numel()), 0, x.device):
-      check(lib().mode_maxpool2x2_fwd(ptr(x), ptr(y), B * C, H, W, stream_of(x)), 'mode_maxpool2x2_fwd')
+      _call('mode_maxpool2x2_fwd', ptr(x), ptr(y), B * C, H, W, stream_of(x))
     ctx.save_for_backward(x)
     return y
 
@@ -2746,7 +2729,7 @@ class MaxPool2x2Function(torch.autograd.Function):
     B, C, H, W = x.shape
     gx = torch.empty_like(x)
     with torch.cuda.device_of(x), profiling.region('maxpool2x2_bwd', 4 * (2 * x.numel() + gy.numel()), 0, x.device):
-      check(lib().mode_maxpool2x2_bwd(ptr(x), ptr(gy), ptr(gx), B * C, H, W, stream_of(x)), 'mode_maxpool2x2_bwd')
+      _call('mode_maxpool2x2_bwd', ptr(x), ptr(gy), ptr(gx), B * C, H, W, stream_of(x))
     return gx
 
 
@@ -2772,7 +2755,7 @@ def _deconv2x2_gemm(x, w):
   with torch.cuda.device_of(x), profiling.region(_tag1('deconv2x2_gemm', Ci, R, 1, H, W), 4 * (x.numel() + y4.numel() + w.numel()),
                                                  2 * y4.numel() * Ci, x.device):
     wp = torch.empty(lib().mode_conv1x1_wpack_bytes(R, Ci) // 4, dtype=torch.float32, device=x.device)
-    check(lib().mode_conv1x1_bwd_data(ptr(x), ptr(w), ptr(y4), ptr(wp), B, R, H, W, Ci, 1, stream_of(x)), 'mode_conv1x1_bwd_data')
+    _call('mode_conv1x1_bwd_data', ptr(x), ptr(w), ptr(y4), ptr(wp), B, R, H, W, Ci, 1, stream_of(x))
   return y4
 
 
@@ -2781,8 +2764,7 @@ def _depth_to_space2(y4, scale, shift, relu):
   Co = R // 4
   y = torch.empty((B, Co, 2 * H, 2 * W), dtype=y4.dtype, device=y4.device)
   with torch.cuda.device_of(y4), profiling.region('depth_to_space2', 8 * y4.numel(), 0, y4.device):
-    check(lib().mode_depth_to_space2(ptr(y4), ptr(scale) if scale is not None else None, ptr(shift) if shift is not None else None, ptr(y),
-                                     B, Co, H, W, int(relu), stream_of(y4)), 'mode_depth_to_space2')
+    _call('mode_depth_to_space2', ptr(y4), _optr(scale), _optr(shift), ptr(y), B, Co, H, W, int(relu), stream_of(y4))
   return y
 
 
@@ -2816,22 +2798,21 @@ class Deconv2x2Function(torch.autograd.Function):
     R = 4 * Co
     g4 = torch.empty((B, R, H, W), dtype=gy.dtype, device=gy.device)
     with torch.cuda.device_of(gy), profiling.region('space_to_depth2', 8 * gy.numel(), 0, gy.device):
-      check(lib().mode_space_to_depth2(ptr(gy), ptr(g4), B, Co, H, W, stream_of(gy)), 'mode_space_to_depth2')
+      _call('mode_space_to_depth2', ptr(gy), ptr(g4), B, Co, H, W, stream_of(gy))
     gx = gw = gb = None
     if ctx.needs_input_grad[0]:  # gx[b, c, q] = sum_r w[c][r] g4[b, r, q]: a 1x1 convolution R -> Ci with the weight as it lies
       gx = torch.empty_like(x)
       with torch.cuda.device_of(x), profiling.region(_tag1('deconv2x2_bwd_data', R, Ci, 1, H, W), 4 * (gx.numel() + g4.numel() + w.numel()),
                                                      2 * g4.numel() * Ci, x.device):
         wp = torch.empty(lib().mode_conv1x1_wpack_bytes(R, Ci) // 4, dtype=torch.float32, device=x.device)
-        check(lib().mode_conv1x1_fwd(ptr(g4), ptr(w), ptr(gx), ptr(wp), B, R, H, W, Ci, 1, stream_of(x)), 'mode_conv1x1_fwd')
+        _call('mode_conv1x1_fwd', ptr(g4), ptr(w), ptr(gx), ptr(wp), B, R, H, W, Ci, 1, stream_of(x))
     if ctx.needs_input_grad[1]:  # gw[c][r] = sum x[b, c, q] g4[b, r, q]: the 1x1 weight gradient with "gy" := x, "x" := g4
       sink = grad_sink(w)
       gw = sink if sink is not None else torch.empty_like(w)
       with torch.cuda.device_of(x), profiling.region(_tag1('deconv2x2_bwd_weight', R, Ci, 1, H, W), 4 * (x.numel() + g4.numel() + w.numel()),
                                                      2 * g4.numel() * Ci, x.device):
         ws = torch.empty(max(lib().mode_conv1x1_bwd_weight_workspace_bytes(B, R, H, W, Ci, 1) // 4, 1), dtype=torch.float32, device=x.device)
-        check(lib().mode_conv1x1_bwd_weight(ptr(x), ptr(g4), ptr(gw), ptr(ws), B, R, H, W, Ci, 1, int(sink is not None), stream_of(x)),
-              'mode_conv1x1_bwd_weight')
+        _call('mode_conv1x1_bwd_weight', ptr(x), ptr(g4), ptr(gw), ptr(ws), B, R, H, W, Ci, 1, int(sink is not None), stream_of(x))
       if sink is not None:
         gw = None
     if ctx.has_bias and ctx.needs_input_grad[2]:
@@ -2872,8 +2853,7 @@ class Conv1x1SigmoidFunction(torch.autograd.Function):
     B, C, H, W = x.shape
     s = torch.empty((B, 1, H, W), dtype=x.dtype, device=x.device)
     with torch.cuda.device_of(x), profiling.region('conv1x1_sigmoid_fwd', 4 * (x.numel() + s.numel()), 2 * x.numel(), x.device):
-      check(lib().mode_conv1x1_sigmoid_fwd(ptr(x), ptr(w), ptr(bias) if bias is not None else None, ptr(s), B, C, H * W, stream_of(x)),
-            'mode_conv1x1_sigmoid_fwd')
+      _call('mode_conv1x1_sigmoid_fwd', ptr(x), ptr(w), _optr(bias), ptr(s), B, C, H * W, stream_of(x))
     ctx.save_for_backward(x, w, s)
     ctx.has_bias = bias is not None
     return s
@@ -2889,8 +2869,7 @@ class Conv1x1SigmoidFunction(torch.autograd.Function):
     gb = torch.empty(1, dtype=x.dtype, device=x.device) if ctx.has_bias else None
     with torch.cuda.device_of(x), profiling.region('conv1x1_sigmoid_bwd', 4 * (3 * x.numel() + 2 * s.numel()), 4 * x.numel(), x.device):
       ws = torch.empty(max(lib().mode_conv1x1_sigmoid_bwd_workspace_bytes(B, H * W) // 4, 1), dtype=torch.float32, device=x.device)
-      check(lib().mode_conv1x1_sigmoid_bwd(ptr(x), ptr(w), ptr(s), ptr(gs), ptr(gx) if gx is not None else None, ptr(gw),
-                                           ptr(gb) if gb is not None else None, 0, ptr(ws), B, C, H * W, stream_of(x)), 'mode_conv1x1_sigmoid_bwd')
+      _call('mode_conv1x1_sigmoid_bwd', ptr(x), ptr(w), ptr(s), ptr(gs), _optr(gx), ptr(gw), _optr(gb), 0, ptr(ws), B, C, H * W, stream_of(x))
     return gx, gw if ctx.needs_input_grad[1] else None, gb if (ctx.has_bias and ctx.needs_input_grad[2]) else None
 
 
@@ -2996,22 +2975,12 @@ def _epilogue(bn, add, relu, out):
     if tuple(add.shape) != tuple(out.shape):
       raise RuntimeError('residual input %s does not match the output %s' % (tuple(add.shape), tuple(out.shape)))
     keep.append(add)
-  e = BnEpilogue(ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(keep[3]), float(bn.eps), ptr(add) if add is not None else None, int(bool(relu)))
+  e = BnEpilogue(ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(keep[3]), float(bn.eps), _optr(add), int(bool(relu)))
   return e, keep
-
-
-def _eval_amax_buffer(device):
-  """The buffer an eval kernel leaves its output's maximum in -- or None (the plain call) when no eval layer runs on the fp16 arithmetic."""
-  return torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=device) if (CONV3D_EVAL_F16 and CONV_ARITH == 'bf16x6') else None
 
 
 def _optr(t):
   return ptr(t) if t is not None else None
-
-
-def _tag_amax(y, ay):
-  if ay is not None:
-    y._mode_amax = (ay, y._version, y.data_ptr())
 
 
 def conv3d_bn_eval(x, w, bn, stride=1, add=None, relu=False):
@@ -3026,34 +2995,27 @@ def conv3d_bn_eval(x, w, bn, stride=1, add=None, relu=False):
   flops = 2 * y.numel() * Ci * 27
   with torch.cuda.device_of(x), profiling.region(_tag3('conv3d_bn_eval', Ci, Co, stride, D, H, W), 4 * (x.numel() + y.numel() + w.numel()),
                                                  flops, x.device):
-    split = _split3d(Ci, Co, stride, 0, (D, H, W))
-    if stride == 1 and split and CONV3D_EVAL_F16:
+    route = _conv3d_route(Ci, Co, stride, 0, (D, H, W), CONV3D_EVAL_F16)
+    tag = {'f32': 'conv3d_fwd_bn s%d' % stride, 'split': 'conv3d_fwd_split', 'split_f16': 'conv3d_fwd_split_f16_bn', 's2_split': 'conv3d_fwd_s2_split'}
+    wp, reuse = _eval_wpack(bn, tag[route], w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
+    ax = ay = None
+    if route == 'split_f16':
       # two fp16 pieces (round 6): the input's maximum is the tag the producing eval kernel left (this one: y's below), else a pass;
       # the folded weights' maximum is taken inside the call, with the pack, and lives in the kept workspace
-      wp, reuse = _eval_wpack(bn, 'conv3d_fwd_split_f16_bn', w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
-      ax = _tagged_abs_max(x)
-      ay = torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=x.device)
-      with reuse:
-        check(lib().mode_conv3d_fwd_split_f16_bn(ptr(x), ptr(w), ptr(ax), ctypes.byref(e), ptr(y), ptr(ay), ptr(wp), B, Ci, D, H, W, Co,
-                                                 stream_of(x)), 'mode_conv3d_fwd_split_f16_bn')
-      y._mode_amax = (ay, y._version, y.data_ptr())
-    elif stride == 1 and split:
-      wp, reuse = _eval_wpack(bn, 'conv3d_fwd_split', w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
-      with reuse:
-        check(lib().mode_conv3d_fwd_split(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)),
-              'mode_conv3d_fwd_split')
-    elif stride == 2 and split:
-      wp, reuse = _eval_wpack(bn, 'conv3d_fwd_s2_split', w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
-      ay = _eval_amax_buffer(x.device)  # (the stride-1 layer behind it runs on the fp16 arithmetic: its operand maximum out of this epilogue)
-      with reuse:
-        check(lib().mode_conv3d_fwd_s2_split_amax(ptr(x), ptr(w), ctypes.byref(e), ptr(y), _optr(ay), ptr(wp), B, Ci, D, H, W, Co, stream_of(x)),
-              'mode_conv3d_fwd_s2_split_amax')
-      _tag_amax(y, ay)
-    else:
-      wp, reuse = _eval_wpack(bn, 'conv3d_fwd_bn s%d' % stride, w, lib().mode_conv3d_wpack_bytes(Ci, Co) // 4, x.device)
-      with reuse:
-        check(lib().mode_conv3d_fwd_bn(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, D, H, W, Co, stride, stream_of(x)),
-              'mode_conv3d_fwd_bn')
+      ax, ay = _tagged_abs_max(x), torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=x.device)
+    elif route == 's2_split':  # (the stride-1 layer behind it runs on the fp16 arithmetic: its operand maximum out of this epilogue)
+      ay = _amax_for_consumer(y, False)
+    tail = (ptr(wp), B, Ci, D, H, W, Co)
+    with reuse:
+      if route == 'split_f16':
+        _call('mode_conv3d_fwd_split_f16_bn', ptr(x), ptr(w), ptr(ax), ctypes.byref(e), ptr(y), ptr(ay), *tail, stream_of(x))
+      elif route == 'split':
+        _call('mode_conv3d_fwd_split', ptr(x), ptr(w), ctypes.byref(e), ptr(y), *tail, stream_of(x))
+      elif route == 's2_split':
+        _call('mode_conv3d_fwd_s2_split_amax', ptr(x), ptr(w), ctypes.byref(e), ptr(y), _optr(ay), *tail, stream_of(x))
+      else:
+        _call('mode_conv3d_fwd_bn', ptr(x), ptr(w), ctypes.byref(e), ptr(y), *tail, stride, stream_of(x))
+    _tag_amax(y, ay)
   return y
 
 
@@ -3067,20 +3029,18 @@ def deconv3d_bn_eval(x, w, bn, add=None, relu=False):
   e, keep = _epilogue(bn, add, relu, y)
   flops = 2 * x.numel() * Cout * 27
   with torch.cuda.device_of(x), profiling.region('deconv3d_bn_eval', 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
-    if lib().mode_deconv3d_split_bn_supported(Cin, Cout) == 1 and _deconv_split3d(Cin, Cout, (D, H, W)):
-      # (round 5: the split kernel with its own epilogue instantiation -- residual values of four channels requested ahead of their
-      # stores; round 3 had measured it no faster than the fp32 kernel with one load next to every store)
-      wp, reuse = _eval_wpack(bn, 'deconv3d_fwd_split_bn', w, lib().mode_conv3d_wpack_bytes(Cin, Cout) // 4, x.device)
-      ay = _eval_amax_buffer(x.device)
-      with reuse:
-        check(lib().mode_deconv3d_fwd_split_bn_amax(ptr(x), ptr(w), ctypes.byref(e), ptr(y), _optr(ay), ptr(wp), B, Cin, D, H, W, Cout,
-                                                    stream_of(x)), 'mode_deconv3d_fwd_split_bn_amax')
-      _tag_amax(y, ay)
-    else:
-      wp, reuse = _eval_wpack(bn, 'deconv3d_fwd_bn', w, lib().mode_conv3d_wpack_bytes(Cin, Cout) // 4, x.device)
-      with reuse:
-        check(lib().mode_deconv3d_fwd_bn(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Cin, D, H, W, Cout, stream_of(x)),
-              'mode_deconv3d_fwd_bn')
+    # (round 5: the split kernel with its own epilogue instantiation -- residual values of four channels requested ahead of their
+    # stores; round 3 had measured it no faster than the fp32 kernel with one load next to every store)
+    split = lib().mode_deconv3d_split_bn_supported(Cin, Cout) == 1 and _deconv_split3d(Cin, Cout, (D, H, W))
+    wp, reuse = _eval_wpack(bn, 'deconv3d_fwd_split_bn' if split else 'deconv3d_fwd_bn', w, lib().mode_conv3d_wpack_bytes(Cin, Cout) // 4, x.device)
+    ay = _amax_for_consumer(y, False) if split else None
+    tail = (ptr(wp), B, Cin, D, H, W, Cout, stream_of(x))
+    with reuse:
+      if split:
+        _call('mode_deconv3d_fwd_split_bn_amax', ptr(x), ptr(w), ctypes.byref(e), ptr(y), _optr(ay), *tail)
+      else:
+        _call('mode_deconv3d_fwd_bn', ptr(x), ptr(w), ctypes.byref(e), ptr(y), *tail)
+    _tag_amax(y, ay)
   return y
 
 
@@ -3094,28 +3054,22 @@ def conv2d_bn_eval(x, w, bn, dilation=1, add=None, relu=False):
   y = torch.empty((B, Co, H, W), dtype=x.dtype, device=x.device)
   e, keep = _epilogue(bn, add, relu, y)
   flops = 2 * y.numel() * Ci * 9
-  with torch.cuda.device_of(x), profiling.region('conv2d_bn_eval[%d->%d d%d %dx%d]' % (Ci, Co, dilation, H, W) if profiling.ENABLED
-                                                 else 'conv2d_bn_eval', 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
-    split = CONV_ARITH == 'bf16x6' and lib().mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 0) == 1
-    if split and CONV2D_EVAL_F16:
+  with torch.cuda.device_of(x), profiling.region(_tag2d('conv2d_bn_eval', Ci, Co, dilation, H, W), 4 * (x.numel() + y.numel() + w.numel()), flops,
+                                                 x.device):
+    route = _conv2d_route(Ci, Co, H, W, dilation, 0, CONV2D_EVAL_F16)
+    tag = {'f32': 'conv2d_fwd_bn', 'split': 'conv2d_fwd_split', 'split_f16': 'conv2d_fwd_split_f16_bn'}
+    wp, reuse = _eval_wpack(bn, tag[route], w, lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, x.device)
+    ax = ay = None
+    if route == 'split_f16':
       # two fp16 pieces (round 6): the input's maximum from its producer's tag (this kernel's own, in the residual blocks) or a pass
-      wp, reuse = _eval_wpack(bn, 'conv2d_fwd_split_f16_bn', w, lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, x.device)
-      ax = _tagged_abs_max(x)
-      ay = torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=x.device)
-      with reuse:
-        check(lib().mode_conv2d_fwd_split_f16_bn(ptr(x), ptr(w), ptr(ax), ctypes.byref(e), ptr(y), ptr(ay), ptr(wp), B, Ci, H, W, Co, dilation,
-                                                 stream_of(x)), 'mode_conv2d_fwd_split_f16_bn')
-      _tag_amax(y, ay)
-    elif split:
-      wp, reuse = _eval_wpack(bn, 'conv2d_fwd_split', w, lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, x.device)
-      with reuse:
-        check(lib().mode_conv2d_fwd_split(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(x)),
-              'mode_conv2d_fwd_split')
-    else:
-      wp, reuse = _eval_wpack(bn, 'conv2d_fwd_bn', w, lib().mode_conv2d_wpack_bytes(Ci, Co) // 4, x.device)
-      with reuse:
-        check(lib().mode_conv2d_fwd_bn(ptr(x), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, dilation, stream_of(x)),
-              'mode_conv2d_fwd_bn')
+      ax, ay = _tagged_abs_max(x), torch.empty(BN_ABSMAX_FLOATS, dtype=torch.float32, device=x.device)
+    tail = (ptr(wp), B, Ci, H, W, Co, dilation, stream_of(x))
+    with reuse:
+      if route == 'split_f16':
+        _call('mode_conv2d_fwd_split_f16_bn', ptr(x), ptr(w), ptr(ax), ctypes.byref(e), ptr(y), ptr(ay), *tail)
+      else:
+        _call('mode_conv2d_fwd_split' if route == 'split' else 'mode_conv2d_fwd_bn', ptr(x), ptr(w), ctypes.byref(e), ptr(y), *tail)
+    _tag_amax(y, ay)
   return y
 
 
@@ -3128,48 +3082,39 @@ def sphere_conv_bn_eval(x, pos, w, bn, stride, groups, add=None, relu=False, tra
   Co, _, Kh, Kw = w.shape
   if transposed:
     B, Ci, W, H = x.shape
-    y = torch.empty((B, Co, W, H), dtype=x.dtype, device=x.device)
+    plan = sphere_plan(pos, Kh, Kw) if (tuple(stride) == (1, 1) and Kh * Kw == 9) else None
+    if plan is None:
+      raise RuntimeError('sphere_conv_bn_eval: plane-transposed storage needs a plannable sampling table')
   else:
     B, Ci, H, W = x.shape
     Ho, Wo = (H - 1) // stride[0] + 1, (W - 1) // stride[1] + 1  # (the table carries padding / dilation: 'same' geometry)
-    y = None
-  plan = None
-  if tuple(stride) == (1, 1) and Kh * Kw == 9:
-    plan = sphere_plan(pos, Kh, Kw)
-    if plan is not None and not transposed:
-      n_wg = sum(plan[1]) * B * groups * (-(-(Co // groups) // 128))
-      if n_wg < SPHERE_FWD_MIN_WG:
-        plan = None
-  if transposed and plan is None:
-    raise RuntimeError('sphere_conv_bn_eval: plane-transposed storage needs a plannable sampling table')
-  if not transposed and not _plan_usable(plan) and tuple(stride) == (1, 1) and Kh * Kw == 9:
-    post = sphere_native_t(pos, Kh, Kw)
-    if post is not None and sphere_t_supported(post, w, B, groups):  # ERP-like table: NCHW storage is its transposed storage
-      return sphere_conv_bn_eval(x, post, w, bn, stride, groups, add, relu, transposed=True)
+    route, plan = _sphere_fwd_route(pos, w, B, groups, stride, True, honour_switch=False)  # (inference never read SPHERE_FWD)
+    if route == 'native_t':  # ERP-like table: NCHW storage is its transposed storage
+      return sphere_conv_bn_eval(x, plan, w, bn, stride, groups, add, relu, transposed=True)
   flops = 2 * B * Co * H * W // (stride[0] * stride[1]) * w[0].numel()
   name = 'sphere_conv_bn_eval[%d->%d %dx%d]' % (Ci, Co, H, W) if profiling.ENABLED else 'sphere_conv_bn_eval'
   with torch.cuda.device_of(x), profiling.region(name, 4 * (2 * x.numel() + w.numel()), flops, x.device):
     if plan is not None:
-      tiles, (n0, n1, n2) = plan[:2]
       wp, reuse = _eval_wpack(bn, 'sphere_fwd_win g%d %dx%d' % (groups, H, W), w,
                               lib().mode_sphere_conv_win_wpack_bytes(Ci, Co, Kh, Kw, groups) // 4, w.device)
-      if transposed:
-        e, keep = _epilogue(bn, add, relu, y)
-        with reuse:
-          _sphere_fwd_win(ptr(x), pos, w, e, ptr(y), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(x))
-      else:  # NCHW caller: the windowed kernel on plane-transposed copies (the residual is transposed with it)
-        xt, yt = transpose_planes(x), torch.empty((B, Co, W, H), dtype=x.dtype, device=x.device)
-        e, keep = _epilogue(bn, transpose_planes(add.contiguous()) if add is not None else None, relu, yt)
-        with reuse:
-          _sphere_fwd_win(ptr(xt), pos, w, e, ptr(yt), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(x))
-        y = transpose_planes(yt)
+      # an NCHW caller: the windowed kernel on plane-transposed copies (the residual is transposed with it)
+      xt = x if transposed else transpose_planes(x)
+      yt = torch.empty((B, Co, W, H), dtype=x.dtype, device=x.device)
+      e, keep = _epilogue(bn, add if transposed or add is None else transpose_planes(add.contiguous()), relu, yt)
     else:
+      wp, reuse = _eval_wpack(bn, 'sphere_conv_fwd_bn g%d' % groups, w, lib().mode_sphere_conv_wpack_bytes(w.shape[1] * groups, Co, Kh, Kw, groups) // 4,
+                              w.device)
       y = torch.empty((B, Co, Ho, Wo), dtype=x.dtype, device=x.device)
       e, keep = _epilogue(bn, add, relu, y)
-      wp, reuse = _eval_wpack(bn, 'sphere_conv_fwd_bn g%d' % groups, w, lib().mode_sphere_conv_wpack_bytes(w.shape[1] * groups, Co, Kh, Kw, groups) // 4, w.device)
-      with reuse:
-        check(lib().mode_sphere_conv_fwd_bn(ptr(x), ptr(pos), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, Kh, Kw, stride[0],
-                                            stride[1], Ho, Wo, groups, stream_of(x)), 'mode_sphere_conv_fwd_bn')
+    with reuse:
+      if plan is not None:
+        tiles, (n0, n1, n2) = plan[:2]
+        _sphere_fwd_win(ptr(xt), pos, w, e, ptr(yt), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(x))
+      else:
+        _call('mode_sphere_conv_fwd_bn', ptr(x), ptr(pos), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, Kh, Kw, stride[0], stride[1],
+              Ho, Wo, groups, stream_of(x))
+    if plan is not None:
+      y = yt if transposed else transpose_planes(yt)
   return y
 
 
@@ -3210,8 +3155,8 @@ def _tabled_bn(x, pos, w, bn, stride, add, relu, Ho, Wo):
   with torch.cuda.device_of(x), profiling.region(name, 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
     wp, reuse = _eval_wpack(bn, 'sphere_conv_fwd_bn g1', w, lib().mode_sphere_conv_wpack_bytes(w.shape[1], Co, Kh, Kw, 1) // 4, w.device)
     with reuse:
-      check(lib().mode_sphere_conv_fwd_bn(ptr(x), ptr(pos), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, Kh, Kw, stride[0],
-                                          stride[1], Ho, Wo, 1, stream_of(x)), 'mode_sphere_conv_fwd_bn')
+      _call('mode_sphere_conv_fwd_bn', ptr(x), ptr(pos), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, Kh, Kw, stride[0], stride[1], Ho,
+            Wo, 1, stream_of(x))
   return y
 
 
@@ -3225,8 +3170,7 @@ def cost_conv_bn_eval(ref, tgt, weight, d4, bn, relu=True):
   out = torch.empty((B, Co, d4, H, W), dtype=R.dtype, device=R.device)
   e, keep = _epilogue(bn, None, relu, out)
   with torch.cuda.device_of(R), profiling.region('cost_conv_assemble_fwd', 4 * (R.numel() + T.numel() + out.numel()), 0, R.device):
-    ay = _eval_amax_buffer(R.device)
-    check(lib().mode_cost_conv_assemble_fwd_bn_amax(ptr(R), ptr(T), ctypes.byref(e), ptr(out), _optr(ay), B, Co, d4, H, W, stream_of(R)),
-          'mode_cost_conv_assemble_fwd_bn_amax')
+    ay = _amax_for_consumer(out, False)
+    _call('mode_cost_conv_assemble_fwd_bn_amax', ptr(R), ptr(T), ctypes.byref(e), ptr(out), _optr(ay), B, Co, d4, H, W, stream_of(R))
     _tag_amax(out, ay)
   return out
