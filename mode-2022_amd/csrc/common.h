@@ -57,6 +57,16 @@ inline int allow_lds(K kernel, size_t bytes, const char* what) {
   return MODE_OK;
 }
 
+// One launch of a kernel with dynamic LDS -- the opt-in above 64 KiB, the launch, the launch check (launch_win of
+// sphere_win_internal.h with the block size as an argument).
+template <typename... P, typename... A>
+int launch_lds(const char* who, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  int rc = allow_lds(kernel, lds, who);
+  if (rc != MODE_OK) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return check_launch(who);
+}
+
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Fill `nwords` 32-bit words at `dst` (4-byte aligned) with `pattern` by a KERNEL on `st`.  The library never calls hipMemsetAsync:

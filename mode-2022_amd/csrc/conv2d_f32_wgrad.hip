@@ -10,8 +10,11 @@
 //   fragment feeds 9 MFMAs.  The next tile travels global -> registers under the MFMAs (same pipeline as conv3d_f32_wgrad.hip: loads
 //   unconditional from clamped addresses, masks at the LDS store, operands of k-step n+1 read before the MFMAs of step n).
 //   The four waves' sums are combined through LDS at the end; split-K partials are reduced in a fixed order: deterministic.
+// reduce_gw2d also reduces the partials of the split kernel (conv2d_split_wgrad.hip).  The C entries are in conv2d.hip.
 #include "common.h"
-#include "conv3d_internal.h"
+#include <string>
+
+#include "conv2d_internal.h"
 
 namespace {
 
@@ -229,106 +232,36 @@ __global__ __launch_bounds__(256) void reduce_gw2d(const float* __restrict__ par
   }
 }
 
-void make_dims(W2Dims& d, int B, int Ci, int H, int W, int Co) {
-  d.B = B; d.Ci = Ci; d.Co = Co; d.H = H; d.W = W;
-  d.nHt = mode::cdiv(H, TH);
-  d.nWt = mode::cdiv(W, 32);
-  d.T = B * d.nHt * d.nWt;
-  d.MTo = mode::cdiv(Co, 32);
-  d.MTc = mode::cdiv(Ci, 32);
-  int S = mode::cdiv(2 * kNumCU, d.MTo * d.MTc);
-  if (S > d.T) S = d.T;
-  d.S = S < 1 ? 1 : S;
-}
-
-template <int DIL>
-int launch(const float* gy, const float* x, float* workspace, const W2Dims& d, hipStream_t st, const char* who) {
-  const size_t lds = std::max(Geo<DIL>::LDS, (size_t)3 * 4 * 1024 * sizeof(float));  // tile buffers, reused by the final cross-wave sum
-  int rc = mode::allow_lds(conv2d_bwd_weight_kernel<DIL>, lds, who);
-  if (rc != MODE_OK) return rc;
-  hipLaunchKernelGGL(conv2d_bwd_weight_kernel<DIL>, dim3(d.S, d.MTo, d.MTc), dim3(NT), lds, st, gy, x, workspace, d);
-  return mode::check_launch(who);
-}
-
 }  // namespace
 
-extern "C" size_t mode_conv2d_bwd_weight_workspace_bytes(int B, int Ci, int H, int W, int Co) {
-  if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return 0;
-  W2Dims d;
-  make_dims(d, B, Ci, H, W, Co);
-  return (size_t)d.S * d.MTo * d.MTc * 9 * 1024 * sizeof(float);
+namespace mode {
+
+Wgrad2Grid conv2d_wgrad_grid(int B, int Ci, int H, int W, int Co) {
+  Wgrad2Grid g;
+  g.nHt = cdiv(H, TH);
+  g.nWt = cdiv(W, 32);
+  g.MTo = cdiv(Co, 32);
+  g.MTc = cdiv(Ci, 32);
+  g.S = std::max(1, std::min(cdiv(2 * kNumCU, g.MTo * g.MTc), B * g.nHt * g.nWt));  // two workgroups per CU, at most one per tile
+  return g;
 }
 
-extern "C" int mode_conv2d_bwd_weight(const float* gy, const float* x, float* gw, float* workspace, int B, int Ci, int H, int W, int Co,
-                                      int dilation, int accumulate, mode_stream_t stream) {
-  const char* who = "mode_conv2d_bwd_weight";
-  MODE_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && H > 0 && W > 0, MODE_ERR_BAD_ARG, "%s: non-positive size", who);
-  MODE_REQUIRE(dilation == 1 || dilation == 2, MODE_ERR_UNSUPPORTED, "%s: dilation %d not implemented (1 or 2)", who, dilation);
-  MODE_REQUIRE((long long)std::max(Ci, Co) * H * W < (1ll << 29), MODE_ERR_UNSUPPORTED, "%s: a sample larger than 2^29 elements", who);
-  hipStream_t st = mode::as_stream(stream);
-  if (B == 0) {
-    if (!accumulate) return mode::zero_floats(gw, (size_t)Co * Ci * 9, st, "mode_conv2d_bwd_weight");
-    return MODE_OK;
-  }
-  MODE_REQUIRE(gy && x && gw && workspace, MODE_ERR_BAD_ARG, "%s: null pointer", who);
-  W2Dims d;
-  make_dims(d, B, Ci, H, W, Co);
-  int rc = dilation == 1 ? launch<1>(gy, x, workspace, d, st, who) : launch<2>(gy, x, workspace, d, st, who);
-  if (rc != MODE_OK) return rc;
-  hipLaunchKernelGGL(reduce_gw2d, dim3(mode::cdiv((long long)d.MTo * d.MTc * 9 * 1024, 32)), dim3(256), 0, st, workspace, gw, d, accumulate);
-  return mode::check_launch("mode_conv2d_bwd_weight(reduce)");
+int conv2d_f32_wgrad_partials(const float* gy, const float* x, float* part, int B, int Ci, int H, int W, int Co, int dilation,
+                              hipStream_t st, const char* who, int* S) {
+  const Wgrad2Grid g = conv2d_wgrad_grid(B, Ci, H, W, Co);
+  const W2Dims d = {B, Ci, Co, H, W, g.nHt, g.nWt, B * g.nHt * g.nWt, g.S, g.MTo, g.MTc};
+  *S = g.S;
+  // tile buffers, reused by the final cross-wave sum
+  const size_t lds = std::max(dilation == 1 ? Geo<1>::LDS : Geo<2>::LDS, (size_t)3 * 4 * 1024 * sizeof(float));
+  return launch_lds(who, dilation == 1 ? conv2d_bwd_weight_kernel<1> : conv2d_bwd_weight_kernel<2>, dim3(d.S, d.MTo, d.MTc), dim3(NT), lds, st,
+                    gy, x, part, d);
 }
 
-static int conv2d_bwd_weight_split(const char* who, const float* gy, const float* x, const float* amax_g, const float* amax_x, float* gw,
-                                   float* workspace, int B, int Ci, int H, int W, int Co, int dilation, int accumulate, mode_stream_t stream);
-
-extern "C" int mode_conv2d_bwd_weight_split(const float* gy, const float* x, float* gw, float* workspace, int B, int Ci, int H, int W, int Co,
-                                            int dilation, int accumulate, mode_stream_t stream) {
-  return conv2d_bwd_weight_split("mode_conv2d_bwd_weight_split", gy, x, nullptr, nullptr, gw, workspace, B, Ci, H, W, Co, dilation, accumulate,
-                                 stream);
+int conv2d_wgrad_reduce(const float* part, float* gw, int Ci, int Co, int S, int accumulate, hipStream_t st, const char* who) {
+  W2Dims d = {};  // (reduce_gw2d reads the channel counts, their 32-blocks and the slices)
+  d.Ci = Ci; d.Co = Co; d.MTo = cdiv(Co, 32); d.MTc = cdiv(Ci, 32); d.S = S;
+  hipLaunchKernelGGL(reduce_gw2d, dim3(cdiv((long long)d.MTo * d.MTc * 9 * 1024, 32)), dim3(256), 0, st, part, gw, d, accumulate);
+  return check_launch((std::string(who) + "(reduce)").c_str());
 }
 
-// The same on the two-piece fp16 arithmetic (mode_conv2d_fwd_split_f16): amax_g / amax_x = the maximum buffers of gy and of x.
-extern "C" int mode_conv2d_bwd_weight_split_f16(const float* gy, const float* x, const float* amax_g, const float* amax_x, float* gw,
-                                                float* workspace, int B, int Ci, int H, int W, int Co, int dilation, int accumulate,
-                                                mode_stream_t stream) {
-  MODE_REQUIRE(amax_g && amax_x, MODE_ERR_BAD_ARG, "mode_conv2d_bwd_weight_split_f16: null maximum");
-  return conv2d_bwd_weight_split("mode_conv2d_bwd_weight_split_f16", gy, x, amax_g, amax_x, gw, workspace, B, Ci, H, W, Co, dilation, accumulate,
-                                 stream);
-}
-
-static int conv2d_bwd_weight_split(const char* who, const float* gy, const float* x, const float* amax_g, const float* amax_x, float* gw,
-                                   float* workspace, int B, int Ci, int H, int W, int Co, int dilation, int accumulate, mode_stream_t stream) {
-  MODE_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && H > 0 && W > 0, MODE_ERR_BAD_ARG, "%s: non-positive size", who);
-  MODE_REQUIRE(dilation == 1 || dilation == 2, MODE_ERR_UNSUPPORTED, "%s: dilation %d not implemented (1 or 2)", who, dilation);
-  MODE_REQUIRE(mode_conv2d_split_shape_supported(Ci, Co, H, W, dilation, 2) == 1, MODE_ERR_UNSUPPORTED,
-               "%s: %dx%d at %d -> %d channels is beyond the 32-bit offsets of the split kernel (mode_conv2d_split_shape_supported)", who, H, W, Ci,
-               Co);
-  hipStream_t st = mode::as_stream(stream);
-  if (B == 0) {
-    if (!accumulate) return mode::zero_floats(gw, (size_t)Co * Ci * 9, st, "mode_conv2d_bwd_weight");
-    return MODE_OK;
-  }
-  MODE_REQUIRE(gy && x && gw && workspace, MODE_ERR_BAD_ARG, "%s: null pointer", who);
-  W2Dims d;
-  make_dims(d, B, Ci, H, W, Co);
-  mode::Wgrad2SplitDims q;
-  q.Ci = Ci; q.Co = Co; q.H = H; q.W = W;
-  q.nWt = d.nWt; q.MTo = d.MTo; q.MTc = d.MTc;
-  q.nGroups = mode::cdiv(H, 4);
-  // one workgroup per CU and (o, c) block pair; a unit starts with an un-pipelined prologue, so runs as long as the image allows
-  // while every workgroup still gets a unit
-  int S = mode::cdiv(kNumCU, d.MTo * d.MTc);
-  int run = q.nGroups;
-  while (run > 4 && (long long)B * d.nWt * mode::cdiv(q.nGroups, run) < S) run = mode::cdiv(run, 2);
-  q.run_groups = run;
-  q.nRun = mode::cdiv(q.nGroups, run);
-  q.units = B * d.nWt * q.nRun;
-  if (S > q.units) S = q.units;
-  if (S > d.S) S = d.S;  // never more slices than the workspace query assumed
-  q.S = d.S = S;
-  int rc = mode::conv2d_bww_split_launch(gy, x, workspace, q, dilation, st, who, amax_g, amax_x);
-  if (rc != MODE_OK) return rc;
-  hipLaunchKernelGGL(reduce_gw2d, dim3(mode::cdiv((long long)d.MTo * d.MTc * 9 * 1024, 32)), dim3(256), 0, st, workspace, gw, d, accumulate);
-  return mode::check_launch("mode_conv2d_bwd_weight_split(reduce)");
-}
+}  // namespace mode

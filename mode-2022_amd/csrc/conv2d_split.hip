@@ -15,7 +15,8 @@
 #include "common.h"
 
 #include "bn_internal.h"
-#include "conv3d_internal.h"
+#include "conv2d_internal.h"
+#include "conv3d_internal.h"  // abs_max_folded
 #include "split_arith.h"
 
 namespace {
@@ -423,48 +424,17 @@ __global__ __launch_bounds__(NT) void conv2d_split_kernel(const float* __restric
   }
 }
 
-// The maximum buffer of an eval layer's FOLDED weights w[o][..] * scale[o] (what pack_w2d_split splits when fold == 1), one block: word 0
-// the value, the slots zero.  n = elements per output row.  (conv3d_split.hip has the same kernel for its layers.)
-__global__ __launch_bounds__(1024) void abs_max_folded2d_kernel(const float* __restrict__ w, mode_bn_epilogue bn, int rows, int n,
-                                                                unsigned* __restrict__ out) {
-  unsigned m = 0;
-  for (int i = threadIdx.x; i < rows * n; i += 1024) m = max(m, mode::absmax_mag(w[i] * fold_scale(bn, i / n)));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-  __shared__ unsigned sh[16];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-  for (int k = threadIdx.x + 1; k < MODE_BN_ABSMAX_FLOATS; k += 1024) out[k] = 0u;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned r = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r = max(r, sh[k]);
-    out[0] = r;
-  }
-}
-
 template <int MT, int TH, int DIL>
 int launch2(const float* x, const uint4* wp, float* y, S2Dims d, hipStream_t st, const char* who, Epi epi, const float* amax_x,
             const float* amax_w, int nblocks) {
   constexpr size_t LDS = Geo2<TH, DIL>::LDS_BYTES;
   d.nHt = mode::cdiv(d.H, TH);
   d.ntiles = d.B * d.nHt * d.nWt;
-  const int grid = kNumCU;
-#define MODE_C2D_LAUNCH(EPIV, F16V)                                                                                                  \
-  {                                                                                                                                  \
-    int rc = mode::allow_lds(conv2d_split_kernel<MT, TH, DIL, EPIV, F16V>, LDS, who);                                                \
-    if (rc != MODE_OK) return rc;                                                                                                    \
-    hipLaunchKernelGGL((conv2d_split_kernel<MT, TH, DIL, EPIV, F16V>), dim3(grid, nblocks), dim3(NT), LDS, st, x, wp, y, d, epi, amax_x, amax_w); \
-  }
-  if (epi.shift && epi.add) {
-    if (amax_x) MODE_C2D_LAUNCH(2, true) else MODE_C2D_LAUNCH(2, false)
-  } else if (epi.shift) {
-    if (amax_x) MODE_C2D_LAUNCH(1, true) else MODE_C2D_LAUNCH(1, false)
-  } else {
-    if (amax_x) MODE_C2D_LAUNCH(0, true) else MODE_C2D_LAUNCH(0, false)
-  }
-#undef MODE_C2D_LAUNCH
-  return mode::check_launch(who);
+  const int e = !epi.shift ? 0 : epi.add ? 2 : 1;  // EPI: plain store | folded BatchNorm | ... with a residual
+  const auto kernel =
+      amax_x ? (e == 2 ? conv2d_split_kernel<MT, TH, DIL, 2, true> : e == 1 ? conv2d_split_kernel<MT, TH, DIL, 1, true> : conv2d_split_kernel<MT, TH, DIL, 0, true>)
+             : (e == 2 ? conv2d_split_kernel<MT, TH, DIL, 2, false> : e == 1 ? conv2d_split_kernel<MT, TH, DIL, 1, false> : conv2d_split_kernel<MT, TH, DIL, 0, false>);
+  return mode::launch_lds(who, kernel, dim3(kNumCU, nblocks), dim3(NT), LDS, st, x, wp, y, d, epi, amax_x, amax_w);
 }
 
 template <int MT>
@@ -491,23 +461,17 @@ bool conv2d_split_supported(int K, int rows, int dilation) {
   return rows > 1 && rows <= 512 && K % 16 == 0 && (dilation == 1 || dilation == 2);
 }
 
-// rows = output channels of THIS GEMM (Co forward, Ci for the input gradient), K = its reduction channels; flip 0 / 1 as pack_w2d_split
+// rows = output channels of THIS GEMM (Co forward, Ci for the input gradient), K = its reduction channels; flip 0 / 1 as pack_w2d_split.
+// Sizes and pointers are the entry's to check (conv2d.hip); the rule here is which optional arguments come together.
 int conv2d_split_run(const float* x, const float* w, float* y, float* wpack, int B, int K, int rows, int H, int W, int dilation, int flip,
                      hipStream_t st, const char* who, const mode_bn_epilogue* bn, const float* acc_in, const float* amax_x,
                      const float* amax_w, float* amax_y) {
-  MODE_REQUIRE(B >= 0 && K > 0 && rows > 0 && H > 0 && W > 0, MODE_ERR_BAD_ARG, "%s: non-positive size", who);
   // eval mode on the fp16 arithmetic (bn, amax_x, amax_y; no amax_w): the weights' maximum is the FOLDED weights', taken with the pack
   // and kept in the workspace behind the shifts (conv3d_split.hip)
   const bool eval16 = amax_x && bn;
   MODE_REQUIRE(eval16 ? (!amax_w && amax_y && !acc_in && flip == 0) : ((amax_x == nullptr) == (amax_w == nullptr) && !amax_y), MODE_ERR_BAD_ARG,
                "%s: the fp16 arithmetic takes both operand maxima (eval epilogue: the input's and the output's)", who);
   MODE_REQUIRE(!(acc_in && bn), MODE_ERR_BAD_ARG, "%s: the accumulate form takes no BatchNorm epilogue", who);
-  MODE_REQUIRE(!acc_in || acc_in != y, MODE_ERR_BAD_ARG, "%s: acc must not be the output tensor", who);
-  MODE_REQUIRE(conv2d_split_supported(K, rows, dilation), MODE_ERR_UNSUPPORTED,
-               "%s: %d output / %d reduction channels, dilation %d not covered by the split kernel", who, rows, K, dilation);
-  MODE_REQUIRE(conv2d_split_fits(K, rows, (long long)H * W), MODE_ERR_UNSUPPORTED, "%s: a sample larger than 2^29 elements", who);
-  if (B == 0) return amax_y ? mode::absmax_begin(amax_y, st, who) : MODE_OK;
-  MODE_REQUIRE(x && w && y && wpack, MODE_ERR_BAD_ARG, "%s: null pointer", who);
   S2Dims d;
   d.B = B; d.K = K; d.Co = rows; d.H = H; d.W = W;
   d.NCHUNK = K / 16;
@@ -519,7 +483,8 @@ int conv2d_split_run(const float* x, const float* w, float* y, float* wpack, int
   if (eval16) amax_w = wmax;
   if (mode::pack_needed()) {
     if (eval16) {
-      hipLaunchKernelGGL(abs_max_folded2d_kernel, dim3(1), dim3(1024), 0, st, w, *bn, rows, K * 9, reinterpret_cast<unsigned*>(wmax));
+      int rc = abs_max_folded(w, *bn, rows, K * 9, wmax, st, who);
+      if (rc != MODE_OK) return rc;
       hipLaunchKernelGGL(pack_w2d_split<true>, dim3(cdiv(npack, 256)), dim3(256), 0, st, w, wp, rows, K, MT, d.NCHUNK, flip, 1, *bn, wmax);
     } else if (amax_x)
       hipLaunchKernelGGL(pack_w2d_split<true>, dim3(cdiv(npack, 256)), dim3(256), 0, st, w, wp, rows, K, MT, d.NCHUNK, flip, acc_in ? 2 : 0,

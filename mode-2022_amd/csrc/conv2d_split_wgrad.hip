@@ -12,11 +12,11 @@
 // global -> registers -> LDS inside the MFMA stream of the current one (loads under the first K-step, split + stores under the
 // second), one LDS-only barrier per group.  A tap's fragment starts kw * d elements into an aligned group of 8: ds_read_b128 +
 // ds_read_b64 per (kh, piece) and one v_perm_b32 per dword for the shifted taps.  Split-K partials and their reduction are shared
-// with the fp32 kernel (conv2d_wgrad.hip).
+// with the fp32 kernel (conv2d_f32_wgrad.hip).
 #include "common.h"
 
 #include "bn_internal.h"
-#include "conv3d_internal.h"
+#include "conv2d_internal.h"
 #include "split_arith.h"
 
 namespace {
@@ -327,20 +327,9 @@ namespace mode {
 
 int conv2d_bww_split_launch(const float* gy, const float* x, float* part, const Wgrad2SplitDims& d, int dilation, hipStream_t st,
                             const char* who, const float* amax_g, const float* amax_x) {
-#define MODE_C2W_LAUNCH(DILV, F16V)                                                                                              \
-  {                                                                                                                              \
-    int rc = allow_lds(conv2d_bww_split_kernel<DILV, F16V>, LDS_BYTES, who);                                                     \
-    if (rc != MODE_OK) return rc;                                                                                                \
-    hipLaunchKernelGGL((conv2d_bww_split_kernel<DILV, F16V>), dim3(d.S, d.MTo, d.MTc), dim3(NT), LDS_BYTES, st, gy, x, part, d, amax_g, \
-                       amax_x);                                                                                                  \
-  }
-  if (dilation == 1) {
-    if (amax_g) MODE_C2W_LAUNCH(1, true) else MODE_C2W_LAUNCH(1, false)
-  } else {
-    if (amax_g) MODE_C2W_LAUNCH(2, true) else MODE_C2W_LAUNCH(2, false)
-  }
-#undef MODE_C2W_LAUNCH
-  return check_launch(who);
+  const auto kernel = dilation == 1 ? (amax_g ? conv2d_bww_split_kernel<1, true> : conv2d_bww_split_kernel<1, false>)
+                                    : (amax_g ? conv2d_bww_split_kernel<2, true> : conv2d_bww_split_kernel<2, false>);
+  return launch_lds(who, kernel, dim3(d.S, d.MTo, d.MTc), dim3(NT), LDS_BYTES, st, gy, x, part, d, amax_g, amax_x);
 }
 
 }  // namespace mode

@@ -5,16 +5,6 @@
 
 namespace mode {
 
-// Host: one launch of a kernel with dynamic LDS -- the opt-in above 64 KiB, the launch, the launch check (launch_win of
-// sphere_win_internal.h with the block size as an argument).
-template <typename... P, typename... A>
-int launch_lds(const char* who, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
-  int rc = allow_lds(kernel, lds, who);
-  if (rc != MODE_OK) return rc;
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
-  return check_launch(who);
-}
-
 #pragma GCC visibility push(hidden)  // (what moved out of conv3d.hip's anonymous namespace stays out of the library's dynamic symbols)
 // conv3d_f32_fwd.hip: the 3x3x3 layers on the fp32 MFMA.  rows = output channels of THIS GEMM (Co for forward, Ci for backward-data),
 // K = its reduction channels; flip selects how `w` is indexed (pack_w3d: 0 forward, 1 backward-data); bn: the folded-BatchNorm
@@ -87,6 +77,11 @@ int conv3d_s1_split(const float* x, const float* w, float* y, float* wpack, int 
 // out[0] (device) = the largest magnitude in x[0..n): the scale source of the fp16 arithmetic (order-independent, graph-capturable)
 int abs_max(const float* x, long long n, float* out, hipStream_t st, const char* who);
 int abs_max_batch(const float* const* ptrs, const long long* sizes, int n, float* out, hipStream_t st, const char* who);
+#pragma GCC visibility push(hidden)
+// out (MODE_BN_ABSMAX_FLOATS floats) = the maximum buffer of an eval layer's FOLDED weights w[o][..] * gamma[o] / sqrt(var[o] + eps): what
+// the split packs split when they fold `bn`.  w is (rows, n); one block (also conv2d_split.hip's eval layers).
+int abs_max_folded(const float* w, const mode_bn_epilogue& bn, int rows, int n, float* out, hipStream_t st, const char* who);
+#pragma GCC visibility pop
 
 // conv3d_split_s2.hip: the stride-2 forward (= input gradient of the transposed convolution) on the same arithmetic; rows = output
 // channels (33..64), K = reduction channels (multiple of 8); w is (rows, K, 27); wpack >= conv3d_s2_split_wpack_floats(K, rows).
@@ -124,25 +119,5 @@ struct WgradS2SplitDims {
   int S, MTo, MTc;
 };
 int conv3d_bww_s2_split_launch(const float* gy, const float* x, float* part, const WgradS2SplitDims& d, hipStream_t st, const char* who);
-
-// conv2d_split.hip: the regular 3x3 Conv2d layers (stride 1, dilation 1 / 2) on the split-bf16 matrix path; arguments as conv2d.hip's
-// run() (rows = output channels of the GEMM, K = its reduction channels, flip 0 forward / 1 input gradient).
-bool conv2d_split_supported(int K, int rows, int dilation);
-size_t conv2d_split_wpack_floats(int K, int rows);
-int conv2d_split_run(const float* x, const float* w, float* y, float* wpack, int B, int K, int rows, int H, int W, int dilation, int flip,
-                     hipStream_t st, const char* who, const mode_bn_epilogue* bn, const float* acc_in = nullptr,
-                     const float* amax_x = nullptr, const float* amax_w = nullptr, float* amax_y = nullptr);
-// acc_in: y = conv(x) + acc_in.  amax_x / amax_w: the two-piece fp16 arithmetic.  With bn (eval): amax_x and amax_y (the stored output's
-// maximum, out), no amax_w -- the folded weights' maximum is taken with the pack and kept in wpack.
-
-// conv2d_split_wgrad.hip: split-K partials of the 3x3 Conv2d weight gradient on the split-bf16 path, in the layout of conv2d_wgrad.hip
-// (part[s][o / 32][c / 32][tap][o % 32][c % 32]); the caller reduces them.
-struct Wgrad2SplitDims {
-  int Ci, Co, H, W;
-  int nWt, nGroups, run_groups, nRun, units;  // units = B * nWt * nRun runs of run_groups 4-row groups x 32 columns
-  int S, MTo, MTc;
-};
-int conv2d_bww_split_launch(const float* gy, const float* x, float* part, const Wgrad2SplitDims& d, int dilation, hipStream_t st,
-                            const char* who, const float* amax_g = nullptr, const float* amax_x = nullptr);
 
 }  // namespace mode

@@ -689,6 +689,11 @@ int abs_max(const float* x, long long n, float* out, hipStream_t st, const char*
   return mode::check_launch(who);
 }
 
+int abs_max_folded(const float* w, const mode_bn_epilogue& bn, int rows, int n, float* out, hipStream_t st, const char* who) {
+  hipLaunchKernelGGL(abs_max_folded_kernel, dim3(1), dim3(1024), 0, st, w, bn, rows, n, reinterpret_cast<unsigned*>(out));
+  return check_launch(who);
+}
+
 size_t conv3d_split_wpack_floats(int K, int rows) {
   return (size_t)cdiv(rows, 32) * cdiv(K, 8) * NPAIR * 3 * 64 * 4 + 32 * (size_t)cdiv(rows, 32);
 }
@@ -733,7 +738,8 @@ int conv3d_s1_split(const float* x, const float* w, float* y, float* wpack, int 
     float* wmax = wpack + npack * NP * 4 + 32 * d.MT;  // (npack * 4 >= 3 584 floats of the third piece's room: MODE_BN_ABSMAX_FLOATS fit)
     static_assert(NPAIR * 64 * 4 >= MODE_BN_ABSMAX_FLOATS + 64, "the folded weights' maximum does not fit behind the shifts");
     if (mode::pack_needed()) {
-      hipLaunchKernelGGL(abs_max_folded_kernel, dim3(1), dim3(1024), 0, st, w, *bn, rows, K * 27, reinterpret_cast<unsigned*>(wmax));
+      int rc = abs_max_folded(w, *bn, rows, K * 27, wmax, st, who);
+      if (rc != MODE_OK) return rc;
       hipLaunchKernelGGL(pack_w3d_split<true>, dim3(cdiv(npack, 256)), dim3(256), 0, st, w, reinterpret_cast<uint4*>(wpack), rows, K, d.MT, d.NCHUNK,
                          flip, 1, *bn, wmax);
     }

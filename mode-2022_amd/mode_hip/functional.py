@@ -199,7 +199,7 @@ def _conv2d_own(x, w):
 def conv2d_wgrad_supported(x, w, dilation=1):
   """Whether conv2d_bwd_weight has a kernel that is right at this size: the split kernel inside its 32-bit contracts
   (_conv2d_route, which 2), else the fp32 kernel, which addresses a sample with 32-bit lane offsets
-  (csrc/conv2d_wgrad.hip: max(Ci, Co) * H * W < 2^29)."""
+  (csrc/conv2d_f32_wgrad.hip; the entry in conv2d.hip refuses max(Ci, Co) * H * W >= 2^29)."""
   co, ci, H, W = int(w.shape[0]), int(w.shape[1]), int(x.shape[2]), int(x.shape[3])
   return _conv2d_route(ci, co, H, W, dilation, 2, False) != 'f32' or max(co, ci) * H * W < 2**29
 
@@ -938,7 +938,7 @@ def conv2d_3x3_s2_supported(x, conv):
 
 class Conv2d3x3S2Function(torch.autograd.Function):
   """Forward on the integer-table gather kernel; both gradients as stride-1 gradients of the zero-inserted output gradient, on the
-  MFMA kernels of the stride-1 layers (csrc/conv2d.hip, conv2d_wgrad.hip)."""
+  MFMA kernels of the stride-1 layers (csrc/conv2d_f32_fwd.hip, conv2d_f32_wgrad.hip; or their split twins)."""
 
   @staticmethod
   def forward(ctx, x, w):
@@ -1362,7 +1362,7 @@ def _wpack3d(ci, co, device):
 #            the rounding of an fp32 convolution -- measured against float64 they are at least as close as the fp32 MFMA kernels' on
 #            the same inputs (tests/test_gpu_split.py) -- at 1.5-2 x their speed.  Layers the split kernels do not cover (stride 2,
 #            transposed, single-channel heads, channel counts off their grid) run on the fp32 kernels.
-#   'f32'    v_mfma_f32_32x32x2_f32 everywhere (csrc/conv3d_f32_fwd.hip, conv3d_f32_wgrad.hip, conv2d.hip).
+#   'f32'    v_mfma_f32_32x32x2_f32 everywhere (csrc/conv3d_f32_fwd.hip, conv3d_f32_wgrad.hip, conv2d_f32_fwd.hip, conv2d_f32_wgrad.hip).
 # Process-wide, read at call time (bench.py --conv-arith; the parity tests run under both).
 CONV_ARITH = 'bf16x6'
 

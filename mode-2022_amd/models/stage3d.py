@@ -48,7 +48,7 @@ def conv3(conv, x, carrier=None):
   if type(conv) is nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.groups == 1 and \
       conv.bias is None and conv.padding == conv.dilation and conv.dilation in ((1, 1), (2, 2)) and conv.padding_mode == 'zeros' and \
       x.dtype == torch.float32 and x.is_cuda:
-    # regular stride-1 3x3 layer of the 2-D extractor: own kernels (csrc/conv2d.hip, conv2d_wgrad.hip)
+    # regular stride-1 3x3 layer of the 2-D extractor: own kernels (csrc/conv2d_f32_fwd.hip, conv2d_f32_wgrad.hip, conv2d_split*.hip)
     if torch.is_grad_enabled() and (conv.weight.requires_grad or x.requires_grad):
       if HF.conv2d_wgrad_supported(x, conv.weight):
         return HF.conv2d_3x3(x.contiguous(), conv.weight, conv.dilation[0], carrier)

@@ -34,7 +34,7 @@ The eval instantiations, read from the launch code of csrc/*, and the case that 
                           (mode_sphere_conv_fwd_win_split)                                            sphere * route split
   conv3d.hip            the fp32 MFMA kernels' folded forms: stride 1, stride 2 (mode_conv3d_fwd_bn), transposed with one and two
                           output tiles (mode_deconv3d_fwd_bn)                                         conv3d_s1 | conv3d_s2 | deconv3d * route f32
-  conv2d.hip            the fp32 3 x 3 kernel, dilation 1 | 2 (mode_conv2d_fwd_bn)                    conv2d * route f32
+  conv2d_f32_fwd.hip    the fp32 3 x 3 kernel, dilation 1 | 2 (mode_conv2d_fwd_bn)                    conv2d * route f32
   conv1x1.hip           the 1 x 1 GEMM, stride 1 | 2, channels off the 8 / 32 blocks (mode_conv1x1_fwd_bn)    conv2d_gen k = 1
   conv_stem.hip         the 7 x 7 stride-2 stem (mode_conv_stem_fwd_bn)                               conv2d_gen k = 7
   sphere_conv.hip       the general gather kernel with the epilogue (mode_sphere_conv_fwd_bn): integer tables (3 x 3 stride 2, 5 x 5),

@@ -673,7 +673,7 @@ def test_conv2d_on_the_integer_table(B, Ci, Co, H, W, k, s, p, d):
   from models import stage3d
   with torch.no_grad():
     via_module = stage3d.conv3(conv, x.to(DEV))
-  if (k, s, p) == (3, 1, d) or k in (1, 7):  # layers with kernels of their own (conv2d.hip, conv1x1.hip, conv_stem.hip): same
+  if (k, s, p) == (3, 1, d) or k in (1, 7):  # layers with kernels of their own (conv2d_f32_fwd.hip, conv1x1.hip, conv_stem.hip): same
     assert (via_module - y.detach()).abs().max() < tol * max(1.0, float(y_ref.abs().max()))  # result up to summation order
   else:
     assert torch.equal(via_module, y.detach())
