@@ -763,6 +763,56 @@ int mode_multiview_handoff_bwd_full(const float* disp, const float* gout, const 
                                     const float* trig, const double* xforms, const int32_t* adj_rowptr, const int32_t* adj_target,
                                     const float* adj_weight, int n_adj, int flags, float* gdisp, float* gconf, mode_stream_t stream);
 
+/* The hand-off for any camera rig (csrc/multiview_rig.hip): the contract of the four entries above with 6 -> P.  A frame has P pairs,
+ * 1 <= P <= MODE_MV_MAX_PAIRS, of any kind in any order, described by P host records:
+ *   kind      MODE_MV_IDENTITY  the sine rule alone                                  (as pair 12 above)
+ *             MODE_MV_ROTATE    + the bilinear border gather on rot_grids[table]      (as pairs 13, 14)
+ *             MODE_MV_VIEW      + the view transform xforms[table] with its z-buffer  (as pairs 23, 24, 34)
+ *   table     the pair's index into rot_grids, 0 <= table < R, or into xforms and the key planes, 0 <= table < V; ignored for
+ *             MODE_MV_IDENTITY.  The R rotate pairs name R different grids and the V view pairs V different transforms
+ *   baseline  of the pair
+ * disp, conf (F, P, H, W) -> out (F, 2P, H, W) with out[f, 2p] = depth, out[f, 2p + 1] = q(confidence), or (F, P, H, W) of the depths
+ * under MODE_MV_DEPTH_ONLY; MODE_MV_CONF_PNG as above.  Every plane has the bits the single-map entries give for its pair.
+ *   R, rot_grids  the number of rotate pairs and their grids, device (R, H, W, 2), 8-byte aligned; NULL when R == 0
+ *   V, xforms     the number of view pairs and their V x (R[9] row-major, t[3]), host; NULL when V == 0
+ *   trig          device, as mode_depth_view_trans; NULL when V == 0
+ *   workspace     device, 8-byte aligned, >= mode_multiview_rig_handoff_workspace_bytes(F, V, H, W) = V F H W 8 bytes: key plane
+ *                 (f, table) at word (f V + table) H W.  With V == 0 it may be NULL, and neither the fill nor the resolve is launched
+ *                 (one launch; three otherwise, whatever F and P are).  The _bytes entry returns 0 for sizes the entries refuse
+ * The gradient entries take the forward's records, trig and xforms, the key planes it left behind (NULL when V == 0) and the adjoint
+ * lists of the R grids: adj_rowptr device int32 (R, H W + 1), offsets into adj_target / adj_weight of n_adj <= 4 R H W entries (NULL
+ * when R == 0).  Two launches, one when V == 0; no atomics, no memset, every element of gdisp (and gconf) (F, P, H, W) written.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for P < 1 or P > MODE_MV_MAX_PAIRS, an unknown kind, R or V that is not the
+ * number of pairs of that kind, a table index out of range or named twice, NULL pointers, unknown flags, H, W <= 0, F < 0 or
+ * 2 P F H W >= 2^31; MODE_ERR_WORKSPACE for a missing or unaligned workspace / key planes when V > 0; _bwd_full refuses
+ * MODE_MV_DEPTH_ONLY and MODE_MV_CONF_PNG as the entry above does.  F = 0 is a no-op.  What the device arrays hold cannot be checked,
+ * as above. */
+#define MODE_MV_MAX_PAIRS 16
+#define MODE_MV_IDENTITY 0
+#define MODE_MV_ROTATE 1
+#define MODE_MV_VIEW 2
+typedef struct mode_mv_pair {
+  int32_t kind;
+  int32_t table;
+  float baseline;
+} mode_mv_pair;
+
+size_t mode_multiview_rig_handoff_workspace_bytes(int F, int V, int H, int W);
+
+int mode_multiview_rig_handoff(const float* disp, const float* conf, int F, int P, int H, int W, const mode_mv_pair* pairs, int R,
+                               const float* rot_grids, const float* trig, int V, const double* xforms, int flags, float* out,
+                               void* workspace, mode_stream_t stream);
+
+int mode_multiview_rig_handoff_bwd(const float* disp, const float* gout, const void* keys, int F, int P, int H, int W,
+                                   const mode_mv_pair* pairs, int R, const float* trig, int V, const double* xforms,
+                                   const int32_t* adj_rowptr, const int32_t* adj_target, const float* adj_weight, int n_adj, int flags,
+                                   float* gdisp, mode_stream_t stream);
+
+int mode_multiview_rig_handoff_bwd_full(const float* disp, const float* gout, const void* keys, int F, int P, int H, int W,
+                                        const mode_mv_pair* pairs, int R, const float* trig, int V, const double* xforms,
+                                        const int32_t* adj_rowptr, const int32_t* adj_target, const float* adj_weight, int n_adj,
+                                        int flags, float* gdisp, float* gconf, mode_stream_t stream);
+
 /* Training forward of convbn_3d (models/submodule.py:20-22) without the statistics pass: the stride-1 split-bf16 convolution kernel
  * takes the BatchNorm batch statistics of its output from the accumulators (per channel: sum(y - K), sum((y - K)^2), K = the layer's own
  * first output value) and leaves them in `stats` = the BatchNorm workspace (>= mode_bn_workspace_bytes(Co) bytes) as

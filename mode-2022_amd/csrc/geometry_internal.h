@@ -1,5 +1,5 @@
 // Per-pixel arithmetic of the export-stage geometry, shared by the single-map entries (geometry.hip) and the batched multi-view
-// hand-off (multiview.hip).  Every helper here is a piece of one of geometry.hip's kernels moved out of it unchanged, so whatever
+// hand-off (multiview.hip; multiview_rig.hip for any camera rig).  Every helper here is a piece of one of geometry.hip's kernels moved out of it unchanged, so whatever
 // includes this header computes the old entries' bits (DESIGN 12 records the instruction-stream comparison of the move).
 // (One later addition, bilinear_border_exact / bilinear_sum_exact for erp_ingest.hip, is new arithmetic beside them; it changes none.)
 // Contraction: the helpers carry no fp-contract pragma of their own except project_pixel's (which was there before); do not add one

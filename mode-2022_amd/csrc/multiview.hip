@@ -8,16 +8,18 @@
 //   23 24 34  the sine rule + depthViewTransWithConf with its z-buffer   (mode_disp2depth + mode_depth_view_trans)
 // and writes out[f, 2p] = depth, out[f, 2p + 1] = q(confidence) -- ModeFusion's channel interleave -- or out[f, p] = depth alone
 // (MODE_MV_DEPTH_ONLY, the Baseline's input).  q is the identity, or with MODE_MV_CONF_PNG the 8-bit PNG round trip of the
-// reference's export (conf_png below).
+// reference's export (conf_png, multiview_internal.h).
 //   launch 1  every key plane of the three view-transformed maps of every frame = +inf (mode::fill_words)
 //   launch 2  one thread per SOURCE pixel of the F x 6 disparity maps
 //   launch 3  one thread per TARGET pixel of the F x 3 view-transformed maps
 #include "common.h"
 #include "geometry_internal.h"
+#include "multiview_internal.h"
 
 namespace {
 
 namespace geom = mode::geom;
+using namespace mode::mv;  // conf_png, sine_rule_raw, sine_rule_slope (shared with multiview_rig.hip)
 constexpr int NT = 256;
 
 struct MvArgs {
@@ -26,13 +28,6 @@ struct MvArgs {
   int png;                 // MODE_MV_CONF_PNG
   int oc;                  // output channels per pair: 2 (depth, confidence) or 1 (MODE_MV_DEPTH_ONLY)
 };
-
-// The reference writes the confidence as an 8-bit PNG (cv2.imwrite(conf * 255): float32 product, saturate_cast<uchar> = round half
-// to even and clamp) and reads it back as / 255.0 in float64, cast to float32 by the fusion loader.  NaN reads back as 0.
-__device__ __forceinline__ float conf_png(float c) {
-  const float r = fminf(255.f, fmaxf(0.f, rintf(c * 255.0f)));
-  return (float)((double)r / 255.0);
-}
 
 __device__ __forceinline__ float conf_out(const MvArgs& a, float c) { return a.png ? conf_png(c) : c; }
 
@@ -99,29 +94,6 @@ __global__ __launch_bounds__(NT) void mv_resolve_kernel(const unsigned long long
 //   launch A  one thread per SOURCE pixel of the F x 6 maps: planes 12, 13, 14 get their value, planes 23, 24, 34 get +0
 //   launch B  one thread per TARGET pixel of the F x 3 view-transformed maps: the winner of its key gets the target's gradient
 // A source bids for one target, so it wins at most one: launch B's stores never collide, and no sum is formed with atomics.
-
-// the sine rule without its clip, operation for operation as geom::sine_rule_depth forms it (d != 0)
-__device__ __forceinline__ float sine_rule_raw(float d, int j, int W, float baseline, float& phi_l) {
-  const float pi_f = 3.14159265358979323846f, half_pi_f = 1.57079632679489661923f;
-  const double start = 0.5 * 3.14159265358979323846 - (0.5 * 3.14159265358979323846 / W);
-  const double step = 3.14159265358979323846 / W;
-  phi_l = (float)(start + (double)j * (-step));
-  const float phi_r = d * pi_f / (float)W + phi_l;
-  return baseline * sinf(half_pi_f - phi_r) / sinf(phi_r - phi_l);
-}
-
-// S(d, j) = d depth / d disparity = -(pi / W) baseline cos(phi_l) / sin^2(d pi / W) where the sine rule passes a gradient: d != 0 and
-// 0 <= raw <= 1000 (the reference clips by assigning to the values strictly outside, so the boundary passes); exactly +0 elsewhere
-// (NaN included).  The closed form has none of the forward's phi_r - phi_l cancellation.
-__device__ __forceinline__ float sine_rule_slope(float d, int j, int W, float baseline) {
-  if (d == 0.f) return 0.f;
-  float phi_l;
-  const float raw = sine_rule_raw(d, j, W, baseline, phi_l);
-  if (!(raw >= 0.f && raw <= 1000.f)) return 0.f;
-  const float pi_f = 3.14159265358979323846f;
-  const float s = sinf(d * pi_f / (float)W);
-  return -(pi_f / (float)W) * baseline * cosf(phi_l) / (s * s);
-}
 
 template <bool FULL>
 __global__ __launch_bounds__(NT) void mv_bwd_sources_kernel(const float* __restrict__ disp, const float* __restrict__ gout,

@@ -1,7 +1,8 @@
 """8-bit frames on the GPU: the host half of the reference's loaders between the decoded PNGs and the two networks, as HIP kernels.
 
   frames_u8_gpu   preprocess.get_transform_stage1(augment=False) of every panorama of (F, 12, H, W, 3) uint8 frames and
-                  models.mode_multiview.split_frames of the result, in one launch (mode_frames_u8_ingest)
+                  models.mode_multiview.split_frames of the result, in one launch (mode_frames_u8_ingest); with rig= the same for the
+                  (F, 2P, H, W, 3) frames of any utils.rig.CameraRig, through the slot table of mode_images_u8_augment
   rgb_half_gpu    Deep360DatasetFusion(resize=True)'s RGB branch (reference dataloader/deep360_loader.py:151-153, 161-163):
                   PIL.Image.resize((w / 2, h / 2)) of the four fusion panoramas, then the same transform (mode_rgb_half_pil)
   erp_pairs_gpu   Dataset3D60Disparity.__getitem__ (reference dataloader/dataset3D60Loader.py:175-248) for a batch of decoded 3D60
@@ -69,12 +70,18 @@ def _half_tables(H, W, device):
     return hit
 
 
-def frames_u8_gpu(frames_u8, want_rgb=True, augment=None):
+def frames_u8_gpu(frames_u8, want_rgb=True, augment=None, rig=None):
   """(F, 12, H, W, 3) uint8 device frames -- the 12 panoramas of a frame in sorted file order, each as np.asarray(PIL image) lays
   it out -> (left (6F, 3, H, W), right (6F, 3, H, W), rgb (F, 12, H, W) or None): split_frames of the ImageNet-normalised panoramas.
   augment: ColourParams for the 12 F panoramas (row 12 f + k: panorama k of frame f) -> the same three tensors of the colour-augmented
   panoramas (augment_u8_gpu): left, right and rgb are three parts of one buffer that mode_images_u8_augment writes through its slot
-  table in one call (panoramas 0, 1, 10, 11 have two slots each: their pair and the fusion RGB)."""
+  table in one call (panoramas 0, 1, 10, 11 have two slots each: their pair and the fusion RGB).
+  rig: a utils.rig.CameraRig of P pairs -> frames (F, 2P, H, W, 3), pair-major, and left, right (P F, 3, H, W) with pair p of frame f
+  at row P f + p, rgb (F, 3 len(rig.rgb), H, W): split_frames(rig=) of the normalised panoramas, bit for bit.  Both the plain and the
+  augmented ingest of a rig go through mode_images_u8_augment and the rig's slot table (plain: no operations, zero shifts, which is
+  the normalisation alone)."""
+  if rig is not None:
+    return _rig_frames_u8(frames_u8, want_rgb, augment, rig)
   _HF.require_u8_frames(frames_u8, 'frames_u8_gpu')
   if augment is None:
     return _HF.frames_u8_ingest(frames_u8, _norm_lut(frames_u8.device), want_rgb)
@@ -99,6 +106,58 @@ def _frame_slots(F, want_rgb, device):
       hit = torch.from_numpy(np.stack([(k & 1) * 6 * F + 6 * f + k // 2, second], 1).astype(np.int32)).to(device)
       _dst_cache[key] = hit
     return hit
+
+
+def _rig_slots(F, rig, want_rgb, device):
+  """_frame_slots for a utils.rig.CameraRig of P pairs with K RGB panoramas: (2P F, 2) int32, panorama k of frame f -> left[P f + k / 2]
+  for even k, right[...] for odd, and for k = rig.rgb[r] with want_rgb also slot K f + r of the fusion RGB viewed as (K F, 3, H, W),
+  behind the 2P F slots of left and right; -1: no second slot.  For CameraRig.deep360() it is _frame_slots row for row."""
+  key = ('rig', rig, F, bool(want_rgb), str(device))
+  with _lock:
+    hit = _dst_cache.get(key)
+    if hit is None:
+      P, K = len(rig.pairs), len(rig.rgb)
+      f, k = np.divmod(np.arange(2 * P * F), 2 * P)
+      rank = np.full(2 * P, -1)
+      rank[list(rig.rgb)] = np.arange(K)
+      second = np.where(rank[k] >= 0, 2 * P * F + K * f + rank[k], -1) if want_rgb else np.full(2 * P * F, -1)
+      hit = torch.from_numpy(np.stack([(k & 1) * P * F + P * f + k // 2, second], 1).astype(np.int32)).to(device)
+      _dst_cache[key] = hit
+    return hit
+
+
+def _identity_params(n, device):
+  """ColourParams of n images with no operation and zero shifts (the normalisation alone), cached per (n, device)."""
+  key = ('identity', n, str(device))
+  with _lock:
+    hit = _dst_cache.get(key)
+  if hit is None:
+    hit = ColourParams([[]] * n, np.ones((n, 3)), None, device)
+    with _lock:
+      _dst_cache[key] = hit
+  return hit
+
+
+def _rig_frames_u8(frames_u8, want_rgb, augment, rig):
+  who = 'frames_u8_gpu'
+  P, K = len(rig.pairs), len(rig.rgb)
+  if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
+    raise TypeError('%s: frames must be a uint8 tensor (got %s)' % (who, getattr(frames_u8, 'dtype', type(frames_u8))))
+  _HF.require_gpu(frames_u8)
+  if not frames_u8.is_contiguous():
+    raise TypeError('%s: frames must be contiguous' % who)
+  if frames_u8.dim() != 5 or frames_u8.shape[1] != 2 * P or frames_u8.shape[4] != 3:
+    raise ValueError('%s: frames of a rig with %d pairs must be (F, %d, H, W, 3), got %s' % (who, P, 2 * P, tuple(frames_u8.shape)))
+  F, _, H, W, _ = frames_u8.shape
+  dev = frames_u8.device
+  if augment is None:
+    augment = _identity_params(2 * P * F, dev)
+  else:
+    _require_params(augment, 2 * P * F, dev, who)
+  all3 = torch.empty(((2 * P + (K if want_rgb else 0)) * F, 3, H, W), dtype=torch.float32, device=dev)
+  if F:
+    _HF.images_u8_augment(frames_u8.view(2 * P * F, H, W, 3), augment.ops, augment.coef, dst=_rig_slots(F, rig, want_rgb, dev), out=all3)
+  return all3[:P * F], all3[P * F:2 * P * F], (all3[2 * P * F:].view(F, 3 * K, H, W) if want_rgb else None)
 
 
 # ------------------------------------------------------------------------------------ colour augmentation

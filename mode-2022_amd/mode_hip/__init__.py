@@ -146,6 +146,14 @@ SIGNATURES = {
     'mode_multiview_handoff': (_c_int, [_c_ptr] * 2 + [_c_int] * 3 + [_c_ptr] * 4 + [_c_int] + [_c_ptr] * 3),
     'mode_multiview_handoff_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr] * 6 + [_c_int] * 2 + [_c_ptr] * 2),
     'mode_multiview_handoff_bwd_full': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr] * 6 + [_c_int] * 2 + [_c_ptr] * 3),
+    # the same for any camera rig (csrc/multiview_rig.hip; utils.rig)
+    'mode_multiview_rig_handoff_workspace_bytes': (_c_size, [_c_int] * 4),
+    'mode_multiview_rig_handoff': (_c_int, [_c_ptr] * 2 + [_c_int] * 4 + [_c_ptr, _c_int] + [_c_ptr] * 2 + [_c_int, _c_ptr, _c_int] +
+                                   [_c_ptr] * 3),
+    'mode_multiview_rig_handoff_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_int] + [_c_ptr] * 4 +
+                                       [_c_int] * 2 + [_c_ptr] * 2),
+    'mode_multiview_rig_handoff_bwd_full': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_int] + [_c_ptr] * 4 +
+                                            [_c_int] * 2 + [_c_ptr] * 3),
     'mode_classif_workspace_bytes': (_c_size, [_c_int] * 5),
     'mode_classif_train_fwd': (_c_int, [_c_ptr] * 6 + [ctypes.c_float] * 2 + [_c_ptr] * 8 + [_c_int] * 5 + [_c_ptr]),
     'mode_classif_train_bwd': (_c_int, [_c_ptr] * 13 + [_c_int] + [_c_ptr] + [_c_int] * 5 + [_c_ptr]),

@@ -40,10 +40,18 @@ from .mode_fusion import Baseline, ModeFusion
 FUSION_RGB = (0, 1, 10, 11)
 
 
-def split_frames(frames):
+def split_frames(frames, rig=None):
   """(F, 12, 3, H, W) panoramas in a frame's sorted file order -> (left (6F, 3, H, W), right (6F, 3, H, W), rgb (F, 12, H, W)).
   Pair p of frame f is left[6f + p] = frames[f, 2p], right[6f + p] = frames[f, 2p + 1] (list_file.py _disparity_subset); rgb is
-  frames[f, FUSION_RGB] with the colour channels flattened.  Works on any device."""
+  frames[f, FUSION_RGB] with the colour channels flattened.  Works on any device.
+  rig: a utils.rig.CameraRig of P pairs -> frames (F, 2P, 3, H, W), left, right (P F, 3, H, W), rgb (F, 3 len(rig.rgb), H, W) of the
+  panoramas rig.rgb."""
+  if rig is not None:
+    P = len(rig.pairs)
+    if frames.dim() != 5 or frames.shape[1] != 2 * P or frames.shape[2] != 3:
+      raise ValueError('ModeMultiView: frames of a rig with %d pairs must be (F, %d, 3, H, W), got %s' % (P, 2 * P, tuple(frames.shape)))
+    F, _, C, H, W = frames.shape
+    return (frames[:, 0::2].reshape(F * P, C, H, W), frames[:, 1::2].reshape(F * P, C, H, W), torch.cat([frames[:, k] for k in rig.rgb], 1))
   if frames.dim() != 5 or frames.shape[1] != 12 or frames.shape[2] != 3:
     raise ValueError('ModeMultiView: frames must be (F, 12, 3, H, W), got %s' % (tuple(frames.shape),))
   F, _, C, H, W = frames.shape
@@ -76,11 +84,27 @@ class ModeMultiView(nn.Module):
   or Baseline with fusion='Baseline'), so the state_dict is theirs under the prefixes 'disparity.' and 'fusion.'.
   handoff_grad selects what fusion_loss fine-tunes stage 1 through when disparity.train(): 'depth' (the default) the depth channels of the
   hand-off alone; 'full' the confidence channels as well (needs conf_png=False with ModeFusion) and, with resize=True, the decimation.
-  It changes nothing else: forward(), evaluate(), fusion_loss with disparity.eval() and the state_dict do not depend on it."""
+  It changes nothing else: forward(), evaluate(), fusion_loss with disparity.eval() and the state_dict do not depend on it.
+  rig: a utils.rig.CameraRig instead of dbname (None: the Deep360 frame of 12 panoramas, as above).  A frame is then the rig's 2P
+  panoramas, pair-major, (F, 2P, 3, H, W) float or (F, 2P, H, W, 3) uint8; stage 1 runs at batch P F, the hand-off on
+  mode_multiview_rig_handoff, and ModeFusion is built for 2P depth / confidence planes and 3 len(rig.rgb) colour planes, so its first
+  two layers (and only they) have other shapes than the reference's checkpoints.  Everything else reads as above with 6 -> P."""
 
   def __init__(self, maxdisp=192, maxdepth=1000., height=1024, width=512, dbname='Deep360', fusion='ModeFusion',
-               channels=(32, 64, 128, 256), conf_png=True, resize=False, handoff_grad='depth'):
+               channels=(32, 64, 128, 256), conf_png=True, resize=False, handoff_grad='depth', rig=None):
     super(ModeMultiView, self).__init__()
+    if rig is not None:
+      if dbname != 'Deep360':
+        raise ValueError('ModeMultiView: rig= and dbname=%r are two descriptions of the cameras; pass one' % (dbname,))
+      if fusion == 'Baseline' and len(rig.pairs) != 6:
+        raise ValueError("ModeMultiView(fusion='Baseline') needs a rig of 6 pairs, not %d: the reference's Baseline stack has 6 input "
+                         'planes' % len(rig.pairs))
+      if resize and not rig.deep360_layout:
+        raise ValueError('ModeMultiView(resize=True) needs a rig whose frames have the layout of Deep360 (6 pairs, rgb = (0, 1, 10, 11)), '
+                         'not %d pairs with rgb = %r: the halving of the 8-bit RGB (mode_rgb_half_pil) reads exactly those panoramas' %
+                         (len(rig.pairs), rig.rgb))
+    self.rig = rig
+    self.pairs = 6 if rig is None else len(rig.pairs)
     if handoff_grad not in ('depth', 'full'):
       raise ValueError("ModeMultiView: handoff_grad must be 'depth' or 'full', not %r" % (handoff_grad,))
     if handoff_grad == 'full' and fusion == 'ModeFusion' and conf_png:
@@ -97,7 +121,8 @@ class ModeMultiView(nn.Module):
     self.maxdepth = float(maxdepth)
     self.disparity = ModeDisparity(maxdisp, 'Sphere', height, width, 'Cassini', out_conf=True)
     if fusion == 'ModeFusion':
-      self.fusion = ModeFusion(maxdepth, list(channels), {'depth': 12, 'rgb': 12})
+      self.fusion = ModeFusion(maxdepth, list(channels),
+                               {'depth': 12, 'rgb': 12} if rig is None else {'depth': 2 * len(rig.pairs), 'rgb': 3 * len(rig.rgb)})
     else:
       self.fusion = Baseline(maxdepth)
     if self.resize:
@@ -125,10 +150,10 @@ class ModeMultiView(nn.Module):
     require_gpu(frames)
     want_rgb = self.fusion_kind == 'ModeFusion'
     if u8:
-      left, right, rgb = gpu_ingest.frames_u8_gpu(frames.contiguous(), want_rgb=want_rgb and not self.resize)
+      left, right, rgb = gpu_ingest.frames_u8_gpu(frames.contiguous(), want_rgb=want_rgb and not self.resize, rig=self.rig)
       H, W = frames.shape[2:4]
     else:
-      left, right, rgb = split_frames(frames)
+      left, right, rgb = split_frames(frames, self.rig)
       H, W = frames.shape[-2:]
     if H % 16 or W % 16:
       raise ValueError('ModeMultiView: %d x %d is not a multiple of 16' % (H, W))
@@ -147,7 +172,7 @@ class ModeMultiView(nn.Module):
     with torch.no_grad():
       disp, conf = self.disparity(left, right)
       fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png,
-                                                    depth_only=self.fusion_kind == 'Baseline')
+                                                    depth_only=self.fusion_kind == 'Baseline', rig=self.rig)
       if self.resize:  # deep360_loader.py:146-155 on the hand-off and the 8-bit panoramas; test_fusion.py:82 on the result
         fusion_input = HF.decimate2(fusion_input)
         rgb = gpu_ingest.rgb_half_gpu(frames.contiguous()) if want_rgb else None
@@ -208,8 +233,8 @@ class ModeMultiView(nn.Module):
     left, right, rgb, want_rgb = self._ingest(frames)
     require_gpu(gt)
     H, W = left.shape[-2:]
-    if tuple(gt.shape) != (left.shape[0] // 6, H, W):
-      raise ValueError('ModeMultiView.fusion_loss: gt %s is not (F, H, W) = %s' % (tuple(gt.shape), (left.shape[0] // 6, H, W)))
+    if tuple(gt.shape) != (left.shape[0] // self.pairs, H, W):
+      raise ValueError('ModeMultiView.fusion_loss: gt %s is not (F, H, W) = %s' % (tuple(gt.shape), (left.shape[0] // self.pairs, H, W)))
     if full:
       size = (self.disparity.maxdisp, H, W)
       disp, conf = HF.head_conf(self.disparity._logits(left, right)[2], size)
@@ -223,7 +248,7 @@ class ModeMultiView(nn.Module):
         disp, conf = self.disparity(left, right)
     depth_only = self.fusion_kind == 'Baseline'
     fusion_input = geometry.disp2depth_frames_gpu(disp, conf, self.dbname, conf_png=self.conf_png, depth_only=depth_only,
-                                                  conf_grad=full and not depth_only)
+                                                  conf_grad=full and not depth_only, rig=self.rig)
     if self.resize:  # deep360_loader.py:146-155 with training=True
       fusion_input = HF.decimate2(fusion_input)
       rgb = gpu_ingest.rgb_half_gpu(frames.contiguous()) if want_rgb else None

@@ -315,7 +315,8 @@ def disp2depth(disp, conf_map, cam_pair, dbname='Deep360'):
 # ------------------------------------------------------------------------------------------------ the multi-view hand-off
 PAIRS = ('12', '13', '14', '23', '24', '34')  # the order of a frame's six pairs (CAM_PAIRS)
 MV_CONF_PNG, MV_DEPTH_ONLY = 1, 2  # MODE_MV_* of include/mode_hip.h
-_frames_cache = _HF._LRU(8)  # (H, W, device, dbname) -> constant tables of mode_multiview_handoff (graph-pinned while captured)
+_frames_cache = _HF._LRU(8)  # (H, W, device, dbname) -> constant tables of mode_multiview_handoff (graph-pinned while captured);
+#                              ('rig', rig, H, W, device) -> those of mode_multiview_rig_handoff for a utils.rig.CameraRig
 _frames_lock = threading.Lock()
 
 
@@ -339,8 +340,11 @@ def _frames_tables(H, W, device, dbname):
     return entry
 
 
-def _as_frames(t, what):
-  """(F, 6, H, W), (6F, 1, H, W) or (6F, H, W) -> a (F, 6, H, W) view."""
+def _as_frames(t, what, rig=None):
+  """(F, 6, H, W), (6F, 1, H, W) or (6F, H, W) -> a (F, 6, H, W) view; with a rig of P pairs, the same with 6 -> P (a (F, 1, H, W)
+  tensor of a one-pair rig is both forms at once)."""
+  if rig is not None:
+    return _as_rig_frames(t, what, len(rig.pairs))
   if t.dim() == 4 and t.shape[1] == 6:
     return t
   if (t.dim() == 4 and t.shape[1] == 1) or t.dim() == 3:
@@ -350,7 +354,45 @@ def _as_frames(t, what):
   raise ValueError('disp2depth_frames_gpu: %s of shape %s is not (F, 6, H, W), (6F, 1, H, W) or (6F, H, W)' % (what, tuple(t.shape)))
 
 
-_adjoint_cache = _HF._LRU(8)  # (H, W, device) -> adjoint lists of the two rotation grids (mode_multiview_handoff_bwd)
+def _as_rig_frames(t, what, P):
+  if t.dim() == 4 and t.shape[1] == P:
+    return t
+  if (t.dim() == 4 and t.shape[1] == 1) or t.dim() == 3:
+    if t.shape[0] % P:
+      raise ValueError('disp2depth_frames_gpu: %s has %d maps, not %d per frame of the rig' % (what, t.shape[0], P))
+    return t.view(t.shape[0] // P, P, t.shape[-2], t.shape[-1])
+  raise ValueError('disp2depth_frames_gpu: %s of shape %s is not (F, %d, H, W), (%dF, 1, H, W) or (%dF, H, W)' % (what, tuple(t.shape), P, P, P))
+
+
+def _check_rig(rig, dbname, who):
+  """A rig carries its own baselines and poses: it does not go together with a database name other than the default."""
+  if rig is not None and dbname != 'Deep360':
+    raise ValueError('%s: rig= and dbname=%r are two descriptions of the cameras; pass one (dbname selects among the reference\'s rigs, '
+                     'utils.rig.CameraRig describes any)' % (who, dbname))
+
+
+def _rig_tables(rig, H, W, device):
+  """(mode_mv_pair records host, R, V, rotation grids (R, H, W, 2) device or None, trig device, V x (R, t) float64 host or None) of
+  mode_multiview_rig_handoff for a utils.rig.CameraRig, built by the functions the single-map calls use and cached like _frames_tables."""
+  key = ('rig', rig, H, W, str(device))
+  with _frames_lock:
+    hit = _frames_cache.get(key)
+    if hit is not None:
+      return hit
+    records, R, V = rig.records()
+    grids = [_rotate_grid(H, W, p.pose[0], p.pose[1], p.pose[2], str(device)) for p in rig.of_kind('rotate')]
+    xforms = []
+    for p in rig.of_kind('view'):
+      y0, z0, x0, pitch, yaw, roll = p.pose
+      xforms += [np.ascontiguousarray(_rotation(pitch, yaw, roll), dtype=np.float64).ravel(), np.array([x0, y0, z0], dtype=np.float64)]
+    entry = (records, R, V, torch.cat(grids).contiguous() if grids else None, _trig_device(H, W, str(device)).clone(),
+             np.ascontiguousarray(np.concatenate(xforms)) if xforms else None)
+    _frames_cache[key] = entry
+    return entry
+
+
+_adjoint_cache = _HF._LRU(8)  # (H, W, device) -> adjoint lists of the two rotation grids (mode_multiview_handoff_bwd);
+#                               (rig, H, W, device) -> those of a rig's R rotation grids (mode_multiview_rig_handoff_bwd)
 
 
 def _bilinear_border_np(grid, Hs, Ws):
@@ -412,8 +454,60 @@ def _frames_adjoint(H, W, device):
     return entry
 
 
-def _handoff_fwd(disp, conf, dbname, conf_png, depth_only):
+def _rig_adjoint(rig, H, W, device):
+  """_frames_adjoint for the R rotation grids of a rig, in pair order: (rowptr int32 (R, H W + 1) or None, target, weight)."""
+  key = (rig, H, W, str(device))
+  with _frames_lock:
+    hit = _adjoint_cache.get(key)
+    if hit is not None:
+      return hit
+    rowptr, targets, weights, base = [], [np.zeros(0, np.int32)], [np.zeros(0, np.float32)], 0
+    for p in rig.of_kind('rotate'):
+      grid = _rotate_grid(H, W, p.pose[0], p.pose[1], p.pose[2], str(device))[0].cpu().numpy()
+      counts, t, w = _grid_adjoint_np(grid, H, W)
+      rowptr.append(base + np.concatenate(([0], np.cumsum(counts))))
+      targets.append(t)
+      weights.append(w)
+      base += len(t)
+    if rowptr:
+      rowptr = np.stack(rowptr)
+      # as _frames_adjoint: the only producer checks what it hands over
+      if (rowptr[0, 0] != 0 or (rowptr[1:, 0] != rowptr[:-1, -1]).any() or rowptr[-1, -1] != base or (np.diff(rowptr.ravel()) < 0).any() or
+          base > 4 * len(rowptr) * H * W or base >= 2 ** 31):
+        raise RuntimeError('_rig_adjoint: inconsistent adjoint lists for %d x %d' % (H, W))
+      rowptr = torch.from_numpy(rowptr.astype(np.int32)).to(device)
+    else:
+      rowptr = None
+    entry = (rowptr, torch.from_numpy(np.concatenate(targets)).to(device), torch.from_numpy(np.concatenate(weights)).to(device))
+    _adjoint_cache[key] = entry
+    return entry
+
+
+def _optr(t):
+  return None if t is None else ptr(t)
+
+
+def _host(a):
+  return None if a is None else a.ctypes.data
+
+
+def _rig_handoff_fwd(disp, conf, rig, conf_png, depth_only):
+  """disp, conf (F, P, H, W) contiguous -> (out, the key planes (F, V, H, W) int64), on mode_multiview_rig_handoff."""
+  F, P, H, W = disp.shape
+  records, R, V, grids, trig, xforms = _rig_tables(rig, H, W, disp.device)
+  out = torch.empty((F, P if depth_only else 2 * P, H, W), dtype=torch.float32, device=disp.device)
+  ws = torch.empty(lib().mode_multiview_rig_handoff_workspace_bytes(F, V, H, W) // 8, dtype=torch.int64, device=disp.device)
+  flags = (MV_CONF_PNG if conf_png else 0) | (MV_DEPTH_ONLY if depth_only else 0)
+  with torch.cuda.device_of(disp):
+    check(lib().mode_multiview_rig_handoff(ptr(disp), ptr(conf), F, P, H, W, records.ctypes.data, R, _optr(grids), ptr(trig), V, _host(xforms),
+                                           flags, ptr(out), ptr(ws) if ws.numel() else None, stream_of(disp)), 'mode_multiview_rig_handoff')
+  return out, ws.view(F, V, H, W)
+
+
+def _handoff_fwd(disp, conf, dbname, conf_png, depth_only, rig=None):
   """disp, conf (F, 6, H, W) contiguous -> (out, the key planes (F, 3, H, W) int64 the launches leave behind)."""
+  if rig is not None:
+    return _rig_handoff_fwd(disp, conf, rig, conf_png, depth_only)
   F, _, H, W = disp.shape
   baselines, grids, trig, xforms = _frames_tables(H, W, disp.device, dbname)
   out = torch.empty((F, 6 if depth_only else 12, H, W), dtype=torch.float32, device=disp.device)
@@ -425,13 +519,44 @@ def _handoff_fwd(disp, conf, dbname, conf_png, depth_only):
   return out, ws.view(F, 3, H, W)
 
 
-def disp2depth_frames_bwd(disp, gout, keys, dbname='Deep360', depth_only=False, conf_grad=False):
+def _rig_handoff_bwd(disp, gout, keys, rig, depth_only, conf_grad):
+  """disp2depth_frames_bwd for a rig, on mode_multiview_rig_handoff_bwd / _bwd_full."""
+  require_gpu(disp, gout, keys)
+  disp, gout, keys = _as_frames(disp.contiguous(), 'disp', rig), gout.contiguous(), keys.contiguous()
+  require_f32c(disp, gout)
+  F, P, H, W = disp.shape
+  records, R, V, _, trig, xforms = _rig_tables(rig, H, W, disp.device)
+  if P != len(rig.pairs) or tuple(gout.shape) != (F, P if depth_only else 2 * P, H, W) or keys.dtype != torch.int64 or keys.numel() != V * F * H * W:
+    raise ValueError('disp2depth_frames_bwd: disp %s, gout %s and keys %s %s do not belong together for a rig of %d pairs, %d of them view '
+                     'transforms' % (tuple(disp.shape), tuple(gout.shape), keys.dtype, tuple(keys.shape), len(rig.pairs), V))
+  rowptr, target, weight = _rig_adjoint(rig, H, W, disp.device)
+  kptr = ptr(keys) if keys.numel() else None
+  gdisp = torch.empty_like(disp)
+  if conf_grad and not depth_only:
+    gconf = torch.empty_like(disp)
+    with torch.cuda.device_of(disp):
+      check(lib().mode_multiview_rig_handoff_bwd_full(ptr(disp), ptr(gout), kptr, F, P, H, W, records.ctypes.data, R, ptr(trig), V, _host(xforms),
+                                                      _optr(rowptr), ptr(target), ptr(weight), target.numel(), 0, ptr(gdisp), ptr(gconf),
+                                                      stream_of(disp)), 'mode_multiview_rig_handoff_bwd_full')
+    return gdisp, gconf
+  with torch.cuda.device_of(disp):
+    check(lib().mode_multiview_rig_handoff_bwd(ptr(disp), ptr(gout), kptr, F, P, H, W, records.ctypes.data, R, ptr(trig), V, _host(xforms),
+                                               _optr(rowptr), ptr(target), ptr(weight), target.numel(), MV_DEPTH_ONLY if depth_only else 0,
+                                               ptr(gdisp), stream_of(disp)), 'mode_multiview_rig_handoff_bwd')
+  return (gdisp, None) if conf_grad else gdisp
+
+
+def disp2depth_frames_bwd(disp, gout, keys, dbname='Deep360', depth_only=False, conf_grad=False, rig=None):
   """The gradient of disp2depth_frames_gpu's depth channels with respect to disp (mode_multiview_handoff_bwd): disp (F, 6, H, W) or one
   of the views the forward takes, gout the gradient of the output in its layout, keys the key planes of the forward on the same disp (return_keys) -> gdisp (F, 6, H, W).
   The confidence channels of gout are not read.  conf_grad=True (the forward with conf_png=False: q the identity) -> (gdisp, gconf):
   the gradient with respect to the confidence maps as well, from the confidence channels of gout, in the same two launches
   (mode_multiview_handoff_bwd_full; gdisp has the same bits; gconf is None with depth_only, which has no confidence channels).
-  Bit-repeatable: sums over the cached adjoint lists in their stored order, no atomics."""
+  Bit-repeatable: sums over the cached adjoint lists in their stored order, no atomics.
+  rig: a utils.rig.CameraRig of P pairs, V of them view transforms, as the forward took it: 6 -> P above, and keys (F, V, H, W)."""
+  _check_rig(rig, dbname, 'disp2depth_frames_bwd')
+  if rig is not None:
+    return _rig_handoff_bwd(disp, gout, keys, rig, depth_only, conf_grad)
   require_gpu(disp, gout, keys)
   disp, gout, keys = _as_frames(disp.contiguous(), 'disp'), gout.contiguous(), keys.contiguous()
   require_f32c(disp, gout)
@@ -461,10 +586,10 @@ class _HandoffFunction(torch.autograd.Function):
   planes kept for the backward."""
 
   @staticmethod
-  def forward(ctx, disp, conf, dbname, conf_png, depth_only, conf_grad=False):
-    out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only)
+  def forward(ctx, disp, conf, dbname, conf_png, depth_only, conf_grad=False, rig=None):
+    out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only, rig)
     ctx.save_for_backward(disp, keys)
-    ctx.dbname, ctx.depth_only, ctx.conf_grad = dbname, depth_only, conf_grad
+    ctx.dbname, ctx.depth_only, ctx.conf_grad, ctx.rig = dbname, depth_only, conf_grad, rig
     ctx.mark_non_differentiable(keys)
     return out, keys
 
@@ -473,13 +598,13 @@ class _HandoffFunction(torch.autograd.Function):
   def backward(ctx, gout, _gkeys):
     disp, keys = ctx.saved_tensors
     if ctx.conf_grad and not ctx.depth_only and ctx.needs_input_grad[1]:
-      gdisp, gconf = disp2depth_frames_bwd(disp, gout, keys, ctx.dbname, conf_grad=True)
-      return (gdisp if ctx.needs_input_grad[0] else None), gconf, None, None, None, None
-    gdisp = disp2depth_frames_bwd(disp, gout, keys, ctx.dbname, ctx.depth_only) if ctx.needs_input_grad[0] else None
-    return gdisp, None, None, None, None, None
+      gdisp, gconf = disp2depth_frames_bwd(disp, gout, keys, ctx.dbname, conf_grad=True, rig=ctx.rig)
+      return (gdisp if ctx.needs_input_grad[0] else None), gconf, None, None, None, None, None
+    gdisp = disp2depth_frames_bwd(disp, gout, keys, ctx.dbname, ctx.depth_only, rig=ctx.rig) if ctx.needs_input_grad[0] else None
+    return gdisp, None, None, None, None, None, None
 
 
-def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_only=False, return_keys=False, conf_grad=False):
+def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_only=False, return_keys=False, conf_grad=False, rig=None):
   """The six pairs of F frames at once: disp, conf (F, 6, H, W) float32 device tensors (pair order PAIRS; (6F, 1, H, W) and
   (6F, H, W) are taken as views) -> (F, 12, H, W) with out[f, 2p], out[f, 2p + 1] = disp2depth_gpu(disp[f, p], conf[f, p], PAIRS[p],
   dbname) -- ModeFusion's channel interleave -- bit for bit, in three launches (mode_multiview_handoff).  conf_png: every confidence
@@ -492,19 +617,27 @@ def disp2depth_frames_gpu(disp, conf, dbname='Deep360', conf_png=False, depth_on
   rotation's taps, the winner's pick -- from the same two launches (mode_multiview_handoff_bwd_full).  That needs q the identity:
   with conf_png=True it raises ValueError (the 8-bit rounding is piecewise constant); with depth_only there are no confidence
   channels and conf gets None.  return_keys: (out, keys) with the forward's z-buffer key planes (F, 3, H, W) int64 (layout:
-  csrc/geometry_internal.h)."""
+  csrc/geometry_internal.h).
+
+  rig: a utils.rig.CameraRig instead of a database name (passing both is a ValueError).  disp, conf are then (F, P, H, W) in the rig's
+  pair order ((P F, 1, H, W) and (P F, H, W) are taken as views), the result (F, 2P, H, W) -- (F, P, H, W) with depth_only -- and the
+  key planes (F, V, H, W) for its V view-transformed pairs, in pair order: every plane has the bits of the single-map calls for its
+  pair (mode_disp2depth, then rotateCassini_gpu or depthViewTransWithConf_gpu with the pair's pose), in three launches, or one when the
+  rig has no view-transformed pair (mode_multiview_rig_handoff).  Everything above holds with 6 -> P.  rig=None is the path above,
+  untouched."""
+  _check_rig(rig, dbname, 'disp2depth_frames_gpu')
   if conf_grad and conf_png:
     raise ValueError('disp2depth_frames_gpu: conf_grad=True needs conf_png=False: the 8-bit PNG rounding of the confidence is piecewise '
                      'constant and passes no gradient')
   require_gpu(disp, conf)
-  disp, conf = _as_frames(disp.contiguous(), 'disp'), _as_frames(conf.contiguous(), 'conf')
+  disp, conf = _as_frames(disp.contiguous(), 'disp', rig), _as_frames(conf.contiguous(), 'conf', rig)
   require_f32c(disp, conf)
   if disp.shape != conf.shape or disp.device != conf.device:
     raise ValueError('disp2depth_frames_gpu: disp %s and conf %s differ' % (tuple(disp.shape), tuple(conf.shape)))
   if torch.is_grad_enabled() and (disp.requires_grad or conf.requires_grad):
-    out, keys = _HandoffFunction.apply(disp, conf, dbname, bool(conf_png), bool(depth_only), bool(conf_grad))
+    out, keys = _HandoffFunction.apply(disp, conf, dbname, bool(conf_png), bool(depth_only), bool(conf_grad), rig)
   else:
-    out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only)
+    out, keys = _handoff_fwd(disp, conf, dbname, conf_png, depth_only, rig)
   return (out, keys) if return_keys else out
 
 

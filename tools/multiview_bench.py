@@ -5,6 +5,7 @@
     python tools/multiview_bench.py --scoring   # the scoring line alone
     python tools/multiview_bench.py --u8        # the ingest line alone: float frames from the host against 8-bit frames, and resize=True
     python tools/multiview_bench.py --train     # the training line alone: fusion_loss + backward per frame, both modes; the hand-off's backward
+    python tools/multiview_bench.py --rig       # the rig line alone: the hand-off through the six-pair entries and through the rig entries
 
 For every F: the frame time of the composed module, eager and replayed from a captured graph; the split between stage 1 (ModeDisparity
 at batch 6F), the hand-off (utils.geometry.disp2depth_frames_gpu) and stage 2 (the fusion network); and the hand-off against the
@@ -24,7 +25,12 @@ with stage 1 fine-tuned (net.train(), batch statistics at batch 6), and the hand
 that frame.  Device events around every single call after a warm-up; medians in ms.  One JSON line.  It also carries the figures of
 fine-tuning through the confidence (ModeMultiView(handoff_grad='full', conf_png=False)): the head's backward with and without the
 confidence gradient at B = 6, D4 = 48, 1024 x 512, timed alternately (head_bwd_ms, head_bwd_conf_ms), the hand-off's backward for both
-outputs (handoff_bwd_full_ms) and the 'full' step and its peak memory (fine_tuning_full_step_ms, fine_tuning_full_peak_GiB)."""
+outputs (handoff_bwd_full_ms) and the 'full' step and its peak memory (fine_tuning_full_step_ms, fine_tuning_full_peak_GiB).
+
+--rig prints the rig line at F = 1: handoff_fwd_ms, handoff_bwd_ms and handoff_bwd_full_ms through the six-pair entries
+('six') and through mode_multiview_rig_handoff* with CameraRig.deep360() ('rig_deep360') -- both move the same bytes -- and with its
+subset 12, 13, 23 ('rig_subset3'), and the forward of that subset as three single calls ('subset3_single_calls'); the sides of a figure
+alternate window by window, a window is about half a second, and beside the device time of every side stands the host time of its calls."""
 import argparse
 import json
 import os
@@ -270,6 +276,71 @@ def train_line(reps=10, warmup=2):
   return row
 
 
+def rig_line(calls=None, windows=4, warmup=20):
+  """The hand-off on a rig description (see the module docstring): at F = 1, 1024 x 512, per side the time per call over `windows`
+  windows of `calls` calls each (default: 4000 for the forward, 1500 for the gradients -- windows of about half a second, so that the
+  clock's ramp and the scheduler are a small part of one).  The sides of a group alternate window by window (A B A B ..., as
+  tools/optim_bench.py takes them), so that a drift of the clocks falls on all of them alike.  Per window two times: the device's, from
+  two events around the window, and the host's, from a host clock around the un-synchronised calls (the device is idle when a window
+  starts).  A call is two torch.empty and one ctypes call; where the host's time per call is not clearly below the device's, the device
+  figure is set by the enqueue rate and not by the kernels.  Every figure is [median, min, max] over its windows."""
+  from utils.rig import CameraRig
+  full = CameraRig.deep360()
+  sub = full.subset(('12', '13', '23'))
+  idx = [full.names.index(n) for n in sub.names]
+  g = torch.Generator().manual_seed(500)
+  disp = (torch.rand(1, 6, H, W, generator=g) * 40).to(DEV)
+  conf = torch.rand(1, 6, H, W, generator=g).to(DEV)
+  gout = torch.randn(1, 12, H, W, generator=g).to(DEV)
+  d3, c3 = disp[:, idx].contiguous(), conf[:, idx].contiguous()
+  g3 = gout[:, [c for p in idx for c in (2 * p, 2 * p + 1)]].contiguous()
+  keys = HG.disp2depth_frames_gpu(disp, conf, conf_png=True, return_keys=True)[1]
+  keys3 = HG.disp2depth_frames_gpu(d3, c3, rig=sub, conf_png=True, return_keys=True)[1]
+  assert torch.equal(HG.disp2depth_frames_gpu(disp, conf, rig=full, conf_png=True), HG.disp2depth_frames_gpu(disp, conf, conf_png=True))
+
+  def singles():  # the P single-call path of the subset
+    return [HG.disp2depth_gpu(d3[0, p], c3[0, p], n) for p, n in enumerate(sub.names)]
+
+  groups = {
+      'handoff_fwd_ms': {'six': lambda: HG.disp2depth_frames_gpu(disp, conf, conf_png=True),
+                         'rig_deep360': lambda: HG.disp2depth_frames_gpu(disp, conf, rig=full, conf_png=True),
+                         'rig_subset3': lambda: HG.disp2depth_frames_gpu(d3, c3, rig=sub, conf_png=True),
+                         'subset3_single_calls': singles},
+      'handoff_bwd_ms': {'six': lambda: HG.disp2depth_frames_bwd(disp, gout, keys),
+                         'rig_deep360': lambda: HG.disp2depth_frames_bwd(disp, gout, keys, rig=full),
+                         'rig_subset3': lambda: HG.disp2depth_frames_bwd(d3, g3, keys3, rig=sub)},
+      'handoff_bwd_full_ms': {'six': lambda: HG.disp2depth_frames_bwd(disp, gout, keys, conf_grad=True),
+                              'rig_deep360': lambda: HG.disp2depth_frames_bwd(disp, gout, keys, rig=full, conf_grad=True),
+                              'rig_subset3': lambda: HG.disp2depth_frames_bwd(d3, g3, keys3, rig=sub, conf_grad=True)},
+  }
+  row = {'stage': 'rig', 'size': [H, W], 'frames': 1, 'windows': windows, 'calls_per_window': {},
+         'figures': '[median, min, max] ms per call: <name> device time, <name>_host host time of the un-synchronised calls'}
+  per_window = calls
+  for name, sides in groups.items():
+    calls = per_window or (4000 if name == 'handoff_fwd_ms' else 1500)
+    row['calls_per_window'][name] = calls
+    ms, host = {k: [] for k in sides}, {k: [] for k in sides}
+    for fn in sides.values():
+      for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(windows):
+      for k, fn in sides.items():
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        s.record()
+        for _ in range(calls):
+          fn()
+        e.record()
+        host[k].append(1e3 * (time.perf_counter() - t0) / calls)
+        e.synchronize()
+        ms[k].append(s.elapsed_time(e) / calls)
+    row[name] = {k: [float(np.median(v)), float(min(v)), float(max(v))] for k, v in ms.items()}
+    row[name + '_host'] = {k: [float(np.median(v)), float(min(v)), float(max(v))] for k, v in host.items()}
+  print(json.dumps(row), flush=True)
+  return row
+
+
 def once():
   disp = (torch.rand(1, 6, H, W, device=DEV) * 40).contiguous()
   conf = torch.rand(1, 6, H, W, device=DEV)
@@ -289,9 +360,13 @@ def main():
   ap.add_argument('--scoring', action='store_true', help='only the scoring line')
   ap.add_argument('--u8', action='store_true', help='only the ingest line: float frames from the host against 8-bit frames, and resize=True')
   ap.add_argument('--train', action='store_true', help='only the training line: fusion_loss + backward in both modes, the hand-off\'s backward')
+  ap.add_argument('--rig', action='store_true', help='only the rig line: the hand-off through the six-pair entries and through the rig entries')
+  ap.add_argument('--calls', type=int, default=None, help='--rig: calls per window (default 4000 for the forward, 1500 for the gradients)')
   args = ap.parse_args()
   if args.once:
     return once()
+  if args.rig:
+    return rig_line(calls=args.calls)
   if args.scoring:
     return scoring_line()
   if args.u8:
