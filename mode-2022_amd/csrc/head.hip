@@ -764,6 +764,11 @@ namespace {
 // The one-block-per-row kernel with the confidence term exists up to D4 = 48 (228 registers, nothing spilled).  At D4 = 64 the plain
 // kernel already fills all 256 registers and spills, and so would the variant: those sizes take the per-pixel fast kernel
 // (168 registers, nothing spilled) and the separate rows pass.
+// mode_head_bwd takes the same route: with gconf == 0 mode_head_bwd_conf promises ITS bits (include/mode_hip.h), and those hold only
+// between the two instantiations of ONE kernel -- the compiler rounds the shared arithmetic (the bilinear fill, the lerp of the walk) of
+// two different kernels independently.  With the row kernel in mode_head_bwd alone the two entries differed by a few ulp at D4 = 64
+// (tests/test_gpu_guard_bands_heads.py).  The cost at D4 = 64: G (B, D4, H, W) is written and read back once more by mode_head_bwd;
+// mode_head_bwd_loss, the training step's backward, keeps the row kernel.
 constexpr int kPixrowsConfMaxD4 = 48;
 
 // mode_head_bwd (CONF = false: c unread) and mode_head_bwd_conf: the same routing between the three forms, the same workspace
@@ -775,10 +780,10 @@ int head_bwd_run(const float* logits, const float* gpred, const HeadConfArgs& c,
   int rc = MODE_OK;
   const long long npix = (long long)B * H * W;
   bool fast = false;
-  if (head_fast(d) && pixrows_fits(d) && (!CONF || D4 <= kPixrowsConfMaxD4)) {  // per-pixel pass and row sums in one kernel, then the column sums
+  if (head_fast(d) && pixrows_fits(d) && D4 <= kPixrowsConfMaxD4) {  // per-pixel pass and row sums in one kernel, then the column sums
     float* R = workspace;
 #define X(N)                                                                                                                       \
-  if constexpr (!CONF || N <= kPixrowsConfMaxD4)                                                                                   \
+  if constexpr (N <= kPixrowsConfMaxD4)                                                                                            \
     if (D4 == N) rc = launch_bwd_pixrows<N, false, CONF>(logits, gpred, c.pred, nullptr, 0.f, nullptr, R, d, st, c.conf, c.gconf);
     MODE_HEAD_FAST_D4(X)
 #undef X
