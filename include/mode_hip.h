@@ -1184,6 +1184,51 @@ int mode_adam_prepare(const float* grad, long long n, void* workspace, size_t wo
 int mode_adam_update(const mode_adam_segment* segments, int n_seg, const mode_adam_chunk* chunks, int n_chunks, const float* grad,
                      float* exp_avg, float* exp_avg_sq, void* block, int n_groups, mode_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Self-supervised stereo loss on rectified Cassini pairs (csrc/photometric.hip; the reference has no counterpart: its
+ * predict.py "for real scene" only loads a checkpoint).  Additive: the ABI version stays as it is.
+ *
+ * left, right (B, 3, H, W) fp32 as the model takes them; disp (K, B, H, W) fp32, 1 <= K <= MODE_PHOTOMETRIC_MAX_MAPS.  With
+ * L = left * std + mean and R likewise, per map k:
+ *   warp      x = w - d(h, w); a pixel is valid iff d is finite and 0 <= x <= W - 1; x0 = min(floor(x), W - 2), t = x - x0,
+ *             Rh = (1 - t) R[h, x0] + t R[h, x0 + 1], and Rh = 0 without a gradient at invalid pixels.
+ *   windows   one per (h, w) with 1 <= w <= W - 2: the 3x3 neighbourhood, rows modulo H (the long axis of a Cassini image is periodic;
+ *             W runs from pole to pole and does not wrap); valid iff all nine pixels are.
+ *   ssim      per channel on the window's centred, biased moments: (2 mx my + c1)(2 cxy + c2) / ((mx^2 + my^2 + c1)(vx + vy + c2)).
+ *   photo_k   = sum over valid windows of mean_c[alpha (1 - ssim_c) / 2 + (1 - alpha) |L_c - Rh_c|(centre)] / max(N_valid_k, 1).
+ *   smooth_k  = mean over w <= W - 2 of |dn(h, w+1) - dn(h, w)| exp(-beta mean_c |L_c(h, w+1) - L_c(h, w)|) + the mean over all pixels
+ *             of the same along h (h + 1 modulo H), dn = d / W, on every pixel, valid or not.
+ *   loss      = sum_k weights[k] (photo_k + lam smooth_k).  lam == 0 leaves the smoothness term out altogether, in the loss and in the
+ *             gradient (a NaN disparity then costs its pixel and nothing else).
+ * mode_photometric_loss_fwd: stats (K x MODE_PHOTOMETRIC_STATS fp64, device): N_valid, the sum of the windows' photometric terms and
+ *   the two smoothness sums; loss: a device fp32 scalar.  Per-pixel arithmetic in fp32, accumulation in fp64 in the fixed-order scheme
+ *   of mode_masked_metrics (two launches, no atomics: the same inputs give the same bits on any stream).  No host synchronisation.
+ *   workspace: device, 8-byte aligned, workspace_bytes >= mode_photometric_loss_workspace_bytes(K, B, H, W) (0 for sizes the entries refuse).
+ * mode_photometric_loss_bwd: gdisp (K, B, H, W) = gloss[0] * d loss / d disp, every element written once by a gather (a pixel collects
+ *   the up to nine windows that contain it and its smoothness neighbours; no scatter, no atomics); N_valid is a constant; sign(0) = 0
+ *   for both absolute values; invalid pixels get the smoothness gradient only.  `stats` as written by the forward for the same inputs.
+ * Arguments are checked before any launch: MODE_ERR_BAD_ARG for NULL pointers, K outside 1..4, B < 1, H < 3 or W < 3;
+ * MODE_ERR_UNSUPPORTED when 3 B H W >= 2^31 (offsets inside an image tensor and the workgroup index are 32-bit) or W >= 2^24 (w as an
+ * exact float); MODE_ERR_WORKSPACE for a missing, misaligned or small workspace. */
+#define MODE_PHOTOMETRIC_MAX_MAPS 4
+#define MODE_PHOTOMETRIC_STATS 4
+#define MODE_PHOTOMETRIC_N_VALID 0
+#define MODE_PHOTOMETRIC_SUM_PE 1
+#define MODE_PHOTOMETRIC_SUM_SMOOTH_X 2
+#define MODE_PHOTOMETRIC_SUM_SMOOTH_Y 3
+typedef struct mode_photometric_params {
+  float alpha, lam, beta, c1, c2;
+  float mean[3], std[3];                    /* the normalisation the images carry (per channel) */
+  float weights[MODE_PHOTOMETRIC_MAX_MAPS]; /* wgt[k]; entries at and beyond K are ignored */
+} mode_photometric_params;
+size_t mode_photometric_loss_workspace_bytes(int K, int B, int H, int W);
+int mode_photometric_loss_fwd(const float* left, const float* right, const float* disp, int K, int B, int H, int W,
+                              const mode_photometric_params* params, void* workspace, size_t workspace_bytes, double* stats, float* loss,
+                              mode_stream_t stream);
+int mode_photometric_loss_bwd(const float* left, const float* right, const float* disp, int K, int B, int H, int W,
+                              const mode_photometric_params* params, const double* stats, const float* gloss, float* gdisp,
+                              mode_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,10 @@ SIGNATURES = {
     'mode_adam_block_bytes': (_c_size, [_c_int]),
     'mode_adam_prepare': (_c_int, [_c_ptr, ctypes.c_longlong, _c_ptr, _c_size, _c_ptr, _c_int, _c_int, _c_ptr]),
     'mode_adam_update': (_c_int, [_c_ptr, _c_int, _c_ptr, _c_int] + [_c_ptr] * 4 + [_c_int, _c_ptr]),
+    # self-supervised stereo loss: Cassini warp, SSIM + L1, edge-aware smoothness (csrc/photometric.hip)
+    'mode_photometric_loss_workspace_bytes': (_c_size, [_c_int] * 4),
+    'mode_photometric_loss_fwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 3),
+    'mode_photometric_loss_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr] * 5),
 }
 
 ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against
@@ -262,6 +266,18 @@ class MetricsParams(ctypes.Structure):
   """struct mode_metrics_params of include/mode_hip.h (host memory, read during the call)."""
   _T = ctypes.c_float * METRICS_MAX_THRESHOLDS
   _fields_ = [('n_px', _c_int), ('px', _T), ('n_d1', _c_int), ('d1_px', _T), ('d1_pct', _T), ('n_ratio', _c_int), ('ratio', _T)]
+
+
+PHOTOMETRIC_MAX_MAPS = 4  # MODE_PHOTOMETRIC_MAX_MAPS
+# MODE_PHOTOMETRIC_* of include/mode_hip.h: the statistics of one disparity map as mode_photometric_loss_fwd leaves them
+(PH_N_VALID, PH_SUM_PE, PH_SUM_SMOOTH_X, PH_SUM_SMOOTH_Y) = range(4)
+PHOTOMETRIC_STATS = 4
+
+
+class PhotometricParams(ctypes.Structure):
+  """struct mode_photometric_params of include/mode_hip.h (host memory, read during the call)."""
+  _fields_ = [('alpha', ctypes.c_float), ('lam', ctypes.c_float), ('beta', ctypes.c_float), ('c1', ctypes.c_float), ('c2', ctypes.c_float),
+              ('mean', ctypes.c_float * 3), ('std', ctypes.c_float * 3), ('weights', ctypes.c_float * PHOTOMETRIC_MAX_MAPS)]
 
 
 def check(rc, what):

@@ -6,7 +6,8 @@ import threading
 
 import torch
 
-from . import METRICS_COUNT, METRICS_MAX_THRESHOLDS, BnEpilogue, MetricsParams, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of
+from . import (METRICS_COUNT, METRICS_MAX_THRESHOLDS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS, BnEpilogue, MetricsParams, PhotometricParams, check, lib,
+               profiling, ptr, require_f32c, require_gpu, stream_of)
 
 
 def _call(entry, *args):
@@ -1940,6 +1941,91 @@ def silog_loss(pred, gt, mask=None, lamda=0.5):
   the compaction: `mask` is the outer selection (gt <= maxdepth; None: every element), gt > 0 and pred > 0 are applied inside.  pred
   may be (B, 1, H, W) with gt and mask (B, H, W).  Returns a 0-d device tensor; no host synchronisation (graph-capturable)."""
   return SilogLossFunction.apply(pred, gt, mask, lamda)
+
+
+# ------------------------------------------------------------------------------------ self-supervised stereo loss (DESIGN 22)
+# Composed from torch operators the loss is about 60 elementwise, pooling and gather launches per disparity map, with autograd's
+# scatter in the backward; here it is two launches forward and one backward for all K maps (csrc/photometric.hip), bit-repeatable.
+def _photometric_params(K, weights, alpha, lam, beta, mean, std, c1=1e-4, c2=9e-4):
+  from dataloader.preprocess import imagenet_stats
+  mean = imagenet_stats['mean'] if mean is None else mean
+  std = imagenet_stats['std'] if std is None else std
+  if len(mean) != 3 or len(std) != 3:
+    raise ValueError('photometric_loss: mean and std have one entry per colour channel (3), got %d and %d' % (len(mean), len(std)))
+  if len(weights) != K:
+    raise ValueError('photometric_loss: %d disparity maps but %d weights' % (K, len(weights)))
+  prm = PhotometricParams()
+  prm.alpha, prm.lam, prm.beta, prm.c1, prm.c2 = float(alpha), float(lam), float(beta), float(c1), float(c2)
+  for c in range(3):
+    prm.mean[c], prm.std[c] = float(mean[c]), float(std[c])
+  for k in range(K):
+    prm.weights[k] = float(weights[k])
+  return prm
+
+
+class PhotometricLossFunction(torch.autograd.Function):
+  """(left, right, prm, disp_0 .. disp_{K-1}) -> (loss 0-d, stats (K, PHOTOMETRIC_STATS) float64): one forward launch pair and one
+  backward launch for all K maps.  Gradient into the disparities only (the images are data); the statistics carry none."""
+
+  @staticmethod
+  def forward(ctx, left, right, prm, *disps):
+    K = len(disps)
+    B, _, H, W = left.shape
+    disp = torch.empty((K, B, H, W), dtype=left.dtype, device=left.device)  # the layout of the entry
+    for k, d in enumerate(disps):
+      disp[k].copy_(d.reshape(B, H, W))
+    require_f32c(left, right, disp)
+    stats = torch.empty((K, PHOTOMETRIC_STATS), dtype=torch.float64, device=left.device)
+    loss = torch.empty(1, dtype=torch.float32, device=left.device)
+    nbytes = 4 * K * (left.numel() + right.numel() + disp[0].numel())
+    with torch.cuda.device_of(left), profiling.region('photometric_loss_fwd', nbytes, 0, left.device):
+      ws = torch.empty(max(lib().mode_photometric_loss_workspace_bytes(K, B, H, W) // 8, 1), dtype=torch.float64, device=left.device)
+      _call('mode_photometric_loss_fwd', ptr(left), ptr(right), ptr(disp), K, B, H, W, ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(stats),
+            ptr(loss), stream_of(left))
+    ctx.save_for_backward(left, right, disp, stats)
+    ctx.prm, ctx.shapes = prm, [d.shape for d in disps]
+    ctx.mark_non_differentiable(stats)
+    return loss.reshape(()), stats
+
+  @staticmethod
+  def backward(ctx, gloss, _gstats):
+    left, right, disp, stats = ctx.saved_tensors
+    K, B, H, W = disp.shape
+    gl = gloss.reshape(1).to(torch.float32).contiguous()
+    gdisp = torch.empty_like(disp)
+    nbytes = 4 * K * (left.numel() + right.numel() + 2 * disp[0].numel())
+    with torch.cuda.device_of(left), profiling.region('photometric_loss_bwd', nbytes, 0, left.device):
+      _call('mode_photometric_loss_bwd', ptr(left), ptr(right), ptr(disp), K, B, H, W, ctypes.byref(ctx.prm), ptr(stats), ptr(gl), ptr(gdisp),
+            stream_of(left))
+    return (None, None, None) + tuple(gdisp[k].view(shape) for k, shape in enumerate(ctx.shapes))
+
+
+def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False):
+  """The self-supervised loss of a rectified Cassini stereo pair (include/mode_hip.h has the definition): the right image
+  warped to the left view by each disparity map, SSIM + L1 over 3x3 windows whose rows wrap along H, plus lam x an edge-aware smoothness
+  term, summed over the maps with `weights`.  left, right (B, 3, H, W) as the model takes them (normalised with mean / std, default
+  dataloader.preprocess.imagenet_stats); disps: 1 .. 4 tensors (B, 1, H, W) or (B, H, W), e.g. the three training outputs.  Returns a
+  0-d device tensor with autograd into every map (not into the images); with return_stats also a (K, 3) float64 device tensor
+  [N_valid, photo, smooth] per map.  No host synchronisation; the counts stay on the device."""
+  disps = list(disps)
+  require_gpu(left, right, *disps)
+  K = len(disps)
+  if not 1 <= K <= PHOTOMETRIC_MAX_MAPS:
+    raise ValueError('photometric_loss: %d disparity maps (1 .. %d)' % (K, PHOTOMETRIC_MAX_MAPS))
+  if left.dim() != 4 or left.shape[1] != 3 or right.shape != left.shape:
+    raise ValueError('photometric_loss: left and right must be (B, 3, H, W), got %s and %s' % (tuple(left.shape), tuple(right.shape)))
+  B, _, H, W = left.shape
+  for d in disps:
+    if tuple(d.shape) not in ((B, 1, H, W), (B, H, W)):
+      raise ValueError('photometric_loss: a disparity map of shape %s for images %s' % (tuple(d.shape), tuple(left.shape)))
+  prm = _photometric_params(K, weights, alpha, lam, beta, mean, std)
+  loss, stats = PhotometricLossFunction.apply(left.contiguous(), right.contiguous(), prm, *disps)
+  if not return_stats:
+    return loss
+  n = stats[:, 0]
+  photo = stats[:, 1] / n.clamp(min=1)
+  smooth = stats[:, 2] / (B * H * (W - 1)) + stats[:, 3] / (B * H * W)
+  return loss, torch.stack([n, photo, smooth], 1)
 
 
 # ------------------------------------------------------------------------------------ scoring in the ERP domain

@@ -73,6 +73,7 @@ class ModeDisparity(nn.Module):
     print("MODE stereo matching network!")
     self.maxdisp = maxdisp
     self.out_conf = out_conf
+    self.sphereType = sphereType
     if conv == 'Regular':
       self.feature_extraction = feature_extraction()
       print("using Regular feature extraction!")
@@ -142,6 +143,25 @@ class ModeDisparity(nn.Module):
     for wgt, o in zip(weights, preds):
       per = F.smooth_l1_loss(o, gt0, reduction='none')
       loss = loss + wgt * torch.where(mask, per, torch.zeros((), dtype=per.dtype, device=per.device)).sum() / count
+    return loss, tuple(p.detach() for p in preds)
+
+  def forward_photometric_loss(self, left, right, weights=(0.5, 0.7, 1.0), **loss_kw):
+    """The training iteration without ground truth, after the precedent of forward_loss: the three training outputs
+    through the differentiable heads, then ONE HF.photometric_loss call over them -- the right image warped to the left view by each
+    output, SSIM + L1 and an edge-aware smoothness term, weighted as the supervised loss weights its heads.  An extension (the reference
+    has no self-supervised entry).  Returns (loss, (pred1, pred2, pred3)), the predictions detached.  loss_kw: alpha, lam, beta, mean,
+    std of HF.photometric_loss.  Cassini only: the loss wraps its windows along H, which is the periodic axis of that projection."""
+    if not self.training:
+      raise RuntimeError('forward_photometric_loss() is a training step; call the module itself for inference')
+    if self.sphereType != 'Cassini':
+      raise ValueError("forward_photometric_loss: sphereType must be 'Cassini', not %r: the loss takes rows modulo H, Cassini's "
+                       'periodic axis' % (self.sphereType,))
+    if loss_kw.get('return_stats'):
+      raise ValueError('forward_photometric_loss returns (loss, predictions); call HF.photometric_loss for the statistics')
+    costs = self._logits(left, right)
+    size = (self.maxdisp, left.size(2), left.size(3))
+    preds = tuple(stage3d.head(c, size) for c in costs)
+    loss = HF.photometric_loss(left, right, preds, weights, **loss_kw)
     return loss, tuple(p.detach() for p in preds)
 
   def _logits(self, left, right):

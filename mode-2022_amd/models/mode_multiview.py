@@ -259,3 +259,15 @@ class ModeMultiView(nn.Module):
       output = self.fusion.feature_extraction(fusion_input)
     loss = HF.silog_loss(output, gt, gt <= (self.maxdepth if maxdepth is None else maxdepth), lamda)
     return loss, output.detach()
+
+  def photometric_loss(self, frames, **loss_kw):
+    """Adapt stage 1 to a rig's own images, which come without depth or disparity ground truth: frames exactly as
+    fusion_loss takes them, float or uint8, with or without rig= -> (loss, disp.detach()), the loss of
+    ModeDisparity.forward_photometric_loss over the P F stereo pairs of the frames and disp (P F, 1, H, W) its third output.  Needs
+    disparity.train().  The fusion network is not run and its parameters get no gradient; resize=True changes nothing here (stage 1
+    always runs at full size).  loss_kw: weights, alpha, lam, beta, mean, std."""
+    if not self.disparity.training:
+      raise RuntimeError('ModeMultiView.photometric_loss trains the disparity stage: call .disparity.train() first')
+    left, right, _, _ = self._ingest(frames)
+    loss, preds = self.disparity.forward_photometric_loss(left, right, **loss_kw)
+    return loss, preds[2]
