@@ -400,6 +400,32 @@ def _check_pos(pos, x, Kh, Kw):
                        (x.shape[2], x.shape[3], pos.shape[2], pos.shape[3]))
 
 
+def _per_table(cache, lock, pos, extra, build):
+  """build() once per (table, extra, device): the idiom of the four table caches below.  The key uses the table's address, so the
+  entry is (value, pos): it keeps `pos` alive.  A value may be None (a table without a plan is remembered as such)."""
+  key = (pos.data_ptr(), pos._version, tuple(pos.shape)) + tuple(extra) + (str(pos.device),)
+  with lock:
+    hit = cache.get(key)
+    if hit is None:
+      hit = cache[key] = (build(), pos)
+    return hit[0]
+
+
+# The plan records: what sphere_plan and sphere_adjplan return.  The kernels trust them blindly (DESIGN 3b, "The plan contract").
+#   tiles    int32 device tensor, 4 words per 64 x 4 tile (origin row, origin column, window base row, window base column with the
+#            class above bit 16), listed wrap-around tiles first, then mid-window, then compact (small-window) ones
+#   counts   (n_small, n_mid, n_wrap)
+#   rest     pixels of the non-small tiles, int32 device tensor (the pixel list of the weight gradient); nrest: their number
+#   rec_w, rec_off   record weights (4 floats) and LDS offsets of the compact tiles' taps
+#   polar    the polar items of the tall-window (mid and wrap-around) tiles as PolarItems, or None where the planner made none
+SpherePlan = collections.namedtuple('SpherePlan', 'tiles counts rest nrest rec_w rec_off polar')
+#   items    20 int32 words per item; rec_w, rec_off: 288 records per item; n: the number of items
+PolarItems = collections.namedtuple('PolarItems', 'items rec_w rec_off n')
+#   tiles    the good tiles, int32 device tensor, 4 words each; ngood: their number
+#   rec_off, rec_w     four-source records of the good tiles; rec_off2, rec_w2: the two further sources of the six-source class
+#   bad_ids  64-pixel tile ids, in plane-transposed storage, of the tiles left to the gather kernel's list form (None if none); nbad: their number
+SphereAdjPlan = collections.namedtuple('SphereAdjPlan', 'tiles ngood rec_off rec_w bad_ids nbad rec_off2 rec_w2')
+
 _plan_cache = _LRU(TABLE_CACHE_ENTRIES)
 _plan_lock = threading.Lock()
 SPHERE_LAYOUT = 'transposed'  # windowed kernels on plane-transposed copies | 'nchw'
@@ -420,14 +446,10 @@ def transpose_planes(t, out=None):
 
 
 def sphere_plan(pos, kh, kw):
-  """Tile plan of the windowed kernels for the sampling table `pos`: (tiles int32 device tensor, (n_small, n_mid, n_wrap),
-  pixels of the non-small tiles int32 device tensor, their number, record weights, record offsets, polar items or None) or None when the table is not spatially compact (the
-  general gather kernels are used then).  Built on the host by
-  mode_sphere_plan_build once per (table, device) and cached, like the adjoint table."""
-  key = (pos.data_ptr(), pos._version, tuple(pos.shape), kh, kw, str(pos.device))
-  with _plan_lock:
-    if key in _plan_cache:
-      return _plan_cache[key][0]
+  """Tile plan of the windowed kernels for the sampling table `pos`: a SpherePlan, or None when the table is not spatially compact
+  (the general gather kernels are used then).  Built on the host by mode_sphere_plan_build once per (table, device) and cached,
+  like the adjoint table."""
+  def build():
     H, W = pos.shape[2:]
     host = pos.detach().to('cpu', torch.float32).contiguous()
     n = lib().mode_sphere_plan_max_tiles(H, W)
@@ -456,12 +478,12 @@ def sphere_plan(pos, kh, kw):
         _call('mode_sphere_plan_polar', ptr(host), ptr(tiles), ptr(counts), H, W, ptr(pitems), ptr(prw), ptr(pro), ptr(npol))
         if int(npol) > 0:
           n = int(npol)
-          polar = (pitems[:20 * n].contiguous().to(pos.device), prw[:4 * 288 * n].contiguous().to(pos.device),
-                   pro[:288 * n].contiguous().to(pos.device), n)
-      plan = (tiles.to(pos.device), (c[0], c[1], c[2]), rest[:max(nrest, 1)].contiguous().to(pos.device), nrest, rec_w.to(pos.device),
-              rec_off.to(pos.device), polar)
-    _plan_cache[key] = (plan, pos)  # keep `pos` alive: the key uses its address
+          polar = PolarItems(pitems[:20 * n].contiguous().to(pos.device), prw[:4 * 288 * n].contiguous().to(pos.device),
+                             pro[:288 * n].contiguous().to(pos.device), n)
+      plan = SpherePlan(tiles.to(pos.device), (c[0], c[1], c[2]), rest[:max(nrest, 1)].contiguous().to(pos.device), nrest,
+                        rec_w.to(pos.device), rec_off.to(pos.device), polar)
     return plan
+  return _per_table(_plan_cache, _plan_lock, pos, (kh, kw), build)
 
 
 SPHERE_FWD_F16 = True  # the small-window tiles of a TRAINING forward on two fp16 pieces / three MFMAs per product (bf16x6 only)
@@ -546,25 +568,71 @@ def _sphere_fwd_route(pos, w, B, groups, stride, same_size, honour_switch, nativ
     ('window', plan)    the LDS-window kernels on the tile plan of pos (on plane-transposed copies where SPHERE_LAYOUT says so);
     ('native_t', post)  an ERP-like table: the `_t` operator on the NCHW tensors themselves, with the transposed table post;
     ('gather', None)    the general gather-and-MAC kernel.
-  The rule, written once: stride 1, 3 x 3 taps and an output of the input's size (same_size) can be planned; a plan of fewer than
-  SPHERE_FWD_MIN_WG workgroups is dropped (one workgroup per 64x4 tile, sample and 128-channel slice: below ~one workgroup per CU the
-  general kernel's 64-pixel tiles fill the chip better -- measured at B = 1, 256x128: 22.9 vs 20.3 ms for the whole eval forward); a plan
-  that is not usable as a whole (_plan_usable) gives way to the transposed table where that one is.
+  The rule: the geometry of sphere_win_geometry can be planned; a plan of fewer than SPHERE_FWD_MIN_WG workgroups is dropped (one
+  workgroup per 64x4 tile, sample and 128-channel slice: below ~one workgroup per CU the general kernel's 64-pixel tiles fill the chip
+  better -- measured at B = 1, 256x128: 22.9 vs 20.3 ms for the whole eval forward); an ERP-like table (_sphere_layout) runs on its
+  transpose where sphere_t_supported takes that one.
   Where the sites differ:
     honour_switch  whether SPHERE_FWD = 'gather' turns the windowed kernels off: the training operator (sphere_conv_fwd) and
                    sphere_t_supported pass True, the inference wrapper (sphere_conv_bn_eval) passes False -- it never read the switch;
     native_t       False for sphere_t_supported, which asks about the table it was given only."""
   Kh, Kw = w.shape[2:]
-  if (honour_switch and SPHERE_FWD != 'window') or tuple(stride) != (1, 1) or Kh * Kw != 9 or not same_size:
+  if (honour_switch and SPHERE_FWD != 'window') or not sphere_win_geometry(stride, Kh, Kw, same_size):
     return 'gather', None
-  plan = sphere_plan(pos, Kh, Kw)
-  if plan is not None and sum(plan[1]) * B * groups * (-(-(w.shape[0] // groups) // 128)) < SPHERE_FWD_MIN_WG:
-    plan = None
-  if native_t and not _plan_usable(plan):
-    post = sphere_native_t(pos, Kh, Kw)
-    if post is not None and sphere_t_supported(post, w, B, groups):
+  if native_t:
+    kind, post = _sphere_layout(pos, Kh, Kw)
+    if kind == 'native_t' and sphere_t_supported(post, w, B, groups):
       return 'native_t', post
+  plan = sphere_plan(pos, Kh, Kw)
+  if plan is not None and sum(plan.counts) * B * groups * (-(-(w.shape[0] // groups) // 128)) < SPHERE_FWD_MIN_WG:
+    plan = None
   return ('window', plan) if plan is not None else ('gather', None)
+
+
+def _sphere_bwd_data_route(pos, kh, kw, stride, same_size, overwrite, have_gyt):
+  """Which form runs the input gradient on NCHW tensors (sphere_conv_bwd_data):
+    ('scatter', None)    SPHERE_BWD_DATA = 'scatter': the atomic form;
+    ('native_t', post)   an ERP-like table: sphere_conv_bwd_data_t on the NCHW tensors themselves, with the transposed table;
+    ('copies_t', None)   sphere_conv_bwd_data_t on the plane-transposed copy of the gradient the caller handed in (have_gyt), then a
+                         transpose back: only for a caller that lets the result be overwritten;
+    ('adjoint', None)    the adjoint gather on the NCHW tensors.
+  The two middle answers need SPHERE_BWD_DATA_T.  'copies_t' does not ask for the tap count or the table's kind: whoever hands a
+  transposed copy in gets the transposed problem (the adjoint gather has no tap limit of its own)."""
+  if SPHERE_BWD_DATA != 'gather':
+    return 'scatter', None
+  if SPHERE_BWD_DATA_T and sphere_win_geometry(stride, kh, kw, same_size):
+    kind, post = _sphere_layout(pos, kh, kw)
+    if kind == 'native_t':
+      return 'native_t', post
+  if SPHERE_BWD_DATA_T and overwrite and have_gyt and sphere_win_geometry(stride, 3, 3, same_size):
+    return 'copies_t', None
+  return 'adjoint', None
+
+
+def _sphere_bwd_data_t_route(pos, kh, kw, B, Ci, Co, groups, H, W):
+  """Which kernel runs the input gradient on plane-transposed storage (sphere_conv_bwd_data_t): ('window', aplan) the windowed split
+  kernel on the adjoint plan of pos plus the gather kernel's list form for the plan's bad tiles, or ('adjoint', None) the adjoint gather
+  alone.  The windowed kernel needs the bf16x6 arithmetic, SPHERE_BWD_DATA_SPLIT, channel counts on its grid and an adjoint plan of at
+  least SPHERE_BWD_SPLIT_MIN_WG workgroups (one per good tile, sample and 128-channel slice)."""
+  if (CONV_ARITH == 'bf16x6' and SPHERE_BWD_DATA_SPLIT and kh * kw == 9 and tuple(pos.shape[2:]) == (H, W) and
+      lib().mode_sphere_conv_bwd_data_win_supported(Ci, Co, groups) == 1):
+    aplan = sphere_adjplan(pos, kh, kw)
+    if aplan is not None and aplan.ngood * B * groups * (-(-(Ci // groups) // 128)) >= SPHERE_BWD_SPLIT_MIN_WG:
+      return 'window', aplan
+  return 'adjoint', None
+
+
+def _sphere_bwd_weight_route(pos, kh, kw, stride, same_size):
+  """Which kernel runs the weight gradient on NCHW tensors (sphere_conv_bwd_weight): ('window', plan) the windowed kernels on the
+  plan of pos (on plane-transposed copies where SPHERE_LAYOUT says so; a plan that is not usable as a whole runs with its pixel
+  list), ('native_t', post) an ERP-like table: sphere_conv_bwd_weight_t on the NCHW tensors, or ('gather', None).  No workgroup
+  floor here, and unlike the forward a plan without a compact tile is dropped: nothing to gain."""
+  if SPHERE_BWD_WEIGHT != 'window' or not sphere_win_geometry(stride, kh, kw, same_size):
+    return 'gather', None
+  kind, plan = _sphere_layout(pos, kh, kw)
+  if kind == 'native_t':
+    return 'native_t', plan
+  return ('window', plan) if plan is not None and plan.counts[0] > 0 else ('gather', None)
 
 
 def sphere_conv_fwd(x, pos, w, out, stride, groups, return_transposed=False, f16=False):
@@ -585,36 +653,33 @@ def sphere_conv_fwd(x, pos, w, out, stride, groups, return_transposed=False, f16
   with torch.cuda.device_of(x), profiling.region(_tag2('sphere_conv_fwd', w, x), nbytes, flops, x.device):
     if route == 'window':
       B, Ci, H, W, Co, Kh, Kw = dims[:7]
-      tiles, (n0, n1, n2) = plan[:2]
       wp = torch.empty(lib().mode_sphere_conv_win_wpack_bytes(Ci, Co, Kh, Kw, groups) // 4, dtype=torch.float32, device=w.device)
       amax = _sphere_f16_maxima(x, w, f16)
       if SPHERE_LAYOUT == 'transposed':
         xt, yt = transpose_planes(x), torch.empty((B, Co, W, H), dtype=x.dtype, device=x.device)
-        _sphere_fwd_win(ptr(xt), pos, w, None, ptr(yt), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(x), amax)
+        _sphere_fwd_win(ptr(xt), pos, w, None, ptr(yt), wp, plan, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(x), amax)
         transpose_planes(yt, out)
       else:
-        _sphere_fwd_win(ptr(x), pos, w, None, ptr(out), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 0, stream_of(x), amax)
+        _sphere_fwd_win(ptr(x), pos, w, None, ptr(out), wp, plan, B, Ci, H, W, Co, Kh, Kw, groups, 0, stream_of(x), amax)
     else:
       wp = _wpack(w, groups)
       _call('mode_sphere_conv_fwd', ptr(x), ptr(pos), ptr(w), ptr(out), ptr(wp), *dims, stream_of(x))
   return xt if return_transposed else out
 
 
-def _sphere_fwd_win(xp, pos, w, e, yp, wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, transposed, stream, amax=None):
+def _sphere_fwd_win(xp, pos, w, e, yp, wp, plan, B, Ci, H, W, Co, Kh, Kw, groups, transposed, stream, amax=None):
   """Windowed spherical forward (optional folded-BatchNorm epilogue `e`): the small-window tiles on the split-bf16 kernel when
   CONV_ARITH says so (the library falls back to the fp32 kernels by itself when the channel count does not fit).
   amax = (max |x|, max |w|) device scalars: the fp16 arithmetic (_sphere_f16_maxima; no epilogue)."""
+  tail = (yp, ptr(wp), ptr(plan.tiles)) + tuple(plan.counts) + (B, Ci, H, W, Co, Kh, Kw, groups, transposed, stream)
   if amax is not None and e is None and CONV_ARITH == 'bf16x6':
-    _call('mode_sphere_conv_fwd_win_split_f16', xp, ptr(pos), ptr(w), ptr(amax[0]), ptr(amax[1]), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co,
-          Kh, Kw, groups, transposed, stream)
+    _call('mode_sphere_conv_fwd_win_split_f16', xp, ptr(pos), ptr(w), ptr(amax[0]), ptr(amax[1]), *tail)
   elif CONV_ARITH == 'bf16x6':
-    _call('mode_sphere_conv_fwd_win_split', xp, ptr(pos), ptr(w), ctypes.byref(e) if e is not None else None, yp, ptr(wp), ptr(tiles), n0, n1, n2, B,
-          Ci, H, W, Co, Kh, Kw, groups, transposed, stream)
+    _call('mode_sphere_conv_fwd_win_split', xp, ptr(pos), ptr(w), ctypes.byref(e) if e is not None else None, *tail)
   elif e is not None:
-    _call('mode_sphere_conv_fwd_win_bn', xp, ptr(pos), ptr(w), ctypes.byref(e), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups,
-          transposed, stream)
+    _call('mode_sphere_conv_fwd_win_bn', xp, ptr(pos), ptr(w), ctypes.byref(e), *tail)
   else:
-    _call('mode_sphere_conv_fwd_win', xp, ptr(pos), ptr(w), yp, ptr(wp), ptr(tiles), n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, transposed, stream)
+    _call('mode_sphere_conv_fwd_win', xp, ptr(pos), ptr(w), *tail)
 
 
 _adjoint_cache = _LRU(TABLE_CACHE_ENTRIES)
@@ -626,11 +691,7 @@ def sphere_adjoint(pos, kh, kw, stride, out_hw):
   """Device copies (rowptr int32, entries int32 pairs) of the transposed sampling table of `pos`; built on the host by
   mode_sphere_adjoint_build once per (table, stride, output size, device) and cached -- the table is a constant of the
   module (sphere_conv.py:150)."""
-  key = (pos.data_ptr(), pos._version, tuple(pos.shape), kh, kw, tuple(stride), tuple(out_hw), str(pos.device))
-  with _adjoint_lock:
-    hit = _adjoint_cache.get(key)
-    if hit is not None:
-      return hit
+  def build():
     H, W = pos.shape[2:]
     host = pos.detach().to('cpu', torch.float32).contiguous()
     nmax = lib().mode_sphere_adjoint_max_entries(kh, kw, out_hw[0], out_hw[1])
@@ -639,9 +700,8 @@ def sphere_adjoint(pos, kh, kw, stride, out_hw):
     n = ctypes.c_int64(0)
     _call('mode_sphere_adjoint_build', ptr(host), H, W, kh, kw, stride[0], stride[1], out_hw[0], out_hw[1], ptr(rowptr), ptr(entries),
           ctypes.cast(ctypes.pointer(n), ctypes.c_void_p))
-    hit = (rowptr.to(pos.device), entries[:2 * max(n.value, 1)].contiguous().to(pos.device), pos)  # keep `pos` alive: key uses its address
-    _adjoint_cache[key] = hit
-    return hit
+    return rowptr.to(pos.device), entries[:2 * max(n.value, 1)].contiguous().to(pos.device)
+  return _per_table(_adjoint_cache, _adjoint_lock, pos, (kh, kw, tuple(stride), tuple(out_hw)), build)
 
 
 SPHERE_BWD_DATA_T = True  # adjoint gather on plane-transposed storage
@@ -651,40 +711,64 @@ _pos_t_cache = _LRU(TABLE_CACHE_ENTRIES)
 def _transposed_table(pos):
   """The sampling table of the plane-transposed problem: image (W rows, H columns), row coordinate = the original column
   coordinate and vice versa.  Cached per table like the adjoint."""
-  key = (pos.data_ptr(), pos._version, tuple(pos.shape), str(pos.device))
-  with _adjoint_lock:
-    hit = _pos_t_cache.get(key)
-    if hit is None:
-      K2, H, W = pos.shape[1:]
-      p = pos[0].view(K2 // 2, 2, H, W)
-      t = torch.stack((p[:, 1].transpose(1, 2), p[:, 0].transpose(1, 2)), 1).reshape(1, K2, W, H).contiguous()
-      hit = _pos_t_cache[key] = (t, pos)
-    return hit[0]
+  def build():
+    K2, H, W = pos.shape[1:]
+    p = pos[0].view(K2 // 2, 2, H, W)
+    return torch.stack((p[:, 1].transpose(1, 2), p[:, 0].transpose(1, 2)), 1).reshape(1, K2, W, H).contiguous()
+  return _per_table(_pos_t_cache, _adjoint_lock, pos, (), build)
 
 
 def _plan_usable(plan):
   """A plan the windowed forward / weight-gradient kernels can run as a whole: compact tiles exist and the tall-window tiles (if
-  any) have polar items."""
-  return plan is not None and plan[1][0] > 0 and not (plan[3] and not (plan[6] is not None and SPHERE_POLAR))
+  any) have polar items.  The question _sphere_layout asks of a table's plan and of its transpose's."""
+  return plan is not None and plan.counts[0] > 0 and not (plan.nrest and not (plan.polar is not None and SPHERE_POLAR))
+
+
+def sphere_win_geometry(stride, kh, kw, same_size):
+  """The geometry the windowed kernels and the `_t` operators are written for, stated once: stride (1, 1), 3 x 3 taps and an output
+  of the input's size (same_size)."""
+  return tuple(stride) == (1, 1) and kh * kw == 9 and bool(same_size)
+
+
+def _sphere_layout(pos, kh, kw):
+  """The kind of the sampling table `pos` -- one answer per table, for all three passes:
+    ('copies', plan)    Cassini-like: its own plan is usable as a whole; the windowed kernels run on plane-transposed copies;
+    ('native_t', post)  ERP-like: the plan of its transpose post is; the `_t` operators run on the NCHW tensors themselves.  The
+                        windowed kernels want the shift-invariant (longitude) axis of the table along the lanes and contiguous in
+                        memory.  For the Cassini layout that axis is H, the strided one, hence the copies.  For an ERP table it is W
+                        -- already contiguous: an ERP problem on NCHW storage IS the Cassini problem of the transposed table on
+                        plane-transposed storage (sphere_conv.py:226-236 builds the Cassini table as exactly that transpose);
+    (None, plan)        neither: no 3 x 3 table, SPHERE_LAYOUT 'nchw', or no usable plan either way.  plan is the table's own (or
+                        None), for the sites that run a plan that is not usable as a whole.
+  SPHERE_LAYOUT and SPHERE_POLAR (_plan_usable) are read at call time."""
+  if kh * kw != 9:
+    return None, None
+  plan = sphere_plan(pos, kh, kw)
+  if SPHERE_LAYOUT != 'transposed':
+    return None, plan
+  if _plan_usable(plan):
+    return 'copies', plan
+  post = _transposed_table(pos)
+  return ('native_t', post) if _plan_usable(sphere_plan(post, kh, kw)) else (None, plan)
 
 
 def sphere_native_t(pos, kh, kw):
-  """sphereType = 'ERP' on the fast path.  The windowed kernels want the shift-invariant (longitude) axis of the table along the
-  lanes and contiguous in memory.  For the Cassini layout that axis is H, the strided one, hence the plane-transposed copies.  For
-  an ERP table it is W -- already contiguous: an ERP problem on NCHW storage IS the Cassini problem of the transposed table on
-  plane-transposed storage (sphere_conv.py:226-236 builds the Cassini table as exactly that transpose), so the `_t` operators run
-  on the NCHW tensors as they are, with no transpose at all.  Returns the transposed table when `pos` itself cannot be planned but
-  its transpose can; else None."""
-  if kh * kw != 9 or SPHERE_LAYOUT != 'transposed' or _plan_usable(sphere_plan(pos, kh, kw)):
-    return None
-  post = _transposed_table(pos)
-  return post if _plan_usable(sphere_plan(post, kh, kw)) else None
+  """sphereType = 'ERP' on the fast path: the transposed table when `pos` itself cannot be planned but its transpose can; else None."""
+  kind, post = _sphere_layout(pos, kh, kw)
+  return post if kind == 'native_t' else None
 
 
 def sphere_uses_transposed_copies(pos, kh, kw):
   """Whether the gradients of this table run on plane-transposed COPIES of their operands (Cassini-like tables); ERP-like tables
   (sphere_native_t) and tables without a plan do not."""
-  return SPHERE_LAYOUT == 'transposed' and kh * kw == 9 and _plan_usable(sphere_plan(pos, kh, kw))
+  return _sphere_layout(pos, kh, kw)[0] == 'copies'
+
+
+def sphere_grads_want_transposed_gy(pos, kh, kw, stride, same_size):
+  """Whether the caller of the two gradients should hand both one plane-transposed copy of grad_output (sphere_conv_backward_cuda
+  asks).  Asked of the table and the geometry only: the copy is also built where SPHERE_BWD_DATA = 'scatter' together with
+  SPHERE_BWD_WEIGHT = 'gather' leaves nobody to read it."""
+  return sphere_win_geometry(stride, kh, kw, same_size) and sphere_uses_transposed_copies(pos, kh, kw)
 
 
 def sphere_conv_bwd_data(gy, pos, w, gx, stride, groups, overwrite=False, gy_transposed=None):
@@ -698,32 +782,29 @@ def sphere_conv_bwd_data(gy, pos, w, gx, stride, groups, overwrite=False, gy_tra
   dims = _sc_dims(gx.shape, w.shape, gy.shape[2:], stride, groups)
   flops = 2 * gy.numel() * w[0].numel()
   nbytes = 4 * (gx.numel() + gy.numel() + pos.numel() + w.numel())
-  if SPHERE_BWD_DATA == 'gather':
-    B, Ci, H, W, Co, Kh, Kw, sH, sW, Ho, Wo, G = dims
-    post = sphere_native_t(pos, Kh, Kw) if ((sH, sW) == (1, 1) and (Ho, Wo) == (H, W) and SPHERE_BWD_DATA_T) else None
-    if post is not None:  # ERP-like table: the adjoint gather of the transposed problem reads and writes the NCHW tensors directly
-      if overwrite:
-        return sphere_conv_bwd_data_t(gy, post, w, gx, groups)
-      gx += sphere_conv_bwd_data_t(gy, post, w, torch.empty_like(gx), groups)
-      return gx
-    use_t = (SPHERE_BWD_DATA_T and overwrite and gy_transposed is not None and (sH, sW) == (1, 1) and (Ho, Wo) == (H, W) and
-             tuple(gy_transposed.shape) == (B, Co, Wo, Ho))
-    if use_t:  # the operator on the plane-transposed problem (windowed split kernel where the adjoint plan allows), then back
-      gxt = sphere_conv_bwd_data_t(gy_transposed, pos, w, torch.empty((B, Ci, W, H), dtype=gx.dtype, device=gx.device), groups)
-      with torch.cuda.device_of(gy):
-        transpose_planes(gxt, gx)
-      return gx
-    with torch.cuda.device_of(gy), profiling.region(_tag2('sphere_conv_bwd_data', w, gx), nbytes, flops, gy.device):
-      wp = _wpack(w, groups)
-      rowptr, entries, _ = sphere_adjoint(pos, Kh, Kw, stride, gy.shape[2:])
-      _call('mode_sphere_conv_bwd_data_adj', ptr(gy), ptr(w), ptr(gx), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, H, W, Co, Kh, Kw, Ho, Wo, G,
-            0 if overwrite else 1, stream_of(gy))
+  B, Ci, H, W, Co, Kh, Kw, sH, sW, Ho, Wo, G = dims
+  route, post = _sphere_bwd_data_route(pos, Kh, Kw, stride, (Ho, Wo) == (H, W), overwrite,
+                                       gy_transposed is not None and tuple(gy_transposed.shape) == (B, Co, Wo, Ho))
+  if route == 'native_t':  # the adjoint gather of the transposed problem reads and writes the NCHW tensors directly
+    if overwrite:
+      return sphere_conv_bwd_data_t(gy, post, w, gx, groups)
+    gx += sphere_conv_bwd_data_t(gy, post, w, torch.empty_like(gx), groups)
     return gx
-  if overwrite:
+  if route == 'copies_t':  # the operator on the plane-transposed problem (windowed split kernel where the adjoint plan allows), then back
+    gxt = sphere_conv_bwd_data_t(gy_transposed, pos, w, torch.empty((B, Ci, W, H), dtype=gx.dtype, device=gx.device), groups)
+    with torch.cuda.device_of(gy):
+      transpose_planes(gxt, gx)
+    return gx
+  if route == 'scatter' and overwrite:
     gx.zero_()  # the scatter form adds with atomics
   with torch.cuda.device_of(gy), profiling.region(_tag2('sphere_conv_bwd_data', w, gx), nbytes, flops, gy.device):
     wp = _wpack(w, groups)
-    _call('mode_sphere_conv_bwd_data', ptr(gy), ptr(pos), ptr(w), ptr(gx), ptr(wp), *dims, stream_of(gy))
+    if route == 'scatter':
+      _call('mode_sphere_conv_bwd_data', ptr(gy), ptr(pos), ptr(w), ptr(gx), ptr(wp), *dims, stream_of(gy))
+    else:
+      rowptr, entries = sphere_adjoint(pos, Kh, Kw, stride, gy.shape[2:])
+      _call('mode_sphere_conv_bwd_data_adj', ptr(gy), ptr(w), ptr(gx), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, H, W, Co, Kh, Kw, Ho, Wo, G,
+            0 if overwrite else 1, stream_of(gy))
   return gx
 
 
@@ -781,17 +862,11 @@ def sphere_conv_bwd_weight(gy, pos, x, gw, stride, groups, x_transposed=None, gy
   B, Ci, H, W, Co, Kh, Kw, sH, sW, Ho, Wo, G = dims
   flops = 2 * gy.numel() * gw[0].numel()
   nbytes = 4 * (x.numel() + gy.numel() + pos.numel() + gw.numel())
-  plan = None
-  if SPHERE_BWD_WEIGHT == 'window' and (sH, sW) == (1, 1) and Kh * Kw == 9 and (Ho, Wo) == (H, W):
-    plan = sphere_plan(pos, Kh, Kw)
-    if plan is not None and plan[1][0] == 0:
-      plan = None  # no compact tile at all: nothing to gain
-    if not _plan_usable(plan):  # the same predicate as the forward and the input gradient: one layout per table
-      post = sphere_native_t(pos, Kh, Kw)
-      if post is not None:  # ERP-like table
-        return sphere_conv_bwd_weight_t(gy, post, x, gw, groups)
+  route, plan = _sphere_bwd_weight_route(pos, Kh, Kw, stride, (Ho, Wo) == (H, W))
+  if route == 'native_t':
+    return sphere_conv_bwd_weight_t(gy, plan, x, gw, groups)
   with torch.cuda.device_of(gy), profiling.region(_tag2('sphere_conv_bwd_weight', gw, x), nbytes, flops, gy.device):
-    if plan is not None:
+    if route == 'window':
       gyt = xt = None
       if SPHERE_LAYOUT == 'transposed':
         gyt = gy_transposed if gy_transposed is not None and tuple(gy_transposed.shape) == (B, Co, Wo, Ho) else transpose_planes(gy)
@@ -824,7 +899,7 @@ def sphere_conv_fwd_t(xt, pos, w, yt, groups, f16=False, amax_out=None):
   B, Ci, W, H = xt.shape
   Co, _, Kh, Kw = w.shape
   assert tuple(pos.shape[2:]) == (H, W) and tuple(yt.shape) == (B, Co, W, H)
-  tiles, (n0, n1, n2) = sphere_plan(pos, Kh, Kw)[:2]
+  plan = sphere_plan(pos, Kh, Kw)
   flops = 2 * yt.numel() * w[0].numel()
   nbytes = 4 * (xt.numel() + yt.numel() + pos.numel() + w.numel())
   with torch.cuda.device_of(xt), profiling.region('sphere_conv_fwd[%d->%d %dx%d]' % (Ci, Co, H, W), nbytes, flops, xt.device):
@@ -832,7 +907,7 @@ def sphere_conv_fwd_t(xt, pos, w, yt, groups, f16=False, amax_out=None):
     amax = _sphere_f16_maxima(xt, w, f16)
     if amax is not None and amax_out is not None:
       amax_out.append(amax)
-    _sphere_fwd_win(ptr(xt), pos, w, None, ptr(yt), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(xt), amax)
+    _sphere_fwd_win(ptr(xt), pos, w, None, ptr(yt), wp, plan, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(xt), amax)
   return yt
 
 
@@ -844,12 +919,8 @@ SPHERE_BWD_SPLIT_MIN_WG = 200  # fewer 64 x 4 tiles x samples than this: the 64-
 def sphere_adjplan(pos, kh, kw):
   """Adjoint-window plan of the sampling table `pos` (H, W) for the windowed input-gradient kernel, or None when no tile qualifies
   (or H is not a multiple of 64: the left-over tiles are handed to the gather kernel as whole 64-pixel runs of one stored row).
-  (good tiles int32 device, n_good, rec_off int32 device, rec_w float32 device, bad 64-pixel tile ids of the plane-transposed
-  storage int32 device, n_bad_ids).  Built on the host by mode_sphere_adjplan_build once per (table, device), cached."""
-  key = (pos.data_ptr(), pos._version, tuple(pos.shape), kh, kw, str(pos.device))
-  with _plan_lock:
-    if key in _adjplan_cache:
-      return _adjplan_cache[key][0]
+  A SphereAdjPlan.  Built on the host by mode_sphere_adjplan_build once per (table, device), cached."""
+  def build():
     H, W = pos.shape[2:]
     plan = None
     if kh * kw == 9 and H % 64 == 0 and W % 4 == 0:
@@ -871,11 +942,11 @@ def sphere_adjplan(pos, kh, kw):
         ids = ((b2[:, 1:2] + torch.arange(4).view(1, 4)) * H + b2[:, 0:1]) // 64 if nb else torch.zeros((0, 4), dtype=torch.int64)
         ids = ids.reshape(-1).sort().values.to(torch.int32)
         dev = pos.device
-        plan = (good[:4 * ng].contiguous().to(dev), ng, rec_off[:ng * 9 * 256 * 4].contiguous().to(dev),
-                rec_w[:ng * 9 * 256 * 4].contiguous().to(dev), ids.contiguous().to(dev) if nb else None, int(ids.numel()),
-                rec_off2[:ng * 9 * 256 * 2].contiguous().to(dev), rec_w2[:ng * 9 * 256 * 2].contiguous().to(dev))
-    _adjplan_cache[key] = (plan, pos)  # keep `pos` alive: the key uses its address
+        plan = SphereAdjPlan(good[:4 * ng].contiguous().to(dev), ng, rec_off[:ng * 9 * 256 * 4].contiguous().to(dev),
+                             rec_w[:ng * 9 * 256 * 4].contiguous().to(dev), ids.contiguous().to(dev) if nb else None, int(ids.numel()),
+                             rec_off2[:ng * 9 * 256 * 2].contiguous().to(dev), rec_w2[:ng * 9 * 256 * 2].contiguous().to(dev))
     return plan
+  return _per_table(_adjplan_cache, _plan_lock, pos, (kh, kw), build)
 
 
 def sphere_conv_bwd_data_t(gyt, pos, w, gxt, groups, w_amax=None):
@@ -886,24 +957,18 @@ def sphere_conv_bwd_data_t(gyt, pos, w, gxt, groups, w_amax=None):
   Ci, Kh, Kw = gxt.shape[1], w.shape[2], w.shape[3]
   flops = 2 * gyt.numel() * w[0].numel()
   nbytes = 4 * (gxt.numel() + gyt.numel() + pos.numel() + w.numel())
-  rowptr, entries, _ = sphere_adjoint(_transposed_table(pos), Kh, Kw, (1, 1), (W, H))
-  aplan = None
-  if (CONV_ARITH == 'bf16x6' and SPHERE_BWD_DATA_SPLIT and Kh * Kw == 9 and tuple(pos.shape[2:]) == (H, W) and
-      lib().mode_sphere_conv_bwd_data_win_supported(Ci, Co, groups) == 1):
-    aplan = sphere_adjplan(pos, Kh, Kw)
-    if aplan is not None and aplan[1] * B * groups * (-(-(Ci // groups) // 128)) < SPHERE_BWD_SPLIT_MIN_WG:
-      aplan = None
+  rowptr, entries = sphere_adjoint(_transposed_table(pos), Kh, Kw, (1, 1), (W, H))
+  route, aplan = _sphere_bwd_data_t_route(pos, Kh, Kw, B, Ci, Co, groups, H, W)
   with torch.cuda.device_of(gyt), profiling.region('sphere_conv_bwd_data[%d->%d %dx%d]' % (Ci, Co, H, W), nbytes, flops, gyt.device):
     wp = _wpack(w, groups)
-    if aplan is not None:
+    if route == 'window':
       tiles, ng, rec_off, rec_w, bad_ids, nbad, rec_off2, rec_w2 = aplan
       wps = torch.empty(lib().mode_sphere_conv_bwd_data_win_wpack_bytes(Ci, Co, Kh, Kw, groups) // 4, dtype=torch.float32, device=w.device)
+      tail = (ptr(gxt), ptr(wps), ptr(tiles), ng, ptr(rec_off), ptr(rec_w), ptr(rec_off2), ptr(rec_w2), B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(gyt))
       if SPHERE_BWD_F16:  # (a backward pass is a training step: the two-piece fp16 arithmetic)
-        _call('mode_sphere_conv_bwd_data_win_split_f16', ptr(gyt), ptr(w), ptr(_tagged_abs_max(gyt)), ptr(_weight_abs_max(w, w_amax)), ptr(gxt),
-              ptr(wps), ptr(tiles), ng, ptr(rec_off), ptr(rec_w), ptr(rec_off2), ptr(rec_w2), B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(gyt))
+        _call('mode_sphere_conv_bwd_data_win_split_f16', ptr(gyt), ptr(w), ptr(_tagged_abs_max(gyt)), ptr(_weight_abs_max(w, w_amax)), *tail)
       else:
-        _call('mode_sphere_conv_bwd_data_win_split', ptr(gyt), ptr(w), ptr(gxt), ptr(wps), ptr(tiles), ng, ptr(rec_off), ptr(rec_w), ptr(rec_off2),
-              ptr(rec_w2), B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(gyt))
+        _call('mode_sphere_conv_bwd_data_win_split', ptr(gyt), ptr(w), *tail)
       if nbad:  # the tiles next to the poles and the few columns with more than four sources per tap: gather kernel on a tile list
         _call('mode_sphere_conv_bwd_data_adj_list', ptr(gyt), ptr(w), ptr(gxt), ptr(wp), ptr(rowptr), ptr(entries), B, Ci, W, H, Co, Kh, Kw, W, H,
               groups, 0, ptr(bad_ids), nbad, stream_of(gyt))
@@ -920,7 +985,7 @@ def sphere_conv_bwd_weight_t(gyt, pos, xt, gw, groups):
   B, Co, W, H = gyt.shape
   Ci, Kh, Kw = xt.shape[1], gw.shape[2], gw.shape[3]
   plan = sphere_plan(pos, Kh, Kw)
-  if plan[3] and plan[6] is None:
+  if plan.nrest and plan.polar is None:
     raise RuntimeError('sphere_conv_bwd_weight_t: the table needs the pixel-list fallback, which reads NCHW tensors')
   flops = 2 * gyt.numel() * gw[0].numel()
   nbytes = 4 * (xt.numel() + gyt.numel() + pos.numel() + gw.numel())
@@ -3168,7 +3233,7 @@ def sphere_conv_bn_eval(x, pos, w, bn, stride, groups, add=None, relu=False, tra
   Co, _, Kh, Kw = w.shape
   if transposed:
     B, Ci, W, H = x.shape
-    plan = sphere_plan(pos, Kh, Kw) if (tuple(stride) == (1, 1) and Kh * Kw == 9) else None
+    plan = sphere_plan(pos, Kh, Kw) if sphere_win_geometry(stride, Kh, Kw, True) else None
     if plan is None:
       raise RuntimeError('sphere_conv_bn_eval: plane-transposed storage needs a plannable sampling table')
   else:
@@ -3180,27 +3245,30 @@ def sphere_conv_bn_eval(x, pos, w, bn, stride, groups, add=None, relu=False, tra
   flops = 2 * B * Co * H * W // (stride[0] * stride[1]) * w[0].numel()
   name = 'sphere_conv_bn_eval[%d->%d %dx%d]' % (Ci, Co, H, W) if profiling.ENABLED else 'sphere_conv_bn_eval'
   with torch.cuda.device_of(x), profiling.region(name, 4 * (2 * x.numel() + w.numel()), flops, x.device):
-    if plan is not None:
-      wp, reuse = _eval_wpack(bn, 'sphere_fwd_win g%d %dx%d' % (groups, H, W), w,
-                              lib().mode_sphere_conv_win_wpack_bytes(Ci, Co, Kh, Kw, groups) // 4, w.device)
-      # an NCHW caller: the windowed kernel on plane-transposed copies (the residual is transposed with it)
-      xt = x if transposed else transpose_planes(x)
-      yt = torch.empty((B, Co, W, H), dtype=x.dtype, device=x.device)
-      e, keep = _epilogue(bn, add if transposed or add is None else transpose_planes(add.contiguous()), relu, yt)
-    else:
-      wp, reuse = _eval_wpack(bn, 'sphere_conv_fwd_bn g%d' % groups, w, lib().mode_sphere_conv_wpack_bytes(w.shape[1] * groups, Co, Kh, Kw, groups) // 4,
-                              w.device)
-      y = torch.empty((B, Co, Ho, Wo), dtype=x.dtype, device=x.device)
-      e, keep = _epilogue(bn, add, relu, y)
+    if plan is None:
+      return _sphere_gather_bn(x, pos, w, bn, stride, groups, add, relu, Ho, Wo)
+    wp, reuse = _eval_wpack(bn, 'sphere_fwd_win g%d %dx%d' % (groups, H, W), w,
+                            lib().mode_sphere_conv_win_wpack_bytes(Ci, Co, Kh, Kw, groups) // 4, w.device)
+    # an NCHW caller: the windowed kernel on plane-transposed copies (the residual is transposed with it)
+    xt = x if transposed else transpose_planes(x)
+    yt = torch.empty((B, Co, W, H), dtype=x.dtype, device=x.device)
+    e, keep = _epilogue(bn, add if transposed or add is None else transpose_planes(add.contiguous()), relu, yt)
     with reuse:
-      if plan is not None:
-        tiles, (n0, n1, n2) = plan[:2]
-        _sphere_fwd_win(ptr(xt), pos, w, e, ptr(yt), wp, tiles, n0, n1, n2, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(x))
-      else:
-        _call('mode_sphere_conv_fwd_bn', ptr(x), ptr(pos), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, Kh, Kw, stride[0], stride[1],
-              Ho, Wo, groups, stream_of(x))
-    if plan is not None:
-      y = yt if transposed else transpose_planes(yt)
+      _sphere_fwd_win(ptr(xt), pos, w, e, ptr(yt), wp, plan, B, Ci, H, W, Co, Kh, Kw, groups, 1, stream_of(x))
+    return yt if transposed else transpose_planes(yt)
+
+
+def _sphere_gather_bn(x, pos, w, bn, stride, groups, add, relu, Ho, Wo):
+  """The general gather kernel with the folded-BatchNorm epilogue, under its packed-weight tag: the one launch of sphere_conv_bn_eval's
+  gather route and of _tabled_bn, each inside its own profiling region."""
+  B, Ci, H, W = x.shape
+  Co, Cig, Kh, Kw = w.shape
+  y = torch.empty((B, Co, Ho, Wo), dtype=x.dtype, device=x.device)
+  e, keep = _epilogue(bn, add, relu, y)
+  wp, reuse = _eval_wpack(bn, 'sphere_conv_fwd_bn g%d' % groups, w, lib().mode_sphere_conv_wpack_bytes(Cig * groups, Co, Kh, Kw, groups) // 4, w.device)
+  with reuse:
+    _call('mode_sphere_conv_fwd_bn', ptr(x), ptr(pos), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, Kh, Kw, stride[0], stride[1], Ho, Wo,
+          groups, stream_of(x))
   return y
 
 
@@ -3233,17 +3301,11 @@ def conv2d_tabled_bn_eval(x, conv, bn, add=None, relu=False):
 
 def _tabled_bn(x, pos, w, bn, stride, add, relu, Ho, Wo):
   B, Ci, H, W = x.shape
-  Co, _, Kh, Kw = w.shape
-  y = torch.empty((B, Co, Ho, Wo), dtype=x.dtype, device=x.device)
-  e, keep = _epilogue(bn, add, relu, y)
-  flops = 2 * y.numel() * w[0].numel()
+  Co = w.shape[0]
+  flops = 2 * B * Co * Ho * Wo * w[0].numel()
   name = 'sphere_conv_bn_eval[%d->%d %dx%d]' % (Ci, Co, H, W) if profiling.ENABLED else 'sphere_conv_bn_eval'
-  with torch.cuda.device_of(x), profiling.region(name, 4 * (x.numel() + y.numel() + w.numel()), flops, x.device):
-    wp, reuse = _eval_wpack(bn, 'sphere_conv_fwd_bn g1', w, lib().mode_sphere_conv_wpack_bytes(w.shape[1], Co, Kh, Kw, 1) // 4, w.device)
-    with reuse:
-      _call('mode_sphere_conv_fwd_bn', ptr(x), ptr(pos), ptr(w), ctypes.byref(e), ptr(y), ptr(wp), B, Ci, H, W, Co, Kh, Kw, stride[0], stride[1], Ho,
-            Wo, 1, stream_of(x))
-  return y
+  with torch.cuda.device_of(x), profiling.region(name, 4 * (x.numel() + B * Co * Ho * Wo + w.numel()), flops, x.device):
+    return _sphere_gather_bn(x, pos, w, bn, stride, 1, add, relu, Ho, Wo)
 
 
 def cost_conv_bn_eval(ref, tgt, weight, d4, bn, relu=True):

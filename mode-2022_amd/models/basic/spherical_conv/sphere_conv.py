@@ -297,7 +297,9 @@ class SphereConv(nn.Module):
   def supports_transposed_io(self, batch, device):
     """Whether forward() can run inside `with transposed_io()` for this batch size: stride 1, 3x3, no bias, a sampling table
     the windowed kernels can plan, and enough tiles to fill the chip."""
-    if self.stride != (1, 1) or self.kernel_size != (3, 3) or self.bias is not None or device.type != 'cuda':
+    if not _F.sphere_win_geometry(self.stride, *self.kernel_size, same_size=True) or self.kernel_size != (3, 3):
+      return False  # (the helper counts nine taps; this site has always asked for the 3 x 3 shape, and never for the padding)
+    if self.bias is not None or device.type != 'cuda':
       return False
     return _F.sphere_t_supported(self.position_on(device), self.weight, batch, self.groups)
 

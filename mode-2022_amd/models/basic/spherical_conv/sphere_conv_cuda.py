@@ -129,8 +129,8 @@ def sphere_conv_backward_cuda(input, weight, bias, ones, position, columns, grad
   pos = position.contiguous()
   # one plane-transposed copy of grad_output serves both gradients (windowed weight gradient, transposed adjoint gather)
   gyt = None
-  if ((stride_h, stride_w) == (1, 1) and gy.shape[2:] == input.shape[2:] and
-      _F.sphere_uses_transposed_copies(pos, kernel_h, kernel_w)):  # (Cassini-like tables; an ERP table runs on the NCHW tensors as they are)
+  if _F.sphere_grads_want_transposed_gy(pos, kernel_h, kernel_w, (stride_h, stride_w), gy.shape[2:] == input.shape[2:]):
+    # (Cassini-like tables; an ERP table runs on the NCHW tensors as they are)
     gyt = _F.transpose_planes(gy)
   _F.sphere_conv_bwd_data(gy, pos, weight.contiguous(), grad_input, (stride_h, stride_w), group, overwrite=overwrite_grad_input,
                           gy_transposed=gyt)

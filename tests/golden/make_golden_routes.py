@@ -21,7 +21,16 @@ Operator cases (shapes (B, Ci, Co, ...) as in make_golden_conv3d_bits.py): see O
 BatchNorm module, so that the second run shows the packed-weight cache hit (mode_weight_pack_reuse) under that layer's tag.
 Sphere cases: SphereConv 32 -> 32 on the (128, 256) Cassini table and on the ERP table, a training step and an eval forward, under
 the settings of SPHERE below; each also records what supports_transposed_io (sphere_t_supported) answers.
-Model cases: one training step and one eval forward of ModeDisparity(16, 'Sphere', 64, 32, 'Cassini') at B = 1."""
+Model cases: one training step and one eval forward of ModeDisparity(16, 'Sphere', 64, 32, 'Cassini') at B = 1.
+
+A second, separate case list (GRAD_CASES) pins the routes of the two spherical GRADIENTS, which the list above runs under none of their
+own switches: taken at the commit BEFORE those routes were written once (_sphere_bwd_data_route, _sphere_bwd_data_t_route,
+_sphere_bwd_weight_route), with this recorder run against that commit's functional.py.
+
+  python tests/golden/make_golden_routes.py sphere_grad     # writes routes_parent_sphere_grad.json (needs the MI355X)
+
+Its cases: the training step of the same SphereConv on both table types, both floors at 0, under SPHERE_BWD_DATA = 'scatter', under
+SPHERE_BWD_DATA_T = False and under SPHERE_BWD_WEIGHT = 'gather'; and one stride-2 layer (kernel 3, stride 2, pad 1) of each type."""
 import collections
 import ctypes
 import json
@@ -38,6 +47,7 @@ for p in (ROOT, os.path.join(ROOT, 'mode-2022_amd'), HERE):
     sys.path.insert(0, p)
 
 OUT = os.path.join(HERE, 'routes_parent.json')
+OUT_GRAD = os.path.join(HERE, 'routes_parent_sphere_grad.json')
 DEV = 'cuda:0'
 
 # name fragments of the entries that launch nothing (the list of tests/test_gpu_repeat.py, restated: a fixture depends on no test module)
@@ -75,6 +85,11 @@ SPHERE = [('wg0', WG0), ('wg200', {'SPHERE_FWD_MIN_WG': 200}), ('gather', dict(W
 SPHERE_CASES = [('sphere_%s_%s_%s' % (typ, mode, name), typ, mode, sw) for typ in ('Cassini', 'ERP') for mode in ('train', 'eval', 'train_t', 'eval_t')
                 for name, sw in SPHERE if mode in ('train', 'eval') or name in ('wg0', 'wg200')]
 MODELS = ('model_train', 'model_eval')
+# the second fixture: (key, table type, mode, module switches, stride)
+GRAD = [('scatter', dict(WG0, SPHERE_BWD_DATA='scatter')), ('nobwdt', dict(WG0, SPHERE_BWD_DATA_T=False)),
+        ('bwwgather', dict(WG0, SPHERE_BWD_WEIGHT='gather'))]
+GRAD_CASES = [('sphere_%s_train_%s' % (typ, name), typ, 'train', sw, 1) for typ in ('Cassini', 'ERP') for name, sw in GRAD] + \
+             [('sphere_%s_train_s2' % typ, typ, 'train', WG0, 2) for typ in ('Cassini', 'ERP')]
 
 
 def op_key(case):
@@ -256,9 +271,10 @@ def run_op(case):
 
 def run_sphere(case, log):
   from models.basic.spherical_conv.sphere_conv import SphereConv, transposed_io
-  key, typ, mode, _ = case
+  key, typ, mode = case[:3]
+  stride = case[4] if len(case) > 4 else 1
   torch.manual_seed(7)
-  conv = SphereConv(128, 256, typ, 32, 32, 3, 1, 1).to(DEV)
+  conv = SphereConv(128, 256, typ, 32, 32, 3, stride, 1).to(DEV)
   hw = (256, 128) if typ == 'Cassini' else (128, 256)
   t_ok = bool(conv.supports_transposed_io(1, torch.device(DEV)))
   log.append(['t_supported', t_ok])
@@ -272,7 +288,7 @@ def run_sphere(case, log):
     if mode.startswith('train'):
       conv.train()
       x.requires_grad_(True)
-      conv(x).backward(_rand((1, 32) + hw, 604))
+      conv(x).backward(_rand((1, 32) + tuple((n - 1) // stride + 1 for n in hw), 604))
     else:
       bn = _bn(32, 2).eval()
       with torch.no_grad():
@@ -333,13 +349,21 @@ def jobs():
       yield '%s/%s' % (sw, m), sw, 'model', m
 
 
+def grad_jobs():
+  for sw in SWITCH_SETS:
+    for c in GRAD_CASES:
+      yield '%s/%s' % (sw, c[0]), sw, 'sphere', c
+
+
 def main():
+  grad = sys.argv[1:2] == ['sphere_grad']
+  path = (sys.argv[2:] if grad else sys.argv[1:])[:1] or [OUT_GRAD if grad else OUT]
   out = {}
-  for key, sw, kind, case in jobs():
+  for key, sw, kind, case in (grad_jobs() if grad else jobs()):
     out[key] = record(sw, kind, case)
     print(key, len(out[key]), flush=True)
-  assert sorted(out) == sorted(all_keys())
-  with open(sys.argv[1] if len(sys.argv) > 1 else OUT, 'w') as f:
+  assert grad or sorted(out) == sorted(all_keys())
+  with open(path[0], 'w') as f:
     f.write('{\n' + ',\n'.join('%s:%s' % (json.dumps(k), json.dumps(out[k], separators=(',', ':'))) for k in sorted(out)) + '\n}\n')  # a case per line
 
 

@@ -1,6 +1,6 @@
 """An interpreter of the plans of the windowed spherical kernels, in plain numpy.  TEST INFRASTRUCTURE.
 
-`check_plan(table, plan, aplan)` takes a sampling table (1, 18, H, W) and the tuples HF.sphere_plan / HF.sphere_adjplan return for it,
+`check_plan(table, plan, aplan)` takes a sampling table (1, 18, H, W) and the records HF.sphere_plan / HF.sphere_adjplan return for it,
 and evaluates them the way the KERNELS consume them -- the indexing is read from csrc/sphere_win_fwd.hip, sphere_win_bww.hip and
 sphere_win_bwd_data.hip (which window word a record offset names, which image pixel that word was staged from), not from the planners of
 csrc/sphere_plan.hip, and no code of csrc/ runs here.  One channel, float64 sums over the plan's float32 weights.
@@ -141,7 +141,7 @@ def _window_read(x, rb, cb, e, wr, W):
 def check_tiles(table, plan):
   """Structure of the tile list; returns (tiles (n, 4) int64 with the class bits removed, class per tile)."""
   H, W = table.shape[2:]
-  tiles, counts = _np(plan[0]).astype(np.int64).reshape(-1, 4), plan[1]
+  tiles, counts = _np(plan.tiles).astype(np.int64).reshape(-1, 4), plan.counts
   n0, n1, n2 = counts
   nth, ntw = -(-H // TH), -(-W // TW)
   _require(n0 + n1 + n2 == nth * ntw and tiles.shape[0] >= nth * ntw, 'counts %s do not add up to the %d x %d tile grid', counts, nth, ntw)
@@ -192,8 +192,8 @@ def sample_records(table, plan, x):
   pixel list."""
   H, W = x.shape
   tiles, cls = check_tiles(table, plan)
-  n0, n1, n2 = plan[1]
-  rest, nrest, rec_w, rec_off, polar = plan[2], plan[3], _np(plan[4]), _np(plan[5]).astype(np.int64), plan[6]
+  n0, n1, n2 = plan.counts
+  rest, nrest, rec_w, rec_off, polar = plan.rest, plan.nrest, _np(plan.rec_w), _np(plan.rec_off).astype(np.int64), plan.polar
   col = np.zeros((KT, H, W))
   covered = np.zeros((H, W), dtype=np.int64)
 
@@ -231,7 +231,7 @@ def sample_records(table, plan, x):
   _require(nrest == want_rest.size and (_np(rest)[:nrest] == want_rest).all(),
            'the pixel list is not the sorted pixels of the tall-window tiles (%d listed, %d wanted)', nrest, want_rest.size)
   if polar is not None:
-    pitems, prw, pro, n = _np(polar[0]).astype(np.int64), _np(polar[1]), _np(polar[2]).astype(np.int64), polar[3]
+    pitems, prw, pro, n = _np(polar.items).astype(np.int64), _np(polar.rec_w), _np(polar.rec_off).astype(np.int64), polar.n
     _require(n > 0 and pitems.size == BP_ITEM_INTS * n and pro.size == KT * BW_TH * n and prw.size == 4 * KT * BW_TH * n, 'polar items: array sizes')
     pitems = pitems.reshape(n, BP_ITEM_INTS)
     _require((pitems[:, 0] % BW_TH == 0).all() and (pitems[:, 0] < H).all() and (pitems[:, 1] < W).all() and (pitems[:, :2] >= 0).all(),

@@ -223,7 +223,7 @@ def test_input_gradient_forms_against_float64(name, ch, recorder):
           (name, ci, co, groups, B, 'two fp16 pieces' if f16 else 'three bf16 pieces', ', '.join(n[len('mode_sphere_conv_bwd_data_'):] for n in ran),
            e, bound, float(o['gx'].abs().max())))
     if windowed:
-      want = ['mode_sphere_conv_bwd_data_win_split' + ('_f16' if f16 else '')] + (['mode_sphere_conv_bwd_data_adj_list'] if aplan[5] else [])
+      want = ['mode_sphere_conv_bwd_data_win_split' + ('_f16' if f16 else '')] + (['mode_sphere_conv_bwd_data_adj_list'] if aplan.nbad else [])
     else:
       want = ['mode_sphere_conv_bwd_data_adj']
     assert ran == want, ran
@@ -276,7 +276,7 @@ def test_weight_gradient_forms_against_float64(name, ch, recorder):
     HF.set_conv_arith(arith)
     HF.SPHERE_BWD_F16 = f16
     if name.startswith('perturbed'):
-      assert plan[6] is None and plan[3] > 0
+      assert plan.polar is None and plan.nrest > 0
       del recorder.names[:]
       with pytest.raises(RuntimeError, match='pixel-list fallback'):
         HF.sphere_conv_bwd_weight_t(gyt, pd, xt, zeros(), groups)
@@ -285,6 +285,6 @@ def test_weight_gradient_forms_against_float64(name, ch, recorder):
       check(form + ', plane-transposed', lambda: HF.sphere_conv_bwd_weight_t(gyt, pd, xt, zeros(), groups), entry)
     for polar in (True, False):
       HF.SPHERE_POLAR = polar
-      check('%s, NCHW, %s' % (form, 'polar kernel' if (polar and plan[6] is not None) else 'pixel list'),
+      check('%s, NCHW, %s' % (form, 'polar kernel' if (polar and plan.polar is not None) else 'pixel list'),
             lambda: HF.sphere_conv_bwd_weight(o['gy'], pd, o['x'], zeros(), (1, 1), groups), entry)
     HF.SPHERE_POLAR = True

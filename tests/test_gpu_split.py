@@ -439,7 +439,7 @@ def test_split_sphere_input_gradient_against_float64(ih, iw, B, ci, co, groups, 
   want, _ = sphere_conv_ref.backward(x0, pos, w.double(), gy.double(), (1, 1), (1, 1), (1, 1), groups)
   pd, wd = pos.to(DEV), w.to(DEV)
   ap = HF.sphere_adjplan(pd, 3, 3)
-  assert ap is not None and ap[1] > 0, 'the windowed adjoint must be planned for this table'
+  assert ap is not None and ap.ngood > 0, 'the windowed adjoint must be planned for this table'
   assert mode_hip.lib().mode_sphere_conv_bwd_data_win_supported(ci, co, groups) == 1
   gyt = gy.to(DEV).transpose(2, 3).contiguous()
   gxt = torch.full((B, ci, W, H), float('nan'), device=DEV)
@@ -454,7 +454,7 @@ def test_split_sphere_input_gradient_against_float64(ih, iw, B, ci, co, groups, 
   rms = float((got.cpu().double() - want).pow(2).mean().sqrt())
   rms_old = float((old.transpose(2, 3).cpu().double() - want).pow(2).mean().sqrt())
   print('sphere_conv_bwd_data %d->%d %dx%d B=%d g=%d: split max %.3e rms %.3e | fp32 gather kernel max %.3e rms %.3e | bound %.3e; %d of %d tiles on '
-        'the split kernel' % (ci, co, H, W, B, groups, e, rms, e_old, rms_old, tol, ap[1], ap[1] + ap[5] // 4))
+        'the split kernel' % (ci, co, H, W, B, groups, e, rms, e_old, rms_old, tol, ap.ngood, ap.ngood + ap.nbad // 4))
   assert torch.isfinite(got).all()
   assert e <= tol
   assert rms <= 1.25 * rms_old + 1e-12, 'the split path must not be less accurate than the fp32 kernel'
@@ -484,7 +484,7 @@ def test_split_sphere_weight_gradient_against_float64(ih, iw, B, ci, co, groups,
   _, want = sphere_conv_ref.backward(x.double(), pos, w0, gy.double(), (1, 1), (1, 1), (1, 1), groups)
   pd = pos.to(DEV)
   plan = HF.sphere_plan(pd, 3, 3)
-  assert plan is not None and plan[1][0] > 0
+  assert plan is not None and plan.counts[0] > 0
   xt, gyt = x.to(DEV).transpose(2, 3).contiguous(), gy.to(DEV).transpose(2, 3).contiguous()
   gw = torch.zeros((co, ci // groups, 3, 3), device=DEV)
   HF.sphere_conv_bwd_weight_t(gyt, pd, xt, gw, groups)

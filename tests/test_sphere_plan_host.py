@@ -26,16 +26,16 @@ def _route(plan):
     return 'none'
   if HF._plan_usable(plan):
     return 'usable'
-  return 'pixel list' if plan[1][0] > 0 else 'forward only'
+  return 'pixel list' if plan.counts[0] > 0 else 'forward only'
 
 
 def _adjoint_counts(aplan):
   """(good tiles, six-source tiles among them, bad tiles) or None."""
   if aplan is None:
     return None
-  six = (aplan[0].view(-1, 4)[:, 3] >> 16) & 1
-  assert aplan[5] % 4 == 0
-  return aplan[1], int(six.sum()), aplan[5] // 4
+  six = (aplan.tiles.view(-1, 4)[:, 3] >> 16) & 1
+  assert aplan.nbad % 4 == 0
+  return aplan.ngood, int(six.sum()), aplan.nbad // 4
 
 
 def _check(table, plan, aplan):
@@ -69,7 +69,7 @@ def test_geometric_tables(ih, iw):
   counts, npolar, adjoint = GEOMETRIC[(ih, iw)]
   plan, aplan = _plans(table)
   assert _route(plan) == 'usable'
-  assert plan[1] == counts and plan[6][3] == npolar, (plan[1], plan[6][3])
+  assert plan.counts == counts and plan.polar.n == npolar, (plan.counts, plan.polar.n)
   assert _adjoint_counts(aplan) == adjoint
   out = _check(table, plan, aplan)
   assert (out['adjoint'] is None) == (adjoint is None)
@@ -83,14 +83,14 @@ def test_a_cassini_table_is_shift_invariant_along_its_rows():
     rolled = torch.roll(base, shift, 2).clone()
     rolled[0, 0::2] = torch.remainder(rolled[0, 0::2] + shift, H)
     plan, aplan = _plans(T._keep('rolled %d' % shift, lambda: rolled))
-    assert plan[1] == GEOMETRIC[(96, 192)][0] and plan[6][3] == GEOMETRIC[(96, 192)][1]
+    assert plan.counts == GEOMETRIC[(96, 192)][0] and plan.polar.n == GEOMETRIC[(96, 192)][1]
 
 
 def test_perturbed_table_takes_the_pixel_list_and_the_six_source_class():
   table = T.perturbed()
   plan, aplan = _plans(table)
   assert _route(plan) == 'pixel list'
-  assert plan[1] == (51, 15, 6) and plan[6] is None and plan[3] == 5376
+  assert plan.counts == (51, 15, 6) and plan.polar is None and plan.nrest == 5376
   good, six, bad = _adjoint_counts(aplan)
   assert (good, six, bad) == (64, 56, 8) and six > good - six
   _check(table, plan, aplan)
@@ -117,8 +117,8 @@ def test_affine_tables(a):
     assert int(((rows > 191) & (rows < 192)).sum()) > 0
   route, counts, npolar, adjoint = AFFINE[a]
   plan, aplan = _plans(table)
-  assert _route(plan) == route and plan[1] == counts
-  assert (plan[6][3] if plan[6] is not None else None) == npolar
+  assert _route(plan) == route and plan.counts == counts
+  assert (plan.polar.n if plan.polar is not None else None) == npolar
   assert _adjoint_counts(aplan) == adjoint
   _check(table, plan, aplan)
 
@@ -131,7 +131,7 @@ def test_halves_fit_demotes_tiles_of_an_affine_table(a):
   table = T.affine(a)
   plan, _ = _plans(table)
   rows = R.tile_rows(table)
-  tiles = plan[0].view(-1, 4)[:sum(plan[1])].tolist()
+  tiles = plan.tiles.view(-1, 4)[:sum(plan.counts)].tolist()
   demoted = [(h0, w0) for h0, w0, _, cw in tiles if cw >> 16 == 1 and 0 < rows[(h0, w0)] <= R.WR_SMALL]
   assert len(demoted) == (12 if a == 0.5 else 4), demoted
 
@@ -145,10 +145,10 @@ def test_dead_taps():
   assert int((t[0::2] == t.shape[1]).sum()) > 0 and int((t[1::2] == t.shape[2]).sum()) > 0
   plan, aplan = _plans(table)
   assert _route(plan) == 'usable'
-  assert plan[1] == (62, 4, 6) and plan[6][3] == 80
+  assert plan.counts == (62, 4, 6) and plan.polar.n == 80
   assert _adjoint_counts(aplan) == (63, 6, 9)
   rows = R.tile_rows(table)
-  tiles = plan[0].view(-1, 4)[:72].tolist()
+  tiles = plan.tiles.view(-1, 4)[:72].tolist()
   assert [(h0, w0) for h0, w0, _, cw in tiles if cw >> 16 == 1 and rows[(h0, w0)] <= R.WR_SMALL] == [(64, 8)]
   _check(table, plan, aplan)
 
@@ -162,7 +162,7 @@ def test_sixteen_source_table_has_bad_adjoint_tiles_only():
   assert all(int(n[:, h0:h0 + 64, w0:w0 + 4].max()) == 32 for h0 in range(0, H, 64) for w0 in range(0, W, 4))
   plan, aplan = _plans(table)
   assert aplan is None
-  assert _route(plan) == 'forward only' and plan[1] == (0, 8, 0)
+  assert _route(plan) == 'forward only' and plan.counts == (0, 8, 0)
   _check(table, plan, None)
 
 
@@ -184,16 +184,19 @@ def test_both_sides_of_the_lds_limit_of_the_wrap_around_window():
   assert H == 628
   below, above = T.affine(2.5, H - 1, 4), T.affine(2.5, H, 4)
   plan, aplan = _plans(below)
-  assert _route(plan) == 'pixel list' and plan[1] == (6, 0, 4) and aplan is None
+  assert _route(plan) == 'pixel list' and plan.counts == (6, 0, 4) and aplan is None
   _check(below, plan, None)
   assert HF.sphere_plan(above, 3, 3) is None and _route(None) == 'none'
 
 
 # ------------------------------------------------------------------------------------------------ the interpreter rejects a wrong plan
 def _mutable(plan):
-  return tuple(t.clone() if isinstance(t, torch.Tensor) else (tuple(u.clone() if isinstance(u, torch.Tensor) else u for u in t)
-                                                              if isinstance(t, tuple) and t and isinstance(t[0], torch.Tensor) else t)
-               for t in plan)
+  """A copy of a plan record, of the same record type, with every tensor cloned (the polar items' too)."""
+  def copy(v):
+    if isinstance(v, torch.Tensor):
+      return v.clone()
+    return _mutable(v) if isinstance(v, HF.PolarItems) else v
+  return type(plan)(*(copy(v) for v in plan))
 
 
 @pytest.fixture(scope='module')
@@ -201,8 +204,8 @@ def real_plan():
   table = T.geometric(96, 192)
   plan, aplan = _plans(table)
   R.check_plan(table, plan, aplan)
-  n0, n1, n2 = plan[1]
-  assert n0 and n1 and n2 and plan[6] is not None and aplan is not None
+  n0, n1, n2 = plan.counts
+  assert n0 and n1 and n2 and plan.polar is not None and aplan is not None
   return table, plan, aplan
 
 
@@ -215,22 +218,22 @@ def _live_record(rec_w, start=0):
 def test_the_interpreter_rejects_a_changed_plan(real_plan, what):
   table, plan, aplan = real_plan
   bad = _mutable(plan)
-  tiles, (n0, n1, n2) = bad[0].view(-1, 4), bad[1]
+  tiles, (n0, n1, n2) = bad.tiles.view(-1, 4), bad.counts
   first_compact = n2 + n1
   if what == 'rbase':
     tiles[first_compact + 5, 2] = (tiles[first_compact + 5, 2] + 1) % table.shape[2]
   elif what == 'record offset':
-    bad[5][_live_record(bad[4], 4000)] += 1
+    bad.rec_off[_live_record(bad.rec_w, 4000)] += 1
   elif what == 'weight':
-    bad[4].view(-1, 4)[_live_record(bad[4], 4000), 2] += 0.25
+    bad.rec_w.view(-1, 4)[_live_record(bad.rec_w, 4000), 2] += 0.25
   elif what == 'class bit':
     tiles[first_compact + 5, 3] |= 1 << 16
   elif what == 'polar rbase':
-    bad[6][0].view(-1, 20)[3, 2 + 4] += 1
+    bad.polar.items.view(-1, 20)[3, 2 + 4] += 1
   elif what == 'polar record offset':
-    bad[6][2][_live_record(bad[6][1], 500)] += 1
+    bad.polar.rec_off[_live_record(bad.polar.rec_w, 500)] += 1
   elif what == 'polar weight':
-    bad[6][1].view(-1, 4)[_live_record(bad[6][1], 500), 1] += 0.25
+    bad.polar.rec_w.view(-1, 4)[_live_record(bad.polar.rec_w, 500), 1] += 0.25
   with pytest.raises(R.PlanError):
     R.check_plan(table, bad, aplan)
   R.check_plan(table, plan, aplan)  # (and the plan it was copied from is untouched)
@@ -239,19 +242,19 @@ def test_the_interpreter_rejects_a_changed_plan(real_plan, what):
 @pytest.mark.parametrize('what', ['rbase', 'record offset', 'weight', 'six flag', 'bad run'])
 def test_the_interpreter_rejects_a_changed_adjoint_plan(real_plan, what):
   table, plan, aplan = real_plan
-  bad = list(_mutable(aplan))
-  tiles = bad[0].view(-1, 4)
+  bad = _mutable(aplan)
+  tiles = bad.tiles.view(-1, 4)
   if what == 'rbase':
     tiles[20, 2] = (tiles[20, 2] + 1) % table.shape[2]
   elif what == 'record offset':
-    rec = _live_record(bad[3], 9000)
-    bad[2][4 * rec + int(bad[3].view(-1, 4)[rec].argmax())] += 1  # (the slot that carries the weight: a slot of 1e-6 stays within the bound)
+    rec = _live_record(bad.rec_w, 9000)
+    bad.rec_off[4 * rec + int(bad.rec_w.view(-1, 4)[rec].argmax())] += 1  # (the slot that carries the weight: a slot of 1e-6 stays within the bound)
   elif what == 'weight':
-    bad[3][4 * _live_record(bad[3], 9000)] += 0.25
+    bad.rec_w[4 * _live_record(bad.rec_w, 9000)] += 0.25
   elif what == 'six flag':
     assert tiles[0, 3] >> 16 == 1  # the six-source tiles come first
     tiles[0, 3] &= 0xffff
   elif what == 'bad run':
-    bad[4][0] += 1
+    bad.bad_ids[0] += 1
   with pytest.raises(R.PlanError):
-    R.check_plan(table, plan, tuple(bad))
+    R.check_plan(table, plan, bad)

@@ -12,23 +12,23 @@ def test_the_table_has_every_tile_class():
   pos = mode_ref.sphere_position(*G.TABLE, 'Cassini').contiguous()
   plan = HF.sphere_plan(pos, 3, 3)
   assert plan is not None and HF._plan_usable(plan)
-  n_small, n_mid, n_wrap = plan[1]
-  assert n_small > 0 and n_mid > 0 and n_wrap > 0, plan[1]
-  assert plan[6] is not None and plan[6][3] > 0  # polar items
+  n_small, n_mid, n_wrap = plan.counts
+  assert n_small > 0 and n_mid > 0 and n_wrap > 0, plan.counts
+  assert plan.polar is not None and plan.polar.n > 0  # polar items
   aplan = HF.sphere_adjplan(pos, 3, 3)
-  assert aplan is not None and aplan[1] > 0
-  six = (aplan[0].view(-1, 4)[:, 3] >> 16) & 1
-  assert 0 < int(six.sum()) < aplan[1]  # both the four- and the six-source class
-  assert aplan[5] > 0  # and tiles left to the gather kernel's list form
+  assert aplan is not None and aplan.ngood > 0
+  six = (aplan.tiles.view(-1, 4)[:, 3] >> 16) & 1
+  assert 0 < int(six.sum()) < aplan.ngood  # both the four- and the six-source class
+  assert aplan.nbad > 0  # and tiles left to the gather kernel's list form
 
 
 def test_the_small_table_is_all_windowed_input_gradient():
   pos = mode_ref.sphere_position(*G.SMALL_TABLE, 'Cassini').contiguous()
   assert tuple(pos.shape[2:]) == (64, 32)
   aplan = HF.sphere_adjplan(pos, 3, 3)
-  assert aplan is not None and aplan[1] == 8 and aplan[4] is None and aplan[5] == 0  # every tile good: nothing for the gather kernel
-  six = (aplan[0].view(-1, 4)[:, 3] >> 16) & 1
-  assert 0 < int(six.sum()) < aplan[1]
+  assert aplan is not None and aplan.ngood == 8 and aplan.bad_ids is None and aplan.nbad == 0  # every tile good: nothing for the gather kernel
+  six = (aplan.tiles.view(-1, 4)[:, 3] >> 16) & 1
+  assert 0 < int(six.sum()) < aplan.ngood
   assert not HF._plan_usable(HF.sphere_plan(pos, 3, 3))  # no compact tile: the model keeps it off the other two windowed passes
 
 

@@ -14,22 +14,22 @@ H, W = pos.shape[2:]
 w = m.weight.detach()
 HF.set_conv_arith('bf16x6')
 plan = HF.sphere_plan(pos, 3, 3)
-tiles, (n0, n1, n2) = plan[:2]
+tiles, (n0, n1, n2) = plan.tiles, plan.counts
 t = tiles.cpu().view(-1, 4).clone()
 ntall = n1 + n2
 small = t[ntall:ntall + n0]
 fake = t.clone()
 for i in range(ntall):
   fake[i] = small[i % n0]
-fake = fake.view(-1).to(dev)
+fake = plan._replace(tiles=fake.view(-1).to(dev), counts=(n0 + n1 + n2, 0, 0))
 
 
-def run(tl, c0, c1, c2, B, what):
+def run(plan, B, what):
   xt = torch.randn(B, 128, W, H, device=dev)
   yt = torch.empty_like(xt)
   wp = torch.empty(HF.lib().mode_sphere_conv_win_wpack_bytes(128, 128, 3, 3, 1) // 4, dtype=torch.float32, device=dev)
   def call():
-    HF._sphere_fwd_win(HF.ptr(xt), pos, w, None, HF.ptr(yt), wp, tl, c0, c1, c2, B, 128, H, W, 128, 3, 3, 1, 1, HF.stream_of(xt))
+    HF._sphere_fwd_win(HF.ptr(xt), pos, w, None, HF.ptr(yt), wp, plan, B, 128, H, W, 128, 3, 3, 1, 1, HF.stream_of(xt))
   for _ in range(3):
     call()
   torch.cuda.synchronize()
@@ -43,5 +43,5 @@ def run(tl, c0, c1, c2, B, what):
 
 
 for B in (2, 4, 8):
-  run(tiles, n0, n1, n2, B, 'real plan (%d small, %d mid, %d wrap)' % (n0, n1, n2))
-  run(fake, n0 + n1 + n2, 0, 0, B, 'all %d tiles small' % (n0 + n1 + n2))
+  run(plan, B, 'real plan (%d small, %d mid, %d wrap)' % (n0, n1, n2))
+  run(fake, B, 'all %d tiles small' % (n0 + n1 + n2))

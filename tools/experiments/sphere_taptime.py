@@ -15,12 +15,13 @@ pos = m.position_on(dev)
 H, W = pos.shape[2:]
 w = m.weight.detach()
 HF.set_conv_arith('bf16x6')
-tiles, (n0, n1, n2) = HF.sphere_plan(pos, 3, 3)[:2]
+plan = HF.sphere_plan(pos, 3, 3)
+tiles, (n0, n1, n2) = plan.tiles, plan.counts
 t = tiles.cpu().view(-1, 4).clone()
 small = t[n1 + n2:n1 + n2 + n0]
 for i in range(n1 + n2):
   t[i] = small[i % n0]
-fake = t.view(-1).to(dev)
+fake = plan._replace(tiles=t.view(-1).to(dev), counts=(n0 + n1 + n2, 0, 0))
 lib = HF.lib()
 lib.mode_debug_taptime.argtypes = [ctypes.c_void_p, ctypes.c_int]
 for B, use_fake in ((2, True), (4, True), (2, False)):
@@ -28,10 +29,7 @@ for B, use_fake in ((2, True), (4, True), (2, False)):
   yt = torch.empty_like(xt)
   wp = torch.empty(lib.mode_sphere_conv_win_wpack_bytes(128, 128, 3, 3, 1) // 4, dtype=torch.float32, device=dev)
   for _ in range(3):
-    if use_fake:
-      HF._sphere_fwd_win(HF.ptr(xt), pos, w, None, HF.ptr(yt), wp, fake, n0 + n1 + n2, 0, 0, B, 128, H, W, 128, 3, 3, 1, 1, HF.stream_of(xt))
-    else:
-      HF._sphere_fwd_win(HF.ptr(xt), pos, w, None, HF.ptr(yt), wp, tiles, n0, n1, n2, B, 128, H, W, 128, 3, 3, 1, 1, HF.stream_of(xt))
+    HF._sphere_fwd_win(HF.ptr(xt), pos, w, None, HF.ptr(yt), wp, fake if use_fake else plan, B, 128, H, W, 128, 3, 3, 1, 1, HF.stream_of(xt))
   torch.cuda.synchronize()
   n = 128 * B
   dbuf = torch.zeros(8 * 8192, dtype=torch.int64, device=dev)
