@@ -606,7 +606,8 @@ int mode_head_bwd_loss(const float* logits, const float* pred, const float* gt, 
  *        updates; save_* hold groups * C values.  Used to run the left and right images through the shared extractor as one batch.
  * `workspace` >= mode_bn_workspace_bytes(C * groups) for the training calls.
  * mode_bn_train_fwd is NOT in-place: `out` must not alias `y` (the normalisation pass re-reads one element per channel of y -- the
- *        pivot of the shifted sums -- while it writes `out`); out == y returns MODE_ERR_BAD_ARG.
+ *        pivot of the shifted sums -- while it writes `out`); out == y returns MODE_ERR_BAD_ARG.  Nor is mode_bn_train_bwd, for the
+ *        same reason (channels whose mean dominates, |mean| > 16 std, sum g * (y - pivot)): gy == y returns MODE_ERR_BAD_ARG.
  */
 size_t mode_bn_workspace_bytes(int C);
 

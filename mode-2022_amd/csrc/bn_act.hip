@@ -267,7 +267,19 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
   if (track) mode::absmax_block_commit(mx, k.amax, reinterpret_cast<unsigned*>(shd));  // (shd: read for the last time in front of the barrier above)
 }
 
-// Backward reduce: g = RELU ? (out > 0 ? gout : 0) : gout;  partial = sum(g), sum(g*y).
+// The pivot K of the backward pass's second sum, sum(g*(y-K)).  sum(g*y) itself, taken in float32, loses dgamma = invstd*(sum(g*y) -
+// mean*sum(g)) to the rounding of products |mean| >> std large (mean -3000 / std 0.5: 4e-3 of dgamma, 14 x what torch's float32 loses;
+// tests/test_gpu_batchnorm_forms.py::test_mean_dominated_channels).  So where the mean dominates, |mean| > 16 std, K is the pivot of
+// bn_stats_kernel (the first element of the group's first sample of the channel) and the apply pass adds (mean-K)*sum(g) back in double.
+// Everywhere else K = 0: y - 0 is y, and the sums, the coefficients and gy keep the bits they always had (16 std: the unshifted sum is
+// then good to ~16 * 2^-24 of sum|g|*std, well inside what the affine gradients are held to).  row = group * C + channel; first = the
+// offset of that group's first sample of the channel in y.  Both backward kernels call this with the same arguments.
+__device__ __forceinline__ float bwd_pivot(const float* __restrict__ y, const float* __restrict__ save_mean,
+                                           const float* __restrict__ save_invstd, long long row, long long first) {
+  return fabsf(save_mean[row]) * save_invstd[row] > 16.f ? y[first] : 0.f;
+}
+
+// Backward reduce: g = RELU ? (out > 0 ? gout : 0) : gout;  partial = sum(g), sum(g*(y-K)), K = bwd_pivot.
 // RELU = 1: the mask is read from the forward output; RELU = 2 (no residual add): it is rebuilt from y with the forward's own
 // float32 coefficients, out = fma(y, scale, shift) -- bit-identical, and one tensor less to read in both backward passes.
 // GADD (RELU = 1, residual add in front of the ReLU): g is also the gradient of the skip branch, and it is stored to `gadd` here,
@@ -278,6 +290,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
                                                           const float* __restrict__ out, const float* __restrict__ mscale,
                                                           const float* __restrict__ mshift, float* __restrict__ partial, int B, int C,
                                                           long long S, int nsplit, unsigned* __restrict__ zero,
+                                                          const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
                                                           float* __restrict__ gadd = nullptr) {
   static_assert(!GADD || RELU == 1, "the masked gradient is stored only where the mask comes from the forward output");
   __shared__ float sh[2 * NW];
@@ -289,6 +302,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
     for (int i = threadIdx.x; i < MODE_BN_ABSMAX_FLOATS; i += NT) zero[i] = 0u;
   const float msc = RELU == 2 ? mscale[prow] : 0.f, msh = RELU == 2 ? mshift[prow] : 0.f;
   const long long S4 = (S & 3) ? 0 : (S >> 2);  // rows that are not multiples of 16 bytes: the scalar loop below takes the whole row
+  const float K = bwd_pivot(y, save_mean, save_invstd, prow, ((long long)b0 * C + c) * S);
   float s0 = 0.f, s1 = 0.f;
   for (int b = b0; b < b0 + Bg; ++b) {
     const long long base = ((long long)b * C + c) * S;
@@ -308,7 +322,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
         g.w = __builtin_fmaf(v.w, msc, msh) > 0.f ? g.w : 0.f;
       }
       s0 += (g.x + g.y) + (g.z + g.w);
-      s1 += (g.x * v.x + g.y * v.y) + (g.z * v.z + g.w * v.w);
+      s1 += (g.x * (v.x - K) + g.y * (v.y - K)) + (g.z * (v.z - K) + g.w * (v.w - K));
     };
     const long long st = (long long)nsplit * NT;  // interleaved 4 KB pieces per block, see bn_stats_kernel
     long long i = (long long)split * NT + threadIdx.x;
@@ -331,7 +345,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
         if (RELU == 2) g = __builtin_fmaf(y[base + i], msc, msh) > 0.f ? g : 0.f;
         if (GADD) gadd[base + i] = g;
         s0 += g;
-        s1 += g * y[base + i];
+        s1 += g * (y[base + i] - K);
       }
   }
   block_sum2(s0, s1, sh);
@@ -342,7 +356,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_stats_kernel(const float* __restric
 }
 
 // grid = (chunks, B*C): g = masked gout; gy = A*g + Bc*y + Cc; optionally gadd = g, with
-//   dgamma = invstd * (sum(g*y) - mean*sum(g)), dbeta = sum(g), A = gamma*invstd, Bc = -A*invstd*dgamma/count,
+//   dgamma = invstd * (sum(g*(y-K)) - (mean-K)*sum(g)), dbeta = sum(g), A = gamma*invstd, Bc = -A*invstd*dgamma/count,
 //   Cc = A*(mean*invstd*dgamma - sum(g))/count
 // derived by every block from the partial sums; the block (chunk 0, sample 0) of each channel stores (or, with
 // `accumulate`, adds into) ggamma / gbeta.
@@ -381,7 +395,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restric
     reduce_partials(partial, grp * C + c, nsplit, sg, sgy, shd);
     if (threadIdx.x == 0) {
       const double mean = save_mean[grp * C + c], invstd = save_invstd[grp * C + c], gm = gamma[c];
-      const double dgamma = invstd * (sgy - mean * sg);
+      const double K = bwd_pivot(y, save_mean, save_invstd, grp * C + c, ((long long)(grp * Bg) * C + c) * S);
+      const double dgamma = invstd * (sgy - (mean - K) * sg);
       const double A = gm * invstd;
       coef[0] = (float)A;
       coef[1] = (float)(-A * invstd * dgamma / count);
@@ -393,7 +408,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restric
       for (int gg = 0; gg < groups; ++gg) {
         double tg, tgy;
         reduce_partials(partial, gg * C + c, nsplit, tg, tgy, shd);
-        dg += (double)save_invstd[gg * C + c] * (tgy - (double)save_mean[gg * C + c] * tg);
+        const double K = bwd_pivot(y, save_mean, save_invstd, gg * C + c, ((long long)(gg * Bg) * C + c) * S);
+        dg += (double)save_invstd[gg * C + c] * (tgy - ((double)save_mean[gg * C + c] - K) * tg);
         db += tg;
       }
       if (threadIdx.x == 0) {
@@ -721,6 +737,8 @@ extern "C" int mode_bn_train_bwd_amax(const float* gout, const float* y, const f
                    (!gadd || aligned_rows(gadd, S)) && aligned16(workspace),
                MODE_ERR_UNSUPPORTED, "mode_bn_train_bwd: unaligned buffer");
   MODE_REQUIRE(groups >= 1 && B % groups == 0, MODE_ERR_BAD_ARG, "mode_bn_train_bwd: batch %d not divisible into %d groups", B, groups);
+  // (where the mean dominates) the apply pass re-reads the pivot of the shifted sum from y while other blocks of the same launch write gy
+  MODE_REQUIRE(gy != y, MODE_ERR_BAD_ARG, "mode_bn_train_bwd: in-place operation (gy == y) is not supported");
   if (gadd) {
     // gadd is written by the statistics pass and read back by the apply pass (mask from `out`), or written by the apply pass while
     // other blocks still read their part of the inputs: it is a tensor of its own
@@ -737,14 +755,16 @@ extern "C" int mode_bn_train_bwd_amax(const float* gout, const float* y, const f
   const float* o = out ? out : y;
   unsigned* zero = reinterpret_cast<unsigned*>(amax);  // (the maximum's buffer is zeroed by the statistics pass)
   if (mode == 0)
-    hipLaunchKernelGGL(bn_bwd_stats_kernel<0>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel<0>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero, save_mean, save_invstd);
   else if (mode == 1 && gadd)  // (the masked gradient is the skip branch's: stored by this pass, see the kernel)
     hipLaunchKernelGGL((bn_bwd_stats_kernel<1, true>), dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S,
-                       nsplit, zero, gadd);
+                       nsplit, zero, save_mean, save_invstd, gadd);
   else if (mode == 1)
-    hipLaunchKernelGGL(bn_bwd_stats_kernel<1>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel<1>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero,
+                       save_mean, save_invstd);
   else
-    hipLaunchKernelGGL(bn_bwd_stats_kernel<2>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel<2>, dim3(nsplit, C, groups), dim3(NT), 0, st, gout, y, o, save_scale, save_shift, partial, B, C, S, nsplit, zero,
+                       save_mean, save_invstd);
   const int BC = B * C;
   const char* who = "mode_bn_train_bwd";
   const double count = (double)(B / groups) * (double)S;

@@ -2491,6 +2491,16 @@ def _bcs(t):
   return B, C, S
 
 
+def _bn_rows(t):
+  """t contiguous, at an address the BatchNorm kernels take: they read rows that are multiples of 16 bytes in 16-byte pieces, so such a
+  tensor starts at a multiple of 16 bytes.  A contiguous view into the middle of a buffer need not; it is copied (allocations are
+  aligned), which costs a pass -- no tensor of the networks here is one."""
+  if t is None:
+    return None
+  t = t.contiguous()
+  return t.clone() if t.data_ptr() % (4 if _bcs(t)[2] % 4 else 16) else t
+
+
 def bn_supported(y):
   B, C, S = _bcs(y)
   return y.is_cuda and y.dtype == torch.float32 and B * C < 65536 and B > 0  # (any S: rows that are not multiples of 16 bytes take the kernels' scalar path)
@@ -2536,8 +2546,7 @@ class BnActFunction(torch.autograd.Function):
               add_carrier=None):
     ctx.add_carrier = add_carrier  # GradCarrier of `add` (the skip tensor has one other consumer), or None
     require_gpu(y, add, gamma, beta)
-    y = y.contiguous()
-    add = add.contiguous() if add is not None else None
+    y, add = _bn_rows(y), _bn_rows(add)
     require_f32c(y, gamma, beta)
     B, C, S = _bcs(y)
     out = torch.empty_like(y)
@@ -2571,7 +2580,7 @@ class BnActFunction(torch.autograd.Function):
   @staticmethod
   def backward(ctx, gout):
     y, out, gamma, beta, mean, invstd, coef = ctx.saved_tensors
-    gout = gout.contiguous()
+    gout = _bn_rows(gout)
     B, C, S = _bcs(y)
     gy = torch.empty_like(y)
     need_gadd = ctx.has_add and ctx.relu and ctx.needs_input_grad[1]
@@ -2608,8 +2617,7 @@ class BnActFunction(torch.autograd.Function):
 
 def bn_eval(y, add, gamma, beta, running_mean, running_var, eps, relu):
   require_gpu(y, add, gamma, beta, running_mean, running_var)
-  y = y.contiguous()
-  add = add.contiguous() if add is not None else None
+  y, add = _bn_rows(y), _bn_rows(add)
   require_f32c(y, gamma, beta, running_mean, running_var)
   B, C, S = _bcs(y)
   out = torch.empty_like(y)
