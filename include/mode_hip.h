@@ -20,8 +20,9 @@
  *     reference throws c10::Error on bad shapes (sphere_conv_cuda.cpp:43-125) but only printf()s
  *     launch errors (sphere_conv_cuda_kernel.cu:286-289); the Python binding raises RuntimeError
  *     for every non-zero code;
- *   - re-entrant across devices and threads: no global mutable state except the thread-local
- *     error string (nn.DataParallel calls forward from one thread per GPU).
+ *   - re-entrant across devices and threads: no global mutable state except two thread-local
+ *     values, the error string and the mode_weight_pack_reuse setting (nn.DataParallel calls
+ *     forward from one thread per GPU).
  */
 #ifndef MODE_HIP_H_
 #define MODE_HIP_H_

@@ -1,4 +1,5 @@
-"""ctypes binding of libmode_hip.so (C-ABI declared in include/mode_hip.h).
+"""ctypes binding of libmode_hip.so, derived from include/mode_hip.h: the header that declares the C-ABI is read (_header.py) and every
+signature, constant and record here is what it says -- nothing of it is written a second time.
 
 This is the only place that touches the native library.  There is NO fallback: if the library is
 missing or a tensor is not on a GPU, the call raises.  PyTorch is used for device memory and
@@ -10,217 +11,18 @@ import threading
 
 import torch
 
+from . import _header
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libmode_hip.so')
 
-_c_int = ctypes.c_int
-_c_ptr = ctypes.c_void_p
-_c_size = ctypes.c_size_t
+HEADER = _header.load()  # include/mode_hip.h, read once: the prototypes, constants and records below are its own
+PROTOTYPES = HEADER.prototypes  # name -> (return C type, [(C type, parameter name)])
+SIGNATURES = HEADER.signatures  # name -> (restype, argtypes) as ctypes classes
+LAUNCHING = frozenset(n for n, (_, params) in PROTOTYPES.items() if any(t == _header.STREAM for t, _ in params))  # enqueue work on a stream
+CONSTANTS = HEADER.constants  # every MODE_* integer of the header, under the header's name
 
-# name -> (restype, argtypes); mirrors include/mode_hip.h one to one (checked by tests/test_abi.py)
-SIGNATURES = {
-    'mode_hip_abi_version': (_c_int, []),
-    'mode_last_error': (ctypes.c_char_p, []),
-    'mode_debug_poison': (_c_int, [ctypes.c_uint, _c_ptr]),
-    'mode_weight_pack_reuse': (_c_int, [_c_int]),
-    'mode_sum_n': (_c_int, [_c_ptr] * 5 + [ctypes.c_longlong, _c_ptr]),
-    'mode_conv3d_fwd_split_stats_partials': (_c_int, []),
-    'mode_conv3d_fwd_split_stats': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_bn_train_fwd_prestats': (_c_int, [_c_ptr] * 7 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 6 + [_c_int] * 3 +
-                                   [ctypes.c_longlong, _c_ptr]),
-    'mode_sphere_conv_wpack_bytes': (_c_size, [_c_int] * 5),
-    'mode_sphere_conv_fwd': (_c_int, [_c_ptr] * 5 + [_c_int] * 12 + [_c_ptr]),
-    'mode_sphere_conv_bwd_data': (_c_int, [_c_ptr] * 5 + [_c_int] * 12 + [_c_ptr]),
-    'mode_sphere_adjoint_max_entries': (_c_size, [_c_int] * 4),
-    'mode_sphere_adjoint_build': (_c_int, [_c_ptr] + [_c_int] * 8 + [_c_ptr] * 3),
-    'mode_sphere_conv_bwd_data_adj': (_c_int, [_c_ptr] * 6 + [_c_int] * 11 + [_c_ptr]),
-    'mode_sphere_conv_bwd_data_adj_list': (_c_int, [_c_ptr] * 6 + [_c_int] * 11 + [_c_ptr, _c_int, _c_ptr]),
-    'mode_sphere_adjplan_build': (_c_int, [_c_ptr] + [_c_int] * 4 + [_c_ptr] * 7),
-    'mode_sphere_conv_bwd_data_win_wpack_bytes': (_c_size, [_c_int] * 5),
-    'mode_sphere_conv_bwd_data_win_supported': (_c_int, [_c_int] * 3),
-    'mode_sphere_conv_bwd_data_win_split': (_c_int, [_c_ptr] * 5 + [_c_int] + [_c_ptr] * 4 + [_c_int] * 9 + [_c_ptr]),
-    'mode_sphere_conv_bwd_data_win_split_f16': (_c_int, [_c_ptr] * 7 + [_c_int] + [_c_ptr] * 4 + [_c_int] * 9 + [_c_ptr]),
-    'mode_sphere_plan_max_tiles': (_c_size, [_c_int] * 2),
-    'mode_sphere_plan_build': (_c_int, [_c_ptr] + [_c_int] * 4 + [_c_ptr] * 2),
-    'mode_sphere_conv_win_wpack_bytes': (_c_size, [_c_int] * 5),
-    'mode_sphere_conv_fwd_win': (_c_int, [_c_ptr] * 6 + [_c_int] * 12 + [_c_ptr]),
-    'mode_transpose_planes': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
-    'mode_sphere_plan_rest_pixels': (_c_int, [_c_ptr] * 2 + [_c_int] * 2 + [_c_ptr] * 2),
-    'mode_sphere_plan_polar_max_items': (_c_size, [_c_ptr]),
-    'mode_sphere_plan_polar': (_c_int, [_c_ptr] * 3 + [_c_int] * 2 + [_c_ptr] * 4),
-    'mode_sphere_conv_bwd_weight_win_workspace_bytes': (_c_size, [_c_int] * 11),
-    'mode_sphere_plan_records_count': (_c_size, [_c_int]),
-    'mode_sphere_plan_records': (_c_int, [_c_ptr] * 3 + [_c_int] * 2 + [_c_ptr] * 2),
-    'mode_sphere_conv_bwd_weight_win': (_c_int, [_c_ptr] * 6 + [_c_int] * 3 + [_c_ptr] * 3 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 9 +
-                                        [_c_ptr] * 3),
-    'mode_sphere_conv_bwd_weight_win_split': (_c_int, [_c_ptr] * 6 + [_c_int] * 3 + [_c_ptr] * 3 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 9 +
-                                              [_c_ptr] * 3),
-    'mode_sphere_conv_bwd_weight_win_split_f16': (_c_int, [_c_ptr] * 8 + [_c_int] * 3 + [_c_ptr] * 3 + [_c_int] + [_c_ptr] * 3 + [_c_int] * 9 +
-                                                  [_c_ptr] * 3),
-    'mode_sphere_conv_bwd_weight_workspace_bytes': (_c_size, [_c_int] * 8),
-    'mode_sphere_conv_bwd_weight': (_c_int, [_c_ptr] * 5 + [_c_int] * 12 + [_c_ptr]),
-    'mode_sphere_conv_fwd_bn': (_c_int, [_c_ptr] * 6 + [_c_int] * 12 + [_c_ptr]),
-    'mode_sphere_conv_fwd_win_bn': (_c_int, [_c_ptr] * 7 + [_c_int] * 12 + [_c_ptr]),
-    'mode_sphere_conv_fwd_win_split': (_c_int, [_c_ptr] * 7 + [_c_int] * 12 + [_c_ptr]),
-    'mode_sphere_conv_fwd_win_split_f16': (_c_int, [_c_ptr] * 8 + [_c_int] * 12 + [_c_ptr]),
-    'mode_cost_volume_fwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 5 + [_c_ptr]),
-    'mode_cost_volume_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 5 + [_c_ptr]),
-    'mode_conv2d_wpack_bytes': (_c_size, [_c_int] * 2),
-    'mode_conv2d_fwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_fwd_bn': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_zero_insert2': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
-    'mode_conv2d_bwd_data': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_bwd_weight_workspace_bytes': (_c_size, [_c_int] * 5),
-    'mode_conv2d_bwd_weight': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv1x1_wpack_bytes': (_c_size, [_c_int] * 2),
-    'mode_conv1x1_fwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv1x1_fwd_bn': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv1x1_bwd_data': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv1x1_bwd_weight_workspace_bytes': (_c_size, [_c_int] * 6),
-    'mode_conv1x1_bwd_weight': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv_stem_wpack_bytes': (_c_size, [_c_int] * 2),
-    'mode_conv_stem_fwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr]),
-    'mode_conv_stem_fwd_bn': (_c_int, [_c_ptr] * 5 + [_c_int] * 5 + [_c_ptr]),
-    'mode_conv_stem_bwd_weight_workspace_bytes': (_c_size, [_c_int] * 5),
-    'mode_conv_stem_bwd_weight': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_cost_conv_assemble_fwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 5 + [_c_ptr]),
-    'mode_cost_conv_assemble_fwd_bn': (_c_int, [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr]),
-    'mode_cost_conv_assemble_fwd_bn_amax': (_c_int, [_c_ptr] * 5 + [_c_int] * 5 + [_c_ptr]),
-    'mode_cost_conv_assemble_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 5 + [_c_ptr]),
-    'mode_conv3d_wpack_bytes': (_c_size, [_c_int] * 2),
-    'mode_conv3d_fwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv3d_fwd_bn': (_c_int, [_c_ptr] * 5 + [_c_int] * 7 + [_c_ptr]),
-    'mode_deconv3d_fwd_bn': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_bwd_data': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv2d_split_supported': (_c_int, [_c_int] * 4),
-    'mode_conv2d_split_shape_supported': (_c_int, [_c_int] * 6),
-    'mode_conv2d_fwd_split': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_bwd_data_split': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_bwd_data_split_acc': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_fwd_split_f16': (_c_int, [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_fwd_split_f16_bn': (_c_int, [_c_ptr] * 7 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_bwd_data_split_f16': (_c_int, [_c_ptr] * 7 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv2d_bwd_weight_split': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv2d_bwd_weight_split_f16': (_c_int, [_c_ptr] * 6 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv3d_split_supported': (_c_int, [_c_int] * 4),
-    'mode_conv3d_split_shape_supported': (_c_int, [_c_int] * 7),
-    'mode_conv3d_fwd_split': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_fwd_s2_split': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_fwd_s2_split_amax': (_c_int, [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr]),
-    'mode_deconv3d_split_supported': (_c_int, [_c_int] * 2),
-    'mode_deconv3d_fwd_split': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_deconv3d_split_bn_supported': (_c_int, [_c_int] * 2),
-    'mode_conv3d_bwd_data_split_acc_supported': (_c_int, [_c_int] * 3),
-    'mode_abs_max': (_c_int, [_c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr]),
-    'mode_abs_max_batch': (_c_int, [_c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr]),
-    'mode_conv3d_fwd_split_f16': (_c_int, [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_fwd_split_f16_bn': (_c_int, [_c_ptr] * 7 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_bwd_data_split_f16': (_c_int, [_c_ptr] * 7 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_bwd_weight_split_f16': (_c_int, [_c_ptr] * 6 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv3d_bwd_data_split_acc': (_c_int, [_c_ptr] * 5 + [_c_int] * 7 + [_c_ptr]),
-    'mode_deconv3d_fwd_split_bn': (_c_int, [_c_ptr] * 5 + [_c_int] * 6 + [_c_ptr]),
-    'mode_deconv3d_fwd_split_bn_amax': (_c_int, [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_bwd_data_s2_split': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_bwd_data_split': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_bwd_weight_split': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv3d_bwd_weight_s2_split': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_conv3d_bwd_weight_workspace_bytes': (_c_size, [_c_int] * 7),
-    'mode_deconv3d_fwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 6 + [_c_ptr]),
-    'mode_conv3d_bwd_weight': (_c_int, [_c_ptr] * 4 + [_c_int] * 8 + [_c_ptr]),
-    'mode_head_fwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr]),
-    'mode_head_bwd_workspace_bytes': (_c_size, [_c_int] * 4),
-    'mode_head_bwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [_c_ptr]),
-    'mode_head_bwd_conf': (_c_int, [_c_ptr] * 7 + [_c_int] * 7 + [_c_ptr]),
-    'mode_smooth_l1_workspace_bytes': (_c_size, [ctypes.c_longlong]),
-    'mode_smooth_l1_masked': (_c_int, [_c_ptr] * 4 + [ctypes.c_float] * 3 + [_c_ptr] * 3 + [ctypes.c_longlong, _c_ptr]),
-    'mode_head_loss_supported': (_c_int, [_c_int] * 7),
-    'mode_head_bwd_loss': (_c_int, [_c_ptr] * 3 + [ctypes.c_float] + [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr]),
-    'mode_disp2depth': (_c_int, [_c_ptr] * 2 + [_c_int] * 2 + [ctypes.c_float, _c_ptr]),
-    'mode_grid_sample_border': (_c_int, [_c_ptr] * 3 + [_c_int] * 7 + [_c_ptr]),
-    'mode_depth_view_trans_workspace_bytes': (_c_size, [_c_int] * 2),
-    'mode_depth_view_trans': (_c_int, [_c_ptr] * 8 + [_c_int] * 2 + [_c_ptr]),
-    'mode_depth_view_project': (_c_int, [_c_ptr] * 6 + [_c_int] * 2 + [_c_ptr]),
-    'mode_zbuffer': (_c_int, [_c_ptr] * 6 + [ctypes.c_longlong, _c_ptr]),
-    # multi-view hand-off (csrc/multiview.hip)
-    'mode_multiview_handoff_workspace_bytes': (_c_size, [_c_int] * 3),
-    'mode_multiview_handoff': (_c_int, [_c_ptr] * 2 + [_c_int] * 3 + [_c_ptr] * 4 + [_c_int] + [_c_ptr] * 3),
-    'mode_multiview_handoff_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr] * 6 + [_c_int] * 2 + [_c_ptr] * 2),
-    'mode_multiview_handoff_bwd_full': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [_c_ptr] * 6 + [_c_int] * 2 + [_c_ptr] * 3),
-    # the same for any camera rig (csrc/multiview_rig.hip; utils.rig)
-    'mode_multiview_rig_handoff_workspace_bytes': (_c_size, [_c_int] * 4),
-    'mode_multiview_rig_handoff': (_c_int, [_c_ptr] * 2 + [_c_int] * 4 + [_c_ptr, _c_int] + [_c_ptr] * 2 + [_c_int, _c_ptr, _c_int] +
-                                   [_c_ptr] * 3),
-    'mode_multiview_rig_handoff_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_int] + [_c_ptr] * 4 +
-                                       [_c_int] * 2 + [_c_ptr] * 2),
-    'mode_multiview_rig_handoff_bwd_full': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_int] + [_c_ptr] * 4 +
-                                            [_c_int] * 2 + [_c_ptr] * 3),
-    'mode_classif_workspace_bytes': (_c_size, [_c_int] * 5),
-    'mode_classif_train_fwd': (_c_int, [_c_ptr] * 6 + [ctypes.c_float] * 2 + [_c_ptr] * 8 + [_c_int] * 5 + [_c_ptr]),
-    'mode_classif_train_bwd': (_c_int, [_c_ptr] * 13 + [_c_int] + [_c_ptr] + [_c_int] * 5 + [_c_ptr]),
-    'mode_bn_workspace_bytes': (_c_size, [_c_int]),
-    'mode_bn_train_fwd': (_c_int, [_c_ptr] * 7 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 6 + [_c_int] * 2 +
-                          [ctypes.c_longlong, _c_int, _c_ptr]),
-    'mode_bn_eval_fwd': (_c_int, [_c_ptr] * 6 + [ctypes.c_float, _c_int] + [_c_ptr] + [_c_int] * 2 + [ctypes.c_longlong, _c_ptr]),
-    'mode_bn_train_bwd': (_c_int, [_c_ptr] * 8 + [_c_int] + [_c_ptr] * 4 + [_c_int] + [_c_ptr] + [_c_int] * 2 +
-                          [ctypes.c_longlong, _c_int, _c_ptr]),
-    # the `_amax` entries: the plain entry's arguments + the maximum's buffer in front of the stream (ABI 30)
-    'mode_bn_train_fwd_amax': (_c_int, [_c_ptr] * 7 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 6 + [_c_int] * 2 +
-                               [ctypes.c_longlong, _c_int, _c_ptr, _c_ptr]),
-    'mode_bn_train_fwd_prestats_amax': (_c_int, [_c_ptr] * 7 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 6 + [_c_int] * 3 +
-                                        [ctypes.c_longlong, _c_ptr, _c_ptr]),
-    'mode_bn_train_bwd_amax': (_c_int, [_c_ptr] * 8 + [_c_int] + [_c_ptr] * 4 + [_c_int] + [_c_ptr] + [_c_int] * 2 +
-                               [ctypes.c_longlong, _c_int, _c_ptr, _c_ptr]),
-    'mode_classif_train_bwd_amax': (_c_int, [_c_ptr] * 13 + [_c_int] + [_c_ptr] + [_c_int] * 5 + [_c_ptr, _c_ptr]),
-    # fusion network (csrc/fusion_ops.hip)
-    'mode_maxpool2x2_fwd': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong, _c_int, _c_int, _c_ptr]),
-    'mode_maxpool2x2_bwd': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong, _c_int, _c_int, _c_ptr]),
-    'mode_depth_to_space2': (_c_int, [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr]),
-    'mode_space_to_depth2': (_c_int, [_c_ptr] * 2 + [_c_int] * 4 + [_c_ptr]),
-    'mode_conv1x1_sigmoid_fwd': (_c_int, [_c_ptr] * 4 + [_c_int] * 2 + [ctypes.c_longlong, _c_ptr]),
-    'mode_conv1x1_sigmoid_bwd_workspace_bytes': (_c_size, [_c_int, ctypes.c_longlong]),
-    'mode_conv1x1_sigmoid_bwd': (_c_int, [_c_ptr] * 7 + [_c_int] + [_c_ptr] + [_c_int] * 2 + [ctypes.c_longlong, _c_ptr]),
-    # metrics and losses (csrc/metrics.hip; reference utils/evaluation.py, train_fusion.py:82-87)
-    'mode_masked_metrics_workspace_bytes': (_c_size, [ctypes.c_longlong]),
-    'mode_masked_metrics': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong] + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 2),
-    'mode_silog_loss_fwd': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong, ctypes.c_float, _c_ptr, _c_size] + [_c_ptr] * 3),
-    'mode_silog_loss_bwd': (_c_int, [_c_ptr] * 3 + [ctypes.c_longlong, ctypes.c_float] + [_c_ptr] * 4),
-    # scoring in the ERP domain (csrc/erp_metrics.hip; reference test_fusion.py:82, 86-100)
-    'mode_erp_depth_metrics_workspace_bytes': (_c_size, [_c_int] * 3),
-    'mode_erp_depth_metrics': (_c_int, [_c_ptr] * 3 + [_c_int] * 3 + [ctypes.c_float] + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 4),
-    'mode_bicubic_up2': (_c_int, [_c_ptr] * 2 + [_c_int] * 4 + [_c_ptr]),
-    # 8-bit ingest of whole frames (csrc/ingest.hip; reference dataloader/deep360_loader.py:108-109, 146-163)
-    'mode_frames_u8_ingest': (_c_int, [_c_ptr] * 2 + [_c_int] * 3 + [_c_ptr] * 4),
-    'mode_rgb_half_pil': (_c_int, [_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr] * 3),
-    'mode_decimate2': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
-    'mode_decimate2_bwd': (_c_int, [_c_ptr] * 2 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
-    # colour augmentation on the 8-bit ingest (csrc/augment.hip; reference dataloader/preprocess.py:33-46, 78-95)
-    'mode_images_u8_augment_workspace_bytes': (_c_size, [_c_int] * 3),
-    'mode_images_u8_augment': (_c_int, [_c_ptr] * 4 + [_c_int] * 5 + [_c_ptr] * 3 + [_c_size, _c_ptr]),
-    # stereo pairs at any working size (csrc/resize.hip; reference dataloader/deep360_loader.py:92-106)
-    'mode_images_u8_resize_pil_workspace_bytes': (_c_size, [_c_int] * 7),
-    'mode_images_u8_resize_pil': (_c_int, [_c_ptr, _c_ptr, _c_int, _c_ptr, _c_int, _c_ptr, _c_ptr] + [_c_int] * 9 + [_c_ptr] * 3 +
-                                  [_c_size, _c_ptr]),
-    'mode_disp_resize_nearest': (_c_int, [_c_ptr] * 4 + [_c_int] * 7 + [ctypes.c_float] + [_c_ptr] * 2),
-    # 3D60 ingest: ERP pairs and depth to rectified Cassini (csrc/erp_ingest.hip; reference dataloader/dataset3D60Loader.py:123-270)
-    'mode_erp_pairs_u8_cassini': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr] * 6),
-    'mode_erp_depth_disp': (_c_int, [_c_ptr] * 3 + [_c_int] * 6 + [ctypes.c_float] * 2 + [_c_int] + [_c_ptr] * 3),
-    # spatial pyramid pooling of the conv='Regular' extractor (csrc/spp.hip; reference models/submodule.py:228-268)
-    'mode_spp_pool_fwd': (_c_int, [_c_ptr] * 5 + [ctypes.c_longlong] + [_c_int] * 2 + [_c_ptr]),
-    'mode_spp_pool_bwd': (_c_int, [_c_ptr] + [_c_int] * 2 + [_c_ptr] * 5 + [_c_int] * 4 + [_c_ptr]),
-    'mode_spp_concat_fwd': (_c_int, [_c_ptr] * 7 + [_c_int] * 6 + [_c_ptr]),
-    'mode_spp_concat_bwd': (_c_int, [_c_ptr] * 6 + [_c_int] * 6 + [_c_ptr]),
-    # the optimizer of the training step (csrc/optim.hip; reference train_disparity.py:293)
-    'mode_adam_workspace_bytes': (_c_size, [ctypes.c_longlong]),
-    'mode_adam_block_bytes': (_c_size, [_c_int]),
-    'mode_adam_prepare': (_c_int, [_c_ptr, ctypes.c_longlong, _c_ptr, _c_size, _c_ptr, _c_int, _c_int, _c_ptr]),
-    'mode_adam_update': (_c_int, [_c_ptr, _c_int, _c_ptr, _c_int] + [_c_ptr] * 4 + [_c_int, _c_ptr]),
-    # self-supervised stereo loss: Cassini warp, SSIM + L1, edge-aware smoothness (csrc/photometric.hip)
-    'mode_photometric_loss_workspace_bytes': (_c_size, [_c_int] * 4),
-    'mode_photometric_loss_fwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr] * 2 + [_c_size] + [_c_ptr] * 3),
-    'mode_photometric_loss_bwd': (_c_int, [_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr] * 5),
-}
-
-ABI_VERSION = 31  # MODE_HIP_ABI_VERSION of include/mode_hip.h this binding was written against
+ABI_VERSION = CONSTANTS['MODE_HIP_ABI_VERSION']
 _lib = None
 _lock = threading.Lock()
 
@@ -247,37 +49,19 @@ def lib():
   return _lib
 
 
-class BnEpilogue(ctypes.Structure):
-  """struct mode_bn_epilogue of include/mode_hip.h (host-side struct of device pointers)."""
-  _fields_ = [('gamma', _c_ptr), ('beta', _c_ptr), ('mean', _c_ptr), ('var', _c_ptr), ('eps', ctypes.c_float), ('add', _c_ptr),
-              ('relu', _c_int)]
+BnEpilogue = _header.structure(HEADER, 'mode_bn_epilogue', 'BnEpilogue', 'struct mode_bn_epilogue (host-side struct of device pointers).')
 
+# indices into the statistic vector of mode_masked_metrics / mode_silog_loss_fwd
+METRICS_MAX_THRESHOLDS, METRICS_COUNT = CONSTANTS['MODE_METRICS_MAX_THRESHOLDS'], CONSTANTS['MODE_METRICS_COUNT']
+(M_N, M_N_GT, M_N_BOTH, M_SUM_ABS, M_SUM_SQ, M_SUM_ABSREL, M_SUM_SQREL, M_SUM_LOG, M_SUM_LOG2, M_MAX_ABS, M_PX, M_D1, M_RATIO) = (
+    CONSTANTS['MODE_METRICS_' + k] for k in 'N N_GT N_BOTH SUM_ABS SUM_SQ SUM_ABSREL SUM_SQREL SUM_LOG SUM_LOG2 MAX_ABS PX D1 RATIO'.split())
+MetricsParams = _header.structure(HEADER, 'mode_metrics_params', 'MetricsParams', 'struct mode_metrics_params (host memory, read during the call).')
 
-METRICS_MAX_THRESHOLDS = 4  # MODE_METRICS_MAX_THRESHOLDS
-# MODE_METRICS_* of include/mode_hip.h: indices into the statistic vector of mode_masked_metrics / mode_silog_loss_fwd
-(M_N, M_N_GT, M_N_BOTH, M_SUM_ABS, M_SUM_SQ, M_SUM_ABSREL, M_SUM_SQREL, M_SUM_LOG, M_SUM_LOG2, M_MAX_ABS) = range(10)
-M_PX = 10
-M_D1 = M_PX + METRICS_MAX_THRESHOLDS
-M_RATIO = M_D1 + METRICS_MAX_THRESHOLDS
-METRICS_COUNT = M_RATIO + METRICS_MAX_THRESHOLDS
-
-
-class MetricsParams(ctypes.Structure):
-  """struct mode_metrics_params of include/mode_hip.h (host memory, read during the call)."""
-  _T = ctypes.c_float * METRICS_MAX_THRESHOLDS
-  _fields_ = [('n_px', _c_int), ('px', _T), ('n_d1', _c_int), ('d1_px', _T), ('d1_pct', _T), ('n_ratio', _c_int), ('ratio', _T)]
-
-
-PHOTOMETRIC_MAX_MAPS = 4  # MODE_PHOTOMETRIC_MAX_MAPS
-# MODE_PHOTOMETRIC_* of include/mode_hip.h: the statistics of one disparity map as mode_photometric_loss_fwd leaves them
-(PH_N_VALID, PH_SUM_PE, PH_SUM_SMOOTH_X, PH_SUM_SMOOTH_Y) = range(4)
-PHOTOMETRIC_STATS = 4
-
-
-class PhotometricParams(ctypes.Structure):
-  """struct mode_photometric_params of include/mode_hip.h (host memory, read during the call)."""
-  _fields_ = [('alpha', ctypes.c_float), ('lam', ctypes.c_float), ('beta', ctypes.c_float), ('c1', ctypes.c_float), ('c2', ctypes.c_float),
-              ('mean', ctypes.c_float * 3), ('std', ctypes.c_float * 3), ('weights', ctypes.c_float * PHOTOMETRIC_MAX_MAPS)]
+# the statistics of one disparity map as mode_photometric_loss_fwd leaves them
+PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS = CONSTANTS['MODE_PHOTOMETRIC_MAX_MAPS'], CONSTANTS['MODE_PHOTOMETRIC_STATS']
+(PH_N_VALID, PH_SUM_PE, PH_SUM_SMOOTH_X, PH_SUM_SMOOTH_Y) = (CONSTANTS['MODE_PHOTOMETRIC_' + k] for k in 'N_VALID SUM_PE SUM_SMOOTH_X SUM_SMOOTH_Y'.split())
+PhotometricParams = _header.structure(HEADER, 'mode_photometric_params', 'PhotometricParams',
+                                      'struct mode_photometric_params (host memory, read during the call).')
 
 
 def check(rc, what):

@@ -6,7 +6,7 @@ import threading
 
 import torch
 
-from . import (METRICS_COUNT, METRICS_MAX_THRESHOLDS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS, BnEpilogue, MetricsParams, PhotometricParams, check, lib,
+from . import (CONSTANTS, METRICS_COUNT, METRICS_MAX_THRESHOLDS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS, BnEpilogue, MetricsParams, PhotometricParams, check, lib,
                profiling, ptr, require_f32c, require_gpu, stream_of)
 
 
@@ -1483,7 +1483,7 @@ CONV3D_EVAL_F16 = True
 CONV2D_EVAL_F16 = True
 
 
-BN_ABSMAX_FLOATS = 2064  # MODE_BN_ABSMAX_FLOATS of include/mode_hip.h: the buffer a tensor's maximum lives in
+BN_ABSMAX_FLOATS = CONSTANTS['MODE_BN_ABSMAX_FLOATS']  # the buffer a tensor's maximum lives in
 
 
 def abs_max(t):
@@ -2234,7 +2234,7 @@ def rgb_half_pil(frames_u8, tab_w, tab_h, lut, return_u8=False):
   return (out, u8) if return_u8 else out
 
 
-RESIZE_MAX_SCALE = 4  # MODE_RESIZE_MAX_SCALE of include/mode_hip.h
+RESIZE_MAX_SCALE = CONSTANTS['MODE_RESIZE_MAX_SCALE']
 RESIZE_MAX_TAPS = 17
 
 

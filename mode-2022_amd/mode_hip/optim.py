@@ -20,13 +20,12 @@ The element arithmetic is that of torch's single-tensor path, operation by opera
 import numpy as np
 import torch
 
-from . import check, functional, lib, profiling, ptr, stream_of
+from . import CONSTANTS, HEADER, _header, check, functional, lib, profiling, ptr, stream_of
 
-CHUNK = 2048  # MODE_ADAM_CHUNK of include/mode_hip.h
-STATE_DOUBLES, GROUP_DOUBLES = 8, 8  # MODE_ADAM_STATE_DOUBLES, MODE_ADAM_GROUP_DOUBLES
-S_STEP, S_SKIPPED, S_GRAD_NORM, S_FOUND_INF, S_NONFINITE = range(5)  # MODE_ADAM_STEP ..
-SEGMENT = np.dtype([('param', '<u8'), ('first', '<i8'), ('numel', '<i8'), ('group', '<i4'), ('unused', '<i4')])  # struct mode_adam_segment
-CHUNK_RECORD = np.dtype([('off', '<i8'), ('seg', '<i4'), ('count', '<i4')])  # struct mode_adam_chunk
+CHUNK, STATE_DOUBLES, GROUP_DOUBLES = (CONSTANTS['MODE_ADAM_' + k] for k in 'CHUNK STATE_DOUBLES GROUP_DOUBLES'.split())
+S_STEP, S_SKIPPED, S_GRAD_NORM, S_FOUND_INF, S_NONFINITE = (CONSTANTS['MODE_ADAM_' + k] for k in 'STEP SKIPPED GRAD_NORM FOUND_INF NONFINITE'.split())
+SEGMENT = np.dtype(_header.structure(HEADER, 'mode_adam_segment'))
+CHUNK_RECORD = np.dtype(_header.structure(HEADER, 'mode_adam_chunk'))
 _HOST_ROWS = 4  # pinned staging rows of the hyper-parameter refresh (a row is rewritten only after its copy has left it)
 
 

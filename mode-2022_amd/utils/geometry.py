@@ -18,7 +18,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from mode_hip import check, lib, ptr, require_f32c, require_gpu, stream_of
+from mode_hip import CONSTANTS, check, lib, ptr, require_f32c, require_gpu, stream_of
 from mode_hip import functional as _HF
 
 _DEV = 'cuda'
@@ -314,7 +314,7 @@ def disp2depth(disp, conf_map, cam_pair, dbname='Deep360'):
 
 # ------------------------------------------------------------------------------------------------ the multi-view hand-off
 PAIRS = ('12', '13', '14', '23', '24', '34')  # the order of a frame's six pairs (CAM_PAIRS)
-MV_CONF_PNG, MV_DEPTH_ONLY = 1, 2  # MODE_MV_* of include/mode_hip.h
+MV_CONF_PNG, MV_DEPTH_ONLY = CONSTANTS['MODE_MV_CONF_PNG'], CONSTANTS['MODE_MV_DEPTH_ONLY']
 _frames_cache = _HF._LRU(8)  # (H, W, device, dbname) -> constant tables of mode_multiview_handoff (graph-pinned while captured);
 #                              ('rig', rig, H, W, device) -> those of mode_multiview_rig_handoff for a utils.rig.CameraRig
 _frames_lock = threading.Lock()

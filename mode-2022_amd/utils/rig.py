@@ -10,10 +10,10 @@ import math
 
 import numpy as np
 
-MAX_PAIRS = 16  # MODE_MV_MAX_PAIRS of include/mode_hip.h
+MAX_PAIRS = 16  # the header's MODE_MV_MAX_PAIRS (this module imports no binding; tests/test_rig_host.py holds both values to the header)
 KINDS = ('identity', 'rotate', 'view')  # their position is MODE_MV_IDENTITY / MODE_MV_ROTATE / MODE_MV_VIEW
 _POSE_LEN = {'identity': 0, 'rotate': 3, 'view': 6}
-PAIR_RECORD = np.dtype([('kind', '<i4'), ('table', '<i4'), ('baseline', '<f4')])  # mode_mv_pair
+PAIR_RECORD = np.dtype([('kind', '<i4'), ('table', '<i4'), ('baseline', '<f4')])  # the header's mode_mv_pair
 
 
 class PairPose(object):

@@ -50,9 +50,6 @@ OUT = os.path.join(HERE, 'routes_parent.json')
 OUT_GRAD = os.path.join(HERE, 'routes_parent_sphere_grad.json')
 DEV = 'cuda:0'
 
-# name fragments of the entries that launch nothing (the list of tests/test_gpu_repeat.py, restated: a fixture depends on no test module)
-HOST_ONLY = ('_bytes', '_supported', '_build', '_plan_', '_max_', 'abi_version', 'last_error', 'debug_poison', 'adjplan', '_partials')
-
 F16_SWITCHES = ('CONV3D_S1_F16', 'CONV3D_EVAL_F16', 'CONV2D_EVAL_F16', 'CONV2D_F16', 'SPHERE_FWD_F16', 'SPHERE_BWD_F16')
 SWITCH_SETS = {
     'default': {'CONV_ARITH': 'bf16x6'},
@@ -127,13 +124,13 @@ class _LibSpy(object):
   def __getattr__(self, name):
     import mode_hip
     fn = getattr(self._real, name)
-    if name != 'mode_abs_max_batch' and any(s in name for s in HOST_ONLY):
+    launching = name in mode_hip.LAUNCHING and name != 'mode_debug_poison'  # (the stream is a launching entry's last parameter)
+    if not launching and name != 'mode_weight_pack_reuse':
       return fn
-    has_stream = mode_hip.SIGNATURES[name][1][-1] is ctypes.c_void_p
     log = self._log
 
     def call(*args):
-      log.append(['call', name, [_enc(a) for a in (args[:-1] if has_stream else args)]])
+      log.append(['call', name, [_enc(a) for a in (args[:-1] if launching else args)]])
       return fn(*args)
     return call
 

@@ -37,9 +37,7 @@ def test_maximum_buffer_size_matches_the_header():
   """functional.BN_ABSMAX_FLOATS (what Python allocates for mode_abs_max / the `_amax` BatchNorm entries) is the header's MODE_BN_ABSMAX_FLOATS (what the
   kernels zero and read: 16 + 128 slots x 16 floats); the fp16 entries reject a missing maximum on the host."""
   from mode_hip import functional as HF
-  src = open(os.path.join(ROOT, 'include', 'mode_hip.h')).read()
-  m = re.search(r'#define\s+MODE_BN_ABSMAX_FLOATS\s+(\d+)', src)
-  assert m and int(m.group(1)) == HF.BN_ABSMAX_FLOATS == 16 * (1 + 128)
+  assert mode_hip.CONSTANTS['MODE_BN_ABSMAX_FLOATS'] == HF.BN_ABSMAX_FLOATS == 16 * (1 + 128)
   lib = mode_hip.lib()
   null, one = ctypes.c_void_p(0), ctypes.c_void_p(16)
   assert lib.mode_conv2d_fwd_split_f16(one, one, null, one, one, one, 1, 16, 8, 8, 16, 1, null) == -1 and b'maximum' in lib.mode_last_error()
@@ -230,8 +228,11 @@ def test_no_state_between_calls_in_the_abi():
   lib = mode_hip.lib()
   for gone in ('mode_bn_next_out_absmax', 'mode_bn_next_gy_absmax'):
     assert not hasattr(lib, gone), gone
-  src = open(os.path.join(ROOT, 'mode-2022_amd', 'csrc', 'bn_act.hip')).read() + open(os.path.join(ROOT, 'mode-2022_amd', 'csrc', 'classif_head.hip')).read()
-  assert 'thread_local' not in src
+  # ... and for every source file: the two thread-local values the header's convention block names (the error string, the
+  # mode_weight_pack_reuse setting) are the only state the library keeps
+  csrc = os.path.join(ROOT, 'mode-2022_amd', 'csrc')
+  found = [(f, line.strip()) for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h')) for line in open(os.path.join(csrc, f)) if 'thread_local' in line]
+  assert found == [('common.hip', 'static thread_local char g_err[512] = "";'), ('common.hip', 'static thread_local int g_pack_reuse = 0;')], found
   # the `_amax` entries check their arguments like the plain ones (host-side, no launch): in-place is refused with a maximum buffer too
   a, b = ctypes.c_void_p(4096), ctypes.c_void_p(8192)
   rc = lib.mode_bn_train_fwd_amax(a, None, b, b, None, None, None, 0.1, 1e-5, 1, a, b, b, None, None, b, 2, 4, 64, 1, b, None)

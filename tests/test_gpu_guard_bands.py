@@ -31,7 +31,6 @@ from mode_hip import functional as HF
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-from test_gpu_repeat import HOST_ONLY  # name fragments of the entries that launch nothing
 
 
 class RecordingLib(object):
@@ -42,7 +41,7 @@ class RecordingLib(object):
 
   def __getattr__(self, name):
     fn = getattr(self._real, name)
-    if not name.startswith('mode_') or any(s in name for s in HOST_ONLY):
+    if name not in mode_hip.LAUNCHING or name == 'mode_debug_poison':
       return fn
 
     def call(*args):
@@ -365,11 +364,11 @@ LAUNCHES = {  # case id -> the launching entries (without their mode_ prefix) th
     'head_loss-2x4x16x8':
         'head_bwd_loss head_fwd smooth_l1_masked',
     'small_ops-1':
-        'abs_max sum_n',
+        'abs_max abs_max_batch sum_n',
     'small_ops-1023':
-        'abs_max sum_n',
+        'abs_max abs_max_batch sum_n',
     'small_ops-4097':
-        'abs_max sum_n',
+        'abs_max abs_max_batch sum_n',
     'planes':
         'transpose_planes zero_insert2',
     'maxpool2x2-(1,3,9,7)':
@@ -399,9 +398,9 @@ LAUNCHES = {  # case id -> the launching entries (without their mode_ prefix) th
     'multiview-3':
         'depth_view_trans disp2depth grid_sample_border multiview_handoff',
     'path_train_step':
-        'abs_max bn_train_bwd_amax bn_train_fwd_amax classif_train_bwd_amax classif_train_fwd conv1x1_bwd_data conv1x1_bwd_weight conv1x1_fwd conv2d_bwd_data_split_f16 conv2d_bwd_weight_split_f16 conv2d_fwd_split_f16 conv3d_bwd_data_s2_split conv3d_bwd_data_split_acc conv3d_bwd_data_split_f16 conv3d_bwd_weight_s2_split conv3d_bwd_weight_split_f16 conv3d_fwd_s2_split conv3d_fwd_split_f16 conv_stem_bwd_weight conv_stem_fwd cost_conv_assemble_bwd cost_conv_assemble_fwd deconv3d_fwd_split head_bwd head_fwd sphere_conv_bwd_data_adj sphere_conv_bwd_weight sphere_conv_bwd_weight_win_split_f16 sphere_conv_fwd sum_n transpose_planes zero_insert2',
+        'abs_max abs_max_batch bn_train_bwd_amax bn_train_fwd_amax classif_train_bwd_amax classif_train_fwd conv1x1_bwd_data conv1x1_bwd_weight conv1x1_fwd conv2d_bwd_data_split_f16 conv2d_bwd_weight_split_f16 conv2d_fwd_split_f16 conv3d_bwd_data_s2_split conv3d_bwd_data_split_acc conv3d_bwd_data_split_f16 conv3d_bwd_weight_s2_split conv3d_bwd_weight_split_f16 conv3d_fwd_s2_split conv3d_fwd_split_f16 conv_stem_bwd_weight conv_stem_fwd cost_conv_assemble_bwd cost_conv_assemble_fwd deconv3d_fwd_split head_bwd head_fwd sphere_conv_bwd_data_adj sphere_conv_bwd_weight sphere_conv_bwd_weight_win_split_f16 sphere_conv_fwd sum_n transpose_planes zero_insert2',
     'path_eval_forward':
-        'abs_max bn_train_fwd_amax conv1x1_fwd conv1x1_fwd_bn conv2d_fwd_split conv2d_fwd_split_f16_bn conv3d_fwd conv3d_fwd_s2_split conv3d_fwd_s2_split_amax conv3d_fwd_split_f16 conv3d_fwd_split_f16_bn conv_stem_fwd conv_stem_fwd_bn cost_conv_assemble_fwd cost_conv_assemble_fwd_bn_amax deconv3d_fwd_split deconv3d_fwd_split_bn_amax head_fwd sphere_conv_fwd sphere_conv_fwd_bn weight_pack_reuse',
+        'abs_max bn_train_fwd_amax conv1x1_fwd conv1x1_fwd_bn conv2d_fwd_split conv2d_fwd_split_f16_bn conv3d_fwd conv3d_fwd_s2_split conv3d_fwd_s2_split_amax conv3d_fwd_split_f16 conv3d_fwd_split_f16_bn conv_stem_fwd conv_stem_fwd_bn cost_conv_assemble_fwd cost_conv_assemble_fwd_bn_amax deconv3d_fwd_split deconv3d_fwd_split_bn_amax head_fwd sphere_conv_fwd sphere_conv_fwd_bn',
     'path_fusion':
         'abs_max bn_train_bwd_amax bn_train_fwd_amax conv1x1_bwd_data conv1x1_bwd_weight conv1x1_fwd conv1x1_sigmoid_bwd conv1x1_sigmoid_fwd conv2d_bwd_data conv2d_bwd_data_split_f16 conv2d_bwd_weight_split_f16 conv2d_fwd conv2d_fwd_bn conv2d_fwd_split_f16 conv2d_fwd_split_f16_bn depth_to_space2 maxpool2x2_bwd maxpool2x2_fwd space_to_depth2',
     'sphere_gather-ERPx16x32x1x40x160-f32':
@@ -1279,7 +1278,7 @@ def b_small(n):
 
 
 for _n in (1, 1023, 4097):
-  case('small_ops', ['mode_abs_max', 'mode_sum_n'], b_small, (_n,))  # (mode_abs_max_batch: matched by HOST_ONLY's '_max_', run all the same)
+  case('small_ops', ['mode_abs_max', 'mode_abs_max_batch', 'mode_sum_n'], b_small, (_n,))
 
 
 def b_planes():

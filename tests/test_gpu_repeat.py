@@ -28,7 +28,6 @@ import op_trace
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_ONLY = ('_bytes', '_supported', '_build', '_plan_', '_max_', 'abi_version', 'last_error', 'debug_poison', 'adjplan', '_partials')
 
 
 class PoisoningLib(object):
@@ -39,11 +38,11 @@ class PoisoningLib(object):
 
   def __getattr__(self, name):
     fn = getattr(self._real, name)
-    if not name.startswith('mode_') or any(s in name for s in HOST_ONLY):
+    if name not in mode_hip.LAUNCHING or name == 'mode_debug_poison':
       return fn
 
     def call(*args):
-      rc = self._real.mode_debug_poison(self._pattern, args[-1])  # (the stream is the last argument of every launching entry)
+      rc = self._real.mode_debug_poison(self._pattern, args[-1])  # (LAUNCHING: the entries with a stream parameter, which is their last)
       assert rc == 0, self._real.mode_last_error()
       self.calls += 1
       return fn(*args)

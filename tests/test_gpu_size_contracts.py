@@ -30,7 +30,6 @@ from oracle import mode_ref
 import mode_hip
 from mode_hip import functional as HF
 from models import stage3d
-from test_gpu_repeat import HOST_ONLY  # name fragments of the entries that launch nothing
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -62,14 +61,16 @@ def _free_between_cases():
 
 
 class RecordingLib(object):
-  """Stands in for the ctypes handle (as test_gpu_repeat.PoisoningLib): the names of the launching entries, in call order."""
+  """Stands in for the ctypes handle (as test_gpu_repeat.PoisoningLib): the names of the launching entries, in call order, and of
+  mode_weight_pack_reuse, which launches nothing but tells a packed-weight cache hit (test_gpu_eval_precision reads it here)."""
+  RECORDED = (mode_hip.LAUNCHING | {'mode_weight_pack_reuse'}) - {'mode_debug_poison'}
 
   def __init__(self, real):
     self._real, self.names = real, []
 
   def __getattr__(self, name):
     fn = getattr(self._real, name)
-    if not name.startswith('mode_') or any(s in name for s in HOST_ONLY):
+    if name not in self.RECORDED:
       return fn
 
     def call(*args):

@@ -12,7 +12,6 @@ import torch
 
 import guard_bands as GB
 import mode_hip
-from test_gpu_repeat import HOST_ONLY  # name fragments of the entries that launch nothing
 
 THIS = os.path.abspath(__file__)
 HERE = os.path.dirname(THIS)
@@ -219,7 +218,7 @@ def _declared_entries():
 
 
 def launching_entries():
-  return {n for n in mode_hip.SIGNATURES if n.startswith('mode_') and not any(s in n for s in HOST_ONLY) and n != 'mode_debug_poison'}
+  return set(mode_hip.LAUNCHING) - {'mode_debug_poison'}
 
 
 def test_every_case_declares_what_it_launches():

@@ -9,7 +9,6 @@ import torch
 
 import mode_hip
 from mode_hip import optim
-from test_gpu_repeat import HOST_ONLY  # name fragments of the entries that launch nothing
 
 SIZES = [1, 3, 5, 864, 4097, 4098, 1000]  # the seven tensors of tests/test_gpu_optim.py
 GROUPS = [0, 0, 0, 0, 1, 1, 1]
@@ -78,14 +77,14 @@ def test_the_entries_refuse_bad_arguments_before_any_launch():
 
 
 def test_the_new_entries_are_named_for_what_they_do():
-  """test_gpu_repeat.HOST_ONLY marks the entries that launch nothing by a fragment of their name; the two launching entries carry none
-  and take the stream last."""
+  """mode_hip.LAUNCHING holds the entries with a stream parameter: the two that launch are in it and take the stream last, the two size
+  queries are not."""
   names = sorted(n for n in mode_hip.SIGNATURES if n.startswith('mode_adam_'))
   assert names == ['mode_adam_block_bytes', 'mode_adam_prepare', 'mode_adam_update', 'mode_adam_workspace_bytes']
   for n in ('mode_adam_prepare', 'mode_adam_update'):
-    assert not any(s in n for s in HOST_ONLY) and mode_hip.SIGNATURES[n][1][-1] is ctypes.c_void_p
+    assert n in mode_hip.LAUNCHING and mode_hip.SIGNATURES[n][1][-1] is ctypes.c_void_p
   for n in ('mode_adam_block_bytes', 'mode_adam_workspace_bytes'):
-    assert any(s in n for s in HOST_ONLY)
+    assert n not in mode_hip.LAUNCHING
   assert optim.SEGMENT.itemsize == 32 and optim.CHUNK_RECORD.itemsize == 16 and optim.CHUNK == 2048  # the header's records
 
 

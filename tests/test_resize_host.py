@@ -99,12 +99,10 @@ def test_abi_entries_are_declared_exported_and_bound():
   names = ('mode_images_u8_resize_pil', 'mode_images_u8_resize_pil_workspace_bytes', 'mode_disp_resize_nearest')
   for name in names:
     assert re.search(r'\b%s\s*\(' % name, src) and hasattr(lib, name) and name in mode_hip.SIGNATURES
-  from test_gpu_repeat import HOST_ONLY
-  assert [any(s in n for s in HOST_ONLY) for n in names] == [False, True, False]
+  assert [n in mode_hip.LAUNCHING for n in names] == [True, False, True]
   assert all(mode_hip.SIGNATURES[n][1][-1] is ctypes.c_void_p for n in (names[0], names[2]))  # the stream is the last argument
-  assert re.search(r'#define\s+MODE_RESIZE_MAX_SCALE\s+4\b', src)
   from mode_hip import functional as HF
-  assert HF.RESIZE_MAX_SCALE == 4 and HF.RESIZE_MAX_TAPS == preprocess.pil_resize_table(64, 16)[2].shape[1]
+  assert HF.RESIZE_MAX_SCALE == mode_hip.CONSTANTS['MODE_RESIZE_MAX_SCALE'] == 4 and HF.RESIZE_MAX_TAPS == preprocess.pil_resize_table(64, 16)[2].shape[1]
   q = lib.mode_images_u8_resize_pil_workspace_bytes
   assert q(3, 64, 32, 24, 12, 24, 12) == 3 * 64 * 12 * 3 and q(3, 64, 32, 24, 12, 5, 7) == 3 * 64 * 7 * 3
   assert q(2, 48, 20, 48, 12, 48, 12) == 0 and q(2, 48, 20, 30, 20, 30, 20) == 0 and q(0, 64, 32, 24, 12, 24, 12) == 0

@@ -158,17 +158,18 @@ def test_copy_and_pickle_round_trip():
 
 # ------------------------------------------------------------------------------------------------ the C entries, without a launch
 def test_the_four_entries_and_their_names():
-  from test_gpu_repeat import HOST_ONLY
   for n in ENTRIES:
     assert n in mode_hip.SIGNATURES and hasattr(mode_hip.lib(), n)
-  assert any(s in ENTRIES[0] for s in HOST_ONLY)
+  assert ENTRIES[0] not in mode_hip.LAUNCHING
   for n in ENTRIES[1:]:
-    assert not any(s in n for s in HOST_ONLY) and mode_hip.SIGNATURES[n][1][-1] is ctypes.c_void_p  # the stream is the last argument
+    assert n in mode_hip.LAUNCHING and mode_hip.SIGNATURES[n][1][-1] is ctypes.c_void_p  # the stream is the last argument
   with open(os.path.join(os.path.dirname(GOLDEN), '..', 'include', 'mode_hip.h')) as f:
     header = f.read()
   for n in ENTRIES:
     assert n + '(' in header
-  assert '#define MODE_MV_MAX_PAIRS 16' in header
+  assert RG.MAX_PAIRS == mode_hip.CONSTANTS['MODE_MV_MAX_PAIRS'] == 16  # utils.rig imports no binding: its two restated values are held to the header here
+  assert RG.PAIR_RECORD == np.dtype(mode_hip._header.structure(mode_hip.HEADER, 'mode_mv_pair'))
+  assert mode_hip.HEADER.records['mode_mv_pair'] == [('kind', 'int32_t', None), ('table', 'int32_t', None), ('baseline', 'float', None)]
   assert mode_hip.lib().mode_hip_abi_version() == 31  # additive: tests/test_abi.py pins the number
 
 
