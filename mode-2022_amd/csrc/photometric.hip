@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "mode_hip_selfsup.h"
 
 namespace {
 
@@ -44,10 +45,13 @@ struct Stage {
 
 __device__ __forceinline__ float sgn(float v) { return (float)((v > 0.f) - (v < 0.f)); }  // sign(0) = 0, sign(NaN) = 0
 
-// The warp of one pixel: row = &right[b][0][h][0], HW the channel stride.  rh: the interpolated colour; slope: d rh / d d = R[x0] - R[x0 + 1].
+// The warp of one pixel: row = &right[b][0][h][0], HW the channel stride.  rh: the interpolated colour; slope: d rh / d d, which is
+// R[x0] - R[x0 + 1] in the left view (VIEW 0: x = w - d) and R[x0 + 1] - R[x0] in the right view (VIEW 1: x = w + d; DESIGN 24, where
+// "right" is the other camera's image, whichever that is).
+template <int VIEW>
 __device__ __forceinline__ bool warp_pixel(const float* __restrict__ row, int HW, int W, int w, float d, const Prm& p, float rh[3],
                                            float slope[3]) {
-  const float x = (float)w - d;
+  const float x = VIEW == 0 ? (float)w - d : (float)w + d;
   const bool ok = __builtin_isfinite(d) && x >= 0.f && x <= (float)(W - 1);
   if (!ok) {
     rh[0] = rh[1] = rh[2] = 0.f;
@@ -62,16 +66,18 @@ __device__ __forceinline__ bool warp_pixel(const float* __restrict__ row, int HW
     const float r0 = row[c * HW + x0] * p.std[c] + p.mean[c];
     const float r1 = row[c * HW + x0 + 1] * p.std[c] + p.mean[c];
     rh[c] = (1.f - t) * r0 + t * r1;
-    slope[c] = r0 - r1;
+    slope[c] = VIEW == 0 ? r0 - r1 : r1 - r0;
   }
   return true;
 }
 
 // Tile (h0, w0) and its halo into LDS.  Rows wrap modulo H; columns outside [0, W) are invalid pixels with L = Rh = dn = 0 (no window
 // that exists contains them: windows have 1 <= w <= W - 2).  left, right: the image of this batch element; disp: this map's plane.
-template <int HALO>
+// MASKED: a pixel whose byte in mask (this map's plane) is zero is invalid; its L, Rh and dn are staged as ever.
+template <int HALO, int VIEW, bool MASKED>
 __device__ __forceinline__ void stage_tile(Stage<HALO>& s, const float* __restrict__ left, const float* __restrict__ right,
-                                           const float* __restrict__ disp, int H, int W, int h0, int w0, const Prm& p) {
+                                           const float* __restrict__ disp, const unsigned char* __restrict__ mask, int H, int W, int h0,
+                                           int w0, const Prm& p) {
   using S = Stage<HALO>;
   const int HW = H * W;
   const float wf = (float)W;
@@ -89,7 +95,8 @@ __device__ __forceinline__ void stage_tile(Stage<HALO>& s, const float* __restri
       dn = d / wf;
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) l[ch] = left[ch * HW + off] * p.std[ch] + p.mean[ch];
-      ok = warp_pixel(right + h * W, HW, W, w, d, p, rh, slope);
+      ok = warp_pixel<VIEW>(right + h * W, HW, W, w, d, p, rh, slope);
+      if (MASKED) ok = ok && mask[off] != 0;
     }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -175,9 +182,10 @@ __device__ __forceinline__ void block_fold(const double (&a)[kS], double (*sh)[k
 }
 
 // grid = (B * tiles, K).  Block (col, k) leaves its four statistics in column col of map k's slab rows.
+template <int VIEW, bool MASKED>
 __global__ __launch_bounds__(NT) void photometric_fwd_kernel(const float* __restrict__ left, const float* __restrict__ right,
-                                                             const float* __restrict__ disp, int B, int H, int W, int tiles_w,
-                                                             int tiles, Prm p, double* __restrict__ slab) {
+                                                             const float* __restrict__ disp, const unsigned char* __restrict__ mask, int B,
+                                                             int H, int W, int tiles_w, int tiles, Prm p, double* __restrict__ slab) {
   using S = Stage<1>;
   __shared__ S s;
   __shared__ double sh[NT / 64][kS];
@@ -185,7 +193,8 @@ __global__ __launch_bounds__(NT) void photometric_fwd_kernel(const float* __rest
   const int b = col / tiles, t = col - b * tiles;
   const int h0 = (t / tiles_w) * TH, w0 = (t % tiles_w) * TW;
   const long long HW = (long long)H * W;
-  stage_tile<1>(s, left + 3 * HW * b, right + 3 * HW * b, disp + HW * ((long long)k * B + b), H, W, h0, w0, p);
+  const long long plane = HW * ((long long)k * B + b);
+  stage_tile<1, VIEW, MASKED>(s, left + 3 * HW * b, right + 3 * HW * b, disp + plane, MASKED ? mask + plane : nullptr, H, W, h0, w0, p);
   __syncthreads();
   double acc[kS] = {0.0, 0.0, 0.0, 0.0};
   for (int j = threadIdx.x; j < TH * TW; j += NT) {
@@ -274,10 +283,11 @@ struct Windows {
 };
 
 // grid = (B * tiles, K).  gdisp is written once per element.
+template <int VIEW, bool MASKED>
 __global__ __launch_bounds__(NT) void photometric_bwd_kernel(const float* __restrict__ left, const float* __restrict__ right,
-                                                             const float* __restrict__ disp, int B, int H, int W, int tiles_w, int tiles,
-                                                             Prm p, const double* __restrict__ stats, const float* __restrict__ gloss,
-                                                             float* __restrict__ gdisp) {
+                                                             const float* __restrict__ disp, const unsigned char* __restrict__ mask, int B,
+                                                             int H, int W, int tiles_w, int tiles, Prm p, const double* __restrict__ stats,
+                                                             const float* __restrict__ gloss, float* __restrict__ gdisp) {
   using S = Stage<2>;
   constexpr int PX = TH * TW / NT;  // pixels per thread
   __shared__ S s;
@@ -288,7 +298,7 @@ __global__ __launch_bounds__(NT) void photometric_bwd_kernel(const float* __rest
   const long long HW = (long long)H * W;
   const float* rimg = right + 3 * HW * b;
   const float* dmap = disp + HW * ((long long)k * B + b);
-  stage_tile<2>(s, left + 3 * HW * b, rimg, dmap, H, W, h0, w0, p);
+  stage_tile<2, VIEW, MASKED>(s, left + 3 * HW * b, rimg, dmap, MASKED ? mask + HW * ((long long)k * B + b) : nullptr, H, W, h0, w0, p);
   __syncthreads();
 
   // this thread's windows (centred on the tile and one pixel around it): which of them exist and are valid
@@ -318,7 +328,7 @@ __global__ __launch_bounds__(NT) void photometric_bwd_kernel(const float* __rest
     slope[n][0] = slope[n][1] = slope[n][2] = 0.f;
     if (valid[n]) {
       float rh[3];
-      warp_pixel(rimg + h * W, (int)HW, W, w, dmap[h * W + w], p, rh, slope[n]);
+      warp_pixel<VIEW>(rimg + h * W, (int)HW, W, w, dmap[h * W + w], p, rh, slope[n]);
     }
   }
 
@@ -425,6 +435,23 @@ int check_common(const char* who, const float* left, const float* right, const f
   return MODE_OK;
 }
 
+// The forward's two launches and the backward's one, for one (view, masked) form of the kernels.
+template <int VIEW, bool MASKED>
+void launch_fwd(const float* left, const float* right, const float* disp, const unsigned char* mask, int K, int B, int H, int W, int tiles_w,
+                int tiles, const Prm& p, double* slab, double* stats, float* loss, hipStream_t st) {
+  const int ncols = B * tiles;
+  hipLaunchKernelGGL((photometric_fwd_kernel<VIEW, MASKED>), dim3(ncols, K), dim3(NT), 0, st, left, right, disp, mask, B, H, W, tiles_w, tiles,
+                     p, slab);
+  hipLaunchKernelGGL(photometric_final_kernel, dim3(1), dim3(NT), 0, st, slab, ncols, K, B, H, W, p, stats, loss);
+}
+
+template <int VIEW, bool MASKED>
+void launch_bwd(const float* left, const float* right, const float* disp, const unsigned char* mask, int K, int B, int H, int W, int tiles_w,
+                int tiles, const Prm& p, const double* stats, const float* gloss, float* gdisp, hipStream_t st) {
+  hipLaunchKernelGGL((photometric_bwd_kernel<VIEW, MASKED>), dim3(B * tiles, K), dim3(NT), 0, st, left, right, disp, mask, B, H, W, tiles_w,
+                     tiles, p, stats, gloss, gdisp);
+}
+
 }  // namespace
 
 extern "C" size_t mode_photometric_loss_workspace_bytes(int K, int B, int H, int W) {
@@ -447,9 +474,7 @@ extern "C" int mode_photometric_loss_fwd(const float* left, const float* right, 
                "%s: workspace of %zu B is too small (needs %zu B)", who, workspace_bytes, mode_photometric_loss_workspace_bytes(K, B, H, W));
   double* slab = static_cast<double*>(workspace);
   hipStream_t st = mode::as_stream(stream);
-  const int ncols = B * tiles;
-  hipLaunchKernelGGL(photometric_fwd_kernel, dim3(ncols, K), dim3(NT), 0, st, left, right, disp, B, H, W, tiles_w, tiles, p, slab);
-  hipLaunchKernelGGL(photometric_final_kernel, dim3(1), dim3(NT), 0, st, slab, ncols, K, B, H, W, p, stats, loss);
+  launch_fwd<0, false>(left, right, disp, nullptr, K, B, H, W, tiles_w, tiles, p, slab, stats, loss, st);
   return mode::check_launch(who);
 }
 
@@ -462,7 +487,49 @@ extern "C" int mode_photometric_loss_bwd(const float* left, const float* right, 
   int rc = check_common(who, left, right, disp, K, B, H, W, params, p, tiles_w, tiles);
   if (rc != MODE_OK) return rc;
   MODE_REQUIRE(stats && gloss && gdisp, MODE_ERR_BAD_ARG, "%s: null pointer", who);
-  hipLaunchKernelGGL(photometric_bwd_kernel, dim3(B * tiles, K), dim3(NT), 0, mode::as_stream(stream), left, right, disp, B, H, W, tiles_w,
-                     tiles, p, stats, gloss, gdisp);
+  launch_bwd<0, false>(left, right, disp, nullptr, K, B, H, W, tiles_w, tiles, p, stats, gloss, gdisp, mode::as_stream(stream));
+  return mode::check_launch(who);
+}
+
+// ---------------------------------------------------------------------------------------------- either view, with a mask
+// include/mode_hip_selfsup.h.  The same kernels with the view and the mask as template parameters; view 0 without a mask launches the
+// instantiation of the entries above.
+extern "C" int mode_selfsup_view_loss_fwd(const float* own_image, const float* other_image, const float* disp, const unsigned char* mask,
+                                          int view, int K, int B, int H, int W, const mode_photometric_params* params, void* workspace,
+                                          size_t workspace_bytes, double* stats, float* loss, mode_stream_t stream) {
+  const char* who = "mode_selfsup_view_loss_fwd";
+  Prm p;
+  int tiles_w, tiles;
+  int rc = check_common(who, own_image, other_image, disp, K, B, H, W, params, p, tiles_w, tiles);
+  if (rc != MODE_OK) return rc;
+  MODE_REQUIRE(view == 0 || view == 1, MODE_ERR_BAD_ARG, "%s: view = %d (0: left, 1: right)", who, view);
+  MODE_REQUIRE(stats && loss, MODE_ERR_BAD_ARG, "%s: null pointer", who);
+  MODE_REQUIRE(workspace && ((size_t)workspace & 7) == 0, MODE_ERR_WORKSPACE, "%s: workspace missing or not 8-byte aligned", who);
+  MODE_REQUIRE(workspace_bytes >= mode_photometric_loss_workspace_bytes(K, B, H, W), MODE_ERR_WORKSPACE,
+               "%s: workspace of %zu B is too small (needs %zu B)", who, workspace_bytes, mode_photometric_loss_workspace_bytes(K, B, H, W));
+  double* slab = static_cast<double*>(workspace);
+  hipStream_t st = mode::as_stream(stream);
+  if (view == 0 && !mask) launch_fwd<0, false>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, slab, stats, loss, st);
+  if (view == 0 && mask) launch_fwd<0, true>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, slab, stats, loss, st);
+  if (view == 1 && !mask) launch_fwd<1, false>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, slab, stats, loss, st);
+  if (view == 1 && mask) launch_fwd<1, true>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, slab, stats, loss, st);
+  return mode::check_launch(who);
+}
+
+extern "C" int mode_selfsup_view_loss_bwd(const float* own_image, const float* other_image, const float* disp, const unsigned char* mask,
+                                          int view, int K, int B, int H, int W, const mode_photometric_params* params, const double* stats,
+                                          const float* gloss, float* gdisp, mode_stream_t stream) {
+  const char* who = "mode_selfsup_view_loss_bwd";
+  Prm p;
+  int tiles_w, tiles;
+  int rc = check_common(who, own_image, other_image, disp, K, B, H, W, params, p, tiles_w, tiles);
+  if (rc != MODE_OK) return rc;
+  MODE_REQUIRE(view == 0 || view == 1, MODE_ERR_BAD_ARG, "%s: view = %d (0: left, 1: right)", who, view);
+  MODE_REQUIRE(stats && gloss && gdisp, MODE_ERR_BAD_ARG, "%s: null pointer", who);
+  hipStream_t st = mode::as_stream(stream);
+  if (view == 0 && !mask) launch_bwd<0, false>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, stats, gloss, gdisp, st);
+  if (view == 0 && mask) launch_bwd<0, true>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, stats, gloss, gdisp, st);
+  if (view == 1 && !mask) launch_bwd<1, false>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, stats, gloss, gdisp, st);
+  if (view == 1 && mask) launch_bwd<1, true>(own_image, other_image, disp, mask, K, B, H, W, tiles_w, tiles, p, stats, gloss, gdisp, st);
   return mode::check_launch(who);
 }

@@ -23,6 +23,12 @@ LAUNCHING = frozenset(n for n, (_, params) in PROTOTYPES.items() if any(t == _he
 CONSTANTS = HEADER.constants  # every MODE_* integer of the header, under the header's name
 
 ABI_VERSION = CONSTANTS['MODE_HIP_ABI_VERSION']
+
+# include/mode_hip_selfsup.h, the second public header, read the same way.  The first header is frozen (its tests pin what it holds);
+# entries added since are declared in the second and bound onto the same handle.  HEADER, SIGNATURES, ... above stay the first header's.
+SELFSUP = _header.load(os.path.join(os.path.dirname(_header.PATH), 'mode_hip_selfsup.h'))
+SELFSUP_LAUNCHING = frozenset(n for n, (_, params) in SELFSUP.prototypes.items() if any(t == _header.STREAM for t, _ in params))
+SELFSUP_VERSION = SELFSUP.constants['MODE_SELFSUP_VERSION']
 _lib = None
 _lock = threading.Lock()
 
@@ -45,6 +51,14 @@ def lib():
         if have != ABI_VERSION:
           raise RuntimeError('libmode_hip.so has ABI version %d, this binding needs %d: rebuild it (python '
                              'mode-2022_amd/mode_hip/build.py)' % (have, ABI_VERSION))
+        have = handle.mode_selfsup_version() if hasattr(handle, 'mode_selfsup_version') else None
+        if have != SELFSUP_VERSION:
+          raise RuntimeError('libmode_hip.so has version %s of the entries of mode_hip_selfsup.h, this binding needs %d: rebuild it '
+                             '(python mode-2022_amd/mode_hip/build.py)' % (have, SELFSUP_VERSION))
+        for name, (res, args) in SELFSUP.signatures.items():
+          fn = getattr(handle, name)
+          fn.restype = res
+          fn.argtypes = args
         _lib = handle
   return _lib
 
@@ -62,6 +76,11 @@ PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS = CONSTANTS['MODE_PHOTOMETRIC_MAX_MAPS']
 (PH_N_VALID, PH_SUM_PE, PH_SUM_SMOOTH_X, PH_SUM_SMOOTH_Y) = (CONSTANTS['MODE_PHOTOMETRIC_' + k] for k in 'N_VALID SUM_PE SUM_SMOOTH_X SUM_SMOOTH_Y'.split())
 PhotometricParams = _header.structure(HEADER, 'mode_photometric_params', 'PhotometricParams',
                                       'struct mode_photometric_params (host memory, read during the call).')
+
+# left-right consistency: the statistics of one view and map as mode_lr_consistency_fwd leaves them
+LR_STATS = SELFSUP.constants['MODE_LR_STATS']
+(LR_N_VALID, LR_SUM_E, LR_N_VISIBLE) = (SELFSUP.constants['MODE_LR_' + k] for k in 'N_VALID SUM_E N_VISIBLE'.split())
+LrParams = _header.structure(SELFSUP, 'mode_lr_params', 'LrParams', 'struct mode_lr_params (host memory, read during the call).')
 
 
 def check(rc, what):

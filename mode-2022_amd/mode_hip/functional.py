@@ -6,8 +6,8 @@ import threading
 
 import torch
 
-from . import (CONSTANTS, METRICS_COUNT, METRICS_MAX_THRESHOLDS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS, BnEpilogue, MetricsParams, PhotometricParams, check, lib,
-               profiling, ptr, require_f32c, require_gpu, stream_of)
+from . import (CONSTANTS, LR_STATS, METRICS_COUNT, METRICS_MAX_THRESHOLDS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS, BnEpilogue, LrParams, MetricsParams,
+               PhotometricParams, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of)
 
 
 def _call(entry, *args):
@@ -2065,15 +2065,67 @@ class PhotometricLossFunction(torch.autograd.Function):
     return (None, None, None) + tuple(gdisp[k].view(shape) for k, shape in enumerate(ctx.shapes))
 
 
-def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False):
+def _stack_maps(disps, B, H, W, like):
+  """K maps (B, 1, H, W) or (B, H, W) -> one (K, B, H, W) tensor, the layout of the entries."""
+  disp = torch.empty((len(disps), B, H, W), dtype=like.dtype, device=like.device)
+  for k, d in enumerate(disps):
+    disp[k].copy_(d.reshape(B, H, W))
+  return disp
+
+
+class ViewLossFunction(torch.autograd.Function):
+  """PhotometricLossFunction from either camera and with an optional mask (mode_selfsup_view_loss_fwd / _bwd):
+  (own, other, mask or None, view 0 / 1, prm, disp_0 .. disp_{K-1}) -> (loss 0-d, stats (K, PHOTOMETRIC_STATS) float64)."""
+
+  @staticmethod
+  def forward(ctx, own, other, mask, view, prm, *disps):
+    K = len(disps)
+    B, _, H, W = own.shape
+    disp = _stack_maps(disps, B, H, W, own)
+    require_f32c(own, other, disp)
+    stats = torch.empty((K, PHOTOMETRIC_STATS), dtype=torch.float64, device=own.device)
+    loss = torch.empty(1, dtype=torch.float32, device=own.device)
+    nbytes = 4 * K * (own.numel() + other.numel() + disp[0].numel()) + (0 if mask is None else mask.numel())
+    with torch.cuda.device_of(own), profiling.region('selfsup_view_loss_fwd', nbytes, 0, own.device):
+      ws = torch.empty(max(lib().mode_photometric_loss_workspace_bytes(K, B, H, W) // 8, 1), dtype=torch.float64, device=own.device)
+      _call('mode_selfsup_view_loss_fwd', ptr(own), ptr(other), ptr(disp), None if mask is None else ptr(mask), view, K, B, H, W,
+            ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(stats), ptr(loss), stream_of(own))
+    ctx.save_for_backward(own, other, disp, stats, *(() if mask is None else (mask,)))
+    ctx.prm, ctx.view, ctx.shapes = prm, view, [d.shape for d in disps]
+    ctx.mark_non_differentiable(stats)
+    return loss.reshape(()), stats
+
+  @staticmethod
+  def backward(ctx, gloss, _gstats):
+    own, other, disp, stats = ctx.saved_tensors[:4]
+    mask = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+    K, B, H, W = disp.shape
+    gl = gloss.reshape(1).to(torch.float32).contiguous()
+    gdisp = torch.empty_like(disp)
+    nbytes = 4 * K * (own.numel() + other.numel() + 2 * disp[0].numel()) + (0 if mask is None else mask.numel())
+    with torch.cuda.device_of(own), profiling.region('selfsup_view_loss_bwd', nbytes, 0, own.device):
+      _call('mode_selfsup_view_loss_bwd', ptr(own), ptr(other), ptr(disp), None if mask is None else ptr(mask), ctx.view, K, B, H, W,
+            ctypes.byref(ctx.prm), ptr(stats), ptr(gl), ptr(gdisp), stream_of(own))
+    return (None, None, None, None, None) + tuple(gdisp[k].view(shape) for k, shape in enumerate(ctx.shapes))
+
+
+def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False, view='left',
+                     masks=None):
   """The self-supervised loss of a rectified Cassini stereo pair (include/mode_hip.h has the definition): the right image
   warped to the left view by each disparity map, SSIM + L1 over 3x3 windows whose rows wrap along H, plus lam x an edge-aware smoothness
   term, summed over the maps with `weights`.  left, right (B, 3, H, W) as the model takes them (normalised with mean / std, default
   dataloader.preprocess.imagenet_stats); disps: 1 .. 4 tensors (B, 1, H, W) or (B, H, W), e.g. the three training outputs.  Returns a
   0-d device tensor with autograd into every map (not into the images); with return_stats also a (K, 3) float64 device tensor
-  [N_valid, photo, smooth] per map.  No host synchronisation; the counts stay on the device."""
+  [N_valid, photo, smooth] per map.  No host synchronisation; the counts stay on the device.
+
+  view, masks: with view='right' the first image is the RIGHT camera's (it supplies L and the smoothness edges), the second the
+  left camera's, the maps are right-view disparities and the warp is x = w + d.  masks: a (K, B, H, W) uint8 or bool device tensor, e.g.
+  lr_consistency's masks[0] (left) or masks[1] (right): a pixel whose byte is zero is invalid; the mask carries no gradient.  The defaults
+  take the entries of DESIGN 22; either option goes through mode_selfsup_view_loss_fwd / _bwd."""
   disps = list(disps)
-  require_gpu(left, right, *disps)
+  if view not in ('left', 'right'):
+    raise ValueError("photometric_loss: view must be 'left' or 'right', not %r" % (view,))
+  require_gpu(left, right, masks, *disps)
   K = len(disps)
   if not 1 <= K <= PHOTOMETRIC_MAX_MAPS:
     raise ValueError('photometric_loss: %d disparity maps (1 .. %d)' % (K, PHOTOMETRIC_MAX_MAPS))
@@ -2084,13 +2136,102 @@ def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0,
     if tuple(d.shape) not in ((B, 1, H, W), (B, H, W)):
       raise ValueError('photometric_loss: a disparity map of shape %s for images %s' % (tuple(d.shape), tuple(left.shape)))
   prm = _photometric_params(K, weights, alpha, lam, beta, mean, std)
-  loss, stats = PhotometricLossFunction.apply(left.contiguous(), right.contiguous(), prm, *disps)
+  if view == 'left' and masks is None:
+    loss, stats = PhotometricLossFunction.apply(left.contiguous(), right.contiguous(), prm, *disps)
+  else:
+    if masks is not None:
+      if tuple(masks.shape) != (K, B, H, W) or masks.dtype not in (torch.uint8, torch.bool):
+        raise ValueError('photometric_loss: masks must be a (K, B, H, W) = %s uint8 or bool tensor, got %s %s' % (
+            (K, B, H, W), tuple(masks.shape), masks.dtype))
+      masks = masks.detach().contiguous()
+      masks = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+    loss, stats = ViewLossFunction.apply(left.contiguous(), right.contiguous(), masks, 0 if view == 'left' else 1, prm, *disps)
   if not return_stats:
     return loss
   n = stats[:, 0]
   photo = stats[:, 1] / n.clamp(min=1)
   smooth = stats[:, 2] / (B * H * (W - 1)) + stats[:, 3] / (B * H * W)
   return loss, torch.stack([n, photo, smooth], 1)
+
+
+# ------------------------------------------------------------------------------------ left-right consistency
+# The remedy for occlusion in a photometric loss: both views' disparities, their disagreement as a loss, and the pixels where they
+# disagree kept out of the photometric term.  Composed from torch operators the gradient into the sampled map is a scatter with atomics;
+# csrc/lr_consistency.hip gathers it over a bounded window, bit-repeatable: two launches forward, one backward, for both views and K maps.
+class LrConsistencyFunction(torch.autograd.Function):
+  """(prm, want_masks, K, dl_0 .. dl_{K-1}, dr_0 .. dr_{K-1}) -> (loss 0-d, stats (2, K, LR_STATS) float64, masks (2, K, B, H, W) uint8 or
+  an empty tensor).  Gradients into every map of both lists; the statistics and the masks carry none."""
+
+  @staticmethod
+  def forward(ctx, prm, want_masks, K, *maps):
+    first = maps[0]
+    B, H, W = first.shape[0], first.shape[-2], first.shape[-1]
+    dl, dr = _stack_maps(maps[:K], B, H, W, first), _stack_maps(maps[K:], B, H, W, first)
+    require_f32c(dl, dr)
+    dev = first.device
+    stats = torch.empty((2, K, LR_STATS), dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    masks = torch.empty((2, K, B, H, W) if want_masks else (0,), dtype=torch.uint8, device=dev)
+    nbytes = 8 * dl.numel() + masks.numel()
+    with torch.cuda.device_of(first), profiling.region('lr_consistency_fwd', nbytes, 0, dev):
+      ws = torch.empty(max(lib().mode_lr_consistency_workspace_bytes(K, B, H, W) // 8, 1), dtype=torch.float64, device=dev)
+      _call('mode_lr_consistency_fwd', ptr(dl), ptr(dr), K, B, H, W, ctypes.byref(prm), ptr(ws), ws.numel() * 8,
+            ptr(masks) if want_masks else None, ptr(stats), ptr(loss), stream_of(first))
+    ctx.save_for_backward(dl, dr, stats)
+    ctx.prm, ctx.shapes = prm, [d.shape for d in maps]
+    ctx.mark_non_differentiable(stats, masks)
+    return loss.reshape(()), stats, masks
+
+  @staticmethod
+  def backward(ctx, gloss, _gstats, _gmasks):
+    dl, dr, stats = ctx.saved_tensors
+    K, B, H, W = dl.shape
+    gl = gloss.reshape(1).to(torch.float32).contiguous()
+    gdl, gdr = torch.empty_like(dl), torch.empty_like(dr)
+    with torch.cuda.device_of(dl), profiling.region('lr_consistency_bwd', 16 * dl.numel(), 0, dl.device):
+      _call('mode_lr_consistency_bwd', ptr(dl), ptr(dr), K, B, H, W, ctypes.byref(ctx.prm), ptr(stats), ptr(gl), ptr(gdl), ptr(gdr),
+            stream_of(dl))
+    grads = [gdl[k] for k in range(K)] + [gdr[k] for k in range(K)]
+    return (None, None, None) + tuple(g.view(shape) for g, shape in zip(grads, ctx.shapes))
+
+
+def lr_consistency(disps_l, disps_r, weights, tau=1.0, dmax=None, return_masks=False, return_stats=False):
+  """Left-right consistency of a Cassini pair's disparity maps (include/mode_hip_selfsup.h has the definition).  disps_l,
+  disps_r: K = 1 .. 4 tensors each, (B, 1, H, W) or (B, H, W): left pixel (h, w) matches right pixel (h, w - dl), right pixel (h, w)
+  matches left pixel (h, w + dr).  Per view and map the mean over the valid pixels of |own - other(x)|, x = w -/+ own (valid: own finite
+  and in [0, dmax], x inside the row, both samples finite), summed over views and maps with `weights`.  dmax (required, e.g. the
+  model's maxdisp) bounds the disparities that take part, and with them the window the backward gathers over.  Returns a 0-d device
+  tensor with autograd into every map of both lists; with return_masks also the visibility masks (2, K, B, H, W) uint8 (left, right;
+  1 = valid and |own - other(x)| <= tau; no gradient), which HF.photometric_loss(..., masks=masks[v]) takes; with return_stats also a
+  (2, K, 3) float64 device tensor [N_valid, lr, N_visible].  Order of the extras: masks, stats.  No host synchronisation."""
+  disps_l, disps_r = list(disps_l), list(disps_r)
+  require_gpu(*(disps_l + disps_r))
+  K = len(disps_l)
+  if not 1 <= K <= PHOTOMETRIC_MAX_MAPS or len(disps_r) != K:
+    raise ValueError('lr_consistency: %d left and %d right disparity maps (1 .. %d of each, as many left as right)' % (
+        K, len(disps_r), PHOTOMETRIC_MAX_MAPS))
+  if len(weights) != K:
+    raise ValueError('lr_consistency: %d disparity maps per view but %d weights' % (K, len(weights)))
+  if dmax is None:
+    raise ValueError('lr_consistency: dmax is required (the largest disparity that takes part, e.g. the maxdisp of the model)')
+  first = disps_l[0]
+  if first.dim() not in (3, 4) or (first.dim() == 4 and first.shape[1] != 1):
+    raise ValueError('lr_consistency: a disparity map is (B, 1, H, W) or (B, H, W), got %s' % (tuple(first.shape),))
+  B, H, W = first.shape[0], first.shape[-2], first.shape[-1]
+  for d in disps_l + disps_r:
+    if tuple(d.shape) not in ((B, 1, H, W), (B, H, W)):
+      raise ValueError('lr_consistency: a disparity map of shape %s among maps of %s' % (tuple(d.shape), (B, H, W)))
+  prm = LrParams()
+  prm.tau, prm.dmax = float(tau), float(dmax)
+  for k in range(K):
+    prm.weights[k] = float(weights[k])
+  loss, stats, masks = LrConsistencyFunction.apply(prm, bool(return_masks), K, *(disps_l + disps_r))
+  out = (loss,)
+  if return_masks:
+    out += (masks,)
+  if return_stats:
+    out += (torch.stack([stats[..., 0], stats[..., 1] / stats[..., 0].clamp(min=1), stats[..., 2]], -1),)
+  return out[0] if len(out) == 1 else out
 
 
 # ------------------------------------------------------------------------------------ scoring in the ERP domain

@@ -164,6 +164,45 @@ class ModeDisparity(nn.Module):
     loss = HF.photometric_loss(left, right, preds, weights, **loss_kw)
     return loss, tuple(p.detach() for p in preds)
 
+  def forward_selfsup_loss(self, left, right, weights=(0.5, 0.7, 1.0), lr_weight=1.0, tau=1.0, occlusion=True, **loss_kw):
+    """The training iteration without ground truth with its remedy for occlusion: both cameras' disparities, a photometric
+    loss in each view, the left-right consistency of the two sets of maps, and -- occlusion=True -- the pixels where the views disagree
+    by more than tau kept out of the photometric terms.  An extension (the reference has no self-supervised entry).
+
+    The left-view maps are the three training outputs for (left, right).  The right-view maps come from a second pass over the pair
+    mirrored along W: dr = flip_W(net(flip_W(right), flip_W(left))).  Mirroring along W is the reflection through the plane normal to
+    the baseline: it exchanges the cameras' roles and keeps the disparity convention (with w' = W - 1 - w the mirrored match
+    w' - d' is W - 1 - (w + dr), so right pixel (h, w) matches left pixel (h, w + dr)).  The two passes move BatchNorm's running
+    statistics twice per step.
+
+    loss = view loss left + view loss right + lr_weight x consistency, all three weighted over the heads with `weights`; the masks
+    are those of HF.lr_consistency on the maps of this same step (they carry no gradient), dmax = self.maxdisp.  Returns
+    (loss, (left predictions), (right predictions)), the predictions detached.  loss_kw: alpha, lam, beta, mean, std of
+    HF.photometric_loss.  Cassini only, as forward_photometric_loss."""
+    if not self.training:
+      raise RuntimeError('forward_selfsup_loss() is a training step; call the module itself for inference')
+    if self.sphereType != 'Cassini':
+      raise ValueError("forward_selfsup_loss: sphereType must be 'Cassini', not %r: the loss takes rows modulo H, Cassini's "
+                       'periodic axis' % (self.sphereType,))
+    for k in ('return_stats', 'view', 'masks'):
+      if k in loss_kw:
+        raise ValueError('forward_selfsup_loss sets %s itself; call HF.photometric_loss / HF.lr_consistency for the pieces' % k)
+    size = (self.maxdisp, left.size(2), left.size(3))
+    preds_l = tuple(stage3d.head(c, size) for c in self._logits(left, right))
+    mirrored = self._logits(right.flip(3).contiguous(), left.flip(3).contiguous())
+    preds_r = tuple(stage3d.head(c, size).flip(3) for c in mirrored)
+    masks_l = masks_r = None
+    if occlusion:
+      lr, masks = HF.lr_consistency(preds_l, preds_r, weights, tau=tau, dmax=self.maxdisp, return_masks=True)
+      masks_l, masks_r = masks[0], masks[1]
+    elif lr_weight != 0:
+      lr = HF.lr_consistency(preds_l, preds_r, weights, tau=tau, dmax=self.maxdisp)
+    loss = (HF.photometric_loss(left, right, preds_l, weights, view='left', masks=masks_l, **loss_kw) +
+            HF.photometric_loss(right, left, preds_r, weights, view='right', masks=masks_r, **loss_kw))
+    if lr_weight != 0:
+      loss = loss + lr_weight * lr
+    return loss, tuple(p.detach() for p in preds_l), tuple(p.detach() for p in preds_r)
+
   def _logits(self, left, right):
     """Everything up to the three classifier outputs cost1, cost2, cost3 (B, 1, D/4, H/4, W/4) (mode_disparity.py:98-129)."""
     if left.is_cuda:

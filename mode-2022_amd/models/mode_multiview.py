@@ -271,3 +271,14 @@ class ModeMultiView(nn.Module):
     left, right, _, _ = self._ingest(frames)
     loss, preds = self.disparity.forward_photometric_loss(left, right, **loss_kw)
     return loss, preds[2]
+
+  def selfsup_loss(self, frames, **kw):
+    """photometric_loss with the remedy for occlusion: frames exactly as photometric_loss takes them ->
+    (loss, disp.detach()), the loss of ModeDisparity.forward_selfsup_loss (both views' photometric terms, their left-right consistency,
+    occlusion masks) over the P F stereo pairs and disp (P F, 1, H, W) the left view's third output.  Needs disparity.train(); the
+    fusion network is not run and its parameters get no gradient.  kw: weights, lr_weight, tau, occlusion, alpha, lam, beta, mean, std."""
+    if not self.disparity.training:
+      raise RuntimeError('ModeMultiView.selfsup_loss trains the disparity stage: call .disparity.train() first')
+    left, right, _, _ = self._ingest(frames)
+    loss, preds, _ = self.disparity.forward_selfsup_loss(left, right, **kw)
+    return loss, preds[2]

@@ -4,12 +4,21 @@ the GPU (A; the only way a user has without HF.photometric_loss: elementwise, ro
 the backward) against HF.photometric_loss (B; csrc/photometric.hip), forward + backward, at 1024 x 512 with K = 3 maps, B = 2 and B = 12.
 
     python tools/photometric_bench.py [--windows 4] [--min-window 0.3] [--out FILE.json]
+    python tools/photometric_bench.py --lr [--out profiles/selfsup_bench_mi355x.json]     (below)
 
 The composition below is written from the definition in include/mode_hip.h.  First the two sides' outputs are compared (loss, and the
 gradient relative to its largest element); then windows alternate A B A B ..., each at least --min-window seconds of device time between
 two events.  Acceptance: every B window faster than every A window.  For B also the algorithmic bytes -- per pixel and map 7 floats read
 (3 left, 3 right, 1 disparity) in each pass and 1 written in the backward, 60 B -- over its device time: an effective rate (the images
-are re-read per map and the halo from cache, so it is not a share of the HBM peak)."""
+are re-read per map and the halo from cache, so it is not a share of the HBM peak).
+
+--lr: the whole bidirectional loss -- left-right consistency of K left and K right maps with dmax = 192, and both views'
+photometric loss gated by the consistency masks -- composed from torch operators (A, written from the definitions in
+include/mode_hip_selfsup.h) against HF.lr_consistency + HF.photometric_loss(view=, masks=) (B).  The maps are integers + 0.5 and
+tau = 0.75: every |own - other(x)| is then a multiple of 0.5 in any precision, no pixel sits near the threshold, and the two sides (and a
+float64 run of the composition) agree on every mask.  Before timing, B's loss and gradients are held to the bound of
+tests/test_gpu_selfsup.py: at most 4 x the yardstick, which is A's own fp32 error against the float64 composition, never below
+2^-23 of the quantity's largest element.  --kernels-only N runs N steps of side B and nothing else (for a kernel trace)."""
 import argparse
 import json
 import math
@@ -24,10 +33,14 @@ for p in (ROOT, os.path.join(ROOT, 'mode-2022_amd')):
 WEIGHTS = (0.5, 0.7, 1.0)
 
 
-def composed_loss(torch, left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, C1=1e-4, C2=9e-4):
+def composed_loss(torch, left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, C1=1e-4, C2=9e-4, s=-1, masks=None):
+  """s, masks: x = w + s d (s = +1: `left` is the right camera's image, the view's own), masks[k] (B, H, W) bool and-ed
+  into the validity of a pixel.  The arithmetic is that of the disparities' dtype."""
   from dataloader.preprocess import imagenet_stats
-  mean = torch.tensor(imagenet_stats['mean'], device=left.device).view(1, 3, 1, 1)
-  std = torch.tensor(imagenet_stats['std'], device=left.device).view(1, 3, 1, 1)
+  dt = disps[0].dtype
+  mean = torch.tensor(imagenet_stats['mean'], device=left.device, dtype=dt).view(1, 3, 1, 1)
+  std = torch.tensor(imagenet_stats['std'], device=left.device, dtype=dt).view(1, 3, 1, 1)
+  left, right = left.to(dt), right.to(dt)
   L, R = left * std + mean, right * std + mean
   B, _, H, W = L.shape
 
@@ -43,12 +56,14 @@ def composed_loss(torch, left, right, disps, weights, alpha=0.85, lam=0.1, beta=
   mx = box(L)
   xs = [m - mx for m in members(L)]
   vx = sum(a * a for a in xs) / 9
-  wcol = torch.arange(W, dtype=torch.float32, device=left.device).view(1, 1, W)
+  wcol = torch.arange(W, dtype=dt, device=left.device).view(1, 1, W)
   loss = 0
-  for d, wgt in zip(disps, weights):
+  for k, (d, wgt) in enumerate(zip(disps, weights)):
     d = d.reshape(B, H, W)
-    x = wcol - d
+    x = wcol + s * d
     valid = torch.isfinite(d) & (x >= 0) & (x <= W - 1)
+    if masks is not None:
+      valid = valid & masks[k]
     xv = torch.where(valid, x, torch.zeros_like(x))
     x0 = xv.detach().floor().clamp(max=W - 2)
     t = (xv - x0).unsqueeze(1)
@@ -67,6 +82,149 @@ def composed_loss(torch, left, right, disps, weights, alpha=0.85, lam=0.1, beta=
     smooth = ((dn[..., 1:] - dn[..., :-1]).abs() * ex).mean() + ((torch.roll(dn, -1, -2) - dn).abs() * ey).mean()
     loss = loss + wgt * (photo + lam * smooth)
   return loss
+
+
+def composed_lr(torch, dls, drs, weights, tau, dmax):
+  """The left-right term of include/mode_hip_selfsup.h -> (loss, masks[view][k] (B, H, W) bool)."""
+  W = dls[0].shape[-1]
+  wcol = torch.arange(W, dtype=dls[0].dtype, device=dls[0].device).view(1, 1, W)
+  loss, masks = 0, ([], [])
+  for dl, dr, wgt in zip(dls, drs, weights):
+    for v, (s, own, other) in enumerate(((-1, dl, dr), (1, dr, dl))):
+      zero = torch.zeros_like(own)
+      x = wcol + s * own
+      valid = torch.isfinite(own) & (own >= 0) & (own <= dmax) & (x >= 0) & (x <= W - 1)
+      own_s, xv = torch.where(valid, own, zero), torch.where(valid, x, zero)
+      x0 = xv.detach().floor().clamp(max=W - 2)
+      t = xv - x0
+      i0 = x0.long()
+      o0, o1 = other.gather(2, i0), other.gather(2, i0 + 1)
+      valid = valid & torch.isfinite(o0) & torch.isfinite(o1)
+      e = torch.where(valid, (own_s - ((1 - t) * torch.where(valid, o0, zero) + t * torch.where(valid, o1, zero))).abs(), zero)
+      loss = loss + wgt * e.sum() / valid.sum().clamp(min=1)
+      masks[v].append(valid & (e.detach() <= tau))
+  return loss, masks
+
+
+def composed_selfsup(torch, left, right, dls, drs, weights, tau, dmax):
+  """Both views' loss with the consistency masks + the consistency term -> (loss, masks)."""
+  lr, masks = composed_lr(torch, dls, drs, weights, tau, dmax)
+  loss = (composed_loss(torch, left, right, dls, weights, s=-1, masks=masks[0]) +
+          composed_loss(torch, right, left, drs, weights, s=1, masks=masks[1]) + lr)
+  return loss, masks
+
+
+def lr_inputs(torch, B, H, W, K, dev, seed):
+  """The images of inputs() and K left and K right maps: integers on a smooth field plus noise, + 0.5 (see the module's text)."""
+  left, right, _ = inputs(torch, B, H, W, K, dev, seed)
+  g = torch.Generator(device=dev).manual_seed(seed + 1)
+  hh = torch.linspace(0, 2 * math.pi, H, device=dev).view(1, H, 1)
+  ww = torch.linspace(0, math.pi, W, device=dev).view(1, 1, W)
+  maps = ([], [])
+  for k in range(K):
+    field = 90 + 80 * torch.sin(hh + k) * torch.sin(ww)  # 10 .. 170: inside dmax = 192
+    for side in maps:
+      side.append((torch.floor(field + 1.5 * torch.rand(B, H, W, generator=g, device=dev)) + 0.5).contiguous())
+  return left, right, maps[0], maps[1]
+
+
+def main_lr(args):
+  import torch
+  from mode_hip import functional as HF
+  assert torch.cuda.is_available(), 'photometric_bench needs a GPU'
+  dev = torch.device('cuda:0')
+  H, W, K, tau, dmax = 1024, 512, 3, 0.75, 192
+  out = {'tool': 'photometric_bench --lr', 'H': H, 'W': W, 'K': K, 'tau': tau, 'dmax': dmax, 'min_window_s': args.min_window,
+         'windows': args.windows, 'batch': {}}
+  ok = True
+  for B in args.batches:
+    left, right, dls, drs = lr_inputs(torch, B, H, W, K, dev, 100 + B)
+
+    def step(side, dtype=torch.float32):
+      ls = [d.detach().to(dtype).requires_grad_(True) for d in dls]
+      rs = [d.detach().to(dtype).requires_grad_(True) for d in drs]
+      if side == 'A':
+        loss, masks = composed_selfsup(torch, left, right, ls, rs, WEIGHTS, tau, dmax)
+        masks = torch.stack([torch.stack(m) for m in masks])
+      else:
+        lr, masks = HF.lr_consistency(ls, rs, WEIGHTS, tau=tau, dmax=dmax, return_masks=True)
+        loss = (HF.photometric_loss(left, right, ls, WEIGHTS, view='left', masks=masks[0]) +
+                HF.photometric_loss(right, left, rs, WEIGHTS, view='right', masks=masks[1]) + lr)
+      loss.backward()
+      return loss.detach(), [d.grad for d in ls + rs], masks
+
+    if args.kernels_only:
+      for _ in range(args.kernels_only):
+        step('B')
+      torch.cuda.synchronize()
+      continue
+
+    l64, g64, m64 = step('A', torch.float64)
+    la, ga, ma = step('A')
+    lb, gb, mb = step('B')
+    torch.cuda.synchronize()
+    row = {'loss_64': float(l64), 'loss_A': float(la), 'loss_B': float(lb), 'visible_fraction': float(m64.float().mean()),
+           'mask_bytes_differing_A_B_from_64': [int((ma != m64).sum()), int((mb.bool() != m64).sum())]}
+    assert row['mask_bytes_differing_A_B_from_64'] == [0, 0], row
+    floor = 2.0 ** -23
+    yl = max(abs(float(la) - float(l64)) / abs(float(l64)), floor)
+    el = abs(float(lb) - float(l64)) / abs(float(l64))
+    row['loss_error_over_yardstick'] = round(el / yl, 3)
+    ratios = []
+    for a, b, r in zip(ga, gb, g64):
+      scale = float(r.abs().max())
+      yg = max(float((a.double() - r).abs().max()) / scale, floor)
+      ratios.append(round(float((b.double() - r).abs().max()) / scale / yg, 3))
+    row['gradient_error_over_yardstick_dl_then_dr'] = ratios
+    print('B=%d: %s' % (B, json.dumps(row)), flush=True)
+    assert el <= 4 * yl and max(ratios) <= 4, row
+    del l64, g64, m64, la, ga, ma, lb, gb, mb
+    torch.cuda.empty_cache()
+
+    def window(side, n):
+      torch.cuda.synchronize()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(n):
+        step(side)
+      e1.record()
+      torch.cuda.synchronize()
+      return 1e-3 * e0.elapsed_time(e1)
+
+    iters = {}
+    for side in ('A', 'B'):
+      window(side, 3)  # warm-up: allocator, kernels loaded
+      per = window(side, 5) / 5
+      iters[side] = max(5, int(math.ceil(1.2 * args.min_window / per)))
+    times = {'A': [], 'B': []}
+    for w in range(args.windows):
+      for side in ('A', 'B'):
+        sec = window(side, iters[side])
+        while sec < args.min_window:  # the calibration ran slow: a longer window, and this one is not counted
+          iters[side] = int(math.ceil(1.3 * iters[side] * args.min_window / sec))
+          sec = window(side, iters[side])
+        times[side].append(1e6 * sec / iters[side])
+        print('B=%d window %d %s: %.1f us per forward + backward (%d in %.3f s)' % (B, w, side, times[side][-1], iters[side], sec), flush=True)
+    for side in ('A', 'B'):
+      v = sorted(times[side])
+      row['%s_us' % side] = [round(x, 1) for x in times[side]]
+      row['%s_us_median_min_max' % side] = [round(0.5 * (v[(len(v) - 1) // 2] + v[len(v) // 2]), 1), round(v[0], 1), round(v[-1], 1)]
+    row['speedup_median'] = round(row['A_us_median_min_max'][0] / row['B_us_median_min_max'][0], 2)
+    row['every_B_window_faster_than_every_A_window'] = max(times['B']) < min(times['A'])
+    # the backward's gather: per row and view, W targets each walk ceil(dmax) + 3 records
+    row['lr_bwd_lds_record_reads'] = 2 * K * B * H * W * (dmax + 3)
+    ok = ok and row['every_B_window_faster_than_every_A_window']
+    out['batch'][str(B)] = row
+  if args.kernels_only:
+    return 0
+  out['every_B_window_faster_than_every_A_window'] = ok
+  line = json.dumps(out)
+  print(line)
+  if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+      f.write(line + '\n')
+  return 0 if ok else 1
 
 
 def inputs(torch, B, H, W, K, dev, seed):
@@ -98,7 +256,11 @@ def main():
   ap.add_argument('--min-window', type=float, default=0.3, help='seconds of device time per window, at least')
   ap.add_argument('--batches', type=int, nargs='+', default=[2, 12])
   ap.add_argument('--out', help='also write the result line to this file')
+  ap.add_argument('--lr', action='store_true', help='the bidirectional loss of DESIGN 24 instead of the left-view loss of DESIGN 22')
+  ap.add_argument('--kernels-only', type=int, default=0, help='with --lr: N steps of side B and nothing else (for a kernel trace)')
   args = ap.parse_args()
+  if args.lr:
+    return main_lr(args)
 
   import torch
   from mode_hip import functional as HF
