@@ -29,6 +29,12 @@ ABI_VERSION = CONSTANTS['MODE_HIP_ABI_VERSION']
 SELFSUP = _header.load(os.path.join(os.path.dirname(_header.PATH), 'mode_hip_selfsup.h'))
 SELFSUP_LAUNCHING = frozenset(n for n, (_, params) in SELFSUP.prototypes.items() if any(t == _header.STREAM for t, _ in params))
 SELFSUP_VERSION = SELFSUP.constants['MODE_SELFSUP_VERSION']
+
+# include/mode_hip_mvphoto.h, the third public header: the second is frozen by its tests as well (its version and its four
+# launching entries are pinned).  Read and bound exactly as the second; SELFSUP* above stay the second header's.
+MVPHOTO = _header.load(os.path.join(os.path.dirname(_header.PATH), 'mode_hip_mvphoto.h'))
+MVPHOTO_LAUNCHING = frozenset(n for n, (_, params) in MVPHOTO.prototypes.items() if any(t == _header.STREAM for t, _ in params))
+MVPHOTO_VERSION = MVPHOTO.constants['MODE_MVPHOTO_VERSION']
 _lib = None
 _lock = threading.Lock()
 
@@ -59,6 +65,14 @@ def lib():
           fn = getattr(handle, name)
           fn.restype = res
           fn.argtypes = args
+        have = handle.mode_mvphoto_version() if hasattr(handle, 'mode_mvphoto_version') else None
+        if have != MVPHOTO_VERSION:
+          raise RuntimeError('libmode_hip.so has version %s of the entries of mode_hip_mvphoto.h, this binding needs %d: rebuild it '
+                             '(python mode-2022_amd/mode_hip/build.py)' % (have, MVPHOTO_VERSION))
+        for name, (res, args) in MVPHOTO.signatures.items():
+          fn = getattr(handle, name)
+          fn.restype = res
+          fn.argtypes = args
         _lib = handle
   return _lib
 
@@ -81,6 +95,10 @@ PhotometricParams = _header.structure(HEADER, 'mode_photometric_params', 'Photom
 LR_STATS = SELFSUP.constants['MODE_LR_STATS']
 (LR_N_VALID, LR_SUM_E, LR_N_VISIBLE) = (SELFSUP.constants['MODE_LR_' + k] for k in 'N_VALID SUM_E N_VISIBLE'.split())
 LrParams = _header.structure(SELFSUP, 'mode_lr_params', 'LrParams', 'struct mode_lr_params (host memory, read during the call).')
+
+# multi-view reprojection loss: the statistics as mode_mvphoto_loss_fwd leaves them
+MVP_MAX_SOURCES, MVP_STATS, MVP_NO_WINNER = (MVPHOTO.constants['MODE_MVP_' + k] for k in 'MAX_SOURCES STATS NO_WINNER'.split())
+(MVP_N, MVP_SUM_MIN, MVP_SUM_SMOOTH_X, MVP_SUM_SMOOTH_Y, MVP_WINS) = (MVPHOTO.constants['MODE_MVP_' + k] for k in 'N SUM_MIN SUM_SMOOTH_X SUM_SMOOTH_Y WINS'.split())
 
 
 def check(rc, what):

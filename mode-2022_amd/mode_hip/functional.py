@@ -6,8 +6,8 @@ import threading
 
 import torch
 
-from . import (CONSTANTS, LR_STATS, METRICS_COUNT, METRICS_MAX_THRESHOLDS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS, BnEpilogue, LrParams, MetricsParams,
-               PhotometricParams, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of)
+from . import (CONSTANTS, LR_STATS, METRICS_COUNT, METRICS_MAX_THRESHOLDS, MVP_MAX_SOURCES, MVP_STATS, MVP_WINS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS,
+               BnEpilogue, LrParams, MetricsParams, PhotometricParams, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of)
 
 
 def _call(entry, *args):
@@ -2231,6 +2231,85 @@ def lr_consistency(disps_l, disps_r, weights, tau=1.0, dmax=None, return_masks=F
     out += (masks,)
   if return_stats:
     out += (torch.stack([stats[..., 0], stats[..., 1] / stats[..., 0].clamp(min=1), stats[..., 2]], -1),)
+  return out[0] if len(out) == 1 else out
+
+
+# ------------------------------------------------------------------------------------ multi-view reprojection loss
+# The self-supervised loss of the fused depth: every pixel lifted by its depth, projected into S other panoramas of known pose and
+# compared there, the per-window minimum over the views.  Composed from torch operators it is some 70 launches per source and a
+# scatter with atomics in the backward; csrc/mv_photometric.hip runs the source loop inside one kernel per pass, bit-repeatable.
+class MvPhotometricLossFunction(torch.autograd.Function):
+  """(ref, src, depth, poses (S, 12) float64 numpy, prm) -> (loss 0-d, stats (MVP_STATS,) float64, win (F, H, W) uint8).  Gradient
+  into depth only (the images are data); the statistics and the winners carry none."""
+
+  @staticmethod
+  def forward(ctx, ref, src, depth, poses, prm):
+    F, S, _, H, W = src.shape
+    d = depth.reshape(F, H, W).contiguous()
+    require_f32c(ref, src, d)
+    dev = ref.device
+    stats = torch.empty(MVP_STATS, dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    win = torch.empty((F, H, W), dtype=torch.uint8, device=dev)
+    pp = poses.ctypes.data_as(ctypes.c_void_p)
+    nbytes = 4 * (ref.numel() + src.numel() + d.numel()) + win.numel()
+    with torch.cuda.device_of(ref), profiling.region('mv_photometric_loss_fwd', nbytes, 0, dev):
+      ws = torch.empty(max(lib().mode_mvphoto_workspace_bytes(S, F, H, W) // 8, 1), dtype=torch.float64, device=dev)
+      _call('mode_mvphoto_loss_fwd', ptr(ref), ptr(src), ptr(d), pp, S, F, H, W, ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(win),
+            ptr(stats), ptr(loss), stream_of(ref))
+    ctx.save_for_backward(ref, src, d, win, stats)
+    ctx.prm, ctx.poses, ctx.shape = prm, poses, depth.shape
+    ctx.mark_non_differentiable(stats, win)
+    return loss.reshape(()), stats, win
+
+  @staticmethod
+  def backward(ctx, gloss, _gstats, _gwin):
+    ref, src, d, win, stats = ctx.saved_tensors
+    F, S, _, H, W = src.shape
+    gl = gloss.reshape(1).to(torch.float32).contiguous()
+    gdepth = torch.empty_like(d)
+    nbytes = 4 * (ref.numel() + src.numel() + 2 * d.numel()) + win.numel()
+    with torch.cuda.device_of(ref), profiling.region('mv_photometric_loss_bwd', nbytes, 0, ref.device):
+      _call('mode_mvphoto_loss_bwd', ptr(ref), ptr(src), ptr(d), ctx.poses.ctypes.data_as(ctypes.c_void_p), S, F, H, W, ctypes.byref(ctx.prm),
+            ptr(win), ptr(stats), ptr(gl), ptr(gdepth), stream_of(ref))
+    return None, None, gdepth.view(ctx.shape), None, None
+
+
+def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False, return_win=False):
+  """The self-supervised loss of a depth map against other panoramas of known pose (include/mode_hip_mvphoto.h has the
+  definition): ref (F, 3, H, W) is the Cassini panorama the depth map belongs to, src (F, S, 3, H, W) are S = 1 .. 8 other panoramas of
+  the same scene, both normalised as the model takes them (mean / std, default dataloader.preprocess.imagenet_stats); depth (F, 1, H, W)
+  or (F, H, W); poses (S, 12) or (S, 3, 4) float64 on the host (numpy, a CPU tensor or nested lists): [A | o] per source, X_s = A X + o
+  (utils.rig.CameraRig.panorama_poses()[sources]).  Every pixel is lifted by its depth, projected into each source and sampled there;
+  SSIM + L1 over 3x3 windows whose rows wrap along H, the minimum over the sources per window, plus lam x an edge-aware smoothness term
+  on log depth.  Returns a 0-d device tensor with autograd into depth (not into the images); with return_stats also a (3 + S,) float64
+  device tensor [N, photo, smooth, wins of source 0 .. S - 1]; with return_win also the (F, H, W) uint8 map of the winning source per
+  window (255: none).  Order of the extras: stats, win.  No host synchronisation."""
+  import numpy as np
+  require_gpu(ref, src, depth)
+  if ref.dim() != 4 or ref.shape[1] != 3:
+    raise ValueError('mv_photometric_loss: ref must be (F, 3, H, W), got %s' % (tuple(ref.shape),))
+  F, _, H, W = ref.shape
+  if src.dim() != 5 or tuple(src.shape[:1] + src.shape[2:]) != (F, 3, H, W):
+    raise ValueError('mv_photometric_loss: src must be (F, S, 3, H, W) = (%d, S, 3, %d, %d), got %s' % (F, H, W, tuple(src.shape)))
+  S = src.shape[1]
+  if not 1 <= S <= MVP_MAX_SOURCES:
+    raise ValueError('mv_photometric_loss: %d source views (1 .. %d)' % (S, MVP_MAX_SOURCES))
+  if tuple(depth.shape) not in ((F, 1, H, W), (F, H, W)):
+    raise ValueError('mv_photometric_loss: a depth map of shape %s for images %s' % (tuple(depth.shape), tuple(ref.shape)))
+  if isinstance(poses, torch.Tensor):
+    poses = poses.detach().cpu().numpy()
+  poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 12))
+  if poses.shape[0] != S:
+    raise ValueError('mv_photometric_loss: %d poses for %d source views' % (poses.shape[0], S))
+  prm = _photometric_params(0, (), alpha, lam, beta, mean, std)
+  loss, stats, win = MvPhotometricLossFunction.apply(ref.contiguous(), src.contiguous(), depth, poses, prm)
+  out = (loss,)
+  if return_stats:
+    smooth = stats[2] / (F * H * (W - 1)) + stats[3] / (F * H * W)
+    out += (torch.cat([torch.stack([stats[0], stats[1] / stats[0].clamp(min=1), smooth]), stats[MVP_WINS:MVP_WINS + S]]),)
+  if return_win:
+    out += (win,)
   return out[0] if len(out) == 1 else out
 
 

@@ -221,20 +221,35 @@ class ModeMultiView(nn.Module):
                          (HF.head_conf), the hand-off with conf_grad=True, and resize=True is taken through the differentiable
                          HF.decimate2 (the halving of the 8-bit RGB needs no backward: the frames are data).
     forward() and evaluate() stay inference only."""
-    if not self.fusion.training:
-      raise RuntimeError('ModeMultiView.fusion_loss is the training step of the fusion network: call .train() first '
-                         '(.disparity.eval() afterwards keeps stage 1 frozen)')
-    joint = self.disparity.training
-    full = joint and self.handoff_grad == 'full'
-    if joint and self.resize and not full:
-      raise ValueError("ModeMultiView(resize=True, handoff_grad='depth').fusion_loss cannot fine-tune the disparity stage: on this path "
-                       "the decimation of the hand-off has no backward; build the module with handoff_grad='full', or call "
-                       '.disparity.eval() to train the fusion network alone')
+    joint, full = self._fusion_training_mode('fusion_loss')
     left, right, rgb, want_rgb = self._ingest(frames)
     require_gpu(gt)
     H, W = left.shape[-2:]
     if tuple(gt.shape) != (left.shape[0] // self.pairs, H, W):
       raise ValueError('ModeMultiView.fusion_loss: gt %s is not (F, H, W) = %s' % (tuple(gt.shape), (left.shape[0] // self.pairs, H, W)))
+    output = self._fusion_training_output(frames, left, right, rgb, want_rgb, joint, full)
+    if self.resize:  # deep360_loader.py:146-155 with training=True
+      gt = gt[:, ::2, ::2]
+    loss = HF.silog_loss(output, gt, gt <= (self.maxdepth if maxdepth is None else maxdepth), lamda)
+    return loss, output.detach()
+
+  def _fusion_training_mode(self, who):
+    """What fusion_loss and fusion_selfsup_loss check before they touch the frames -> (joint, full)."""
+    if not self.fusion.training:
+      raise RuntimeError('ModeMultiView.%s is the training step of the fusion network: call .train() first '
+                         '(.disparity.eval() afterwards keeps stage 1 frozen)' % who)
+    joint = self.disparity.training
+    full = joint and self.handoff_grad == 'full'
+    if joint and self.resize and not full:
+      raise ValueError("ModeMultiView(resize=True, handoff_grad='depth').%s cannot fine-tune the disparity stage: on this path "
+                       "the decimation of the hand-off has no backward; build the module with handoff_grad='full', or call "
+                       '.disparity.eval() to train the fusion network alone' % who)
+    return joint, full
+
+  def _fusion_training_output(self, frames, left, right, rgb, want_rgb, joint, full):
+    """The chain both training entries share, from the ingested frames to the fusion network's output with its autograd graph
+    (stage 1 with or without a gradient as fusion_loss's docstring says, the hand-off, the decimation of resize=True, stage 2)."""
+    H, W = left.shape[-2:]
     if full:
       size = (self.disparity.maxdisp, H, W)
       disp, conf = HF.head_conf(self.disparity._logits(left, right)[2], size)
@@ -252,12 +267,53 @@ class ModeMultiView(nn.Module):
     if self.resize:  # deep360_loader.py:146-155 with training=True
       fusion_input = HF.decimate2(fusion_input)
       rgb = gpu_ingest.rgb_half_gpu(frames.contiguous()) if want_rgb else None
-      gt = gt[:, ::2, ::2]
     if self.fusion_kind == 'ModeFusion':
-      output = self.fusion.feature_extraction(fusion_input, rgb)
-    else:
-      output = self.fusion.feature_extraction(fusion_input)
-    loss = HF.silog_loss(output, gt, gt <= (self.maxdepth if maxdepth is None else maxdepth), lamda)
+      return self.fusion.feature_extraction(fusion_input, rgb)
+    return self.fusion.feature_extraction(fusion_input)
+
+  def fusion_selfsup_loss(self, frames, sources=None, **loss_kw):
+    """fusion_loss without ground truth: frames exactly as fusion_loss takes them -> (loss, depth.detach()).  The chain is
+    fusion_loss's with the SILog term replaced by HF.mv_photometric_loss: the fused depth lives in the common view's Cassini frame, and
+    every other panorama of the frame is a picture of the same scene from a pose the rig knows, so each pixel is lifted by its depth,
+    projected into the source panoramas and compared there (SSIM + L1, the per-window minimum over the sources, smoothness on log depth).
+    The reference image is the frame's own panorama rig.reference_panorama(); sources: panorama indices, default rig.default_sources()
+    (one panorama per camera that stands elsewhere), 1 .. 8 of them; their poses are rig.panorama_poses().  rig=None with
+    dbname='Deep360' means CameraRig.deep360().  disparity.eval() trains the fusion network alone; disparity.train() fine-tunes stage 1
+    through the hand-off, under either handoff_grad.  loss_kw: alpha, lam, beta, mean, std.  The fusion network must be in training mode.
+    Refused: resize=True (the loss compares at the frames' own size) and dbname='other' (that setting keeps the unit square's
+    translations with other baselines, so its camera centres are not one rig; CameraRig.square(0.6 * sqrt(2)) is)."""
+    from utils.rig import CameraRig
+    if self.resize:
+      raise ValueError('ModeMultiView(resize=True).fusion_selfsup_loss: the reprojection loss compares the panoramas at their own size, '
+                       'and the fusion network runs at half size here; build the module with resize=False')
+    rig = self.rig
+    if rig is None:
+      if self.dbname != 'Deep360':
+        raise ValueError("ModeMultiView(dbname=%r).fusion_selfsup_loss: that setting takes the baselines 0.6 sqrt(2) and 1.2 but keeps the "
+                         'unit square\'s translations, so its camera centres are not one rig and the panoramas have no consistent poses; '
+                         'build the module with rig=CameraRig.square(0.6 * sqrt(2))' % (self.dbname,))
+      rig = CameraRig.deep360()
+    for k in loss_kw:
+      if k not in ('alpha', 'lam', 'beta', 'mean', 'std'):
+        raise ValueError('fusion_selfsup_loss returns (loss, depth); %r is not a parameter of the loss (alpha, lam, beta, mean, std); call '
+                         'HF.mv_photometric_loss for the statistics' % (k,))
+    joint, full = self._fusion_training_mode('fusion_selfsup_loss')
+    ref_index = rig.reference_panorama()
+    sources = rig.default_sources() if sources is None else tuple(int(k) for k in sources)
+    if not 1 <= len(sources) <= 8 or any(not 0 <= k < 2 * len(rig.pairs) for k in sources):
+      raise ValueError('ModeMultiView.fusion_selfsup_loss: sources %r must be 1 .. 8 panorama indices in [0, %d)' % (sources, 2 * len(rig.pairs)))
+    poses = rig.panorama_poses()[list(sources)]
+    left, right, rgb, want_rgb = self._ingest(frames)
+    P = self.pairs
+    H, W = left.shape[-2:]
+
+    def panorama(k):  # panorama 2p / 2p + 1 of frame f is left / right[P f + p]
+      return (left, right)[k % 2].reshape(-1, P, 3, H, W)[:, k // 2]
+
+    ref = panorama(ref_index)
+    src = torch.stack([panorama(k) for k in sources], 1)
+    output = self._fusion_training_output(frames, left, right, rgb, want_rgb, joint, full)
+    loss = HF.mv_photometric_loss(ref, src, output, poses, **loss_kw)
     return loss, output.detach()
 
   def photometric_loss(self, frames, **loss_kw):

@@ -16,12 +16,22 @@ _POSE_LEN = {'identity': 0, 'rotate': 3, 'view': 6}
 PAIR_RECORD = np.dtype([('kind', '<i4'), ('table', '<i4'), ('baseline', '<f4')])  # the header's mode_mv_pair
 
 
+def _rotation(pitch, yaw, roll):
+  """R = Rx(roll) Rz(yaw) Ry(pitch) of the PairPose docstring, float64."""
+  cp, sp, cy, sy, cr, sr = math.cos(pitch), math.sin(pitch), math.cos(yaw), math.sin(yaw), math.cos(roll), math.sin(roll)
+  Ry = np.array([[cp, 0, -sp], [0, 1, 0], [sp, 0, cp]])
+  Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]])
+  Rx = np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]])
+  return Rx @ Rz @ Ry
+
+
 class PairPose(object):
   """One stereo pair of a rig: PairPose(name, baseline, kind, pose=()).
 
   baseline  the distance between the pair's two cameras, in the unit the depth comes out in (> 0; kept as float32, which is what the
-            sine rule  depth = baseline sin(pi/2 - phi_r) / sin(phi_r - phi_l)  computes with).
-  kind      how the pair's depth map, which lives in the Cassini frame of the pair's LEFT camera, gets into the common view:
+            sine rule  depth = baseline sin(pi/2 - phi_r) / sin(phi_r - phi_l)  computes with).  `exact` keeps the number as it was
+            given, in double, for CameraRig.panorama_poses alone.
+  kind     how the pair's depth map, which lives in the Cassini frame of the pair's LEFT camera, gets into the common view:
     'identity'  it is there already.  pose = ().
     'rotate'    the left camera stands where the common view's camera stands, turned: the map is resampled as the reference's
                 rotateCassini(map, pitch, yaw, roll) resamples it.  pose = (pitch, yaw, roll), radians.
@@ -43,7 +53,7 @@ class PairPose(object):
   unit; R is as above.  The nearest point wins a target pixel; its confidence travels with it.
   In Deep360, pair 13 is 'rotate' by a pitch of pi/2 and pair 24 is 'view' from (y0, z0, x0) = (0, -1, 0) with a pitch of pi/2."""
 
-  __slots__ = ('name', 'baseline', 'kind', 'pose')
+  __slots__ = ('name', 'baseline', 'kind', 'pose', 'exact')
 
   def __init__(self, name, baseline, kind, pose=()):
     name = str(name)
@@ -52,6 +62,7 @@ class PairPose(object):
     try:
       pose = tuple(float(v) for v in pose)
       b = float(np.float32(baseline))
+      exact = float(baseline)
     except (TypeError, ValueError):
       raise ValueError('PairPose %r: baseline and pose must be numbers, got %r and %r' % (name, baseline, pose))
     if not (math.isfinite(b) and b > 0):
@@ -62,6 +73,10 @@ class PairPose(object):
       raise ValueError('PairPose %r: pose %r is not finite' % (name, pose))
     object.__setattr__(self, 'name', name)
     object.__setattr__(self, 'baseline', b)
+    # The baseline as it was given, before the rounding to float32: what CameraRig.panorama_poses places the right camera with, so
+    # that a camera which belongs to several pairs stands at one place (float32(sqrt 2) is 1.7e-8 short of a unit square's diagonal).
+    # It is no part of equality, hash or repr, which speak of what the hand-off computes with.
+    object.__setattr__(self, 'exact', exact if math.isfinite(exact) and float(np.float32(exact)) == b else b)
     object.__setattr__(self, 'kind', kind)
     object.__setattr__(self, 'pose', pose)
 
@@ -69,7 +84,7 @@ class PairPose(object):
     raise AttributeError('PairPose is immutable')
 
   def __reduce__(self):  # (copy and pickle rebuild through the constructor: the default protocol restores slots with setattr)
-    return (PairPose, (self.name, self.baseline, self.kind, self.pose))
+    return (PairPose, (self.name, self.exact, self.kind, self.pose))
 
   def _key(self):
     return (self.name, self.baseline, self.kind, self.pose)
@@ -160,6 +175,53 @@ class CameraRig(object):
       count[p.kind] += 1
     return rec, count['rotate'], count['view']
 
+  # ------------------------------------------------------------------------------------------------ panorama poses
+  def panorama_poses(self):
+    """(2P, 3, 4) float64 [A | o]: a point X in the common view's axes has the coordinates X_s = A_s X + o_s in the Cassini frame of
+    panorama s.  From the conventions of PairPose: the left image of an 'identity' pair has A = I, o = 0; of a 'rotate' pair A = R^T,
+    o = 0; of a 'view' pair (X2 = R (X1 - t)) A = R^T, o = t.  The right camera of a pair stands at (-b, 0, 0) in the left camera's
+    axes with the same orientation -- the sine rule r = b cos(phi_r) / sin(phi_r - phi_l) is tan(phi_r) = (b + r sin(phi_l)) /
+    (r cos(phi_l)) -- so the right image has the left's A and the left's o + (b, 0, 0).  The camera of panorama s stands at -A^T o."""
+    out = np.zeros((2 * len(self.pairs), 3, 4))
+    for k, p in enumerate(self.pairs):
+      A, o = np.eye(3), np.zeros(3)
+      if p.kind == 'rotate':
+        A = _rotation(*p.pose).T
+      elif p.kind == 'view':
+        y0, z0, x0 = p.pose[:3]
+        A, o = _rotation(*p.pose[3:]).T, np.array([x0, y0, z0])
+      out[2 * k, :, :3] = out[2 * k + 1, :, :3] = A
+      out[2 * k, :, 3] = o
+      out[2 * k + 1, :, 3] = o + np.array([p.exact, 0.0, 0.0])
+    return out
+
+  def camera_centres(self):
+    """(2P, 3) float64: where the camera of every panorama stands, in the common view's axes."""
+    poses = self.panorama_poses()
+    return -np.einsum('sji,sj->si', poses[:, :, :3], poses[:, :, 3])
+
+  def reference_panorama(self):
+    """The first panorama that IS the common view (A = I, o = 0): the image the fused depth map is a depth map of.  ValueError if the
+    rig has none: the common view then has no image."""
+    for s, pose in enumerate(self.panorama_poses()):
+      if np.abs(pose[:, :3] - np.eye(3)).max() <= 1e-12 and np.abs(pose[:, 3]).max() <= 1e-12:
+        return s
+    raise ValueError('CameraRig.reference_panorama: no panorama of %s is taken from the common view (A = I, o = 0; the left image of an '
+                     "'identity' pair is): the common view has no image" % (', '.join(self.names),))
+
+  def default_sources(self):
+    """For every distinct camera centre other than the common view's own, the first panorama taken from it, in index order.  A
+    panorama at the common view's centre sees every point along the ray of the pixel it is compared with, whatever the depth: it
+    carries no depth signal and is never a default source."""
+    centres = self.camera_centres()
+    scale = max(1.0, float(np.abs(centres).max()))
+    seen, out = [np.zeros(3)], []
+    for s, c in enumerate(centres):
+      if all(np.abs(c - q).max() > 1e-9 * scale for q in seen):
+        seen.append(c)
+        out.append(s)
+    return tuple(out)
+
   @property
   def deep360_layout(self):
     """Whether a frame has Deep360's layout: six pairs, the fusion RGB at panoramas 0, 1, 10, 11."""
@@ -172,7 +234,9 @@ class CameraRig(object):
     """The rig of Deep360: four cameras on a unit square, pairs 12, 13, 14, 23, 24, 34 in camera 1's frame, from the tables of
     utils.geometry (_baselines('Deep360'), _ROT_PITCH, _VIEW_POSES); the fusion RGB is both images of pair 12 and of pair 34."""
     from . import geometry  # (geometry loads torch and the native package's Python side; the classes above need neither)
-    return cls._square(geometry._baselines('Deep360'), 1.0, 'Deep360')
+    baselines = np.array([1.0, 1.0, math.sqrt(2), math.sqrt(2), 1.0, 1.0])  # PairPose rounds them to float32 and keeps them as given
+    assert np.array_equal(baselines.astype(np.float32), geometry._baselines('Deep360'))
+    return cls._square(baselines, 1.0, 'Deep360')
 
   @classmethod
   def square(cls, side, name=None):
@@ -185,7 +249,7 @@ class CameraRig(object):
       raise ValueError('CameraRig.square: side must be finite and > 0, got %r' % (side,))
     # the unit square's side and diagonal per pair, in double: what utils.geometry._baselines('Deep360') rounds to float32
     unit = np.array([1.0, 1.0, math.sqrt(2), math.sqrt(2), 1.0, 1.0])
-    return cls._square((side * unit).astype(np.float32), side, name if name is not None else 'square(%r)' % side)
+    return cls._square(side * unit, side, name if name is not None else 'square(%r)' % side)
 
   @classmethod
   def _square(cls, baselines, side, name):

@@ -1,0 +1,243 @@
+#!/usr/bin/env python3
+"""A/B of the multi-view reprojection loss on one MI355X, in one process: the loss composed from torch operators on the GPU
+(A; written from the definition in include/mode_hip_mvphoto.h: the geometry in float64, everything after in fp32, gathers and autograd's
+scatter in the backward) against HF.mv_photometric_loss (B; csrc/mv_photometric.hip), forward + backward, at 1024 x 512 with S = 3
+sources (Deep360's panoramas 1, 3, 5), F = 1 and F = 2.
+
+    python tools/mvphoto_bench.py [--windows 4] [--min-window 0.3] [--out profiles/mvphoto_bench_mi355x.json]
+
+First the two sides' outputs are compared, by the bound of tests/test_gpu_mvphoto.py: the composition is also run in float64, the
+yardstick of the loss and of the gradient is A's own fp32 error against that run (never below 2^-23 of the largest element), and B may
+take 4 times it.  Both sides are fp32 after the geometry, so a window whose two best sources are within rounding of each other may go
+to another source than in float64; such windows are counted (at most 1e-4 of all, on either side) and the gradient is compared on the
+pixels that no such window touches.  Likewise |L - Ih| has a kink at 0: where it is below 1e-6 in float64 at the centre of a window,
+fp32 may take either sign; and so has |log D(a) - log D(b)| of the smoothness term: two neighbours whose fp32 depths are one ulp
+apart may have the same fp32 logarithm (at 1024 x 512 about one pair per run has).  The pixels of either kind are counted and left out
+as well.  Then windows alternate A B A B ..., each at least --min-window seconds of device time between two events.
+Acceptance: every B window faster than every A window.  For B also the algorithmic bytes -- per pixel 4 + 3 S floats read in each pass
+(3 reference, 1 depth, 3 per source), a winner byte written then read, 1 float written in the backward -- over its device time: an
+effective rate, not a share of the HBM peak (each source word is gathered up to four times, from cache)."""
+import argparse
+import json
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'mode-2022_amd')):
+  if p not in sys.path:
+    sys.path.insert(0, p)
+
+
+def composed_loss(torch, ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, C1=1e-4, C2=9e-4):
+  """-> (loss, win (F, H, W - 2) long, 255 = no winner, l1 (F, H, W - 2): min_c |L_c - Ih_c| at the centre of every window for its
+  winning source, inf where there is none).  poses: (S, 3, 4) float64 tensor on the device.  The arithmetic after the geometry is that
+  of the depth's dtype."""
+  from dataloader.preprocess import imagenet_stats
+  dev, dt = ref.device, depth.dtype
+  ref, src = ref.to(dt), src.to(dt)
+  mean = torch.tensor(imagenet_stats['mean'], device=dev, dtype=dt).view(1, 3, 1, 1)
+  std = torch.tensor(imagenet_stats['std'], device=dev, dtype=dt).view(1, 3, 1, 1)
+  F, S, _, H, W = src.shape
+  L = ref * std + mean
+
+  def box(t):  # mean over the 3x3 window, rows wrapped, columns 1 .. W - 2
+    rows = t + torch.roll(t, 1, -2) + torch.roll(t, -1, -2)
+    return (rows[..., :-2] + rows[..., 1:-1] + rows[..., 2:]) / 9
+
+  def members(t):
+    return [torch.roll(t, -dy, -2)[..., 1 + dx:W - 1 + dx] for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+
+  theta = (math.pi - (torch.arange(H, dtype=torch.float64, device=dev) + 0.5) * 2.0 * math.pi / H).view(H, 1)
+  phi = (math.pi / 2 - (torch.arange(W, dtype=torch.float64, device=dev) + 0.5) * math.pi / W).view(1, W)
+  n = torch.stack([torch.sin(phi).expand(H, W), torch.cos(phi) * torch.sin(theta), torch.cos(phi) * torch.cos(theta)], -1)
+  mx = box(L)
+  xs = [m - mx for m in members(L)]
+  vx = sum(a * a for a in xs) / 9
+  good = torch.isfinite(depth) & (depth > 0)
+  D = torch.where(good, depth, torch.ones_like(depth)).double()
+  best, idx = None, torch.full((F, H, W - 2), 255, dtype=torch.long, device=dev)
+  l1 = torch.full((F, H, W - 2), float('inf'), dtype=dt, device=dev)
+  for s in range(S):
+    m = n @ poses[s, :, :3].T
+    Y = D.unsqueeze(-1) * m + poses[s, :, 3]
+    rho = Y.norm(dim=-1)
+    ok = good & (rho > 0)
+    u = (math.pi / 2 - torch.asin((Y[..., 0] / torch.where(ok, rho, torch.ones_like(rho))).clamp(-1, 1))) * W / math.pi - 0.5
+    v = (math.pi - torch.atan2(Y[..., 1], Y[..., 2])) * H / (2.0 * math.pi) - 0.5
+    valid = ok & (u >= 0) & (u <= W - 1)
+    us, vs = torch.where(valid, u, torch.zeros_like(u)), torch.where(valid, v, torch.zeros_like(v))
+    x0, y0 = us.detach().floor().clamp(max=W - 2), vs.detach().floor()
+    t, q = (us - x0).to(dt).unsqueeze(1), (vs - y0).to(dt).unsqueeze(1)
+    x0 = x0.long()
+    ya, yb = torch.remainder(y0.long(), H), torch.remainder(y0.long() + 1, H)
+    flat = (src[:, s] * std + mean).reshape(F, 3, H * W)
+
+    def at(y, x):
+      return flat.gather(2, (y * W + x).unsqueeze(1).expand(F, 3, H, W).reshape(F, 3, H * W)).reshape(F, 3, H, W)
+
+    top = (1 - t) * at(ya, x0) + t * at(ya, x0 + 1)
+    bot = (1 - t) * at(yb, x0) + t * at(yb, x0 + 1)
+    Ih = torch.where(valid.unsqueeze(1), (1 - q) * top + q * bot, torch.zeros_like(top))
+    wvalid = torch.stack(members(valid)).all(0)
+    my = box(Ih)
+    ys = [m_ - my for m_ in members(Ih)]
+    vy = sum(b * b for b in ys) / 9
+    cxy = sum(a * b for a, b in zip(xs, ys)) / 9
+    ssim = (2 * mx * my + C1) * (2 * cxy + C2) / ((mx * mx + my * my + C1) * (vx + vy + C2))
+    pe = (alpha * (1 - ssim) / 2 + (1 - alpha) * (L - Ih).abs()[..., 1:-1]).mean(1)
+    better = wvalid & ((idx == 255) | (pe.detach() < (pe.detach() if best is None else best.detach())))
+    best = torch.where(better, pe, torch.zeros_like(pe) if best is None else best)
+    idx = torch.where(better, torch.full_like(idx, s), idx)
+    l1 = torch.where(better, (L - Ih).detach().abs().min(1).values[..., 1:-1], l1)
+  has = idx != 255
+  photo = torch.where(has, best, torch.zeros_like(best)).sum() / has.sum().clamp(min=1)
+  ld = torch.log(torch.where(good, depth, torch.ones_like(depth)))
+  ex = torch.exp(-beta * (L[..., 1:] - L[..., :-1]).abs().mean(1))
+  ey = torch.exp(-beta * (torch.roll(L, -1, -2) - L).abs().mean(1))
+  sx = torch.where(good[..., 1:] & good[..., :-1], (ld[..., 1:] - ld[..., :-1]).abs() * ex, torch.zeros_like(ex))
+  sy = torch.where(torch.roll(good, -1, -2) & good, (torch.roll(ld, -1, -2) - ld).abs() * ey, torch.zeros_like(ey))
+  loss = photo + lam * (sx.mean() + sy.mean()) if lam != 0 else photo
+  return loss, idx, l1
+
+
+def inputs(torch, F, H, W, S, dev, seed):
+  """Low-passed noise images, the sources half independent, and a depth map of a smooth field plus noise in [1.5, 8]."""
+  g = torch.Generator(device=dev).manual_seed(seed)
+  from dataloader.preprocess import imagenet_stats
+  mean = torch.tensor(imagenet_stats['mean'], device=dev).view(1, 3, 1, 1)
+  std = torch.tensor(imagenet_stats['std'], device=dev).view(1, 3, 1, 1)
+
+  def lowpass(u):
+    return (u + torch.roll(u, 1, -1) + torch.roll(u, 1, -2)) / 3
+
+  base = lowpass(torch.rand(F, 3, H, W, generator=g, device=dev))
+  ref = (base - mean) / std
+  src = torch.stack([(0.5 * base + 0.5 * lowpass(torch.rand(F, 3, H, W, generator=g, device=dev)) - mean) / std for _ in range(S)], 1)
+  hh = torch.linspace(0, 2 * math.pi, H, device=dev).view(1, H, 1)
+  ww = torch.linspace(0, math.pi, W, device=dev).view(1, 1, W)
+  depth = 4.5 + 2.5 * torch.sin(hh) * torch.sin(ww) + 0.5 * torch.rand(F, H, W, generator=g, device=dev)
+  return ref.contiguous(), src.contiguous(), depth.contiguous()
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--windows', type=int, default=4, help='windows per side and number of frames')
+  ap.add_argument('--min-window', type=float, default=0.3, help='seconds of device time per window, at least')
+  ap.add_argument('--frames', type=int, nargs='+', default=[1, 2])
+  ap.add_argument('--out', help='also write the result line to this file')
+  args = ap.parse_args()
+
+  import torch
+  from mode_hip import functional as HF
+  from utils.rig import CameraRig
+  assert torch.cuda.is_available(), 'mvphoto_bench needs a GPU'
+  dev = torch.device('cuda:0')
+  H, W, S = 1024, 512, 3
+  rig = CameraRig.deep360()
+  poses = rig.panorama_poses()[list(rig.default_sources())]
+  poses_dev = torch.from_numpy(poses).to(dev)
+  out = {'tool': 'mvphoto_bench', 'H': H, 'W': W, 'S': S, 'min_window_s': args.min_window, 'windows': args.windows, 'frames': {}}
+  ok = True
+  for F in args.frames:
+    ref, src, depth = inputs(torch, F, H, W, S, dev, 100 + F)
+
+    def step(side, dtype=torch.float32):
+      d = depth.detach().to(dtype).requires_grad_(True)
+      if side == 'A':
+        loss, win, l1 = composed_loss(torch, ref, src, d, poses_dev)
+      else:
+        loss, win = HF.mv_photometric_loss(ref, src, d, poses, return_win=True)
+        win, l1 = win[..., 1:-1].long(), None
+      loss.backward()
+      return loss.detach(), d.grad, win, l1
+
+    l64, g64, w64, l1 = step('A', torch.float64)
+    la, ga, wa, _ = step('A')
+    lb, gb, wb, _ = step('B')
+    torch.cuda.synchronize()
+    differ = (wa != w64) | (wb != w64)
+    touched = torch.zeros_like(depth, dtype=torch.bool)
+    touched[..., 1:-1] = differ
+    for _ in range(2):  # two pixels around a differing window: its own nine pixels and the windows that share them
+      touched = touched | torch.roll(touched, 1, -2) | torch.roll(touched, -1, -2)
+      touched[..., 1:] |= touched[..., :-1].clone()
+      touched[..., :-1] |= touched[..., 1:].clone()
+    kink = l1 < 1e-6
+    touched[..., 1:-1] |= kink
+    ld = torch.log(depth.double())
+    kx, ky = (ld[..., 1:] - ld[..., :-1]).abs() < 1e-6, (torch.roll(ld, -1, -2) - ld).abs() < 1e-6
+    flat = torch.zeros_like(touched)
+    flat[..., 1:] |= kx
+    flat[..., :-1] |= kx
+    flat |= ky | torch.roll(ky, 1, -2)
+    touched |= flat
+    floor = 2.0 ** -23
+    yl = max(abs(float(la) - float(l64)) / abs(float(l64)), floor)
+    el = abs(float(lb) - float(l64)) / abs(float(l64))
+    scale = float(g64.abs().max())
+    yg = max(float(((ga.double() - g64).abs() * (~touched)).max()) / scale, floor)
+    eg = float(((gb.double() - g64).abs() * (~touched)).max()) / scale
+    row = {'loss_64': float(l64), 'loss_A': float(la), 'loss_B': float(lb), 'windows_with_a_winner': int((w64 != 255).sum()),
+           'windows_whose_winner_differs_from_64_A_B': [int((wa != w64).sum()), int((wb != w64).sum())],
+           'pixels_on_the_kink_of_the_L1_term': int(kink.sum()), 'pixels_on_the_kink_of_the_smoothness_term': int(flat.sum()),
+           'loss_error_over_yardstick': round(el / yl, 3), 'gradient_yardstick_of_max': yg, 'gradient_error_over_yardstick': round(eg / yg, 3)}
+    print('F=%d: %s' % (F, json.dumps(row)), flush=True)
+    if eg > 4 * yg:  # where, before the assertion below says that it is
+      i = int(((gb.double() - g64).abs() * (~touched)).argmax())
+      f, h, w = i // (H * W), (i // W) % H, i % W
+      print('largest gradient error at (f, h, w) = (%d, %d, %d): float64 %.9e, A %.9e, B %.9e; winners there %s; depth around it\n%s' % (
+          f, h, w, float(g64.view(-1)[i]), float(ga.view(-1)[i]), float(gb.view(-1)[i]), w64[f, h, max(w - 2, 0):w + 1].tolist(),
+          depth[f, max(h - 1, 0):h + 2, max(w - 1, 0):w + 2].double().cpu().numpy().tolist()), flush=True)
+    assert int(differ.sum()) <= 1e-4 * differ.numel() and el <= 4 * yl and eg <= 4 * yg, row
+    del l64, g64, w64, l1, la, lb, ga, gb, wa, wb, differ, touched, kink, flat, ld, kx, ky
+    torch.cuda.empty_cache()
+
+    def window(side, n):
+      torch.cuda.synchronize()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(n):
+        step(side)
+      e1.record()
+      torch.cuda.synchronize()
+      return 1e-3 * e0.elapsed_time(e1)
+
+    iters = {}
+    for side in ('A', 'B'):
+      window(side, 3)  # warm-up: allocator, kernels loaded
+      per = window(side, 5) / 5
+      iters[side] = max(5, int(math.ceil(1.2 * args.min_window / per)))
+    times = {'A': [], 'B': []}
+    for w in range(args.windows):
+      for side in ('A', 'B'):
+        sec = window(side, iters[side])
+        while sec < args.min_window:  # the calibration ran slow: a longer window, and this one is not counted
+          iters[side] = int(math.ceil(1.3 * iters[side] * args.min_window / sec))
+          sec = window(side, iters[side])
+        times[side].append(1e6 * sec / iters[side])
+        print('F=%d window %d %s: %.1f us per forward + backward (%d in %.3f s)' % (F, w, side, times[side][-1], iters[side], sec), flush=True)
+    nbytes = (2 * 4 * (4 + 3 * S) + 2 + 4) * F * H * W
+    for side in ('A', 'B'):
+      v = sorted(times[side])
+      row['%s_us' % side] = [round(x, 1) for x in times[side]]
+      row['%s_us_median_min_max' % side] = [round(0.5 * (v[(len(v) - 1) // 2] + v[len(v) // 2]), 1), round(v[0], 1), round(v[-1], 1)]
+    row['B_algorithmic_bytes'] = nbytes
+    row['B_effective_GBps'] = [round(nbytes / (us * 1e-6) / 1e9, 1) for us in times['B']]
+    row['B_ns_per_pixel_and_source'] = [round(1e3 * us / (F * H * W * S), 3) for us in times['B']]
+    row['speedup_median'] = round(row['A_us_median_min_max'][0] / row['B_us_median_min_max'][0], 2)
+    row['every_B_window_faster_than_every_A_window'] = max(times['B']) < min(times['A'])
+    ok = ok and row['every_B_window_faster_than_every_A_window']
+    out['frames'][str(F)] = row
+  out['every_B_window_faster_than_every_A_window'] = ok
+  line = json.dumps(out)
+  print(line)
+  if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+      f.write(line + '\n')
+  return 0 if ok else 1
+
+
+if __name__ == '__main__':
+  sys.exit(main())
