@@ -4,25 +4,24 @@
 //
 // The term has no coupling along H: one workgroup per row of one (map, batch element).  The row of both maps is staged in LDS once
 // and both views are built from it.  The forward writes the two mask bytes of every pixel and leaves six statistics per workgroup in
-// its slab column (the scheme of photometric.hip / metrics_internal.h: a thread walks its pixels in ascending order, a fixed
-// butterfly, the waves in index order, a one-block fold of the columns in index order; fp32 terms, fp64 sums).
+// its slab column (the two folds of photometric_internal.h: a thread walks its pixels in ascending order, a fixed butterfly, the
+// waves in index order, a one-block fold of the columns in index order; fp32 terms, fp64 sums).
 //
 // The gradient into the SAMPLED map is a scatter by nature.  Here it is a gather: 0 <= own <= dmax is part of validity, so the source
 // columns that can reach target column c lie in c - 1 <= w <= c + 1 + dmax (left view) or c - 1 - dmax <= w <= c + 1 (right view).  Every
 // pixel leaves a record (x0 and the sign of own - oh in one word; t in another) in LDS, and a thread per target walks its window in
 // ascending w and adds in that order.  No atomics; every output element is written exactly once; the arithmetic of a pixel does not
 // depend on where its row lies, so rolling the inputs along H rolls the masks and the gradients bit for bit.
-#include <math.h>
-
-#include "common.h"
 #include "mode_hip_selfsup.h"
+#include "photometric_internal.h"
 
 static_assert(MODE_LR_MAX_MAPS == MODE_PHOTOMETRIC_MAX_MAPS, "mode_hip_selfsup.h restates MODE_PHOTOMETRIC_MAX_MAPS as a literal");
 static_assert(MODE_SELFSUP_VIEW_STATS == MODE_PHOTOMETRIC_STATS, "mode_hip_selfsup.h restates MODE_PHOTOMETRIC_STATS as a literal");
 
 namespace {
 
-constexpr int NT = 256;  // threads per workgroup (4 waves)
+using namespace mode::photometric;  // NT threads per workgroup; sgn; the two folds; the workspace check
+
 constexpr int kS = MODE_LR_STATS;
 constexpr int kMaxK = MODE_LR_MAX_MAPS;
 constexpr int kAcc = 2 * kS;            // both views' statistics of one row
@@ -101,58 +100,19 @@ __global__ __launch_bounds__(NT) void lr_fwd_kernel(const float* __restrict__ dl
       if (mask) mask[v * view_stride + row + w] = vis ? 1 : 0;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < kAcc; ++j) {
-    double t = acc[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (lane == 0) sh[wave][j] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < kAcc) {
-    const int v = threadIdx.x / kS, j = threadIdx.x - v * kS;
-    double t = sh[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) t += sh[w][threadIdx.x];
-    slab[(((long long)v * K + k) * kS + j) * gridDim.x + col] = t;
-  }
+  block_fold<kAcc, NT>(acc, sh, slab, [K, k](int a) {  // accumulator a = (view, statistic) -> slab row (view, map, statistic)
+    const int v = a / kS, j = a - v * kS;
+    return ((long long)v * K + k) * kS + j;
+  }, gridDim.x, col);
 }
 
-// One block: fold the columns of every (view, map, statistic) row in index order, as photometric_final_kernel does (all rows side by
-// side: the loads of the rows are independent); write stats (2, K, kS) and loss = sum_k wgt[k] (lr_left_k + lr_right_k).
+// One block: fold the columns of every (view, map, statistic) row in index order; write stats (2, K, kS) and
+// loss = sum_k wgt[k] (lr_left_k + lr_right_k).
 __global__ __launch_bounds__(NTF) void lr_final_kernel(const double* __restrict__ slab, int ncols, int K, Prm p, double* __restrict__ stats,
                                                       float* __restrict__ loss) {
   __shared__ double sh[NTF / 64][kRows];
   __shared__ double fin[kRows];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nrows = 2 * K * kS;
-  double v[kRows];
-#pragma unroll
-  for (int row = 0; row < kRows; ++row) v[row] = 0.0;
-  for (int c = threadIdx.x; c < ncols; c += NTF) {
-    double t[kRows];  // rows at and beyond nrows re-read row 0 and are never written out
-#pragma unroll
-    for (int row = 0; row < kRows; ++row) t[row] = slab[(long long)(row < nrows ? row : 0) * ncols + c];
-#pragma unroll
-    for (int row = 0; row < kRows; ++row) v[row] += t[row];
-  }
-#pragma unroll
-  for (int row = 0; row < kRows; ++row) {
-    double t = v[row];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (lane == 0) sh[wave][row] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < nrows) {
-    const int row = threadIdx.x;
-    double t = sh[0][row];
-#pragma unroll
-    for (int w = 1; w < NTF / 64; ++w) t += sh[w][row];
-    stats[row] = t;
-    fin[row] = t;
-  }
+  fold_rows<kRows, NTF>(slab, ncols, 2 * K * kS, sh, stats, fin);
   __syncthreads();
   if (threadIdx.x == 0) {
     double total = 0.0;
@@ -168,8 +128,6 @@ __global__ __launch_bounds__(NTF) void lr_final_kernel(const double* __restrict_
     loss[0] = (float)total;
   }
 }
-
-__device__ __forceinline__ float sgn(float v) { return (float)((v > 0.f) - (v < 0.f)); }  // sign(0) = 0
 
 // What the sources of one view send to target column c: the records of columns lo .. hi (clamped to the row) in ascending order.
 // rx: (x0 << 1) | (own < oh), or kNoRecord; rt: t.  cf = gloss wgt / N of that view.
@@ -279,9 +237,8 @@ extern "C" int mode_lr_consistency_fwd(const float* disp_l, const float* disp_r,
   int rc = check_common(who, disp_l, disp_r, K, B, H, W, params, p);
   if (rc != MODE_OK) return rc;
   MODE_REQUIRE(stats && loss, MODE_ERR_BAD_ARG, "%s: null pointer", who);
-  MODE_REQUIRE(workspace && ((size_t)workspace & 7) == 0, MODE_ERR_WORKSPACE, "%s: workspace missing or not 8-byte aligned", who);
-  MODE_REQUIRE(workspace_bytes >= mode_lr_consistency_workspace_bytes(K, B, H, W), MODE_ERR_WORKSPACE,
-               "%s: workspace of %zu B is too small (needs %zu B)", who, workspace_bytes, mode_lr_consistency_workspace_bytes(K, B, H, W));
+  rc = check_workspace(who, workspace, workspace_bytes, mode_lr_consistency_workspace_bytes(K, B, H, W));
+  if (rc != MODE_OK) return rc;
   double* slab = static_cast<double*>(workspace);
   hipStream_t st = mode::as_stream(stream);
   const int ncols = B * H;

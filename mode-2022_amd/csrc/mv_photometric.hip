@@ -3,9 +3,10 @@
 // windows between the reference and each warped source, the per-window minimum over the sources, and an edge-aware smoothness term
 // on log depth -- forward with a deterministic reduction, backward as a gather.
 //
-// The frame is that of photometric.hip: one workgroup per 16 x 32 tile of one frame, the tile and its halo staged in LDS once for all
-// three channels.  The de-normalised reference L, log depth and its validity are staged once; the source loop runs inside the kernel:
-// for each source the warped image Ih_s and its validity byte go into the same LDS planes (four global gathers per pixel and channel),
+// The frame is that of photometric_internal.h: one workgroup per 16 x 32 tile of one frame, the tile and its halo staged in LDS once
+// for all three channels, the window arithmetic and the reduction from there.  What is here is this loss's own: the fp64 projection
+// and its staging, the minimum over the sources, the smoothness on log depth, and the entries.
+// The de-normalised reference L, log depth and its validity are staged once; the source loop runs inside the kernel: for each source the warped image Ih_s and its validity byte go into the same LDS planes (four global gathers per pixel and channel),
 // pe_s is formed per window, and the running minimum and its index stay in registers.  A thread stages the same pixels for every
 // source, so their viewing directions (fp64 sin / cos) are computed once and kept in registers.
 // The geometry -- u, v and their slopes in depth -- is fp64, in one function that both passes call, and is rounded to fp32 at t, q
@@ -19,19 +20,16 @@
 // The reduction is the scheme of metrics_internal.h with twelve statistics: a thread walks its pixels in ascending order, a fixed
 // butterfly, the waves in index order, one slab column per workgroup, and a second launch folds the columns in index order.
 // No atomics; the same inputs give the same bits on any stream.
-#include <math.h>
-
-#include "common.h"
 #include "mode_hip_mvphoto.h"
+#include "photometric_internal.h"
 
 static_assert(MODE_MVP_STATS == MODE_MVP_WINS + MODE_MVP_MAX_SOURCES, "one win count per source after the four sums");
 static_assert(MODE_MVP_NO_WINNER >= MODE_MVP_MAX_SOURCES && MODE_MVP_NO_WINNER <= 255, "win is a byte");
 
 namespace {
 
-constexpr int NT = 256;  // threads per workgroup (4 waves)
-constexpr int TH = 16;   // tile rows (along H, the periodic axis)
-constexpr int TW = 32;   // tile columns (along W, contiguous in memory)
+using namespace mode::photometric;
+
 constexpr int PX = TH * TW / NT;  // tile pixels per thread
 constexpr int kS = MODE_MVP_STATS;
 constexpr int kMaxS = MODE_MVP_MAX_SOURCES;
@@ -39,10 +37,7 @@ constexpr int kNone = MODE_MVP_NO_WINNER;
 constexpr double kPi = 3.14159265358979323846;
 
 // Kernel-side copies of the parameters and of the poses (by value: they travel in the kernel arguments).
-struct Prm {
-  float alpha, lam, beta, c1, c2;
-  float mean[3], std[3];
-};
+using Prm = Colour;
 
 struct Poses {
   double p[kMaxS][12];  // [A | o], row-major 3 x 4
@@ -58,8 +53,6 @@ struct Stage {
   unsigned char ok[N];   // valid for the current source
   unsigned char dok[N];  // depth finite and > 0
 };
-
-__device__ __forceinline__ float sgn(float v) { return (float)((v > 0.f) - (v < 0.f)); }  // sign(0) = 0, sign(NaN) = 0
 
 struct Dir {
   double x, y, z;
@@ -205,79 +198,6 @@ __device__ __forceinline__ void stage_src(Stage<HALO>& s, const float* __restric
   }
 }
 
-template <int RW>
-__device__ __forceinline__ bool window_ok(const unsigned char* ok, int centre) {
-  unsigned v = 1;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) v &= ok[centre + dy * RW + dx];
-  return v != 0;
-}
-
-// The centred, biased moments of one window and channel, every sum in the order dy = -1..1, dx = -1..1 (as photometric.hip).
-struct Moments {
-  float mx, my, vx, vy, cxy;
-};
-
-template <int RW>
-__device__ __forceinline__ Moments window_moments(const float* __restrict__ L, const float* __restrict__ R, int centre) {
-  float sx = 0.f, sy = 0.f;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      sx += L[centre + dy * RW + dx];
-      sy += R[centre + dy * RW + dx];
-    }
-  Moments m;
-  constexpr float k9 = 1.f / 9.f;
-  m.mx = sx * k9;
-  m.my = sy * k9;
-  float vx = 0.f, vy = 0.f, cxy = 0.f;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      const float a = L[centre + dy * RW + dx] - m.mx, b = R[centre + dy * RW + dx] - m.my;
-      vx += a * a;
-      vy += b * b;
-      cxy += a * b;
-    }
-  m.vx = vx * k9;
-  m.vy = vy * k9;
-  m.cxy = cxy * k9;
-  return m;
-}
-
-// exp(-beta mean_c |L_c(a) - L_c(b)|): the edge weight between two staged pixels
-template <int N>
-__device__ __forceinline__ float edge_weight(const float (*L)[N], int a, int b, float beta) {
-  const float e = (fabsf(L[0][a] - L[0][b]) + fabsf(L[1][a] - L[1][b]) + fabsf(L[2][a] - L[2][b])) * (1.f / 3.f);
-  return expf(-beta * e);
-}
-
-// The whole block (all NT threads call it): fixed butterfly over the lanes, the waves in index order, statistic j into
-// slab[j * ncols + col].
-__device__ __forceinline__ void block_fold(const double (&a)[kS], double (*sh)[kS], double* __restrict__ slab, int ncols, int col) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < kS; ++j) {
-    double v = a[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) sh[wave][j] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kS) {
-    const int j = threadIdx.x;
-    double v = sh[0][j];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) v += sh[w][j];
-    slab[(long long)j * ncols + col] = v;
-  }
-}
-
 // grid = F * tiles.  Block col leaves its twelve statistics in column col of the slab and the winners of its tile in win.
 __global__ __launch_bounds__(NT) void mvphoto_fwd_kernel(const float* __restrict__ ref, const float* __restrict__ src,
                                                          const float* __restrict__ depth, Poses poses, int S, int H, int W, int tiles_w,
@@ -317,7 +237,7 @@ __global__ __launch_bounds__(NT) void mvphoto_fwd_kernel(const float* __restrict
       for (int ch = 0; ch < 3; ++ch) {
         const Moments m = window_moments<St::RW>(s.L[ch], s.R[ch], i);
         const float ssim = (2.f * m.mx * m.my + p.c1) * (2.f * m.cxy + p.c2) / ((m.mx * m.mx + m.my * m.my + p.c1) * (m.vx + m.vy + p.c2));
-        pe += p.alpha * (1.f - ssim) / 2.f + (1.f - p.alpha) * fabsf(s.L[ch][i] - s.R[ch][i]);
+        pe += window_term(ssim, s.L[ch][i], s.R[ch][i], p.alpha);
       }
       pe *= 1.f / 3.f;
       if (idx[k] == kNone || pe < best[k]) {  // ascending s and a strict comparison: the smallest s that attains the minimum
@@ -350,7 +270,7 @@ __global__ __launch_bounds__(NT) void mvphoto_fwd_kernel(const float* __restrict
       if (s.dok[i + St::RW]) acc[MODE_MVP_SUM_SMOOTH_Y] += (double)(fabsf(s.ld[i + St::RW] - ld) * edge_weight(s.L, i + St::RW, i, p.beta));
     }
   }
-  block_fold(acc, sh, slab, gridDim.x, col);
+  block_fold<kS, NT>(acc, sh, slab, [](int j) { return (long long)j; }, gridDim.x, col);
 }
 
 // One block: fold the columns of every statistic in index order (thread t takes columns t, t + NT, ...; then the fixed butterfly and
@@ -359,33 +279,7 @@ __global__ __launch_bounds__(NT) void mvphoto_final_kernel(const double* __restr
                                                            double* __restrict__ stats, float* __restrict__ loss) {
   __shared__ double sh[NT / 64][kS];
   __shared__ double fin[kS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double v[kS];
-#pragma unroll
-  for (int row = 0; row < kS; ++row) v[row] = 0.0;
-  for (int c = threadIdx.x; c < ncols; c += NT) {
-    double t[kS];  // every load issued before the first sum
-#pragma unroll
-    for (int row = 0; row < kS; ++row) t[row] = slab[(long long)row * ncols + c];
-#pragma unroll
-    for (int row = 0; row < kS; ++row) v[row] += t[row];
-  }
-#pragma unroll
-  for (int row = 0; row < kS; ++row) {
-    double t = v[row];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (lane == 0) sh[wave][row] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < kS) {
-    const int row = threadIdx.x;
-    double t = sh[0][row];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) t += sh[w][row];
-    stats[row] = t;
-    fin[row] = t;
-  }
+  fold_rows<kS, NT>(slab, ncols, kS, sh, stats, fin);
   __syncthreads();
   if (threadIdx.x == 0) {
     const double n = fin[MODE_MVP_N];
@@ -395,16 +289,6 @@ __global__ __launch_bounds__(NT) void mvphoto_final_kernel(const double* __restr
     loss[0] = (float)total;
   }
 }
-
-// d ssim / d Ih_i of a window = (P + Q (L_i - mx) - R (Ih_i - my)) / 9; P, Q, R are kept scaled by the factor of the photometric
-// term, -alpha / (2 x 3 x 9), next to the two means, for one channel at a time (as photometric.hip).  win: the winner of every window
-// centred on the tile and one pixel around it.
-struct Windows {
-  static constexpr int RH = TH + 2, RW = TW + 2, N = RH * RW;
-  static constexpr int PER_THREAD = (N + NT - 1) / NT;
-  float P[N], Q[N], R[N], mx[N], my[N];
-  unsigned char win[N];
-};
 
 // grid = F * tiles.  gdepth is written once per element.
 __global__ __launch_bounds__(NT) void mvphoto_bwd_kernel(const float* __restrict__ ref, const float* __restrict__ src,
@@ -435,14 +319,14 @@ __global__ __launch_bounds__(NT) void mvphoto_bwd_kernel(const float* __restrict
       h = h < 0 ? h + H : h;
       const int w = w0 - 1 + c;
       if (w >= 1 && w <= W - 2) mine[k] = win[HW * f + h * W + w];
-      wn.win[i] = (unsigned char)mine[k];
+      wn.tag[i] = (unsigned char)mine[k];
     }
   }
 
   float gph[PX];
 #pragma unroll
   for (int k = 0; k < PX; ++k) gph[k] = 0.f;
-  const float scale = -p.alpha / 54.f;
+  const float scale = window_scale(p);
   for (int sv = 0; sv < S; ++sv) {
     int any = 0;
 #pragma unroll
@@ -455,28 +339,7 @@ __global__ __launch_bounds__(NT) void mvphoto_bwd_kernel(const float* __restrict
 #pragma unroll
       for (int k = 0; k < Windows::PER_THREAD; ++k) {
         const int i = threadIdx.x + k * NT;
-        if (i < Windows::N) {
-          float P = 0.f, Q = 0.f, R = 0.f, mx = 0.f, my = 0.f;
-          if (mine[k] == sv) {
-            const int r = i / Windows::RW, c = i - r * Windows::RW;
-            const Moments m = window_moments<St::RW>(s.L[ch], s.R[ch], (r + 1) * St::RW + (c + 1));
-            const float a1 = 2.f * m.mx * m.my + p.c1, a2 = 2.f * m.cxy + p.c2;
-            const float b1 = m.mx * m.mx + m.my * m.my + p.c1, b2 = m.vx + m.vy + p.c2;
-            const float r1 = 1.f / b1, r2 = 1.f / b2;
-            const float inv = r1 * r2;
-            const float ssim = a1 * a2 * inv;
-            P = scale * 2.f * (m.mx * a2 * inv - ssim * m.my * r1);
-            Q = scale * 2.f * a1 * inv;
-            R = scale * 2.f * ssim * r2;
-            mx = m.mx;
-            my = m.my;
-          }
-          wn.P[i] = P;
-          wn.Q[i] = Q;
-          wn.R[i] = R;
-          wn.mx[i] = mx;
-          wn.my[i] = my;
-        }
+        if (i < Windows::N) put_window<St::RW>(wn, i, mine[k] == sv, s.L[ch], s.R[ch], scale, p);
       }
       __syncthreads();
 #pragma unroll
@@ -490,11 +353,8 @@ __global__ __launch_bounds__(NT) void mvphoto_bwd_kernel(const float* __restrict
 #pragma unroll
         for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
-          for (int dx = -1; dx <= 1; ++dx) {
-            const int q = wc + dy * Windows::RW + dx;
-            a += wn.P[q] + wn.Q[q] * (x - wn.mx[q]) - wn.R[q] * (y - wn.my[q]);
-          }
-        if (wn.win[wc] == sv) a += (1.f - p.alpha) * (1.f / 3.f) * sgn(y - x);
+          for (int dx = -1; dx <= 1; ++dx) a += window_share(wn, wc + dy * Windows::RW + dx, x, y);
+        if (wn.tag[wc] == sv) a += (1.f - p.alpha) * (1.f / 3.f) * sgn(y - x);
         gph[k] += slope[ch][j] * a;  // (the slope is 0 where the pixel is invalid for s; no window of s contains such a pixel)
       }
       __syncthreads();  // the next channel overwrites the windows
@@ -536,7 +396,8 @@ int check_common(const char* who, const float* ref, const float* src, const floa
   MODE_REQUIRE(ref && src && depth && poses && params, MODE_ERR_BAD_ARG, "%s: null pointer", who);
   MODE_REQUIRE(S >= 1 && S <= kMaxS, MODE_ERR_BAD_ARG, "%s: S = %d source views (1 .. %d)", who, S, kMaxS);
   MODE_REQUIRE(F >= 1, MODE_ERR_BAD_ARG, "%s: bad number of frames %d", who, F);
-  MODE_REQUIRE(H >= 3 && W >= 3, MODE_ERR_BAD_ARG, "%s: %d x %d: H and W must be at least 3 (one 3x3 window)", who, H, W);
+  int rc = check_tiling(who, H, W, tiles_w, tiles);
+  if (rc != MODE_OK) return rc;
   for (int s = 0; s < kMaxS; ++s)
     for (int k = 0; k < 12; ++k) ps.p[s][k] = 0.0;
   for (int s = 0; s < S; ++s) {
@@ -553,17 +414,7 @@ int check_common(const char* who, const float* ref, const float* src, const floa
   // Offsets into the sources of one call (3 F S H W) and the workgroup index (F x tiles) are 32-bit quantities; bases are 64-bit.
   MODE_REQUIRE(3ll * F * S * H * W < (1ll << 31), MODE_ERR_UNSUPPORTED,
                "%s: sources of 3 x %d x %d x %d x %d elements: 32-bit indices need 3 F S H W < 2^31", who, F, S, H, W);
-  p.alpha = params->alpha;
-  p.lam = params->lam;
-  p.beta = params->beta;
-  p.c1 = params->c1;
-  p.c2 = params->c2;
-  for (int c = 0; c < 3; ++c) {
-    p.mean[c] = params->mean[c];
-    p.std[c] = params->std[c];
-  }
-  tiles_w = mode::cdiv(W, TW);
-  tiles = tiles_w * mode::cdiv(H, TH);
+  load_colour(params, p);
   return MODE_OK;
 }
 
@@ -573,8 +424,7 @@ extern "C" int mode_mvphoto_version(void) { return MODE_MVPHOTO_VERSION; }
 
 extern "C" size_t mode_mvphoto_workspace_bytes(int S, int F, int H, int W) {
   if (S < 1 || S > kMaxS || F < 1 || H < 3 || W < 3 || 3ll * F * S * H * W >= (1ll << 31)) return 0;
-  const size_t cols = (size_t)F * mode::cdiv(W, TW) * mode::cdiv(H, TH);
-  return ((size_t)kS * cols * sizeof(double) + 15) / 16 * 16;
+  return ((size_t)kS * F * tiles_of(H, W) * sizeof(double) + 15) / 16 * 16;
 }
 
 extern "C" int mode_mvphoto_loss_fwd(const float* ref, const float* src, const float* depth, const double* poses, int S, int F, int H, int W,
@@ -587,9 +437,8 @@ extern "C" int mode_mvphoto_loss_fwd(const float* ref, const float* src, const f
   MODE_REQUIRE(win && stats && loss, MODE_ERR_BAD_ARG, "%s: null pointer", who);
   int rc = check_common(who, ref, src, depth, poses, S, F, H, W, params, p, ps, tiles_w, tiles);
   if (rc != MODE_OK) return rc;
-  MODE_REQUIRE(workspace && ((size_t)workspace & 7) == 0, MODE_ERR_WORKSPACE, "%s: workspace missing or not 8-byte aligned", who);
-  MODE_REQUIRE(workspace_bytes >= mode_mvphoto_workspace_bytes(S, F, H, W), MODE_ERR_WORKSPACE,
-               "%s: workspace of %zu B is too small (needs %zu B)", who, workspace_bytes, mode_mvphoto_workspace_bytes(S, F, H, W));
+  rc = check_workspace(who, workspace, workspace_bytes, mode_mvphoto_workspace_bytes(S, F, H, W));
+  if (rc != MODE_OK) return rc;
   double* slab = static_cast<double*>(workspace);
   hipStream_t st = mode::as_stream(stream);
   const int ncols = F * tiles;

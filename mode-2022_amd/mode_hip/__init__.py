@@ -24,17 +24,16 @@ CONSTANTS = HEADER.constants  # every MODE_* integer of the header, under the he
 
 ABI_VERSION = CONSTANTS['MODE_HIP_ABI_VERSION']
 
-# include/mode_hip_selfsup.h, the second public header, read the same way.  The first header is frozen (its tests pin what it holds);
-# entries added since are declared in the second and bound onto the same handle.  HEADER, SIGNATURES, ... above stay the first header's.
-SELFSUP = _header.load(os.path.join(os.path.dirname(_header.PATH), 'mode_hip_selfsup.h'))
-SELFSUP_LAUNCHING = frozenset(n for n, (_, params) in SELFSUP.prototypes.items() if any(t == _header.STREAM for t, _ in params))
-SELFSUP_VERSION = SELFSUP.constants['MODE_SELFSUP_VERSION']
-
-# include/mode_hip_mvphoto.h, the third public header: the second is frozen by its tests as well (its version and its four
-# launching entries are pinned).  Read and bound exactly as the second; SELFSUP* above stay the second header's.
-MVPHOTO = _header.load(os.path.join(os.path.dirname(_header.PATH), 'mode_hip_mvphoto.h'))
-MVPHOTO_LAUNCHING = frozenset(n for n, (_, params) in MVPHOTO.prototypes.items() if any(t == _header.STREAM for t, _ in params))
-MVPHOTO_VERSION = MVPHOTO.constants['MODE_MVPHOTO_VERSION']
+# The extension headers, read the same way.  A public header is frozen once its tests pin what it holds (the first; the second with
+# its version and its four launching entries), so entries added since are declared in a header of their own and bound onto the same
+# handle.  Per header (NAME, file, version constant, version function) the module gets NAME (the header), NAME_LAUNCHING and
+# NAME_VERSION; HEADER, SIGNATURES, ... above stay the first header's.  The next header is one more row.
+EXTENSIONS = (('SELFSUP', 'mode_hip_selfsup.h', 'MODE_SELFSUP_VERSION', 'mode_selfsup_version'),
+              ('MVPHOTO', 'mode_hip_mvphoto.h', 'MODE_MVPHOTO_VERSION', 'mode_mvphoto_version'))
+for _name, _file, _const, _ in EXTENSIONS:
+  _h = _header.load(os.path.join(os.path.dirname(_header.PATH), _file))
+  globals().update({_name: _h, _name + '_VERSION': _h.constants[_const], _name + '_LAUNCHING': frozenset(
+      n for n, (_, params) in _h.prototypes.items() if any(t == _header.STREAM for t, _ in params))})
 _lib = None
 _lock = threading.Lock()
 
@@ -57,22 +56,16 @@ def lib():
         if have != ABI_VERSION:
           raise RuntimeError('libmode_hip.so has ABI version %d, this binding needs %d: rebuild it (python '
                              'mode-2022_amd/mode_hip/build.py)' % (have, ABI_VERSION))
-        have = handle.mode_selfsup_version() if hasattr(handle, 'mode_selfsup_version') else None
-        if have != SELFSUP_VERSION:
-          raise RuntimeError('libmode_hip.so has version %s of the entries of mode_hip_selfsup.h, this binding needs %d: rebuild it '
-                             '(python mode-2022_amd/mode_hip/build.py)' % (have, SELFSUP_VERSION))
-        for name, (res, args) in SELFSUP.signatures.items():
-          fn = getattr(handle, name)
-          fn.restype = res
-          fn.argtypes = args
-        have = handle.mode_mvphoto_version() if hasattr(handle, 'mode_mvphoto_version') else None
-        if have != MVPHOTO_VERSION:
-          raise RuntimeError('libmode_hip.so has version %s of the entries of mode_hip_mvphoto.h, this binding needs %d: rebuild it '
-                             '(python mode-2022_amd/mode_hip/build.py)' % (have, MVPHOTO_VERSION))
-        for name, (res, args) in MVPHOTO.signatures.items():
-          fn = getattr(handle, name)
-          fn.restype = res
-          fn.argtypes = args
+        for ext, file, _, version_fn in EXTENSIONS:
+          have = getattr(handle, version_fn)() if hasattr(handle, version_fn) else None
+          want = globals()[ext + '_VERSION']  # read now, not at import
+          if have != want:
+            raise RuntimeError('libmode_hip.so has version %s of the entries of %s, this binding needs %d: rebuild it '
+                               '(python mode-2022_amd/mode_hip/build.py)' % (have, file, want))
+          for name, (res, args) in globals()[ext].signatures.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
         _lib = handle
   return _lib
 

@@ -2028,43 +2028,6 @@ def _photometric_params(K, weights, alpha, lam, beta, mean, std, c1=1e-4, c2=9e-
   return prm
 
 
-class PhotometricLossFunction(torch.autograd.Function):
-  """(left, right, prm, disp_0 .. disp_{K-1}) -> (loss 0-d, stats (K, PHOTOMETRIC_STATS) float64): one forward launch pair and one
-  backward launch for all K maps.  Gradient into the disparities only (the images are data); the statistics carry none."""
-
-  @staticmethod
-  def forward(ctx, left, right, prm, *disps):
-    K = len(disps)
-    B, _, H, W = left.shape
-    disp = torch.empty((K, B, H, W), dtype=left.dtype, device=left.device)  # the layout of the entry
-    for k, d in enumerate(disps):
-      disp[k].copy_(d.reshape(B, H, W))
-    require_f32c(left, right, disp)
-    stats = torch.empty((K, PHOTOMETRIC_STATS), dtype=torch.float64, device=left.device)
-    loss = torch.empty(1, dtype=torch.float32, device=left.device)
-    nbytes = 4 * K * (left.numel() + right.numel() + disp[0].numel())
-    with torch.cuda.device_of(left), profiling.region('photometric_loss_fwd', nbytes, 0, left.device):
-      ws = torch.empty(max(lib().mode_photometric_loss_workspace_bytes(K, B, H, W) // 8, 1), dtype=torch.float64, device=left.device)
-      _call('mode_photometric_loss_fwd', ptr(left), ptr(right), ptr(disp), K, B, H, W, ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(stats),
-            ptr(loss), stream_of(left))
-    ctx.save_for_backward(left, right, disp, stats)
-    ctx.prm, ctx.shapes = prm, [d.shape for d in disps]
-    ctx.mark_non_differentiable(stats)
-    return loss.reshape(()), stats
-
-  @staticmethod
-  def backward(ctx, gloss, _gstats):
-    left, right, disp, stats = ctx.saved_tensors
-    K, B, H, W = disp.shape
-    gl = gloss.reshape(1).to(torch.float32).contiguous()
-    gdisp = torch.empty_like(disp)
-    nbytes = 4 * K * (left.numel() + right.numel() + 2 * disp[0].numel())
-    with torch.cuda.device_of(left), profiling.region('photometric_loss_bwd', nbytes, 0, left.device):
-      _call('mode_photometric_loss_bwd', ptr(left), ptr(right), ptr(disp), K, B, H, W, ctypes.byref(ctx.prm), ptr(stats), ptr(gl), ptr(gdisp),
-            stream_of(left))
-    return (None, None, None) + tuple(gdisp[k].view(shape) for k, shape in enumerate(ctx.shapes))
-
-
 def _stack_maps(disps, B, H, W, like):
   """K maps (B, 1, H, W) or (B, H, W) -> one (K, B, H, W) tensor, the layout of the entries."""
   disp = torch.empty((len(disps), B, H, W), dtype=like.dtype, device=like.device)
@@ -2073,12 +2036,20 @@ def _stack_maps(disps, B, H, W, like):
   return disp
 
 
-class ViewLossFunction(torch.autograd.Function):
-  """PhotometricLossFunction from either camera and with an optional mask (mode_selfsup_view_loss_fwd / _bwd):
-  (own, other, mask or None, view 0 / 1, prm, disp_0 .. disp_{K-1}) -> (loss 0-d, stats (K, PHOTOMETRIC_STATS) float64)."""
+class StereoLossFunction(torch.autograd.Function):
+  """(name, own, other, mask or None, view 0 / 1, prm, disp_0 .. disp_{K-1}) -> (loss 0-d, stats (K, PHOTOMETRIC_STATS) float64): one
+  forward launch pair and one backward launch for all K maps.  Gradient into the disparities only (the images are data); the statistics
+  carry none.  name is the entry pair and the profiling regions: 'photometric_loss' (mode_photometric_loss_fwd / _bwd, the
+  left view without a mask, which is all those entries take) or 'selfsup_view_loss' (mode_selfsup_view_loss_fwd / _bwd,
+  either camera and an optional mask)."""
 
   @staticmethod
-  def forward(ctx, own, other, mask, view, prm, *disps):
+  def _form(name, mask, view):
+    """The arguments that only the entries of DESIGN 24 take."""
+    return () if name == 'photometric_loss' else (None if mask is None else ptr(mask), view)
+
+  @staticmethod
+  def forward(ctx, name, own, other, mask, view, prm, *disps):
     K = len(disps)
     B, _, H, W = own.shape
     disp = _stack_maps(disps, B, H, W, own)
@@ -2086,12 +2057,12 @@ class ViewLossFunction(torch.autograd.Function):
     stats = torch.empty((K, PHOTOMETRIC_STATS), dtype=torch.float64, device=own.device)
     loss = torch.empty(1, dtype=torch.float32, device=own.device)
     nbytes = 4 * K * (own.numel() + other.numel() + disp[0].numel()) + (0 if mask is None else mask.numel())
-    with torch.cuda.device_of(own), profiling.region('selfsup_view_loss_fwd', nbytes, 0, own.device):
+    with torch.cuda.device_of(own), profiling.region(name + '_fwd', nbytes, 0, own.device):
       ws = torch.empty(max(lib().mode_photometric_loss_workspace_bytes(K, B, H, W) // 8, 1), dtype=torch.float64, device=own.device)
-      _call('mode_selfsup_view_loss_fwd', ptr(own), ptr(other), ptr(disp), None if mask is None else ptr(mask), view, K, B, H, W,
+      _call('mode_%s_fwd' % name, ptr(own), ptr(other), ptr(disp), *StereoLossFunction._form(name, mask, view), K, B, H, W,
             ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(stats), ptr(loss), stream_of(own))
     ctx.save_for_backward(own, other, disp, stats, *(() if mask is None else (mask,)))
-    ctx.prm, ctx.view, ctx.shapes = prm, view, [d.shape for d in disps]
+    ctx.name, ctx.view, ctx.prm, ctx.shapes = name, view, prm, [d.shape for d in disps]
     ctx.mark_non_differentiable(stats)
     return loss.reshape(()), stats
 
@@ -2103,10 +2074,20 @@ class ViewLossFunction(torch.autograd.Function):
     gl = gloss.reshape(1).to(torch.float32).contiguous()
     gdisp = torch.empty_like(disp)
     nbytes = 4 * K * (own.numel() + other.numel() + 2 * disp[0].numel()) + (0 if mask is None else mask.numel())
-    with torch.cuda.device_of(own), profiling.region('selfsup_view_loss_bwd', nbytes, 0, own.device):
-      _call('mode_selfsup_view_loss_bwd', ptr(own), ptr(other), ptr(disp), None if mask is None else ptr(mask), ctx.view, K, B, H, W,
+    with torch.cuda.device_of(own), profiling.region(ctx.name + '_bwd', nbytes, 0, own.device):
+      _call('mode_%s_bwd' % ctx.name, ptr(own), ptr(other), ptr(disp), *StereoLossFunction._form(ctx.name, mask, ctx.view), K, B, H, W,
             ctypes.byref(ctx.prm), ptr(stats), ptr(gl), ptr(gdisp), stream_of(own))
-    return (None, None, None, None, None) + tuple(gdisp[k].view(shape) for k, shape in enumerate(ctx.shapes))
+    return (None,) * 6 + tuple(gdisp[k].view(shape) for k, shape in enumerate(ctx.shapes))
+
+
+class PhotometricLossFunction:
+  """StereoLossFunction through the entries of DESIGN 22: apply(left, right, prm, disp_0 .. disp_{K-1})."""
+  apply = staticmethod(lambda left, right, prm, *disps: StereoLossFunction.apply('photometric_loss', left, right, None, 0, prm, *disps))
+
+
+class ViewLossFunction:
+  """StereoLossFunction through the entries of DESIGN 24: apply(own, other, mask or None, view 0 / 1, prm, disp_0 .. disp_{K-1})."""
+  apply = staticmethod(lambda *args: StereoLossFunction.apply('selfsup_view_loss', *args))
 
 
 def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False, view='left',
@@ -2136,16 +2117,14 @@ def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0,
     if tuple(d.shape) not in ((B, 1, H, W), (B, H, W)):
       raise ValueError('photometric_loss: a disparity map of shape %s for images %s' % (tuple(d.shape), tuple(left.shape)))
   prm = _photometric_params(K, weights, alpha, lam, beta, mean, std)
-  if view == 'left' and masks is None:
-    loss, stats = PhotometricLossFunction.apply(left.contiguous(), right.contiguous(), prm, *disps)
-  else:
-    if masks is not None:
-      if tuple(masks.shape) != (K, B, H, W) or masks.dtype not in (torch.uint8, torch.bool):
-        raise ValueError('photometric_loss: masks must be a (K, B, H, W) = %s uint8 or bool tensor, got %s %s' % (
-            (K, B, H, W), tuple(masks.shape), masks.dtype))
-      masks = masks.detach().contiguous()
-      masks = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
-    loss, stats = ViewLossFunction.apply(left.contiguous(), right.contiguous(), masks, 0 if view == 'left' else 1, prm, *disps)
+  if masks is not None:
+    if tuple(masks.shape) != (K, B, H, W) or masks.dtype not in (torch.uint8, torch.bool):
+      raise ValueError('photometric_loss: masks must be a (K, B, H, W) = %s uint8 or bool tensor, got %s %s' % (
+          (K, B, H, W), tuple(masks.shape), masks.dtype))
+    masks = masks.detach().contiguous()
+    masks = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+  name = 'photometric_loss' if view == 'left' and masks is None else 'selfsup_view_loss'
+  loss, stats = StereoLossFunction.apply(name, left.contiguous(), right.contiguous(), masks, 0 if view == 'left' else 1, prm, *disps)
   if not return_stats:
     return loss
   n = stats[:, 0]

@@ -102,15 +102,7 @@ def warp(img, depth, pose):
   return torch.where(valid.unsqueeze(1), Ih, torch.zeros_like(Ih)), valid, u, v
 
 
-def pe_map(L, Ih, valid, alpha, C1=1e-4, C2=9e-4):
-  """tests/photometric_ref.py's pe, word for word: -> (pe (F, H, W - 2), wvalid (F, H, W - 2))."""
-  wvalid = R._shifts(valid).all(0)
-  mx, my = R._box(L), R._box(Ih)
-  xs, ys = R._shifts(L) - mx, R._shifts(Ih) - my
-  vx, vy, cxy = (xs * xs).mean(0), (ys * ys).mean(0), (xs * ys).mean(0)
-  ssim = (2 * mx * my + C1) * (2 * cxy + C2) / ((mx * mx + my * my + C1) * (vx + vy + C2))
-  l1 = (L - Ih).abs()[..., 1:-1]
-  return (alpha * (1 - ssim) / 2 + (1 - alpha) * l1).mean(1), wvalid
+pe_map = R.pe_map  # (L, Ih, valid, alpha) -> (pe (F, H, W - 2), wvalid (F, H, W - 2)): the window term of tests/photometric_ref.py
 
 
 def smoothness(L, depth, beta):
@@ -193,21 +185,7 @@ def evaluate(ref, src, depth, poses, dtype, **kw):
   return loss.detach(), info, torch.zeros_like(d) if g is None else g
 
 
-def yardstick(got32, want64):
-  """The float32 restatement's own error of a quantity against float64, relative to max|want64| and never below one fp32 ulp of it
-  (DESIGN 24's bound).  -> (yardstick, scale)."""
-  want64 = torch.as_tensor(want64, dtype=torch.float64)
-  scale = float(want64.abs().max())
-  if scale == 0:
-    return 0.0, 0.0
-  err = float((torch.as_tensor(got32).double() - want64).abs().max()) / scale
-  return max(err, 2.0 ** -23), scale
-
-
-def error(got, want64, scale):
-  want64 = torch.as_tensor(want64, dtype=torch.float64)
-  diff = float((torch.as_tensor(got).double() - want64).abs().max())
-  return diff / scale if scale else diff
+yardstick, error = R.yardstick, R.error  # DESIGN 24's bound: the float32 restatement's own error against float64
 
 
 # ------------------------------------------------------------------------------------------------ a scene with a known answer

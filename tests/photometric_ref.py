@@ -31,11 +31,12 @@ def _shifts(t):
   return torch.stack([torch.roll(t, -dy, -2)[..., 1 + dx:t.shape[-1] - 1 + dx] for dy in (-1, 0, 1) for dx in (-1, 0, 1)])
 
 
-def warp(R, d):
-  """R (B, 3, H, W) de-normalised, d (B, H, W) -> Rh (B, 3, H, W) with zeros at the invalid pixels, valid (B, H, W) bool."""
+def warp(R, d, s=-1):
+  """R (B, 3, H, W) de-normalised, d (B, H, W) -> Rh (B, 3, H, W) with zeros at the invalid pixels, valid (B, H, W) bool.  x = w + s d:
+  s = -1 is the left view, s = +1 the right view of DESIGN 24."""
   B, _, H, W = R.shape
   w = torch.arange(W, dtype=d.dtype).view(1, 1, W)
-  x = w - d
+  x = w + s * d
   valid = torch.isfinite(d) & (x >= 0) & (x <= W - 1)
   xs = torch.where(valid, x, torch.zeros_like(x))
   x0 = xs.detach().floor().clamp(max=W - 2)
@@ -45,21 +46,29 @@ def warp(R, d):
   return torch.where(valid.unsqueeze(1), Rh, torch.zeros_like(Rh)), valid
 
 
-def loss_terms(left, right, d, alpha=0.85, beta=1.0, C1=1e-4, C2=9e-4, mean=None, std=None):
-  """One disparity map d (B, H, W) -> (N_valid (python int), photo, smooth) in d's dtype."""
-  dt = d.dtype
-  mean = torch.tensor(IMAGENET['mean'] if mean is None else mean, dtype=dt).view(1, 3, 1, 1)
-  std = torch.tensor(IMAGENET['std'] if std is None else std, dtype=dt).view(1, 3, 1, 1)
-  L, R = left.to(dt) * std + mean, right.to(dt) * std + mean
-  B, _, H, W = L.shape
-  Rh, valid = warp(R, d)
-  wvalid = _shifts(valid).all(0)  # (B, H, W - 2)
+def pe_map(L, Rh, valid, alpha, C1=1e-4, C2=9e-4):
+  """The window term between L and a warped image Rh (B, 3, H, W) with its validity (B, H, W): -> (pe, wvalid), both (B, H, W - 2)."""
+  wvalid = _shifts(valid).all(0)
   mx, my = _box(L), _box(Rh)
   xs, ys = _shifts(L) - mx, _shifts(Rh) - my
   vx, vy, cxy = (xs * xs).mean(0), (ys * ys).mean(0), (xs * ys).mean(0)
   ssim = (2 * mx * my + C1) * (2 * cxy + C2) / ((mx * mx + my * my + C1) * (vx + vy + C2))
   l1 = (L - Rh).abs()[..., 1:-1]
-  pe = (alpha * (1 - ssim) / 2 + (1 - alpha) * l1).mean(1)
+  return (alpha * (1 - ssim) / 2 + (1 - alpha) * l1).mean(1), wvalid
+
+
+def loss_terms(left, right, d, alpha=0.85, beta=1.0, C1=1e-4, C2=9e-4, mean=None, std=None, s=-1, mask=None):
+  """One disparity map d (B, H, W) -> (N_valid (python int), photo, smooth) in d's dtype.  s, mask: `left` is the view's own
+  image, x = w + s d, and a mask (B, H, W) is and-ed into the validity of a pixel."""
+  dt = d.dtype
+  mean = torch.tensor(IMAGENET['mean'] if mean is None else mean, dtype=dt).view(1, 3, 1, 1)
+  std = torch.tensor(IMAGENET['std'] if std is None else std, dtype=dt).view(1, 3, 1, 1)
+  L, R = left.to(dt) * std + mean, right.to(dt) * std + mean
+  B, _, H, W = L.shape
+  Rh, valid = warp(R, d, s)
+  if mask is not None:
+    valid = valid & (mask != 0)
+  pe, wvalid = pe_map(L, Rh, valid, alpha, C1, C2)
   n = int(wvalid.sum())
   photo = torch.where(wvalid, pe, torch.zeros_like(pe)).sum() / max(n, 1)
   dn = d / W
@@ -69,11 +78,11 @@ def loss_terms(left, right, d, alpha=0.85, beta=1.0, C1=1e-4, C2=9e-4, mean=None
   return n, photo, smooth
 
 
-def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None):
-  """disps: K tensors (B, H, W) -> (loss, stats (K, 3) = [N_valid, photo, smooth] detached)."""
+def photometric_loss(left, right, disps, weights, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, s=-1, masks=None):
+  """disps: K tensors (B, H, W); masks: None or (K, B, H, W) -> (loss, stats (K, 3) = [N_valid, photo, smooth] detached)."""
   loss, rows = 0, []
-  for d, wgt in zip(disps, weights):
-    n, photo, smooth = loss_terms(left, right, d, alpha, beta, mean=mean, std=std)
+  for k, (d, wgt) in enumerate(zip(disps, weights)):
+    n, photo, smooth = loss_terms(left, right, d, alpha, beta, mean=mean, std=std, s=s, mask=None if masks is None else masks[k])
     loss = loss + wgt * (photo + lam * smooth if lam != 0 else photo)
     rows.append(torch.stack([torch.tensor(float(n), dtype=d.dtype), photo.detach(), smooth.detach()]))
   return loss, torch.stack(rows)
@@ -130,3 +139,20 @@ def reference(case, dtype, **kw):
     grads = [torch.zeros_like(d) if g is None else g for g, d in zip(grads, ds)]
     _cache[key] = (loss.detach(), stats, grads)
   return _cache[key]
+
+
+def yardstick(got32, want64):
+  """The float32 restatement's own error of a quantity against float64, relative to max|want64| and never below one fp32 ulp of it
+  (a correctly rounded fp32 result already errs by half an ulp: a smaller yardstick is luck; DESIGN 24's bound).  -> (yardstick, scale)."""
+  want64 = torch.as_tensor(want64, dtype=torch.float64)
+  scale = float(want64.abs().max())
+  if scale == 0:
+    return 0.0, 0.0
+  err = float((torch.as_tensor(got32).double() - want64).abs().max()) / scale
+  return max(err, 2.0 ** -23), scale
+
+
+def error(got, want64, scale):
+  want64 = torch.as_tensor(want64, dtype=torch.float64)
+  diff = float((torch.as_tensor(got).double() - want64).abs().max())
+  return diff / scale if scale else diff

@@ -55,54 +55,17 @@ def lr_consistency(dls, drs, weights, tau, dmax):
   return loss, torch.stack([torch.stack(r) for r in rows]), torch.stack([torch.stack(m) for m in masks])
 
 
-def warp(Rimg, d, s):
-  """photometric_ref.warp with x = w + s d."""
-  B, _, H, W = Rimg.shape
-  w = torch.arange(W, dtype=d.dtype).view(1, 1, W)
-  x = w + s * d
-  valid = torch.isfinite(d) & (x >= 0) & (x <= W - 1)
-  xs = torch.where(valid, x, torch.zeros_like(x))
-  x0 = xs.detach().floor().clamp(max=W - 2)
-  t = (xs - x0).unsqueeze(1)
-  i0 = x0.long().unsqueeze(1).expand(B, 3, H, W)
-  Rh = (1 - t) * Rimg.gather(3, i0) + t * Rimg.gather(3, i0 + 1)
-  return torch.where(valid.unsqueeze(1), Rh, torch.zeros_like(Rh)), valid
+warp = R.warp  # (Rimg, d, s): photometric_ref.warp with x = w + s d
 
 
 def view_terms(own_image, other_image, d, s, mask=None, alpha=0.85, beta=1.0, C1=1e-4, C2=9e-4):
   """photometric_ref.loss_terms from either camera: one map d (B, H, W) -> (N_valid, photo, smooth)."""
-  dt = d.dtype
-  mean = torch.tensor(R.IMAGENET['mean'], dtype=dt).view(1, 3, 1, 1)
-  std = torch.tensor(R.IMAGENET['std'], dtype=dt).view(1, 3, 1, 1)
-  L, Rimg = own_image.to(dt) * std + mean, other_image.to(dt) * std + mean
-  B, _, H, W = L.shape
-  Rh, valid = warp(Rimg, d, s)
-  if mask is not None:
-    valid = valid & (mask != 0)
-  wvalid = R._shifts(valid).all(0)
-  mx, my = R._box(L), R._box(Rh)
-  xs, ys = R._shifts(L) - mx, R._shifts(Rh) - my
-  vx, vy, cxy = (xs * xs).mean(0), (ys * ys).mean(0), (xs * ys).mean(0)
-  ssim = (2 * mx * my + C1) * (2 * cxy + C2) / ((mx * mx + my * my + C1) * (vx + vy + C2))
-  l1 = (L - Rh).abs()[..., 1:-1]
-  pe = (alpha * (1 - ssim) / 2 + (1 - alpha) * l1).mean(1)
-  n = int(wvalid.sum())
-  photo = torch.where(wvalid, pe, torch.zeros_like(pe)).sum() / max(n, 1)
-  dn = d / W
-  ex = torch.exp(-beta * (L[..., 1:] - L[..., :-1]).abs().mean(1))
-  ey = torch.exp(-beta * (torch.roll(L, -1, -2) - L).abs().mean(1))
-  smooth = ((dn[..., 1:] - dn[..., :-1]).abs() * ex).mean() + ((torch.roll(dn, -1, -2) - dn).abs() * ey).mean()
-  return n, photo, smooth
+  return R.loss_terms(own_image, other_image, d, alpha, beta, C1, C2, s=s, mask=mask)
 
 
 def view_loss(own_image, other_image, disps, weights, s, masks=None, alpha=0.85, lam=0.1, beta=1.0):
   """disps: K tensors (B, H, W); masks: None or (K, B, H, W) -> (loss, stats (K, 3) = [N_valid, photo, smooth] detached)."""
-  loss, rows = 0, []
-  for k, (d, wgt) in enumerate(zip(disps, weights)):
-    n, photo, smooth = view_terms(own_image, other_image, d, s, None if masks is None else masks[k], alpha, beta)
-    loss = loss + wgt * (photo + lam * smooth if lam != 0 else photo)
-    rows.append(torch.stack([torch.tensor(float(n), dtype=d.dtype), photo.detach(), smooth.detach()]))
-  return loss, torch.stack(rows)
+  return R.photometric_loss(own_image, other_image, disps, weights, alpha, lam, beta, s=s, masks=masks)
 
 
 def make_case(B, H, W, K, maxd):
@@ -172,21 +135,7 @@ def view_reference(case, dtype, view, masked):
   return _cache[key]
 
 
-def yardstick(got32, want64):
-  """The float32 restatement's own error of a quantity against float64, relative to max|want64| and never below one fp32 ulp of it
-  (a correctly rounded fp32 result already errs by half an ulp: a smaller yardstick is luck).  -> (yardstick, scale)."""
-  want64 = torch.as_tensor(want64, dtype=torch.float64)
-  scale = float(want64.abs().max())
-  if scale == 0:
-    return 0.0, 0.0
-  err = float((torch.as_tensor(got32).double() - want64).abs().max()) / scale
-  return max(err, 2.0 ** -23), scale
-
-
-def error(got, want64, scale):
-  want64 = torch.as_tensor(want64, dtype=torch.float64)
-  diff = float((torch.as_tensor(got).double() - want64).abs().max())
-  return diff / scale if scale else diff
+yardstick, error = R.yardstick, R.error  # the bound of the GPU tests: the float32 restatement's own error against float64
 
 
 def two_planes():
