@@ -29,7 +29,8 @@ ABI_VERSION = CONSTANTS['MODE_HIP_ABI_VERSION']
 # handle.  Per header (NAME, file, version constant, version function) the module gets NAME (the header), NAME_LAUNCHING and
 # NAME_VERSION; HEADER, SIGNATURES, ... above stay the first header's.  The next header is one more row.
 EXTENSIONS = (('SELFSUP', 'mode_hip_selfsup.h', 'MODE_SELFSUP_VERSION', 'mode_selfsup_version'),
-              ('MVPHOTO', 'mode_hip_mvphoto.h', 'MODE_MVPHOTO_VERSION', 'mode_mvphoto_version'))
+              ('MVPHOTO', 'mode_hip_mvphoto.h', 'MODE_MVPHOTO_VERSION', 'mode_mvphoto_version'),
+              ('MVPOSE', 'mode_hip_mvpose.h', 'MODE_MVPOSE_VERSION', 'mode_mvpose_version'))
 for _name, _file, _const, _ in EXTENSIONS:
   _h = _header.load(os.path.join(os.path.dirname(_header.PATH), _file))
   globals().update({_name: _h, _name + '_VERSION': _h.constants[_const], _name + '_LAUNCHING': frozenset(

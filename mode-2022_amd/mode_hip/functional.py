@@ -2254,6 +2254,37 @@ class MvPhotometricLossFunction(torch.autograd.Function):
     return None, None, gdepth.view(ctx.shape), None, None
 
 
+class MvPhotometricPoseLossFunction(torch.autograd.Function):
+  """MvPhotometricLossFunction with the poses as an input of the graph: poses is a float64 CPU tensor (S, 12) or (S, 3, 4).
+  The forward is that function's; the backward runs mode_mvphoto_loss_bwd if the depth needs a gradient and mode_mvpose_grad
+  (csrc/mv_pose_grad.hip) if the poses do, and returns the latter on the host in the input's shape: one device-to-host copy, so this
+  backward synchronises."""
+
+  @staticmethod
+  def forward(ctx, ref, src, depth, poses, prm):
+    import numpy as np
+    ctx.pose_shape = poses.shape
+    return MvPhotometricLossFunction.forward(ctx, ref, src, depth, np.ascontiguousarray(poses.detach().numpy().reshape(-1, 12)), prm)
+
+  @staticmethod
+  def backward(ctx, gloss, _gstats, _gwin):
+    gdepth = MvPhotometricLossFunction.backward(ctx, gloss, None, None)[2] if ctx.needs_input_grad[2] else None
+    gposes = None
+    if ctx.needs_input_grad[3]:
+      ref, src, d, win, stats = ctx.saved_tensors
+      F, S, _, H, W = src.shape
+      dev = ref.device
+      gl = gloss.reshape(1).to(torch.float32).contiguous()
+      out = torch.empty((S, 12), dtype=torch.float64, device=dev)
+      nbytes = 4 * (ref.numel() + src.numel() + d.numel()) + win.numel()
+      with torch.cuda.device_of(ref), profiling.region('mv_pose_grad', nbytes, 0, dev):
+        ws = torch.empty(max(lib().mode_mvpose_workspace_bytes(S, F, H, W) // 8, 1), dtype=torch.float64, device=dev)
+        _call('mode_mvpose_grad', ptr(ref), ptr(src), ptr(d), ctx.poses.ctypes.data_as(ctypes.c_void_p), S, F, H, W, ctypes.byref(ctx.prm),
+              ptr(win), ptr(stats), ptr(gl), ptr(ws), ws.numel() * 8, ptr(out), stream_of(ref))
+      gposes = out.cpu().view(ctx.pose_shape)
+    return None, None, gdepth, gposes, None
+
+
 def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False, return_win=False):
   """The self-supervised loss of a depth map against other panoramas of known pose (include/mode_hip_mvphoto.h has the
   definition): ref (F, 3, H, W) is the Cassini panorama the depth map belongs to, src (F, S, 3, H, W) are S = 1 .. 8 other panoramas of
@@ -2263,7 +2294,14 @@ def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, m
   SSIM + L1 over 3x3 windows whose rows wrap along H, the minimum over the sources per window, plus lam x an edge-aware smoothness term
   on log depth.  Returns a 0-d device tensor with autograd into depth (not into the images); with return_stats also a (3 + S,) float64
   device tensor [N, photo, smooth, wins of source 0 .. S - 1]; with return_win also the (F, H, W) uint8 map of the winning source per
-  window (255: none).  Order of the extras: stats, win.  No host synchronisation."""
+  window (255: none).  Order of the extras: stats, win.  No host synchronisation.
+
+  Self-calibration (include/mode_hip_mvpose.h): when poses is a torch.Tensor with requires_grad -- float64 on the CPU,
+  (S, 12) or (S, 3, 4), e.g. utils.rig_refine.RigRefinement(rig)()[sources] -- the gradient flows into it as well: (S, 12) holds
+  d loss / d A in the first three columns of each 3 x 4 table and d loss / d o in the fourth.  That gradient comes back to the host,
+  one device-to-host copy, so backward() then synchronises; every other form of poses runs exactly as before.  The gradient is
+  one-sided where v is an integer (exactly rectified poses: the right camera of the reference's own pair), and a source that wins
+  no window gets an exactly zero row: calibrate a source at a time, or only sources that are comparably off."""
   import numpy as np
   require_gpu(ref, src, depth)
   if ref.dim() != 4 or ref.shape[1] != 3:
@@ -2276,13 +2314,20 @@ def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, m
     raise ValueError('mv_photometric_loss: %d source views (1 .. %d)' % (S, MVP_MAX_SOURCES))
   if tuple(depth.shape) not in ((F, 1, H, W), (F, H, W)):
     raise ValueError('mv_photometric_loss: a depth map of shape %s for images %s' % (tuple(depth.shape), tuple(ref.shape)))
-  if isinstance(poses, torch.Tensor):
-    poses = poses.detach().cpu().numpy()
-  poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 12))
-  if poses.shape[0] != S:
-    raise ValueError('mv_photometric_loss: %d poses for %d source views' % (poses.shape[0], S))
+  learned = isinstance(poses, torch.Tensor) and poses.requires_grad
+  if learned:
+    if poses.is_cuda or poses.dtype != torch.float64 or tuple(poses.shape) not in ((S, 12), (S, 3, 4)):
+      raise ValueError('mv_photometric_loss: poses that require a gradient must be float64 on the CPU, (S, 12) or (S, 3, 4) with S = %d, '
+                       'got %s %s on %s' % (S, poses.dtype, tuple(poses.shape), poses.device))
+  else:
+    if isinstance(poses, torch.Tensor):
+      poses = poses.detach().cpu().numpy()
+    poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 12))
+    if poses.shape[0] != S:
+      raise ValueError('mv_photometric_loss: %d poses for %d source views' % (poses.shape[0], S))
   prm = _photometric_params(0, (), alpha, lam, beta, mean, std)
-  loss, stats, win = MvPhotometricLossFunction.apply(ref.contiguous(), src.contiguous(), depth, poses, prm)
+  loss, stats, win = (MvPhotometricPoseLossFunction if learned else MvPhotometricLossFunction).apply(ref.contiguous(), src.contiguous(), depth,
+                                                                                                   poses, prm)
   out = (loss,)
   if return_stats:
     smooth = stats[2] / (F * H * (W - 1)) + stats[3] / (F * H * W)

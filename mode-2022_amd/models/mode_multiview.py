@@ -271,7 +271,7 @@ class ModeMultiView(nn.Module):
       return self.fusion.feature_extraction(fusion_input, rgb)
     return self.fusion.feature_extraction(fusion_input)
 
-  def fusion_selfsup_loss(self, frames, sources=None, **loss_kw):
+  def fusion_selfsup_loss(self, frames, sources=None, poses=None, **loss_kw):
     """fusion_loss without ground truth: frames exactly as fusion_loss takes them -> (loss, depth.detach()).  The chain is
     fusion_loss's with the SILog term replaced by HF.mv_photometric_loss: the fused depth lives in the common view's Cassini frame, and
     every other panorama of the frame is a picture of the same scene from a pose the rig knows, so each pixel is lifted by its depth,
@@ -281,7 +281,11 @@ class ModeMultiView(nn.Module):
     dbname='Deep360' means CameraRig.deep360().  disparity.eval() trains the fusion network alone; disparity.train() fine-tunes stage 1
     through the hand-off, under either handoff_grad.  loss_kw: alpha, lam, beta, mean, std.  The fusion network must be in training mode.
     Refused: resize=True (the loss compares at the frames' own size) and dbname='other' (that setting keeps the unit square's
-    translations with other baselines, so its camera centres are not one rig; CameraRig.square(0.6 * sqrt(2)) is)."""
+    translations with other baselines, so its camera centres are not one rig; CameraRig.square(0.6 * sqrt(2)) is).
+    poses: (2P, 3, 4) or (2P, 12) float64 on the host, used in place of rig.panorama_poses(); `sources` indexes it as
+    before.  With utils.rig_refine.RigRefinement(rig)() the loss's gradient reaches the refinement's twist (the backward then copies
+    S x 12 doubles to the host and synchronises); calibrate a source at a time, or only sources that are comparably off: a source
+    that loses every window gets no gradient."""
     from utils.rig import CameraRig
     if self.resize:
       raise ValueError('ModeMultiView(resize=True).fusion_selfsup_loss: the reprojection loss compares the panoramas at their own size, '
@@ -302,7 +306,15 @@ class ModeMultiView(nn.Module):
     sources = rig.default_sources() if sources is None else tuple(int(k) for k in sources)
     if not 1 <= len(sources) <= 8 or any(not 0 <= k < 2 * len(rig.pairs) for k in sources):
       raise ValueError('ModeMultiView.fusion_selfsup_loss: sources %r must be 1 .. 8 panorama indices in [0, %d)' % (sources, 2 * len(rig.pairs)))
-    poses = rig.panorama_poses()[list(sources)]
+    if poses is None:
+      poses = rig.panorama_poses()[list(sources)]
+    else:
+      if not isinstance(poses, torch.Tensor):
+        poses = torch.as_tensor(poses, dtype=torch.float64)
+      if tuple(poses.shape) not in ((2 * len(rig.pairs), 3, 4), (2 * len(rig.pairs), 12)):
+        raise ValueError('ModeMultiView.fusion_selfsup_loss: poses must be (2P, 3, 4) or (2P, 12) with P = %d pairs, one per panorama as '
+                         'rig.panorama_poses() gives them, got %s' % (len(rig.pairs), tuple(poses.shape)))
+      poses = poses.reshape(2 * len(rig.pairs), 12)[list(sources)]
     left, right, rgb, want_rgb = self._ingest(frames)
     P = self.pairs
     H, W = left.shape[-2:]

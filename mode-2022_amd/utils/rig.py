@@ -25,6 +25,22 @@ def _rotation(pitch, yaw, roll):
   return Rx @ Rz @ Ry
 
 
+def _euler(R):
+  """The inverse of _rotation: (pitch, yaw, roll) of an orthonormal R = Rx(roll) Rz(yaw) Ry(pitch), yaw in (-pi/2, pi/2), pitch and
+  roll in (-pi, pi].  The first row of R is (cos y cos p, -sin y, -cos y sin p) and its second column (-sin y, cos r cos y,
+  sin r cos y).  ValueError within 1e-6 of |yaw| = pi/2, where pitch and roll turn about one axis and only their sum is defined."""
+  R = np.asarray(R, dtype=np.float64)
+  if R.shape != (3, 3):
+    raise ValueError('_euler: R must be 3 x 3, got %s' % (R.shape,))
+  cy = math.hypot(R[0][0], R[0][2])
+  if cy < math.sin(1e-6):
+    raise ValueError('_euler: |yaw| is within 1e-6 of pi/2 (R[0][1] = %.17g): pitch and roll are not separate there' % R[0][1])
+  yaw = math.atan2(-R[0][1], cy)  # asin(-R[0][1]), from both the sine and the cosine: asin alone loses digits towards the bound
+  pitch = math.atan2(-R[0][2], R[0][0])
+  roll = math.atan2(R[2][1], R[1][1])
+  return pitch, yaw, roll
+
+
 class PairPose(object):
   """One stereo pair of a rig: PairPose(name, baseline, kind, pose=()).
 

@@ -120,13 +120,132 @@ def inputs(torch, F, H, W, S, dev, seed):
   return ref.contiguous(), src.contiguous(), depth.contiguous()
 
 
+def main_poses(args):
+  """--poses: the same A/B with the pose tensor requiring a gradient on both sides.  A: the composition with the poses a
+  float64 device tensor, autograd into depth and poses.  B: HF.mv_photometric_loss with a float64 CPU pose tensor: forward +
+  mode_mvphoto_loss_bwd + mode_mvpose_grad and the copy of S x 12 doubles to the host.  B0: B without the pose gradient (the B of the
+  run without --poses), so that the cost of the new pass stands alone.  The poses are generic: Deep360's sources, each turned by a
+  seeded rotation vector uniform in +-0.005 and shifted by a vector uniform in +-0.01 (at the exact poses the gradient is one-sided;
+  include/mode_hip_mvpose.h).  Before timing, B's pose gradient is held against the float64 composition by the bound of
+  tests/test_gpu_mvpose.py over all S x 12 elements: the yardstick is A's own fp32 error, never below 2^-23 of max|g64|, and B may take
+  4 times it.  A window whose two best sources are within fp32 rounding of each other may go to another source on either side; such
+  windows are counted, and their effect on the sums is in A's yardstick as it is in B's error.  A miss of that bound is printed with
+  both sides' error tables, recorded in the result ('gposes_within_4_yardsticks'), and fails the tool at its end, after the windows
+  were timed and the result written.  Measured on an MI355X: F = 1 misses, B 7.70e-7 of max|g64| against a yardstick of
+  1.79e-7 (4.29 yardsticks); F = 2 holds, 1.49e-7 against 5.44e-7 (0.27).  Over four runs either side lay between 1.5e-7 and 7.7e-7:
+  the fp32 noise of G_v in the columns next to the poles, the same on both sides."""
+  import torch
+  from mode_hip import functional as HF
+  from utils.rig import CameraRig
+  assert torch.cuda.is_available(), 'mvphoto_bench needs a GPU'
+  dev = torch.device('cuda:0')
+  H, W, S = 1024, 512, 3
+  rig = CameraRig.deep360()
+  base = torch.from_numpy(rig.panorama_poses()[list(rig.default_sources())])
+  g = torch.Generator().manual_seed(27)
+  rot = (torch.rand(S, 3, generator=g, dtype=torch.float64) * 2 - 1) * 0.005
+  z = torch.zeros(S, dtype=torch.float64)
+  K = torch.stack([torch.stack([z, -rot[:, 2], rot[:, 1]], -1), torch.stack([rot[:, 2], z, -rot[:, 0]], -1),
+                   torch.stack([-rot[:, 1], rot[:, 0], z], -1)], -2)
+  poses = torch.cat([torch.linalg.matrix_exp(K) @ base[:, :, :3],
+                     base[:, :, 3:] + ((torch.rand(S, 3, generator=g, dtype=torch.float64) * 2 - 1) * 0.01).unsqueeze(-1)], -1).contiguous()
+  out = {'tool': 'mvphoto_bench --poses', 'H': H, 'W': W, 'S': S, 'min_window_s': args.min_window, 'windows': args.windows, 'frames': {}}
+  ok, missed = True, []
+  for F in args.frames:
+    ref, src, depth = inputs(torch, F, H, W, S, dev, 100 + F)
+
+    def step(side, dtype=torch.float32):
+      d = depth.detach().to(dtype).requires_grad_(True)
+      if side == 'A':
+        p = poses.to(dev).requires_grad_(True)
+        loss, win, _ = composed_loss(torch, ref, src, d, p)
+      elif side == 'B':
+        p = poses.clone().requires_grad_(True)
+        loss, win = HF.mv_photometric_loss(ref, src, d, p, return_win=True)
+        win = win[..., 1:-1].long()
+      else:
+        p = None
+        loss, win = HF.mv_photometric_loss(ref, src, d, poses.numpy(), return_win=True)
+      loss.backward()
+      return loss.detach(), None if p is None else p.grad.detach().cpu().reshape(S, 12), win
+
+    l64, g64, w64 = step('A', torch.float64)
+    la, ga, wa = step('A')
+    lb, gb, wb = step('B')
+    torch.cuda.synchronize()
+    scale = float(g64.abs().max())
+    yg = max(float((ga - g64).abs().max()) / scale, 2.0 ** -23)
+    eg = float((gb - g64).abs().max()) / scale
+    row = {'loss_64': float(l64), 'loss_A': float(la), 'loss_B': float(lb), 'windows_with_a_winner': int((w64 != 255).sum()),
+           'windows_whose_winner_differs_from_64_A_B': [int((wa != w64).sum()), int((wb != w64).sum())], 'max_abs_gposes_64': scale,
+           'gposes_yardstick_of_max': yg, 'gposes_error_of_max': eg, 'gposes_error_over_yardstick': round(eg / yg, 3)}
+    row['gposes_within_4_yardsticks'] = eg <= 4 * yg
+    print('F=%d: %s' % (F, json.dumps(row)), flush=True)
+    if eg > 4 * yg:  # where; the windows below are still timed and written, and the tool fails at its end
+      print('gposes error of max|g64|, A then B:\n%s\n%s' % (((ga - g64) / scale).numpy(), ((gb - g64) / scale).numpy()), flush=True)
+      missed.append((F, row['gposes_error_over_yardstick']))
+    del l64, g64, w64, la, lb, ga, gb, wa, wb
+    torch.cuda.empty_cache()
+
+    def window(side, n):
+      torch.cuda.synchronize()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(n):
+        step(side)
+      e1.record()
+      torch.cuda.synchronize()
+      return 1e-3 * e0.elapsed_time(e1)
+
+    sides = ('A', 'B', 'B0')
+    iters = {}
+    for side in sides:
+      window(side, 3)  # warm-up: allocator, kernels loaded
+      per = window(side, 5) / 5
+      iters[side] = max(5, int(math.ceil(1.2 * args.min_window / per)))
+    times = {side: [] for side in sides}
+    for w in range(args.windows):
+      for side in sides:
+        sec = window(side, iters[side])
+        while sec < args.min_window:  # the calibration ran slow: a longer window, and this one is not counted
+          iters[side] = int(math.ceil(1.3 * iters[side] * args.min_window / sec))
+          sec = window(side, iters[side])
+        times[side].append(1e6 * sec / iters[side])
+        print('F=%d window %d %s: %.1f us per forward + backward (%d in %.3f s)' % (F, w, side, times[side][-1], iters[side], sec), flush=True)
+    med = {}
+    for side in sides:
+      v = sorted(times[side])
+      med[side] = 0.5 * (v[(len(v) - 1) // 2] + v[len(v) // 2])
+      row['%s_us' % side] = [round(x, 1) for x in times[side]]
+      row['%s_us_median_min_max' % side] = [round(med[side], 1), round(v[0], 1), round(v[-1], 1)]
+    row['pose_pass_us_median_B_minus_B0'] = round(med['B'] - med['B0'], 1)  # the two kernels, the host copy and its synchronisation
+    row['pose_pass_ns_per_pixel_and_source'] = round(1e3 * (med['B'] - med['B0']) / (F * H * W * S), 3)
+    row['speedup_median'] = round(med['A'] / med['B'], 2)
+    row['every_B_window_faster_than_every_A_window'] = max(times['B']) < min(times['A'])
+    ok = ok and row['every_B_window_faster_than_every_A_window']
+    out['frames'][str(F)] = row
+  out['every_B_window_faster_than_every_A_window'] = ok
+  line = json.dumps(out)
+  print(line)
+  if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+      f.write(line + '\n')
+  assert not missed, 'B\'s pose gradient is outside 4 x the yardstick of A (F, error / yardstick): %s' % (missed,)
+  return 0 if ok else 1
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--windows', type=int, default=4, help='windows per side and number of frames')
   ap.add_argument('--min-window', type=float, default=0.3, help='seconds of device time per window, at least')
   ap.add_argument('--frames', type=int, nargs='+', default=[1, 2])
   ap.add_argument('--out', help='also write the result line to this file')
+  ap.add_argument('--poses', action='store_true', help='the pose tensor requires a gradient on both sides (DESIGN 27; '
+                  '--out profiles/mvpose_bench_mi355x.json)')
   args = ap.parse_args()
+  if args.poses:
+    return main_poses(args)
 
   import torch
   from mode_hip import functional as HF
