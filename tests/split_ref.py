@@ -31,7 +31,10 @@ the first five sixths of the row (contract_columns); the columns beyond are repo
 
 The eval entries (convolution + folded eval BatchNorm (+ residual) (+ ReLU) in one launch) have a layer of their own at the end of this
 file: EVAL_CASES, eval_linear / eval_reference, the BatchNorm kinds and the epilogue mutants, shared by the host tier and
-tests/test_gpu_eval_precision.py."""
+tests/test_gpu_eval_precision.py.
+
+The training entries of the fp32 kernels have the last layer: GRAD32_CASES, grad32_roles, the structural faults of those kernels, shared
+by the host tier and tests/test_gpu_grad32_precision.py."""
 import collections
 import math
 
@@ -284,7 +287,8 @@ WGRAD_ROWS = {
 
 
 def _rows(case, t, stride=1):
-  h = WGRAD_ROWS.get((case.family, case.shape, case.kind))
+  fam = 'grad32/' + case.family if type(case).__name__ == 'GradCase' else case.family  # (GradCase, below: keys of its own)
+  h = WGRAD_ROWS.get((fam, case.shape, case.kind))
   return t if h is None else t.narrow(-2, 0, h * stride).contiguous()
 
 
@@ -488,6 +492,16 @@ def reference(case, role):
     emu = {k: v + role.acc.double() for k, v in emu.items()}
   T = min(mutant_size(case, role, m, emu[m], want, den) for m in muts) / 3.0
   return Ref(want, den, T, emu, muts)
+
+
+def with_acc(case, role, base):
+  """The Ref of a role that adds into `role.acc`, from the Ref `base` of the same operands without it (the operator is not evaluated
+  again: want, den and every emulation gain the tensor that is there; T is taken from them as always)."""
+  acc = role.acc.double()
+  want, den = base.want + acc, base.den + acc.abs()
+  emu = {k: v + acc for k, v in base.emu.items()}
+  T = min(mutant_size(case, role, m, emu[m], want, den) for m in base.mutants) / 3.0
+  return Ref(want, den, T, emu, base.mutants)
 
 
 def mutant_size(case, role, m, value, want, den):
@@ -785,4 +799,330 @@ def epilogue_mutants(case, lin, relu, with_add):
     hi = min(Co, 64)
     bad[:, 32:hi].narrow(-1, n - k, k).copy_(add[:, 0:hi - 32].narrow(-1, n - k, k))
     out['residual'] = epilogue64(base, shift_e, bad, relu)
+  return out
+
+
+# ================================================================================================ the fp32 gradient entries
+# The training-time entries of the fp32 kernels -- forward, input gradient, weight gradient of the layers the split kernels do not take
+# (1 x 1, stem, 32 -> 1 head, channel counts off the grid, stride 2 with 128 outputs) and of every layer under CONV_ARITH = 'f32' -- judged
+# under the three-piece T of the same inputs (arith 'bf16x6', unit 2^-24), as the fp32 inference entries are: their products are exact,
+# so what T holds them to is the accumulation and every tail, clamp and partial sum of the hand-written reductions.
+#
+# route: 'f32' -- the family's fp32 entries, reached through the public switches (tests/test_gpu_grad32_precision.py); 'default' -- the
+# roles the default arithmetic itself sends to the fp32 kernels (the SPLITPREC-NOT-JUDGED lines of tests/test_gpu_split_precision.py).
+GradCase = collections.namedtuple('GradCase', 'family shape kind arith route seed')
+
+G32_CONV3D_S1 = [(2, 16, 20, 5, 7, 33), (1, 32, 32, 6, 10, 40), (2, 20, 40, 5, 7, 33)]
+G32_CONV3D_S2 = [(2, 12, 24, 6, 10, 36), (3, 64, 128, 2, 4, 8)]
+G32_DECONV3D = [(2, 24, 40, 3, 5, 34), (2, 8, 16, 4, 4, 4)]
+G32_CONV3D_C1 = [(1, 20, 3, 5, 33), (2, 32, 6, 12, 40), (2, 32, 1, 1, 7)]  # (B, Ci, D, H, W): Co = 1, csrc/conv3d_c1.hip
+G32_CONV2D = [(2, 20, 40, 9, 40, 1), (1, 8, 8, 2, 3, 2), (2, 3, 5, 5, 70, 2)]
+G32_CONV2D_S2 = [(1, 20, 40, 10, 36), (2, 8, 8, 2, 4)]  # (B, Ci, Co, H, W): Conv2d3x3S2Function
+G32_CONV1X1 = [(2, 64, 64, 16, 32, 2), (1, 5, 7, 3, 12, 1), (2, 12, 200, 6, 8, 1), (2, 16, 24, 7, 16, 2), (1, 256, 128, 8, 16, 1)]  # (B, Ci, Co, H, W, s)
+G32_STEM = [(2, 20, 26, 70), (1, 32, 8, 8)]  # (B, Co, H, W): 3 -> Co, 7 x 7, stride 2
+# The gather kernels of csrc/sphere_conv.hip: the three general tables of SPHERE_GEN (type, ih, iw, B, ci, co, groups, stride) and the
+# integer tables of Conv2dTabledFunction ('table', k, stride, B, Ci, Co, H, W; padding k // 2)
+G32_SPHERE_GEN = SPHERE_GEN + [('table', 3, 2, 1, 5, 7, 9, 11), ('table', 5, 3, 1, 6, 4, 10, 13)]
+# the roles of the split cases that the default arithmetic runs on fp32 kernels
+G32_DEFAULT = [('conv3d_s1', (2, 16, 20, 5, 7, 33), ('input gradient',)), ('conv2d', (2, 16, 40, 7, 33, 1), ('input gradient',))]
+# The third role the split tier leaves out, the stride-2 FORWARD with 128 output channels, is no case: no kernel takes it.  The split
+# kernel stops at 64 output channels and so does the fp32 one -- mode_conv3d_fwd refuses it with an error (csrc/conv3d_f32_fwd.hip,
+# conv3d_s2: "more than 64 output channels"; the network has no such layer, its widest 3-D layer is 32 -> 64).  The GPU tier asserts the
+# refusal; the input gradient and the weight gradient of that shape run (the transposed kernel over 64 rows, the split-K partials).
+G32_NO_FORWARD = {('conv3d_s2', (3, 64, 128, 2, 4, 8))}
+G32_DEFAULT_ROLES = {(f, s): r for f, s, r in G32_DEFAULT}
+
+# Weight gradients shortened for the host condition (WGRAD_ROWS above: the same mechanism, the same reason), keyed 'grad32/<family>';
+# worst slice of torch's fp32 operator / T before the trim beside each entry, and with it.  Untrimmed and close: the stem's weight
+# gradient at (2, 20, 26, 70), the shape with the ragged tiles, at 0.52 / 0.46 / 0.55; everything else is at or under 0.52, the 1 x 1 roles
+# at 0.03 - 0.43, the gather kernels' weight gradients at 0.07 - 0.61 (1024 pixels at most: nothing to shorten there).
+WGRAD_ROWS.update({
+    ('grad32/conv3d_c1', (2, 32, 6, 12, 40), 'unit variance'): 4,            # 0.79 (4 rows: 0.47)
+    ('grad32/conv3d_c1', (2, 32, 6, 12, 40), 'six decades along a row'): 4,  # 1.58 (4 rows: 0.44)
+    ('grad32/conv3d_c1', (2, 32, 6, 12, 40), 'gradient-sized'): 4,           # 0.84 (4 rows: 0.43)
+    ('grad32/conv2d', (2, 20, 40, 9, 40, 1), 'unit variance'): 6,            # 0.62 - 0.70 (with 6 rows: 0.52)
+    ('grad32/conv2d', (2, 20, 40, 9, 40, 1), 'six decades along a row'): 6,  # (with 6 rows: 0.41)
+    ('grad32/conv2d', (2, 20, 40, 9, 40, 1), 'gradient-sized'): 6,           # (with 6 rows: 0.50)
+    ('grad32/conv3d_s1', (2, 20, 40, 5, 7, 33), 'unit variance'): 2,            # 0.99 (4 rows: 0.79; 2: 0.46)
+    ('grad32/conv3d_s1', (2, 20, 40, 5, 7, 33), 'six decades along a row'): 2,  # 1.95 (2 rows: 0.40)
+    ('grad32/conv3d_s1', (2, 20, 40, 5, 7, 33), 'gradient-sized'): 2,           # 1.03 (4 rows: 0.78; 2: 0.46)
+    ('grad32/deconv3d', (2, 24, 40, 3, 5, 34), 'unit variance'): 3,             # 0.69 (4 rows: 0.60; 3: 0.51)
+    ('grad32/deconv3d', (2, 24, 40, 3, 5, 34), 'six decades along a row'): 3,   # 0.84 (3 rows: 0.47)
+    ('grad32/deconv3d', (2, 24, 40, 3, 5, 34), 'gradient-sized'): 3,            # 0.69 (4 rows: 0.62; 3: 0.51)
+})
+G32_NO_CASE = set()  # (family, shape, kind) that cannot meet the host condition at any trim: none
+
+
+def _grad32_cases():
+  out = []
+  seed = 30000
+  fams = (('conv3d_s1', G32_CONV3D_S1), ('conv3d_s2', G32_CONV3D_S2), ('deconv3d', G32_DECONV3D), ('conv3d_c1', G32_CONV3D_C1),
+          ('conv2d', G32_CONV2D), ('conv2d_s2', G32_CONV2D_S2), ('conv1x1', G32_CONV1X1), ('conv_stem', G32_STEM),
+          ('sphere_gen', G32_SPHERE_GEN))
+  for fam, shapes in fams:
+    for shape in shapes:
+      seed += 10
+      for kind in KINDS:
+        if (fam, shape, kind) not in G32_NO_CASE:
+          out.append(GradCase(fam, shape, kind, 'bf16x6', 'f32', seed))
+  for fam, shape, names in G32_DEFAULT:
+    seed += 10
+    for kind in KINDS:
+      out.append(GradCase(fam, shape, kind, 'bf16x6', 'default', seed))
+  return out
+
+
+GRAD32_CASES = _grad32_cases()
+
+
+def grad32_case_id(c):
+  return 'grad32-%s-%s-%s-%s' % (c.family, 'x'.join(str(v) for v in c.shape), c.route, c.kind.replace(' ', '_'))
+
+
+def grad32_judges(family, shape, role_name, kind):
+  """What tests/test_gpu_split_precision.py appends to the line of a role it does not judge: the id of the default-route case that
+  judges it on the fp32 kernel it runs on, or that no kernel takes it, or nothing."""
+  if role_name == 'forward' and (family, shape) in G32_NO_FORWARD:
+    return ': no kernel does -- the operator refuses it, tests/test_gpu_grad32_precision.py asserts that'
+  if role_name.replace(' + acc', '') not in G32_DEFAULT_ROLES.get((family, shape), ()):
+    return ''
+  c = next(c for c in GRAD32_CASES if (c.family, c.shape, c.kind, c.route) == (family, shape, kind, 'default'))
+  if role_name.endswith(' + acc'):  # (functional adds the gradient that is there behind the fp32 entry: no form of its own)
+    return ': the fp32 entry judged as %s, then a separate add' % grad32_case_id(c)
+  return ': judged on the fp32 kernel as %s' % grad32_case_id(c)
+
+
+def grad32_roles(case):
+  """(roles, tensors) of a GradCase, in the order forward, input gradient, weight gradient, weight gradient + acc.  Operands as in
+  `roles`: forward a = x, b = w; input gradient a = gy, b = w; weight gradient a = gy, b = x (the transposed layer: a = x, b = gy, the
+  stride-2 kernel with the operands exchanged).  The weight gradient's output channels are axis 0 -- for Co = 1 the input channels, axis 1."""
+  fam, shape, stride, wchan = case.family, case.shape, 1, 0
+  want = ('forward', 'input gradient', 'weight gradient')
+  if fam == 'sphere_gen':
+    return _sphere_gen_roles(case)
+  if fam in ('conv3d_s1', 'conv3d_s2', 'conv3d_c1'):
+    B, Ci, Co, D, H, W = shape if fam != 'conv3d_c1' else (shape[0], shape[1], 1) + tuple(shape[2:])
+    stride = 2 if fam == 'conv3d_s2' else 1
+    xs, ws = (B, Ci, D, H, W), (Co, Ci, 3, 3, 3)
+    ys = (B, Co) + tuple((n - 1) // stride + 1 for n in (D, H, W))
+    fwd = lambda x, w: conv3d_fwd(x, w, stride)
+    bwd = lambda gy, w: conv3d_bwd_data(gy, w, xs, stride)
+    wgr = lambda gy, x: conv3d_bwd_weight(gy, x, (Co, Ci), stride)
+    wscale, wchan = (2.0 / (27 * Co))**0.5, 1 if Co == 1 else 0
+  elif fam == 'deconv3d':
+    B, cin, cout, D, H, W = shape
+    xs, ws, ys = (B, cin, D, H, W), (cin, cout, 3, 3, 3), (B, cout, 2 * D, 2 * H, 2 * W)
+    fwd = deconv3d_fwd
+    bwd = lambda g, w: conv3d_fwd(g, w, 2)
+    wgr = lambda x, g: conv3d_bwd_weight(x, g, (cin, cout), 2)
+    wscale = (2.0 / (27 * cin))**0.5 * 2
+  elif fam in ('conv2d', 'conv2d_s2', 'conv1x1', 'conv_stem'):
+    if fam == 'conv2d':
+      B, Ci, Co, H, W, dil = shape
+      k, pad = 3, dil
+    elif fam == 'conv2d_s2':
+      (B, Ci, Co, H, W), k, stride, pad, dil = shape, 3, 2, 1, 1
+    elif fam == 'conv1x1':
+      (B, Ci, Co, H, W, stride), k, pad, dil = shape, 1, 0, 1
+    else:
+      (B, Co, H, W), Ci, k, stride, pad, dil = shape, 3, 7, 2, 3, 1
+      want = ('forward', 'weight gradient')  # (the stem's input needs no gradient)
+    xs, ws = (B, Ci, H, W), (Co, Ci, k, k)
+    ys = (B, Co) + tuple((n + 2 * pad - dil * (k - 1) - 1) // stride + 1 for n in (H, W))
+    fwd = lambda x, w: F.conv2d(x, w, None, stride, pad, dil)
+    bwd = lambda gy, w: torch.nn.grad.conv2d_input(xs, w, gy, stride, pad, dil)
+    wgr = lambda gy, x: torch.nn.grad.conv2d_weight(x, ws, gy, stride, pad, dil)
+    wscale = (2.0 / (k * k * Ci))**0.5
+  else:
+    raise ValueError(fam)
+  if case.route == 'default':
+    want = G32_DEFAULT_ROLES[(fam, shape)]
+  if (fam, shape) in G32_NO_FORWARD:
+    want = tuple(n for n in want if n != 'forward')
+  kind, s = case.kind, case.seed
+  x = data(xs, s + 1, kind)
+  w = _randn(ws, s + 2, wscale)
+  gy = data(ys, s + 3, kind, gradient=True)
+  tensors = {'x': x, 'w': w, 'gy': gy}
+  last = len(xs) - 1
+  out = []
+  if 'forward' in want and kind != 'gradient-sized':
+    out.append(Role('forward', x, w, fwd, lambda: fwd(x, w), None, 1, last, ys[-1]))
+  if 'input gradient' in want:
+    out.append(Role('input gradient', gy, w, bwd, lambda: bwd(gy, w), None, 1, last, xs[-1]))
+  if 'weight gradient' in want:
+    if fam == 'deconv3d':
+      aw, bw = _rows(case, x), _rows(case, gy, 2)  # (the operands exchanged: x is the small one)
+    else:
+      aw, bw = _rows(case, gy), _rows(case, x, stride)
+    tensors['wgrad a'], tensors['wgrad b'] = aw, bw
+    out.append(Role('weight gradient', aw, bw, wgr, lambda: wgr(aw, bw), None, wchan, None, None))
+    acc = tensors['acc'] = _acc_for(wgr(aw.double(), bw.double()), kind, s + 4)
+    out.append(Role('weight gradient + acc', aw, bw, wgr, lambda: wgr(aw, bw) + acc, acc, wchan, None, None))
+  return out, tensors
+
+
+def int_table(H, W, k, pad):
+  """The integer sampling table of a k x k convolution with padding `pad` (functional.conv2d_table restated: tap (i, j) of the output
+  pixel whose table position is (h, w) reads input pixel (h + i - pad, w + j - pad); the operator indexes it at (h_out s, w_out s))."""
+  hh = torch.arange(H, dtype=torch.float32).view(H, 1).expand(H, W)
+  ww = torch.arange(W, dtype=torch.float32).view(1, W).expand(H, W)
+  planes = []
+  for i in range(k):
+    for j in range(k):
+      planes += [hh + float(i - pad), ww + float(j - pad)]
+  return torch.stack(planes, 0).unsqueeze(0).contiguous()
+
+
+def _sphere_gen_roles(case):
+  """The roles of _sphere_roles for any kernel size, stride and table: the operand of the forward and of the weight gradient is the
+  column sampled in float64 and rounded to fp32, that of the input gradient the adjoint-sampled output gradient, tap by tap; the exact
+  results come from the unrounded samples (oracle/sphere_conv_ref).  Input gradient and weight gradient both ADD into their output
+  (overwrite=False; the weight gradient always): each has a '+ acc' role."""
+  from oracle import mode_ref
+  from oracle import sphere_conv_ref as R
+  if case.shape[0] == 'table':
+    _, k, st, B, ci, co, H, W = case.shape
+    g, pad = 1, k // 2
+    pos = int_table(H, W, k, pad)
+  else:
+    typ, ih, iw, B, ci, co, g, st = case.shape
+    k, pad = 3, 1
+    pos = mode_ref.sphere_position(ih, iw, typ).contiguous()
+    H, W = pos.shape[2:]
+  K = k * k
+  Ho, Wo = R.out_size(H, k, st, pad, 1), R.out_size(W, k, st, pad, 1)
+  cig, cog, N = ci // g, co // g, Ho * Wo
+  kind, s = case.kind, case.seed
+  x = data((B, ci, H, W), s + 1, kind)
+  w = _randn((co, cig, k, k), s + 2, (2.0 / (K * cig))**0.5)
+  gy = data((B, co, Ho, Wo), s + 3, kind, gradient=True)
+  pos64 = pos.double()
+  geom = ((st, st), (pad, pad), (1, 1), g)
+  tensors = {'x': x, 'w': w, 'gy': gy, 'pos': pos, 'geom': geom}
+  col = R.im2col(x.double(), pos64, k, k, st, st, Ho, Wo).float().contiguous()  # (B, ci, K, Ho, Wo)
+  col_abs = R.im2col(x.double().abs(), pos64, k, k, st, st, Ho, Wo)
+
+  def fwd(c, w_):
+    return torch.einsum('gok,bgkn->bgon', w_.reshape(g, cog, cig * K), c.reshape(B, g, cig * K, N)).reshape(B, co, Ho, Wo)
+
+  def wgr(gy_, c):
+    return torch.einsum('bgon,bgkn->gok', gy_.reshape(B, g, cog, N), c.reshape(B, g, cig * K, N)).reshape(co, cig, k, k)
+
+  def adjoint(g_):
+    return torch.stack([R.col2im_scatter(g_[:, :, None], pos64[:, 2 * t:2 * t + 2], H, W, 1, 1, st, st) for t in range(K)], 2)
+
+  def bwd(G_, w_):
+    return torch.einsum('gock,bgokn->bgcn', w_.reshape(g, cog, cig, K), G_.reshape(B, g, cog, K, H * W)).reshape(B, ci, H, W)
+
+  x64, w64, gy64 = x.double(), w.double(), gy.double()
+  grads = {}
+
+  def exact_grads():
+    if not grads:
+      grads['gx'], grads['gw'] = R.backward(x64, pos64, w64, gy64, *geom)
+    return grads
+
+  out = []
+  if kind != 'gradient-sized':
+    out.append(Role('forward', col, w, fwd, lambda: fwd(col, w), None, 1, 3, Wo, lambda: R.forward(x64, pos64, w64, *geom), (col_abs, w64.abs())))
+  G, G_abs = adjoint(gy64).float().contiguous(), adjoint(gy64.abs())
+  acc_x = tensors['acc gx'] = _acc_for(bwd(G.double(), w64), kind, s + 4)
+  out.append(Role('input gradient', G, w, bwd, lambda: bwd(G, w), None, 1, 3, W, lambda: exact_grads()['gx'], (G_abs, w64.abs())))
+  if case.shape[0] != 'table':  # (Conv2dTabledFunction overwrites its input gradient: that route has no such form)
+    out.append(Role('input gradient + acc', G, w, bwd, lambda: bwd(G, w) + acc_x, acc_x, 1, 3, W, lambda: exact_grads()['gx'], (G_abs, w64.abs())))
+  acc_w = tensors['acc'] = _acc_for(wgr(gy64, col.double()), kind, s + 5)
+  out.append(Role('weight gradient', gy, col, wgr, lambda: wgr(gy, col), None, 0, None, None, lambda: exact_grads()['gw'], (gy64.abs(), col_abs)))
+  out.append(Role('weight gradient + acc', gy, col, wgr, lambda: wgr(gy, col) + acc_w, acc_w, 0, None, None, lambda: exact_grads()['gw'],
+                  (gy64.abs(), col_abs)))
+  return out, tensors
+
+
+# The structural faults these kernels can commit (the host tier shows each exceeds T; the admit-factors of the older bounds are taken
+# from them): a SUBSET OF THE TERMS of the reduction left out for one block of output channels.  Every operator is bilinear, so the lost
+# terms are the operator on an operand masked to them:
+#   'reduction tail'      forward / input gradient: the last K mod 8 reduction channels (a whole step of 8 where K is a multiple) of one
+#                         32-row block of output channels meet zero instead of their weight;
+#   'lost K-slice'        weight gradients: one of four interleaved 32-pixel K-slices left out for one 64-row block (one wave's share,
+#                         or one split-K partial);
+#   'last pixel segment'  weight gradients: the last, partial 32-pixel segment of the last sample left out of the sum (64-row block);
+#   'dropped tap'         conv3d_c1, input and weight gradient: the middle tap of the 27 dropped for one input channel.
+def column_fault_resolvable(role, t):
+  """Whether a fault confined to the last partial column tile (n % 32 columns, 8 where that is 0) CAN exceed T in the slice that holds it:
+  a mutant is 3 T over the whole tensor, a slice of which a fraction f is faulty shows 3 T sqrt(f), so f must exceed 1 / 9.  Outputs of
+  a few hundred elements (Co = 1 at 3 x 5 x 33: one column is 15 elements of a 225-element slice) cannot resolve a column."""
+  n = role.cols
+  k = n % 32 or 8
+  g = max(1, -(-MIN_SLICE // max(t.numel() // t.shape[role.col_axis], 1)))
+  starts = list(range(0, n, g))
+  if len(starts) > 1 and n - starts[-1] < g:
+    starts.pop()
+  return 9 * k > n - starts[-1]
+
+
+def _out_block(role, like, rows):
+  C = like.shape[role.chan_axis]
+  return min(rows, max(1, C // 2)) if C > 1 else 1
+
+
+def structural_faults(case, role, ref):
+  """{name: (value, block)}: the faithful emulation with one structural fault in the leading `block` indices of role.chan_axis."""
+  if case.family == 'sphere_gen':
+    return {}  # (the gather kernels reduce tap by tap over a table: the tails of the GEMM kernels are not theirs)
+  a, b = role.a.double(), role.b.double()
+  base = ref.emu[None]
+  out = {}
+
+  def lose(name, a_lost, b_lost, rows):
+    lost = role.op(a_lost, b_lost)
+    n = _out_block(role, base, rows)
+    v = base.clone()
+    v.narrow(role.chan_axis, 0, n).sub_(lost.narrow(role.chan_axis, 0, n))
+    out[name] = (v, n)
+
+  if role.name in ('forward', 'input gradient'):
+    K = a.shape[1]
+    t = K % 8 or min(8, K)
+    m = torch.zeros_like(a)
+    m[:, K - t:] = a[:, K - t:]
+    lose('reduction tail', m, b, 32)
+    if case.family == 'conv3d_c1' and role.name == 'input gradient':
+      wl = torch.zeros_like(b)
+      c = b.shape[1] // 2
+      wl[:, c, 1, 1, 1] = b[:, c, 1, 1, 1]
+      lost = role.op(a, wl)  # (touches input channel c alone)
+      out['dropped tap'] = (base - lost, None)
+  else:
+    flat = a.reshape(a.shape[0], a.shape[1], -1)
+    npix = flat.shape[2]
+    idx = torch.arange(npix)
+    # every fourth pixel (K-step), the loudest of the four slices in the operand: on the smallest cases (7 pixels, half of them zero
+    # under relu) a slice can hold next to nothing, and a lost nothing is no fault
+    r = max(range(4), key=lambda q: float(flat[:, :, idx % 4 == q].abs().sum()))
+    m = torch.zeros_like(flat)
+    m[:, :, idx % 4 == r] = flat[:, :, idx % 4 == r]
+    lose('lost K-slice', m.reshape(a.shape), b, 64)
+    # (not on the six-decades kind: the end of a sample is the end of a row there, its 1 - 31 pixels hold the row's smallest columns --
+    # 1e-5 .. 1e-6 of the sum, 0.03 - 0.7 units against a T of 3.5 - 6.7: nothing relative to the sum can see them, and nothing needs to)
+    if case.kind != 'six decades along a row':
+      t = npix % 32 or min(32, npix)
+      m = torch.zeros_like(flat)
+      m[-1, :, npix - t:] = flat[-1, :, npix - t:]
+      lose('last pixel segment', m.reshape(a.shape), b, 64)
+    if case.family == 'conv3d_c1':
+      v = base.clone()
+      c = v.shape[1] // 2
+      v[:, c, 1, 1, 1] = role.acc.double()[:, c, 1, 1, 1] if role.acc is not None else 0.0  # (what was there, or nothing)
+      out['dropped tap'] = (v, None)
+  return out
+
+
+def grad32_references(case, roles_):
+  """[(role, Ref)] of a GradCase: a '+ acc' role shares the emulations of the role before it (the same operands)."""
+  out = []
+  for role in roles_:
+    if role.acc is not None and out and out[-1][0].a is role.a and out[-1][0].b is role.b and out[-1][0].acc is None:
+      out.append((role, with_acc(case, role, out[-1][1])))
+    else:
+      out.append((role, reference(case, role)))
   return out

@@ -10,7 +10,7 @@ pieces also an operand scaled 2^4 too low -- gives on the same inputs (computed 
 tests/test_split_ref_host.py shows on the CPU that a faithful kernel with an fp32 accumulator stays below T / 1.5 and a mutant confined to
 one channel or one column tile exceeds T, on every one of these cases.  A role whose layer the split kernel does not take at that shape
 (an input gradient over 20 or 40 output channels, a spherical forward with 6 input channels per group -- which the split ENTRY runs on
-its fp32 kernels --, ...) is not judged here: it prints a line, and the roles that ARE judged are written out per shape (JUDGED) and
+its fp32 kernels --, ...) is not judged here: it prints a line (with the case of tests/test_gpu_grad32_precision.py that judges it), and the roles that ARE judged are written out per shape (JUDGED) and
 asserted, so that a probe or planner that starts to say no cannot quietly empty a case.
 
 What the spherical entries are judged on: the windowed forward at 16 -> 32 and 128 -> 128 (64 x 128 table), 32 -> 64 with groups 2
@@ -221,9 +221,10 @@ COMPUTE = ('mode_conv', 'mode_deconv', 'mode_sphere_conv')  # (maximum passes, p
 
 # The roles of each shape that reach a split kernel, written out: a `*_supported` probe or a planner that starts to say no must fail the
 # test, not quietly empty it.  (The 'gradient-sized' kind has no forward, the spherical six-decades kind a weight gradient at 16 x 32 only:
-# tests/split_ref.py.)  What is NOT here runs on fp32 kernels and is not judged -- each such role prints a line:
-#   3-D 16 -> 20 and 3 x 3 16 -> 40: the input gradient reduces over 20 / 40 channels, off the kernels' 8 / 16 grid;
-#   stride-2 64 -> 128: the forward's 128 output channels;
+# tests/split_ref.py.)  What is NOT here is not judged HERE -- each such role prints a line, which names the case of
+# tests/test_gpu_grad32_precision.py that judges it on the fp32 kernel it runs on, where there is one:
+#   3-D 16 -> 20 and 3 x 3 16 -> 40: the input gradient reduces over 20 / 40 channels, off the kernels' 8 / 16 grid (fp32 kernels);
+#   stride-2 64 -> 128: the forward's 128 output channels, which NO kernel takes (the operator raises; asserted there);
 #   sphere: see SPHERE in tests/split_ref.py (compact tiles, 16 input channels per group, an adjoint plan).
 ALL4 = ('forward', 'input gradient', 'input gradient + acc', 'weight gradient')
 ALL3 = ('forward', 'input gradient', 'weight gradient')
@@ -286,7 +287,8 @@ def test_split_kernel_keeps_the_componentwise_contract(case, switches, recorder)
   for role in roles:
     entry, run = _launch(case, role, tensors)
     if entry is None:
-      print('SPLITPREC-NOT-JUDGED | %s | %s | %s | %s | %s | no split kernel takes this role at this shape' % (case.family, shape, role.name, case.arith, case.kind))
+      print('SPLITPREC-NOT-JUDGED | %s | %s | %s | %s | %s | no split kernel takes this role at this shape%s' %
+            (case.family, shape, role.name, case.arith, case.kind, S.grad32_judges(case.family, case.shape, role.name, case.kind)))
       continue
     del recorder.names[:]
     got = run()

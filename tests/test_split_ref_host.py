@@ -11,7 +11,12 @@ For every shared case and role, from the case's own inputs:
 Pieces and the scale are checked bit for bit against their definitions in csrc/split_arith.h.
 
 The eval entries (tests/test_gpu_eval_precision.py) get the same three conditions for every case and epilogue variant, the three epilogue
-mutants on top, and the factors by which the bounds of the older eval tests admit a lost product and a stale fold (end of this file)."""
+mutants on top, and the factors by which the bounds of the older eval tests admit a lost product and a stale fold.
+
+The training entries of the fp32 kernels (tests/test_gpu_grad32_precision.py) get the three conditions for every role of
+GRAD32_CASES, the structural faults of those kernels on top (end of this file), and -- in
+test_the_bounds_of_the_older_tests_admit_every_single_pair_mutant -- the factors by which the max-abs bounds of tests/test_gpu_kernels.py
+admit each of those faults in a quiet block of channels."""
 import numpy as np
 import pytest
 import torch
@@ -158,6 +163,35 @@ def test_the_bounds_of_the_older_tests_admit_every_single_pair_mutant():
       print('%-16s %-14s max error %.2e, old bound %.2e (x %.0f) | componentwise rms %.2f, T %.2f' % (name, m, e, bound, bound / e, whole, T))
       assert e <= bound / 4, (name, m)  # admitted, faithful and mutant alike
       assert (whole <= T / 1.5) if m is None else (whole >= 2.5 * T), (name, m, whole, T)
+  # The fp32 training entries: tests/test_gpu_kernels.py holds an output or an input gradient to 2e-6 (reduction terms)
+  # max(1, max|ref|) and a weight gradient to 2e-5 max(1, max|gw|), relative to the tensor's LARGEST element.  One line per family and
+  # structural fault (S.structural_faults, on the family's first unit-variance case): the factor by which that bound admits the fault
+  # when the output channels it sits in are quiet -- scaled by 2^-20, a power of two: want, den and the fault scale exactly, so the
+  # componentwise figure is the one the host tier asserts to exceed T, unchanged.  The fp32 accumulator's own error rides along at full size.
+  quiet = 2.0**-20
+  for fam in ('conv3d_s1', 'conv3d_s2', 'deconv3d', 'conv3d_c1', 'conv2d', 'conv2d_s2', 'conv1x1', 'conv_stem'):
+    case = next(c for c in S.GRAD32_CASES if c.family == fam and c.kind == 'unit variance' and c.route == 'f32')
+    lines = 0
+    for role, ref in S.grad32_references(case, S.grad32_roles(case)[0]):
+      if role.acc is not None:
+        continue
+      noise = float((role.plain32().double() - ref.want).abs().max())
+      C = ref.want.shape[role.chan_axis]
+      terms = role.b.numel() // role.b.shape[0 if role.name == 'forward' and fam != 'deconv3d' else 1]
+      if fam == 'deconv3d':
+        terms = 27 * role.a.shape[1]
+      for name, (value, n) in S.structural_faults(case, role, ref).items():
+        if n is not None and n >= C:
+          continue  # (the block is the whole tensor: nothing louder beside it)
+        loud = ref.want.narrow(role.chan_axis, n, C - n) if n is not None else ref.want
+        bound = (2e-5 if role.name == 'weight gradient' else 2e-6 * terms) * max(1.0, float(loud.abs().max()))
+        e = float((value - ref.emu[None]).abs().max()) * quiet + noise
+        worst = S.measure(case, role, ref, value)[1].rms
+        print('%-10s %-16s %-20s in a block 2^-20 of the rest: max error %.2e, old bound %.2e (x %.0f) | componentwise worst slice %.3g, T %.2f' %
+              (fam, role.name, name, e, bound, bound / e, worst, ref.T))
+        assert bound / e > 1 and worst > ref.T, (fam, role.name, name)
+        lines += 1
+    assert lines, fam
 
 
 # ------------------------------------------------------------------------------------------------ the eval entries
@@ -249,3 +283,39 @@ def test_the_bounds_of_the_older_eval_tests_admit_the_mutants(fam, shape, arith)
           assert e < 1e-4, (name, e)  # admitted by the absolute bound
         if name != 'stale fold 1e-5' and arith == 'bf16x6':
           assert e <= bounds['2^-22 sqrt(terms) max'], (name, e)
+
+
+# ------------------------------------------------------------------------------------------------ the fp32 gradient entries
+def _worst_in(case, role, ref, value):
+  return S.measure(case, role, ref, value)[1]
+
+
+@pytest.mark.parametrize('case', S.GRAD32_CASES, ids=S.grad32_case_id)
+def test_grad32_faithful_passes_and_every_mutant_fails(case):
+  """The three conditions of test_faithful_passes_and_every_mutant_fails for every role of every case tests/test_gpu_grad32_precision.py
+  runs on the fp32 kernels (judged under the three-piece T of the same inputs), and: each structural fault these kernels can commit
+  (S.structural_faults: a reduction tail that meets zero, a lost K-slice, a lost last pixel segment, a dropped tap -- all confined to one
+  block of output channels) has a worst slice > T."""
+  roles, _ = S.grad32_roles(case)
+  assert roles
+  for role, ref in S.grad32_references(case, roles):
+    tag = (S.grad32_case_id(case), role.name)
+    assert ref.T > 0, tag
+    plain = role.plain32().double()
+    whole, worst, _ = S.measure(case, role, ref, ref.emu[None] + (plain - ref.want))
+    line = 'GRAD32HOST %-58s %-22s T %.3f | faithful + fp32: rms %.3f worst slice %.3f (/T %.2f; axis %d @ %d)' % (
+        tag + (ref.T, whole, worst.rms, worst.rms / ref.T, worst.axis, worst.index))
+    assert worst.rms <= ref.T / 1.5 and whole <= ref.T / 1.5, line
+    for m in ref.mutants:
+      assert S.mutant_size(case, role, m, ref.emu[m], ref.want, ref.den) >= 3 * ref.T * (1 - 1e-12), (tag, m)
+      for where in ('channel', 'columns'):
+        if where == 'columns' and (role.col_axis is None or not S.column_fault_resolvable(role, ref.want)):
+          continue
+        w = _worst_in(case, role, ref, _localised(case, role, ref, m, where))
+        line += ' | %s in one %s: %.2f' % ('x'.join(str(v) for v in m), where, w.rms)
+        assert w.rms > ref.T, (tag, m, where, w, ref.T)
+    for name, (value, _) in S.structural_faults(case, role, ref).items():
+      w = _worst_in(case, role, ref, value)
+      line += ' | %s: %.3g' % (name, w.rms)
+      assert w.rms > ref.T, (tag, name, w, ref.T)
+    print(line)
