@@ -20,15 +20,18 @@
 // The reduction is the scheme of metrics_internal.h with twelve statistics: a thread walks its pixels in ascending order, a fixed
 // butterfly, the waves in index order, one slab column per workgroup, and a second launch folds the columns in index order.
 // No atomics; the same inputs give the same bits on any stream.
-#include "mode_hip_mvphoto.h"
+#include "mode_hip_mvvis.h"
 #include "mv_photometric_internal.h"
 
 namespace {
 
 // grid = F * tiles.  Block col leaves its twelve statistics in column col of the slab and the winners of its tile in win.
+// MASKED (include/mode_hip_mvvis.h): a pixel is valid for source s iff it is valid there and vis (F, S, H, W) != 0.
+template <bool MASKED>
 __global__ __launch_bounds__(NT) void mvphoto_fwd_kernel(const float* __restrict__ ref, const float* __restrict__ src,
                                                          const float* __restrict__ depth, Poses poses, int S, int H, int W, int tiles_w,
-                                                         int tiles, Prm p, unsigned char* __restrict__ win, double* __restrict__ slab) {
+                                                         int tiles, Prm p, const unsigned char* __restrict__ vis,
+                                                         unsigned char* __restrict__ win, double* __restrict__ slab) {
   using St = Stage<1>;
   __shared__ St s;
   __shared__ double sh[NT / 64][kS];
@@ -50,6 +53,19 @@ __global__ __launch_bounds__(NT) void mvphoto_fwd_kernel(const float* __restrict
   for (int sv = 0; sv < S; ++sv) {
     if (sv > 0) __syncthreads();  // every window of the previous source has been read
     stage_src<1, false>(s, src + 3 * HW * ((long long)f * S + sv), poses.p[sv], H, W, p, n, dep, nullptr);
+    if (MASKED) {  // a thread masks the validity bytes it has just written itself: no barrier in between
+      const unsigned char* m = vis + HW * ((long long)f * S + sv);
+#pragma unroll
+      for (int k = 0; k < St::PER_THREAD; ++k) {
+        const int i = threadIdx.x + k * NT;
+        if (i >= St::N) continue;
+        const int r = i / St::RW, c = i - r * St::RW;
+        int h = (h0 - 1 + r) % H;
+        h = h < 0 ? h + H : h;
+        const int w = w0 - 1 + c;
+        if (w >= 0 && w < W && s.ok[i] && !m[h * W + w]) s.ok[i] = 0;  // (columns outside [0, W) are invalid already)
+      }
+    }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
@@ -217,6 +233,27 @@ __global__ __launch_bounds__(NT) void mvphoto_bwd_kernel(const float* __restrict
   }
 }
 
+// The forward entry and its masked form: the same checks, the same two launches.
+template <bool MASKED>
+int loss_fwd(const char* who, const float* ref, const float* src, const float* depth, const double* poses, int S, int F, int H, int W,
+             const mode_photometric_params* params, void* workspace, size_t workspace_bytes, const unsigned char* vis, unsigned char* win,
+             double* stats, float* loss, mode_stream_t stream) {
+  Prm p;
+  Poses ps;
+  int tiles_w, tiles;
+  MODE_REQUIRE(win && stats && loss && (vis || !MASKED), MODE_ERR_BAD_ARG, "%s: null pointer", who);
+  int rc = check_common(who, ref, src, depth, poses, S, F, H, W, params, p, ps, tiles_w, tiles);
+  if (rc != MODE_OK) return rc;
+  rc = check_workspace(who, workspace, workspace_bytes, mode_mvphoto_workspace_bytes(S, F, H, W));
+  if (rc != MODE_OK) return rc;
+  double* slab = static_cast<double*>(workspace);
+  hipStream_t st = mode::as_stream(stream);
+  const int ncols = F * tiles;
+  hipLaunchKernelGGL(mvphoto_fwd_kernel<MASKED>, dim3(ncols), dim3(NT), 0, st, ref, src, depth, ps, S, H, W, tiles_w, tiles, p, vis, win, slab);
+  hipLaunchKernelGGL(mvphoto_final_kernel, dim3(1), dim3(NT), 0, st, slab, ncols, F, H, W, p, stats, loss);
+  return mode::check_launch(who);
+}
+
 }  // namespace
 
 extern "C" int mode_mvphoto_version(void) { return MODE_MVPHOTO_VERSION; }
@@ -229,21 +266,15 @@ extern "C" size_t mode_mvphoto_workspace_bytes(int S, int F, int H, int W) {
 extern "C" int mode_mvphoto_loss_fwd(const float* ref, const float* src, const float* depth, const double* poses, int S, int F, int H, int W,
                                      const mode_photometric_params* params, void* workspace, size_t workspace_bytes, unsigned char* win,
                                      double* stats, float* loss, mode_stream_t stream) {
-  const char* who = "mode_mvphoto_loss_fwd";
-  Prm p;
-  Poses ps;
-  int tiles_w, tiles;
-  MODE_REQUIRE(win && stats && loss, MODE_ERR_BAD_ARG, "%s: null pointer", who);
-  int rc = check_common(who, ref, src, depth, poses, S, F, H, W, params, p, ps, tiles_w, tiles);
-  if (rc != MODE_OK) return rc;
-  rc = check_workspace(who, workspace, workspace_bytes, mode_mvphoto_workspace_bytes(S, F, H, W));
-  if (rc != MODE_OK) return rc;
-  double* slab = static_cast<double*>(workspace);
-  hipStream_t st = mode::as_stream(stream);
-  const int ncols = F * tiles;
-  hipLaunchKernelGGL(mvphoto_fwd_kernel, dim3(ncols), dim3(NT), 0, st, ref, src, depth, ps, S, H, W, tiles_w, tiles, p, win, slab);
-  hipLaunchKernelGGL(mvphoto_final_kernel, dim3(1), dim3(NT), 0, st, slab, ncols, F, H, W, p, stats, loss);
-  return mode::check_launch(who);
+  return loss_fwd<false>("mode_mvphoto_loss_fwd", ref, src, depth, poses, S, F, H, W, params, workspace, workspace_bytes, nullptr, win, stats,
+                         loss, stream);
+}
+
+extern "C" int mode_mvphoto_loss_fwd_masked(const float* ref, const float* src, const float* depth, const double* poses, int S, int F, int H,
+                                            int W, const mode_photometric_params* params, void* workspace, size_t workspace_bytes,
+                                            const unsigned char* vis, unsigned char* win, double* stats, float* loss, mode_stream_t stream) {
+  return loss_fwd<true>("mode_mvphoto_loss_fwd_masked", ref, src, depth, poses, S, F, H, W, params, workspace, workspace_bytes, vis, win,
+                        stats, loss, stream);
 }
 
 extern "C" int mode_mvphoto_loss_bwd(const float* ref, const float* src, const float* depth, const double* poses, int S, int F, int H, int W,

@@ -31,7 +31,10 @@ ABI_VERSION = CONSTANTS['MODE_HIP_ABI_VERSION']
 EXTENSIONS = (('SELFSUP', 'mode_hip_selfsup.h', 'MODE_SELFSUP_VERSION', 'mode_selfsup_version'),
               ('MVPHOTO', 'mode_hip_mvphoto.h', 'MODE_MVPHOTO_VERSION', 'mode_mvphoto_version'),
               ('MVPOSE', 'mode_hip_mvpose.h', 'MODE_MVPOSE_VERSION', 'mode_mvpose_version'))
-for _name, _file, _const, _ in EXTENSIONS:
+# EXTENSIONS is pinned to those three rows by the fourth header's tests; the rows since stand in a second tuple that the same two
+# loops walk after the first.  The next header is one more row here.
+EXTENSIONS_2 = (('MVVIS', 'mode_hip_mvvis.h', 'MODE_MVVIS_VERSION', 'mode_mvvis_version'),)
+for _name, _file, _const, _ in EXTENSIONS + EXTENSIONS_2:
   _h = _header.load(os.path.join(os.path.dirname(_header.PATH), _file))
   globals().update({_name: _h, _name + '_VERSION': _h.constants[_const], _name + '_LAUNCHING': frozenset(
       n for n, (_, params) in _h.prototypes.items() if any(t == _header.STREAM for t, _ in params))})
@@ -57,7 +60,7 @@ def lib():
         if have != ABI_VERSION:
           raise RuntimeError('libmode_hip.so has ABI version %d, this binding needs %d: rebuild it (python '
                              'mode-2022_amd/mode_hip/build.py)' % (have, ABI_VERSION))
-        for ext, file, _, version_fn in EXTENSIONS:
+        for ext, file, _, version_fn in EXTENSIONS + EXTENSIONS_2:
           have = getattr(handle, version_fn)() if hasattr(handle, version_fn) else None
           want = globals()[ext + '_VERSION']  # read now, not at import
           if have != want:

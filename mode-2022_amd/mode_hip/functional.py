@@ -2222,7 +2222,7 @@ class MvPhotometricLossFunction(torch.autograd.Function):
   into depth only (the images are data); the statistics and the winners carry none."""
 
   @staticmethod
-  def forward(ctx, ref, src, depth, poses, prm):
+  def forward(ctx, ref, src, depth, poses, prm, masks=None):
     F, S, _, H, W = src.shape
     d = depth.reshape(F, H, W).contiguous()
     require_f32c(ref, src, d)
@@ -2232,12 +2232,18 @@ class MvPhotometricLossFunction(torch.autograd.Function):
     win = torch.empty((F, H, W), dtype=torch.uint8, device=dev)
     pp = poses.ctypes.data_as(ctypes.c_void_p)
     nbytes = 4 * (ref.numel() + src.numel() + d.numel()) + win.numel()
-    with torch.cuda.device_of(ref), profiling.region('mv_photometric_loss_fwd', nbytes, 0, dev):
-      ws = torch.empty(max(lib().mode_mvphoto_workspace_bytes(S, F, H, W) // 8, 1), dtype=torch.float64, device=dev)
-      _call('mode_mvphoto_loss_fwd', ptr(ref), ptr(src), ptr(d), pp, S, F, H, W, ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(win),
-            ptr(stats), ptr(loss), stream_of(ref))
+    if masks is None:
+      with torch.cuda.device_of(ref), profiling.region('mv_photometric_loss_fwd', nbytes, 0, dev):
+        ws = torch.empty(max(lib().mode_mvphoto_workspace_bytes(S, F, H, W) // 8, 1), dtype=torch.float64, device=dev)
+        _call('mode_mvphoto_loss_fwd', ptr(ref), ptr(src), ptr(d), pp, S, F, H, W, ctypes.byref(prm), ptr(ws), ws.numel() * 8, ptr(win),
+              ptr(stats), ptr(loss), stream_of(ref))
+    else:  # the same loss over the pixels that each source sees; win and stats then serve the two backward entries as they are
+      with torch.cuda.device_of(ref), profiling.region('mv_photometric_loss_fwd', nbytes + masks.numel(), 0, dev):
+        ws = torch.empty(max(lib().mode_mvphoto_workspace_bytes(S, F, H, W) // 8, 1), dtype=torch.float64, device=dev)
+        _call('mode_mvphoto_loss_fwd_masked', ptr(ref), ptr(src), ptr(d), pp, S, F, H, W, ctypes.byref(prm), ptr(ws), ws.numel() * 8,
+              ptr(masks), ptr(win), ptr(stats), ptr(loss), stream_of(ref))
     ctx.save_for_backward(ref, src, d, win, stats)
-    ctx.prm, ctx.poses, ctx.shape = prm, poses, depth.shape
+    ctx.prm, ctx.poses, ctx.shape, ctx.extra = prm, poses, depth.shape, () if masks is None else (None,)
     ctx.mark_non_differentiable(stats, win)
     return loss.reshape(()), stats, win
 
@@ -2251,7 +2257,7 @@ class MvPhotometricLossFunction(torch.autograd.Function):
     with torch.cuda.device_of(ref), profiling.region('mv_photometric_loss_bwd', nbytes, 0, ref.device):
       _call('mode_mvphoto_loss_bwd', ptr(ref), ptr(src), ptr(d), ctx.poses.ctypes.data_as(ctypes.c_void_p), S, F, H, W, ctypes.byref(ctx.prm),
             ptr(win), ptr(stats), ptr(gl), ptr(gdepth), stream_of(ref))
-    return None, None, gdepth.view(ctx.shape), None, None
+    return (None, None, gdepth.view(ctx.shape), None, None) + ctx.extra
 
 
 class MvPhotometricPoseLossFunction(torch.autograd.Function):
@@ -2261,10 +2267,10 @@ class MvPhotometricPoseLossFunction(torch.autograd.Function):
   backward synchronises."""
 
   @staticmethod
-  def forward(ctx, ref, src, depth, poses, prm):
+  def forward(ctx, ref, src, depth, poses, prm, masks=None):
     import numpy as np
     ctx.pose_shape = poses.shape
-    return MvPhotometricLossFunction.forward(ctx, ref, src, depth, np.ascontiguousarray(poses.detach().numpy().reshape(-1, 12)), prm)
+    return MvPhotometricLossFunction.forward(ctx, ref, src, depth, np.ascontiguousarray(poses.detach().numpy().reshape(-1, 12)), prm, masks)
 
   @staticmethod
   def backward(ctx, gloss, _gstats, _gwin):
@@ -2282,10 +2288,11 @@ class MvPhotometricPoseLossFunction(torch.autograd.Function):
         _call('mode_mvpose_grad', ptr(ref), ptr(src), ptr(d), ctx.poses.ctypes.data_as(ctypes.c_void_p), S, F, H, W, ctypes.byref(ctx.prm),
               ptr(win), ptr(stats), ptr(gl), ptr(ws), ws.numel() * 8, ptr(out), stream_of(ref))
       gposes = out.cpu().view(ctx.pose_shape)
-    return None, None, gdepth, gposes, None
+    return (None, None, gdepth, gposes, None) + ctx.extra
 
 
-def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False, return_win=False):
+def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, mean=None, std=None, return_stats=False, return_win=False,
+                        masks=None):
   """The self-supervised loss of a depth map against other panoramas of known pose (include/mode_hip_mvphoto.h has the
   definition): ref (F, 3, H, W) is the Cassini panorama the depth map belongs to, src (F, S, 3, H, W) are S = 1 .. 8 other panoramas of
   the same scene, both normalised as the model takes them (mean / std, default dataloader.preprocess.imagenet_stats); depth (F, 1, H, W)
@@ -2301,7 +2308,11 @@ def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, m
   d loss / d A in the first three columns of each 3 x 4 table and d loss / d o in the fourth.  That gradient comes back to the host,
   one device-to-host copy, so backward() then synchronises; every other form of poses runs exactly as before.  The gradient is
   one-sided where v is an integer (exactly rectified poses: the right camera of the reference's own pair), and a source that wins
-  no window gets an exactly zero row: calibrate a source at a time, or only sources that are comparably off."""
+  no window gets an exactly zero row: calibrate a source at a time, or only sources that are comparably off.
+
+  Visibility (include/mode_hip_mvvis.h): masks is a (F, S, H, W) uint8 device tensor, e.g. HF.mv_visibility(depth.detach(),
+  poses); a pixel then counts as valid for source s only where masks[f, s, h, w] != 0, so a source wins a window only if it sees all
+  nine of its pixels.  The masks are constants of the gradient; the gradients to the depth and to a pose tensor run as without."""
   import numpy as np
   require_gpu(ref, src, depth)
   if ref.dim() != 4 or ref.shape[1] != 3:
@@ -2326,8 +2337,15 @@ def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, m
     if poses.shape[0] != S:
       raise ValueError('mv_photometric_loss: %d poses for %d source views' % (poses.shape[0], S))
   prm = _photometric_params(0, (), alpha, lam, beta, mean, std)
-  loss, stats, win = (MvPhotometricPoseLossFunction if learned else MvPhotometricLossFunction).apply(ref.contiguous(), src.contiguous(), depth,
-                                                                                                   poses, prm)
+  fn = MvPhotometricPoseLossFunction if learned else MvPhotometricLossFunction
+  if masks is None:
+    loss, stats, win = fn.apply(ref.contiguous(), src.contiguous(), depth, poses, prm)
+  else:
+    require_gpu(masks)
+    if masks.dtype != torch.uint8 or tuple(masks.shape) != (F, S, H, W):
+      raise ValueError('mv_photometric_loss: masks must be a (F, S, H, W) = %s uint8 tensor (HF.mv_visibility), got %s %s' % (
+          (F, S, H, W), masks.dtype, tuple(masks.shape)))
+    loss, stats, win = fn.apply(ref.contiguous(), src.contiguous(), depth, poses, prm, masks.contiguous())
   out = (loss,)
   if return_stats:
     smooth = stats[2] / (F * H * (W - 1)) + stats[3] / (F * H * W)
@@ -2335,6 +2353,53 @@ def mv_photometric_loss(ref, src, depth, poses, alpha=0.85, lam=0.1, beta=1.0, m
   if return_win:
     out += (win,)
   return out[0] if len(out) == 1 else out
+
+
+# ------------------------------------------------------------------------------------ visibility of the fused depth
+# The per-window minimum above chooses among whatever the sources show; a source that looks at an occluder still offers its colour.
+# The fused depth forward-projected into a source is a depth map of that source (a z-buffer of 64-bit integer minima, as the hand-off's),
+# and a pixel farther from the source's centre than what its landing place holds is hidden there.  Three launches for any F and S.
+def mv_visibility(depth, poses, tol=0.05, radius=0, return_zbuf=False):
+  """Which pixels of a depth map each of S source panoramas sees (include/mode_hip_mvvis.h has the definition): depth
+  (F, 1, H, W) or (F, H, W) fp32 on the device, poses in every form HF.mv_photometric_loss takes -- (S, 12) or (S, 3, 4) float64 on the
+  host as numpy, a tensor (one that requires a gradient gives its detached values: the masks are constants) or nested lists.  A pixel
+  is visible to source s iff it is valid for s and its range rho to that source's centre is at most (1 + tol) times the smallest rho
+  that lands on the same source pixel (radius = 0) or on its 3 x 3 neighbourhood (radius = 1: closes the holes of a magnified occluder,
+  and marks slanted surfaces hidden).  Returns vis (F, S, H, W) uint8, 0 or 1, for HF.mv_photometric_loss(masks=); with return_zbuf
+  also zbuf (F, S, H, W) fp32: the range map of every source view rendered from the depth, +inf where nothing lands.  No autograd,
+  no host synchronisation."""
+  import math
+
+  import numpy as np
+  require_gpu(depth)
+  if depth.dim() not in (3, 4) or (depth.dim() == 4 and depth.shape[1] != 1):
+    raise ValueError('mv_visibility: a depth map is (F, 1, H, W) or (F, H, W), got %s' % (tuple(depth.shape),))
+  F, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
+  if isinstance(poses, torch.Tensor):
+    poses = poses.detach().cpu().numpy()
+  poses = np.asarray(poses, dtype=np.float64)
+  if poses.ndim not in (2, 3) or poses.size % 12 or tuple(poses.shape[1:]) not in ((12,), (3, 4)):
+    raise ValueError('mv_visibility: poses must be (S, 12) or (S, 3, 4), got %s' % (tuple(poses.shape),))
+  poses = np.ascontiguousarray(poses.reshape(-1, 12))
+  S = poses.shape[0]
+  if not 1 <= S <= MVP_MAX_SOURCES:
+    raise ValueError('mv_visibility: %d source views (1 .. %d)' % (S, MVP_MAX_SOURCES))
+  tol = float(tol)
+  if not (math.isfinite(tol) and tol >= 0):
+    raise ValueError('mv_visibility: tol = %r must be finite and >= 0' % (tol,))
+  if radius not in (0, 1):
+    raise ValueError('mv_visibility: radius = %r (0 or 1)' % (radius,))
+  d = depth.detach().reshape(F, H, W).contiguous()
+  require_f32c(d)
+  dev = d.device
+  vis = torch.empty((F, S, H, W), dtype=torch.uint8, device=dev)
+  zbuf = torch.empty((F, S, H, W), dtype=torch.float32, device=dev) if return_zbuf else None
+  n = vis.numel()
+  with torch.cuda.device_of(d), profiling.region('mv_visibility', 4 * d.numel() + (2 * 20 + 8 + 1 + (4 if return_zbuf else 0)) * n, 0, dev):
+    ws = torch.empty(max(lib().mode_mvvis_workspace_bytes(S, F, H, W) // 8, 1), dtype=torch.float64, device=dev)
+    _call('mode_mv_visibility', ptr(d), poses.ctypes.data_as(ctypes.c_void_p), S, F, H, W, tol, int(radius), ptr(ws), ws.numel() * 8, ptr(vis),
+          _optr(zbuf), stream_of(d))
+  return (vis, zbuf) if return_zbuf else vis
 
 
 # ------------------------------------------------------------------------------------ scoring in the ERP domain

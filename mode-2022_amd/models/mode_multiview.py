@@ -271,7 +271,7 @@ class ModeMultiView(nn.Module):
       return self.fusion.feature_extraction(fusion_input, rgb)
     return self.fusion.feature_extraction(fusion_input)
 
-  def fusion_selfsup_loss(self, frames, sources=None, poses=None, **loss_kw):
+  def fusion_selfsup_loss(self, frames, sources=None, poses=None, visibility=None, **loss_kw):
     """fusion_loss without ground truth: frames exactly as fusion_loss takes them -> (loss, depth.detach()).  The chain is
     fusion_loss's with the SILog term replaced by HF.mv_photometric_loss: the fused depth lives in the common view's Cassini frame, and
     every other panorama of the frame is a picture of the same scene from a pose the rig knows, so each pixel is lifted by its depth,
@@ -285,7 +285,10 @@ class ModeMultiView(nn.Module):
     poses: (2P, 3, 4) or (2P, 12) float64 on the host, used in place of rig.panorama_poses(); `sources` indexes it as
     before.  With utils.rig_refine.RigRefinement(rig)() the loss's gradient reaches the refinement's twist (the backward then copies
     S x 12 doubles to the host and synchronises); calibrate a source at a time, or only sources that are comparably off: a source
-    that loses every window gets no gradient."""
+    that loses every window gets no gradient.
+    visibility: True, or a dict with tol and / or radius (HF.mv_visibility's; defaults 0.05 and 0): the loss counts a pixel
+    for a source only where that source sees it -- the masks are HF.mv_visibility of the detached fused depth of this call with the
+    same poses (the detached values of learned ones), constants of every gradient."""
     from utils.rig import CameraRig
     if self.resize:
       raise ValueError('ModeMultiView(resize=True).fusion_selfsup_loss: the reprojection loss compares the panoramas at their own size, '
@@ -301,6 +304,13 @@ class ModeMultiView(nn.Module):
       if k not in ('alpha', 'lam', 'beta', 'mean', 'std'):
         raise ValueError('fusion_selfsup_loss returns (loss, depth); %r is not a parameter of the loss (alpha, lam, beta, mean, std); call '
                          'HF.mv_photometric_loss for the statistics' % (k,))
+    visibility = None if visibility is False else visibility
+    if visibility is None or visibility is True:
+      vis_kw = {}
+    elif isinstance(visibility, dict) and all(k in ('tol', 'radius') for k in visibility):
+      vis_kw = dict(visibility)
+    else:
+      raise ValueError('ModeMultiView.fusion_selfsup_loss: visibility is None, True or a dict with tol and / or radius, got %r' % (visibility,))
     joint, full = self._fusion_training_mode('fusion_selfsup_loss')
     ref_index = rig.reference_panorama()
     sources = rig.default_sources() if sources is None else tuple(int(k) for k in sources)
@@ -325,7 +335,10 @@ class ModeMultiView(nn.Module):
     ref = panorama(ref_index)
     src = torch.stack([panorama(k) for k in sources], 1)
     output = self._fusion_training_output(frames, left, right, rgb, want_rgb, joint, full)
-    loss = HF.mv_photometric_loss(ref, src, output, poses, **loss_kw)
+    if visibility is None:
+      loss = HF.mv_photometric_loss(ref, src, output, poses, **loss_kw)
+    else:
+      loss = HF.mv_photometric_loss(ref, src, output, poses, masks=HF.mv_visibility(output.detach(), poses, **vis_kw), **loss_kw)
     return loss, output.detach()
 
   def photometric_loss(self, frames, **loss_kw):

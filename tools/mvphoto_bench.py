@@ -5,6 +5,7 @@ scatter in the backward) against HF.mv_photometric_loss (B; csrc/mv_photometric.
 sources (Deep360's panoramas 1, 3, 5), F = 1 and F = 2.
 
     python tools/mvphoto_bench.py [--windows 4] [--min-window 0.3] [--out profiles/mvphoto_bench_mi355x.json]
+    python tools/mvphoto_bench.py --visibility [--out profiles/mvvis_bench_mi355x.json]   (main_visibility below)
 
 First the two sides' outputs are compared, by the bound of tests/test_gpu_mvphoto.py: the composition is also run in float64, the
 yardstick of the loss and of the gradient is A's own fp32 error against that run (never below 2^-23 of the largest element), and B may
@@ -235,6 +236,124 @@ def main_poses(args):
   return 0 if ok else 1
 
 
+def composed_visibility(torch, depth, poses, tol=0.05, radius=0):
+  """The masks of include/mode_hip_mvvis.h composed from torch operators on the GPU, in float64, from the definition: the projection,
+  a scatter_reduce with amin for z, gathers at the landing pixels.  depth (F, H, W), poses (S, 3, 4) float64 on the device ->
+  vis (F, S, H, W) uint8."""
+  F, H, W = depth.shape
+  dev = depth.device
+  theta = (math.pi - (torch.arange(H, dtype=torch.float64, device=dev) + 0.5) * 2.0 * math.pi / H).view(H, 1)
+  phi = (math.pi / 2 - (torch.arange(W, dtype=torch.float64, device=dev) + 0.5) * math.pi / W).view(1, W)
+  n = torch.stack([torch.sin(phi).expand(H, W), torch.cos(phi) * torch.sin(theta), torch.cos(phi) * torch.cos(theta)], -1)
+  good = torch.isfinite(depth) & (depth > 0)
+  D = torch.where(good, depth, torch.ones_like(depth)).double()
+  inf = torch.full((F, H, W), float('inf'), dtype=torch.float64, device=dev)
+  out = []
+  for s in range(poses.shape[0]):
+    Y = D.unsqueeze(-1) * (n @ poses[s, :, :3].T) + poses[s, :, 3]
+    rho = Y.norm(dim=-1)
+    ok = good & (rho > 0)
+    u = (math.pi / 2 - torch.asin((Y[..., 0] / torch.where(ok, rho, torch.ones_like(rho))).clamp(-1, 1))) * W / math.pi - 0.5
+    v = (math.pi - torch.atan2(Y[..., 1], Y[..., 2])) * H / (2.0 * math.pi) - 0.5
+    valid = ok & (u >= 0) & (u <= W - 1)
+    at = torch.where(valid, torch.remainder(torch.floor(v + 0.5).long(), H) * W + torch.floor(u + 0.5).long(), torch.zeros_like(u, dtype=torch.long))
+    z = inf.reshape(F, -1).scatter_reduce(1, at.reshape(F, -1), torch.where(valid, rho, inf).reshape(F, -1), 'amin').reshape(F, H, W)
+    if radius:
+      rows = torch.minimum(z, torch.minimum(torch.roll(z, 1, -2), torch.roll(z, -1, -2)))
+      z = torch.minimum(rows, torch.minimum(torch.cat([inf[..., :1], rows[..., :-1]], -1), torch.cat([rows[..., 1:], inf[..., :1]], -1)))
+    zmin = z.reshape(F, -1).gather(1, at.reshape(F, -1)).reshape(F, H, W)
+    out.append((valid & (rho <= (1.0 + tol) * zmin)).to(torch.uint8))
+  return torch.stack(out, 1)
+
+
+def main_visibility(args):
+  """--visibility: the z-buffer visibility masks at 1024 x 512 with S = 3 (Deep360's sources), tol = 0.05, radius = 0.
+  A: composed_visibility.  B: HF.mv_visibility (csrc/mv_visibility.hip).  Before timing, B's masks must equal A's exactly.  Beside
+  them the loss, forward + backward, without masks (L0: the B of the run without flags) and with B's masks (L1: the masked
+  instantiation).  The windows alternate A B L0 L1 ...; no ratio is fixed in advance, the medians and the window ranges are the
+  result.  For B also the algorithmic bytes -- per pixel a depth read, per pixel and source a key written, an atomic on a key, rho
+  and the landing index written and read, a key read and a byte written -- over its device time."""
+  import torch
+  from mode_hip import functional as HF
+  from utils.rig import CameraRig
+  assert torch.cuda.is_available(), 'mvphoto_bench needs a GPU'
+  dev = torch.device('cuda:0')
+  H, W, S = 1024, 512, 3
+  rig = CameraRig.deep360()
+  poses = rig.panorama_poses()[list(rig.default_sources())]
+  poses_dev = torch.from_numpy(poses).to(dev)
+  out = {'tool': 'mvphoto_bench --visibility', 'H': H, 'W': W, 'S': S, 'tol': 0.05, 'radius': 0, 'min_window_s': args.min_window,
+         'windows': args.windows, 'frames': {}}
+  for F in args.frames:
+    ref, src, depth = inputs(torch, F, H, W, S, dev, 100 + F)
+    va = composed_visibility(torch, depth, poses_dev)
+    vb = HF.mv_visibility(depth, poses)
+    torch.cuda.synchronize()
+    differ = int((va != vb).sum())
+    row = {'pixel_source_pairs': va.numel(), 'visible_A': int(va.sum()), 'visible_B': int(vb.sum()), 'masks_that_differ': differ,
+           'visible_share_per_source': [round(float(vb[:, s].float().mean()), 4) for s in range(S)]}
+    print('F=%d: %s' % (F, json.dumps(row)), flush=True)
+    assert differ == 0, row
+    masks = vb
+    del va
+
+    def step(side):
+      if side == 'A':
+        return composed_visibility(torch, depth, poses_dev)
+      if side == 'B':
+        return HF.mv_visibility(depth, poses)
+      d = depth.detach().requires_grad_(True)
+      loss = HF.mv_photometric_loss(ref, src, d, poses, masks=masks if side == 'L1' else None)
+      loss.backward()
+      return loss
+
+    def window(side, n):
+      torch.cuda.synchronize()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(n):
+        step(side)
+      e1.record()
+      torch.cuda.synchronize()
+      return 1e-3 * e0.elapsed_time(e1)
+
+    sides = ('A', 'B', 'L0', 'L1')
+    iters = {}
+    for side in sides:
+      window(side, 3)  # warm-up: allocator, kernels loaded
+      per = window(side, 5) / 5
+      iters[side] = max(5, int(math.ceil(1.2 * args.min_window / per)))
+    times = {side: [] for side in sides}
+    for w in range(args.windows):
+      for side in sides:
+        sec = window(side, iters[side])
+        while sec < args.min_window:  # the calibration ran slow: a longer window, and this one is not counted
+          iters[side] = int(math.ceil(1.3 * iters[side] * args.min_window / sec))
+          sec = window(side, iters[side])
+        times[side].append(1e6 * sec / iters[side])
+        print('F=%d window %d %s: %.1f us (%d in %.3f s)' % (F, w, side, times[side][-1], iters[side], sec), flush=True)
+    med = {}
+    for side in sides:
+      v = sorted(times[side])
+      med[side] = 0.5 * (v[(len(v) - 1) // 2] + v[len(v) // 2])
+      row['%s_us' % side] = [round(x, 1) for x in times[side]]
+      row['%s_us_median_min_max' % side] = [round(med[side], 1), round(v[0], 1), round(v[-1], 1)]
+    nbytes = 4 * F * H * W + (8 + 8 + 2 * (8 + 4) + 8 + 1) * F * S * H * W
+    row['B_algorithmic_bytes'] = nbytes
+    row['B_effective_GBps'] = [round(nbytes / (us * 1e-6) / 1e9, 1) for us in times['B']]
+    row['B_ns_per_pixel_and_source'] = [round(1e3 * us / (F * H * W * S), 3) for us in times['B']]
+    row['A_over_B_median'] = round(med['A'] / med['B'], 2)
+    row['masked_over_unmasked_loss_median'] = round(med['L1'] / med['L0'], 3)
+    out['frames'][str(F)] = row
+  line = json.dumps(out)
+  print(line)
+  if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+      f.write(line + '\n')
+  return 0
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--windows', type=int, default=4, help='windows per side and number of frames')
@@ -243,9 +362,13 @@ def main():
   ap.add_argument('--out', help='also write the result line to this file')
   ap.add_argument('--poses', action='store_true', help='the pose tensor requires a gradient on both sides (DESIGN 27; '
                   '--out profiles/mvpose_bench_mi355x.json)')
+  ap.add_argument('--visibility', action='store_true', help='the z-buffer visibility masks and the masked loss (DESIGN 28; '
+                  '--out profiles/mvvis_bench_mi355x.json)')
   args = ap.parse_args()
   if args.poses:
     return main_poses(args)
+  if args.visibility:
+    return main_visibility(args)
 
   import torch
   from mode_hip import functional as HF
