@@ -138,10 +138,13 @@ int mode_sphere_conv_bwd_data_adj_list(const float* gy, const float* w, float* g
  * sphere_conv_cuda_kernel.cu:293-356 + the GEMM of sphere_conv_cuda.cpp:275-315 for stride 1, 3x3 taps, output grid = input grid).
  * Host planning, once per table: mode_sphere_adjplan_build(pos_host, H, W, Kh, Kw, good_tiles[4 n], bad_tiles[2 n], counts[2],
  *   rec_off_host[n * 9 * 256 * 4], rec_w_host[same], rec_off2_host[n * 9 * 256 * 2], rec_w2_host[same]) with n =
- *   mode_sphere_plan_max_tiles(H, W): for every 64 x 4 tile of INPUT pixels whose adjoint lists all have <= 6 entries inside one 81-row
+ *   mode_sphere_plan_max_tiles(H, W): for every 64 x 4 tile of INPUT pixels whose adjoint lists all have <= 6 entries, with weights
+ *   that sum to <= 65504 / 2^15 = 2 - 2^-10 per list (the plan's promise to the fp16 entry below), inside one 81-row
  *   x 8-column window of gy it writes (h0, w0, rbase, cbase | six << 16) and, per (tile, tap, pixel), 4 (window offset, weight) slots
  *   + 2 more in the second pair of arrays (six = 1 when any list of the tile uses them); the other tiles go to bad_tiles as (h0, w0).
- *   counts = (good, bad).
+ *   counts = (good, bad).  A tile that fails the weight sum alone is bad, and its entry (bit 17 of the fourth word set) and records follow
+ *   those of the good tiles: mode_sphere_conv_bwd_data_win_split (three bf16 pieces, no headroom to keep) may run them once the bit is
+ *   cleared and they are taken off the bad list; the fp16 entry must not.
  * mode_sphere_conv_bwd_data_win_split WRITES gx on the good tiles (fp32 operands split exactly into 3 bf16 pieces, 6 bf16 MFMAs per
  *   product, fp32 accumulation); the caller runs mode_sphere_conv_bwd_data_adj_list (accumulate = 0) on the bad ones.  `transposed`: gy
  *   and gx are plane-transposed (B, C, W, H).  Needs mode_sphere_conv_bwd_data_win_supported(Ci, Co, groups) == 1 (output channels per
@@ -157,7 +160,9 @@ int mode_sphere_conv_bwd_data_win_split(const float* gy, const float* w, float* 
                                         const int32_t* rec_off, const float* rec_w, const int32_t* rec_off2, const float* rec_w2, int B,
                                         int Ci, int H, int W, int Co, int Kh, int Kw, int groups, int transposed, mode_stream_t stream);
 /* The same on the two-piece fp16 arithmetic of mode_sphere_conv_fwd_win_split_f16 (a backward pass is a training step): amax_g / amax_w =
- * the maximum buffers (MODE_BN_ABSMAX_FLOATS floats; mode_abs_max, mode_bn_train_bwd_amax) of gy and of w. */
+ * the maximum buffers (MODE_BN_ABSMAX_FLOATS floats; mode_abs_max, mode_bn_train_bwd_amax) of gy and of w.  The operand it splits is
+ * the adjoint-sampled gradient scaled by f16_scale_of(max |gy|): at most (a list's weight sum) x 2^15.  It is a finite fp16 number for
+ * ANY gy because the plan holds every list of a good tile to a sum <= 2 - 2^-10; records from another source must keep that too. */
 int mode_sphere_conv_bwd_data_win_split_f16(const float* gy, const float* w, const float* amax_g, const float* amax_w, float* gx, float* wpack,
                                             const int32_t* tiles, int n_tiles, const int32_t* rec_off, const float* rec_w,
                                             const int32_t* rec_off2, const float* rec_w2, int B, int Ci, int H, int W, int Co, int Kh,

@@ -251,13 +251,18 @@ extern "C" int mode_sphere_plan_polar(const float* pos_host, const int32_t* tile
 
 // Host-side plan of the adjoint windows (stride 1, output grid = input grid).  For every 64 x 4 tile of INPUT pixels q (same tiling as
 // mode_sphere_plan_build) it collects L(k, q) for all nine taps and all pixels of the tile.  A tile is "good" when every list has at
-// most 4 entries and all their source pixels lie in one window of WR_SMALL rows x WC columns:
+// most 6 entries whose weights sum to no more than ADJ_F16_HEADROOM = 2 - 2^-10 (sphere_win_geometry.h: what keeps the fp16 form's
+// scaled operand finite; next to a pole of a small table six output pixels crowd onto one source with a sum of 2.18) and all their
+// source pixels lie in one window of WR_SMALL rows x WC columns:
 //   good_tiles[4 i ..] = (h0, w0, rbase, cbase | six << 16), six = 1 when some list of the tile has 5 or 6 entries (slots 4, 5 in
 //   rec_off2 / rec_w2 [((i * 9 + tap) * 256 + pixel) * 2 + slot - 4]; lists longer than 6 make a tile bad);
 //   rec_off / rec_w [((i * 9 + tap) * 256 + pixel) * 4 + slot], pixel =
 //   ((rowblock * 4 + column) * 32 + row) -- the lane order of the kernel; offset = (source column - cbase) * WR_SMALL + (source row -
 //   rbase) mod H, unused slots (0, 0.0f); slots in ascending source-pixel order (the gather kernel's summation order).
 //   bad_tiles[2 j ..] = (h0, w0) of the others.  counts = (good, bad).
+// A tile that qualifies but for a list heavier than the headroom is a BAD tile (listed, counted).  Its entry and records are written all
+// the same, behind those of the counts[0] good tiles, with bit 17 of the fourth word set: the three-piece bf16 form has no headroom
+// to keep and may take them (mode_hip/functional.py does, after clearing the bit); the fp16 form must not.
 extern "C" int mode_sphere_adjplan_build(const float* pos_host, int H, int W, int Kh, int Kw, int32_t* good_tiles, int32_t* bad_tiles,
                                          int32_t* counts, int32_t* rec_off_host, float* rec_w_host, int32_t* rec_off2_host,
                                          float* rec_w2_host) {
@@ -312,13 +317,14 @@ extern "C" int mode_sphere_adjplan_build(const float* pos_host, int H, int W, in
   struct GoodTile {
     int h0, w0, rbase, cbase, six;
   };
-  std::vector<GoodTile> good;
+  std::vector<GoodTile> good, heavy_tiles;
   for (int hg = 0; hg < nth; hg += kNumXCD)  // tile order as in mode_sphere_plan_build (tiles sharing rows meet on one XCD)
     for (int tw = 0; tw < ntw; ++tw)
       for (int hs = 0; hs < kNumXCD && hg + hs < nth; ++hs) {
         const int h0 = (hg + hs) * TH, w0 = tw * TW;
         bool ok = h0 + TH <= H && w0 + TW <= W;  // whole tiles only: ragged edges stay on the gather kernel
         bool six = false;                        // some list has 5 or 6 entries: the 6-slot class
+        bool heavy = false;                      // some list weighs more than the fp16 form's headroom
         int dmin = 1 << 30, dmax = -(1 << 30), cmin = 1 << 30, cmax = -(1 << 30);
         for (int k = 0; k < KT && ok; ++k)
           for (int h = h0; h < h0 + TH && ok; ++h)
@@ -330,6 +336,9 @@ extern "C" int mode_sphere_adjplan_build(const float* pos_host, int H, int W, in
                 break;
               }
               if (nent > 4) six = true;
+              double wsum = 0.0;  // (weights are products of numbers in [0, 1]: non-negative)
+              for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) wsum += (double)ew[e];
+              if (wsum > (double)ADJ_F16_HEADROOM) heavy = true;
               for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) {
                 const int hp = ep[e] / W, wp = ep[e] % W;
                 int dr = (hp - h0) % H;
@@ -353,14 +362,24 @@ extern "C" int mode_sphere_adjplan_build(const float* pos_host, int H, int W, in
           ++nbad;
           continue;
         }
+        if (heavy) {  // a bad tile for whoever follows counts; its records are kept behind the good tiles' (below)
+          bad_tiles[2 * nbad] = h0;
+          bad_tiles[2 * nbad + 1] = w0;
+          ++nbad;
+          heavy_tiles.push_back({h0, w0, rbase, cbase, six ? 1 : 0});
+          continue;
+        }
         good.push_back({h0, w0, rbase, cbase, six ? 1 : 0});
       }
   // the 6-slot tiles first: they are the slowest workgroups of the launch, and started first they end inside its last round
   std::stable_sort(good.begin(), good.end(), [](const GoodTile& a, const GoodTile& b2) { return a.six > b2.six; });
-  for (const GoodTile& gt : good) {
+  const size_t nlight = good.size();
+  good.insert(good.end(), heavy_tiles.begin(), heavy_tiles.end());
+  for (size_t gi = 0; gi < good.size(); ++gi) {
+    const GoodTile& gt = good[gi];
     const int h0 = gt.h0, w0 = gt.w0, rbase = gt.rbase, cbase = gt.cbase;
     int32_t* tl = good_tiles + 4 * (size_t)ngood;
-    tl[0] = h0; tl[1] = w0; tl[2] = rbase; tl[3] = cbase | (gt.six << 16);
+    tl[0] = h0; tl[1] = w0; tl[2] = rbase; tl[3] = cbase | (gt.six << 16) | (gi >= nlight ? 1 << 17 : 0);
     for (int k = 0; k < KT; ++k)
       for (int pix = 0; pix < AJ_PIX; ++pix) {
         const int wv = pix >> 5, h = h0 + (wv / TW) * 32 + (pix & 31), w = w0 + (wv % TW);
@@ -387,7 +406,7 @@ extern "C" int mode_sphere_adjplan_build(const float* pos_host, int H, int W, in
       }
     ++ngood;
   }
-  counts[0] = ngood;
+  counts[0] = (int32_t)nlight;  // (ngood - nlight heavy tiles follow, bit 17 set: not good tiles for the kernels as they stand)
   counts[1] = nbad;
   return MODE_OK;
 }

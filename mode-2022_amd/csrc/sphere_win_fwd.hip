@@ -1336,7 +1336,8 @@ static int sphere_conv_fwd_win_impl(const float* x, const float* pos, const floa
     hipLaunchKernelGGL(pack_w_win, dim3(mode::cdiv(npack, 256)), dim3(256), 0, st, w, wpack, d, bn ? 1 : 0, bn ? *bn : mode_bn_epilogue());
   const Epi epi = make_epi(bn, wpack + npack);
   if (split_path) {
-    // small-window tiles (the tail of the tile list) on the split-bf16 kernel, the tall-window classes on the fp32 kernels
+    // ALL window classes on the split kernel, in the arithmetic of the entry (three bf16 pieces, or two fp16 pieces: the tall-window
+    // tiles too, pack_w_win_split_tall<f16>) -- but for wrap-around tiles that cannot be double-buffered (wrap_on_fp32: fp32 kernel)
     const int NCH16 = d.Cig / SP_CCH;
     uint4* wps = reinterpret_cast<uint4*>(wpack + ((npack + d.Co + 3) / 4) * 4);
     const long long nsplit = (long long)d.G * d.MG * NCH16 * KT * MTW * 64;

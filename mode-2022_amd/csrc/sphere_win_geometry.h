@@ -17,6 +17,10 @@ constexpr int SROWS = NTHREADS / WC;    // window rows staged per pass
 constexpr int WR_SMALL = TH + 17, WR_MID = TH + 81;  // window rows of the two compact classes (odd: conflict-free column pitch)
 constexpr int WR_PIPE_MAX = 5 * SROWS;  // tallest window whose next chunk still fits in registers while the current one computes
 constexpr int AJ_PIX = TH * TW;  // 256 pixels per tile = 8 waves x 32 lanes (the record order of the adjoint plan)
+// The fp16 form of the windowed input gradient splits sx * G_k[o][q], G_k the sum of an adjoint list's weights times gy, with
+// max |gy| sx < 2^15: the operand stays a finite fp16 number (<= 65504) whatever gy holds only while the list's weights sum to no more
+// than 65504 / 2^15 = 2 - 2^-10.  The planner keeps a tile with a heavier list off the windowed kernel (a bad tile: fp32 gather).
+constexpr float ADJ_F16_HEADROOM = 65504.f / 32768.f;
 
 // weight gradient: a work item is one 32-row half of a tile column
 constexpr int BW_TH = 32;                  // rows per work item

@@ -616,7 +616,7 @@ def _sphere_bwd_data_t_route(pos, kh, kw, B, Ci, Co, groups, H, W):
   least SPHERE_BWD_SPLIT_MIN_WG workgroups (one per good tile, sample and 128-channel slice)."""
   if (CONV_ARITH == 'bf16x6' and SPHERE_BWD_DATA_SPLIT and kh * kw == 9 and tuple(pos.shape[2:]) == (H, W) and
       lib().mode_sphere_conv_bwd_data_win_supported(Ci, Co, groups) == 1):
-    aplan = sphere_adjplan(pos, kh, kw)
+    aplan = sphere_adjplan(pos, kh, kw, f16=SPHERE_BWD_F16)
     if aplan is not None and aplan.ngood * B * groups * (-(-(Ci // groups) // 128)) >= SPHERE_BWD_SPLIT_MIN_WG:
       return 'window', aplan
   return 'adjoint', None
@@ -916,13 +916,15 @@ SPHERE_BWD_DATA_SPLIT = True  # windowed adjoint on the split-bf16 kernel where 
 SPHERE_BWD_SPLIT_MIN_WG = 200  # fewer 64 x 4 tiles x samples than this: the 64-pixel tiles of the gather kernel fill the chip better
 
 
-def sphere_adjplan(pos, kh, kw):
+def sphere_adjplan(pos, kh, kw, f16=None):
   """Adjoint-window plan of the sampling table `pos` (H, W) for the windowed input-gradient kernel, or None when no tile qualifies
   (or H is not a multiple of 64: the left-over tiles are handed to the gather kernel as whole 64-pixel runs of one stored row).
-  A SphereAdjPlan.  Built on the host by mode_sphere_adjplan_build once per (table, device), cached."""
+  A SphereAdjPlan.  Built on the host by mode_sphere_adjplan_build once per (table, device), cached.
+  f16: the plan of the two-piece fp16 form (None: what SPHERE_BWD_F16 says) -- tiles with an adjoint list heavier than the fp16 headroom
+  (2 - 2^-10: the scaled operand would pass 65504) are bad tiles there; the three-piece bf16 form keeps them."""
   def build():
     H, W = pos.shape[2:]
-    plan = None
+    plan = full = None
     if kh * kw == 9 and H % 64 == 0 and W % 4 == 0:
       host = pos.detach().to('cpu', torch.float32).contiguous()
       n = lib().mode_sphere_plan_max_tiles(H, W)
@@ -936,17 +938,32 @@ def sphere_adjplan(pos, kh, kw):
       _call('mode_sphere_adjplan_build', ptr(host), H, W, kh, kw, ptr(good), ptr(bad), ptr(counts), ptr(rec_off), ptr(rec_w), ptr(rec_off2),
             ptr(rec_w2))
       ng, nb = int(counts[0]), int(counts[1])
-      if ng > 0:
+      nh = 0  # the heavy tiles: entries behind the good ones, bit 17 set (bad tiles of the fp16 form)
+      while ng + nh < n and (int(good[4 * (ng + nh) + 3]) >> 17) & 1:
+        nh += 1
+      dev = pos.device
+
+      def make(ng, b2):
         # a bad tile (h0, w0) = the 64-pixel runs h0 .. h0 + 63 of the stored rows w0 .. w0 + 3 of the (W, H) planes
-        b2 = bad[:2 * nb].view(nb, 2).to(torch.int64)
+        nb = b2.shape[0]
         ids = ((b2[:, 1:2] + torch.arange(4).view(1, 4)) * H + b2[:, 0:1]) // 64 if nb else torch.zeros((0, 4), dtype=torch.int64)
         ids = ids.reshape(-1).sort().values.to(torch.int32)
-        dev = pos.device
-        plan = SphereAdjPlan(good[:4 * ng].contiguous().to(dev), ng, rec_off[:ng * 9 * 256 * 4].contiguous().to(dev),
+        tiles = good[:4 * ng].clone()
+        tiles.view(-1, 4)[:, 3] &= ~(1 << 17)
+        return SphereAdjPlan(tiles.contiguous().to(dev), ng, rec_off[:ng * 9 * 256 * 4].contiguous().to(dev),
                              rec_w[:ng * 9 * 256 * 4].contiguous().to(dev), ids.contiguous().to(dev) if nb else None, int(ids.numel()),
                              rec_off2[:ng * 9 * 256 * 2].contiguous().to(dev), rec_w2[:ng * 9 * 256 * 2].contiguous().to(dev))
-    return plan
-  return _per_table(_adjplan_cache, _plan_lock, pos, (kh, kw), build)
+      b2 = bad[:2 * nb].view(nb, 2).to(torch.int64)
+      if ng > 0:
+        plan = make(ng, b2)
+      full = plan
+      if nh > 0:
+        heavy = {(int(h0), int(w0)) for h0, w0 in good[4 * ng:4 * (ng + nh)].view(nh, 4)[:, :2].tolist()}
+        keep = [i for i in range(nb) if (int(b2[i, 0]), int(b2[i, 1])) not in heavy]
+        full = make(ng + nh, b2[keep].reshape(-1, 2))
+    return plan, full
+  plans = _per_table(_adjplan_cache, _plan_lock, pos, (kh, kw), build)
+  return plans[0 if (SPHERE_BWD_F16 if f16 is None else f16) else 1]
 
 
 def sphere_conv_bwd_data_t(gyt, pos, w, gxt, groups, w_amax=None):

@@ -12,8 +12,11 @@ anywhere fails it.  Do not regenerate this file together with a kernel change --
 
 The table is sphere_position(128, 256, 'Cassini'), the smallest with compact, mid and wrap tiles, polar items and six-source adjoint
 tiles all present (tests/test_sphere_win_bits_plan.py checks that on the host).  The (32, 64) table (stored 64 x 32) serves the input
-gradient alone: its adjoint plan has 8 good tiles, three of them six-source, and none left to the gather kernel, so the whole result
-comes from sphere_bwd_data_split_kernel at W = 32 -- which the large table, with its 64 left-over tile ids, never shows.  Its forward
+gradient alone: on three bf16 pieces its adjoint plan has 8 good tiles, three of them six-source, and none left to the gather kernel, so
+the whole result comes from sphere_bwd_data_split_kernel at W = 32 -- which the large table, with its 64 left-over tile ids, never
+shows.  On two fp16 pieces tile (0, 0), whose adjoint lists weigh more than that form's headroom, is left to the gather kernel (7 good
+tiles, two of them six-source): the hash of that one case was taken again with this recipe when the planner learned the headroom, and
+the result outside tile (0, 0) kept its bits.  Its forward
 plan is (0, 8, 0) with no polar items: without compact tiles the model keeps such a table off the windowed forward and weight gradient
 (HF._plan_usable), so it has no case there.  HF.SPHERE_BWD_SPLIT_MIN_WG is 0 for the duration of an input-gradient case: the default
 sends problems this small to the gather kernel.

@@ -84,3 +84,20 @@ def dead_taps(ih=96, iw=192, seed=5):
         t[0, 2 * k + which, h, w] = (float(H), float(W))[which] if value is None else value
     return t
   return _keep('dead taps %dx%d' % (iw, ih), make)
+
+
+def clustered(H=192, W=16):
+  """Integer coordinates that send three output rows and two output columns to ONE source pixel in the columns w < 8 (row coordinate
+  h - h % 3 + dh, column coordinate w - w % 2 + dw) and the identity h + dh, w + dw in the columns beyond: every adjoint list of the left
+  half has six entries of weight exactly 1 inside one 81 x 8 window -- short and compact enough for the windowed input gradient, and
+  three times what its fp16 form can take (a weight sum <= 2 - 2^-10 per list); the right half has lists of one entry."""
+  def make():
+    t = torch.zeros((1, 18, H, W), dtype=torch.float64)
+    h = torch.arange(H, dtype=torch.float64).view(H, 1).expand(H, W)
+    w = torch.arange(W, dtype=torch.float64).view(1, W).expand(H, W)
+    left = w < 8
+    for k, (dh, dw) in enumerate(TAPS):
+      t[0, 2 * k] = torch.where(left, h - h % 3, h) + dh
+      t[0, 2 * k + 1] = torch.where(left, w - w % 2, w) + dw
+    return t
+  return _keep('clustered %dx%d' % (H, W), make)

@@ -100,22 +100,25 @@ def pieces_f16(a, scale, trunc_last=False):
 
 
 # ------------------------------------------------------------------------------------------------ emulation
-def _pieces(a, b, arith, mutant):
+def _pieces(a, b, arith, mutant, amax=None):
+  """amax = (max_a, max_b): the maxima the fp16 scales are taken from where they are not the operands' own (the spherical entries are
+  given the maximum of the RAW tensor, max |x| or max |gy|, and split the SAMPLED one); None for either: the operand's own maximum."""
   trunc = mutant == ('trunc',)
   if arith == 'bf16x6':
     return pieces_bf16(a, trunc), pieces_bf16(b, trunc), 1.0
-  sa, sb = f16_scale_of(a.abs().max()), f16_scale_of(b.abs().max())
+  ma, mb = amax if amax is not None else (None, None)
+  sa, sb = f16_scale_of(a.abs().max() if ma is None else ma), f16_scale_of(b.abs().max() if mb is None else mb)
   if mutant is not None and mutant[0] == 'scale':
     sa = sa / 2.0**mutant[1]
   return pieces_f16(a, sa, trunc), pieces_f16(b, sb, trunc), sa * sb
 
 
-def emulate(op, a, b, arith, mutant=None):
+def emulate(op, a, b, arith, mutant=None, amax=None):
   """The float64 value of operator `op` (a callable of two float64 tensors, bilinear) on the split arithmetic `arith` ('bf16x6' |
-  'f16x3') for fp32 operands a and b, or of a mutant of that arithmetic (module docstring)."""
+  'f16x3') for fp32 operands a and b, or of a mutant of that arithmetic (module docstring).  amax: see _pieces."""
   if mutant is not None and mutant[0] == 'scale':
     assert arith == 'f16x3'
-  pa, pb, s = _pieces(a, b, arith, mutant)
+  pa, pb, s = _pieces(a, b, arith, mutant, amax)
   pairs = [p for p in PAIRS[arith] if not (mutant is not None and mutant[0] == 'drop' and p == tuple(mutant[1:]))]
   out = None
   for i in sorted({p[0] for p in pairs}):  # bilinear: sum over j first (exact in float64: the pieces of one value do not overlap)
@@ -125,15 +128,15 @@ def emulate(op, a, b, arith, mutant=None):
   return out / s
 
 
-def emulations(op, a, b, arith, mutants):
+def emulations(op, a, b, arith, mutants, amax=None):
   """{None: faithful, mutant: value, ...}; a dropped pair is the faithful value minus that pair's product (one evaluation, not three)."""
-  out = {None: emulate(op, a, b, arith)}
-  pa, pb, s = _pieces(a, b, arith, None)
+  out = {None: emulate(op, a, b, arith, None, amax)}
+  pa, pb, s = _pieces(a, b, arith, None, amax)
   for m in mutants:
     if m[0] == 'drop':
       out[m] = out[None] - op(pa[m[1] - 1].double(), pb[m[2] - 1].double()) / s
     else:
-      out[m] = emulate(op, a, b, arith, m)
+      out[m] = emulate(op, a, b, arith, m, amax)
   return out
 
 
@@ -153,9 +156,13 @@ def rms(u):
 Worst = collections.namedtuple('Worst', 'rms axis index')
 
 
-def worst_slice(u):
+def worst_slice(u, regions=None, mask=None):
   """The largest rms over slices along every axis: consecutive indices grouped until a slice holds >= MIN_SLICE elements (a short tail
-  joins the group before it), so that every element is in one slice per axis."""
+  joins the group before it), so that every element is in one slice per axis.  regions: {name: bool mask broadcastable to u} -- each is
+  a slice of its own (axis 'region', index its name).  mask: a bool mask broadcastable to u -- only those elements are judged (slices
+  are grouped by the number of judged elements; regions are intersected with it)."""
+  if regions or mask is not None:
+    return _worst_slice_masked(u, regions or {}, mask)
   worst = Worst(-1.0, -1, -1)
   sq = u.pow(2)
   for ax in range(u.dim()):
@@ -170,6 +177,40 @@ def worst_slice(u):
       r = float(per[s0:s1].mean().sqrt())
       if r > worst.rms:
         worst = Worst(r, ax, s0)
+  return worst
+
+
+def _worst_slice_masked(u, regions, mask):
+  m = torch.ones_like(u, dtype=torch.bool) if mask is None else mask.expand_as(u)
+  sq = torch.where(m, u.pow(2), torch.zeros_like(u))  # (what is not judged may be anything, NaN included)
+  cnt = m.double()
+  worst = Worst(-1.0, -1, -1)
+  for ax in range(u.dim()):
+    others = [d for d in range(u.dim()) if d != ax]
+    num, den = (sq.sum(others), cnt.sum(others)) if others else (sq, cnt)
+    n, s0 = u.shape[ax], 0
+    groups = []
+    while s0 < n:  # consecutive indices until the group holds MIN_SLICE judged elements
+      s1 = s0 + 1
+      while s1 < n and float(den[s0:s1].sum()) < MIN_SLICE:
+        s1 += 1
+      groups.append((s0, s1))
+      s0 = s1
+    if len(groups) > 1 and float(den[groups[-1][0]:groups[-1][1]].sum()) < MIN_SLICE:
+      last = groups.pop()
+      groups[-1] = (groups[-1][0], last[1])
+    for s0, s1 in groups:
+      c = float(den[s0:s1].sum())
+      if c > 0:
+        r = float((num[s0:s1].sum() / c).sqrt())
+        if not r <= worst.rms:  # (a NaN among the judged elements is the worst there is)
+          worst = Worst(r, ax, s0)
+  for name, rm in regions.items():
+    rr = rm.expand_as(u) & m
+    if bool(rr.any()):
+      r = float(u[rr].pow(2).mean().sqrt())
+      if not r <= worst.rms:
+        worst = Worst(r, 'region', name)
   return worst
 
 
@@ -1126,3 +1167,294 @@ def grad32_references(case, roles_):
     else:
       out.append((role, reference(case, role)))
   return out
+
+
+# ================================================================================================ the fp16 spherical training entries
+# A default training step runs the spherical forward, input gradient and weight gradient on two fp16 pieces
+# (mode_sphere_conv_fwd_win_split_f16, mode_sphere_conv_bwd_data_win_split_f16, mode_sphere_conv_bwd_weight_win_split_f16).  Which pixel
+# runs on which arithmetic is read from the plans the kernels are given (sphere_f16_maps):
+#   forward           every output pixel on two fp16 pieces, the tall-window (mid, wrap) tiles too -- except wrap-around tiles the entry
+#                     hands to the fp32 kernel (wrap_on_fp32; none of the tables here has one: asserted);
+#   input gradient    input pixels of the adjoint plan's good tiles on two fp16 pieces; the bad tiles are an fp32 gather, judged under
+#                     the three-piece T of the same inputs (as the grad32 layer judges fp32 kernels);
+#   weight gradient   a sum over two disjoint pixel sets: the compact tiles on two fp16 pieces, the polar items on three bf16 pieces.
+# The fp16 scales come from the RAW tensors' maxima (max |x|, max |gy|, max |w|: what the entries are given), not from the sampled
+# operand's.  A role is judged in PARTS (an arithmetic, the pixels it covers, a T of its own from the mutants over those pixels) and,
+# inside a part, in REGIONS (window classes, four- / six-slot tiles) beside the slices along every axis.  The weight gradient is judged
+# in three runs: gy zeroed on the polar pixels (fp16 part alone), gy zeroed on the compact pixels (bf16 part alone; the masked tensor's
+# maximum sets the scale), and unmasked in 2^-22 units with T from the fp16 part's mutants.
+# (ih, iw, B, ci, co, groups).  The input gradient needs an adjoint plan: of these tables the planner gives one to 32 x 64 alone (64 x 128,
+# stored 128 x 64, has no good tile; the others have H % 64 != 0).
+SPHERE_F16_ROLES = {
+    (16, 32, 1, 16, 32, 1): ('forward', 'weight gradient'),
+    (33, 66, 1, 32, 64, 2): ('forward', 'weight gradient'),
+    (64, 128, 1, 16, 32, 1): ('forward', 'weight gradient'),
+    (32, 64, 1, 32, 32, 1): ('input gradient',),
+    (32, 64, 1, 16, 16, 1): ('input gradient',),  # the plateau kind alone (below)
+}
+PLATEAU = 'plateau'  # input gradient only: the data that finds the headroom of the adjoint-sampled operand
+# The plateau runs at 16 -> 16: on the bad tile, which an fp32 gather computes, every pixel of a plateau channel holds the SAME sum, so
+# the accumulator's rounding does not average over a slice of pixels as it does on noise.  Worst slice of the faithful emulation with an
+# fp32 accumulator / T of the fp32 part: 1.04 at 32 -> 32, 0.63 at 32 -> 16, 0.58 at 16 -> 16 (the host tier asks for <= 1 / 1.5).
+SPHERE_F16_KINDS = {(32, 64, 1, 16, 16, 1): (PLATEAU,)}
+PLATEAU_C = 1.96875  # c sx = 2^15 (1 - 2^-6) >= 2^15 (1 - 2^-5)
+ADJ_F16_HEADROOM = 65504.0 / 2.0**15  # csrc/sphere_win_geometry.h: the weight sum of an adjoint list the fp16 form can take
+
+
+def _sphere_f16_cases():
+  out, seed = [], 40000
+  for shape, names in SPHERE_F16_ROLES.items():
+    seed += 10
+    for kind in SPHERE_F16_KINDS.get(shape, KINDS):
+      out.append(Case('sphere_f16', shape, kind, 'f16x3', seed))
+  return out
+
+
+SPHERE_F16_CASES = _sphere_f16_cases()
+
+
+def plateau(shape, seed):
+  """gy of one sign and one magnitude c on every pixel of the first half of the channels, unit-variance noise at c / 10 on the rest."""
+  t = _randn(shape, seed) * (PLATEAU_C / 10)
+  t[:, :shape[1] // 2] = PLATEAU_C
+  assert float(t.abs().max()) == PLATEAU_C
+  return t.contiguous()
+
+
+def wrap_on_fp32(H, n_wrap):
+  """csrc/sphere_win_fwd.hip, restated from its two conditions: wrap-around tiles leave the split kernel when their window of H + 1 rows
+  cannot be double-buffered (more than 5 x 64 rows, or two windows beyond 160 KiB) or does not fit beside the tall tiles' weights."""
+  def chan_pitch(wr):
+    return 8 * wr + ((32 - (8 * wr) % 64) + 64) % 64
+  two_windows = (2 * 8 * chan_pitch(H + 1) + H + 1 + 8) * 4
+  piped = H + 1 <= 5 * 64 and two_windows <= 160 * 1024
+  tall = (two_windows + 15) // 16 * 16 + 2 * 4 * 3 * 64 * 16
+  return n_wrap > 0 and (not piped or tall > 160 * 1024)
+
+
+SphereMaps = collections.namedtuple('SphereMaps', 'cls fwd_fp32 good six plan aplan')
+
+
+def sphere_f16_maps(pos):
+  """The arithmetic maps of a table, from the plans the kernels are given (checked by tests/sphere_plan_ref.py first): cls (H, W) the
+  window class of every pixel (0 compact, 1 mid, 2 wrap); fwd_fp32 (H, W) the pixels the forward entry sends to the fp32 kernel; good / six
+  (H, W) the pixels of the adjoint plan's good / six-slot tiles (None without an adjoint plan)."""
+  import sphere_plan_ref as PR
+  from mode_hip import functional as HF
+  plan, aplan = HF.sphere_plan(pos, 3, 3), HF.sphere_adjplan(pos, 3, 3, f16=True)
+  assert plan is not None
+  PR.check_plan(pos, plan, aplan)
+  H, W = pos.shape[2:]
+  cls = torch.full((H, W), -1, dtype=torch.int64)
+  for h0, w0, _, cw in plan.tiles.cpu().view(-1, 4)[:sum(plan.counts)].tolist():
+    cls[h0:h0 + 64, w0:w0 + 4] = cw >> 16
+  assert int(cls.min()) >= 0
+  fwd_fp32 = (cls == 2) & bool(wrap_on_fp32(H, plan.counts[2]))
+  good = six = None
+  if aplan is not None:
+    good, six = torch.zeros((H, W), dtype=torch.bool), torch.zeros((H, W), dtype=torch.bool)
+    for h0, w0, _, cw in aplan.tiles.cpu().view(-1, 4).tolist():
+      good[h0:h0 + 64, w0:w0 + 4] = True
+      six[h0:h0 + 64, w0:w0 + 4] = bool((cw >> 16) & 1)
+  return SphereMaps(cls, fwd_fp32, good, six, plan, aplan)
+
+
+def adjoint_weight_sums(pos):
+  """(9, H, W) float64: the sum of the weights of every adjoint list L(k, q) -- the adjoint sampling of a tensor of ones."""
+  from oracle import sphere_conv_ref as R
+  H, W = pos.shape[2:]
+  one = torch.ones((1, 1, 1, H, W), dtype=torch.float64)
+  return torch.stack([R.col2im_scatter(one, pos.double()[:, 2 * k:2 * k + 2], H, W, 1, 1, 1, 1)[0, 0] for k in range(9)])
+
+
+# A part of a role: the pixels `mask` (broadcastable to the output; None: all of it) run on `arith`; T, the emulations {None: faithful,
+# mutant: ...} and the regions {name: mask} are the part's own.  A role: one launch judged in its parts.  gy: the gradient the launch is
+# given (the weight gradient's masked runs); noise(): the rounding of an fp32 accumulator in the kernel's summation structure; faults:
+# {name: (value, part name)} structural faults.
+Part = collections.namedtuple('Part', 'name arith mask T emu mutants regions')
+F16Role = collections.namedtuple('F16Role', 'name gy want den parts chan_axis noise faults')
+
+
+def _in(mask, t):
+  return t if mask is None else t[mask.expand_as(t)]
+
+
+def part_measure(role, part, got):
+  """(rms over the part, its worst slice or region) of `got` in the part's units."""
+  u = units(got, role.want, role.den, part.arith)
+  return rms(_in(part.mask, u)), worst_slice(u, part.regions, part.mask)
+
+
+def _part_T(want, den, part_arith, mask, regions, emu, muts):
+  sizes = []
+  for m in muts:
+    u = units(emu[m], want, den, part_arith)
+    sizes.append(worst_slice(u, regions, mask).rms if m[0] == 'scale' else rms(_in(mask, u)))
+  return min(sizes) / 3.0
+
+
+def _f16_mutants(kind, W, has_cols):
+  m = list(DROPS['f16x3'])
+  if kind == 'six decades along a row' and has_cols and W >= 21:  # (mutants_of: where the scale mutant can be judged)
+    m.append(SCALE_MUTANT)
+  return m
+
+
+def _seq32(terms, like):
+  """An fp32 accumulator over `terms` (an iterable of float64 tensors, exact products): one rounding per addition, as an fma chain."""
+  acc = torch.zeros_like(like, dtype=torch.float32)
+  for t in terms:
+    acc = (acc.double() + t).float()
+  return acc.double()
+
+
+def sphere_f16_roles(case):
+  """(roles, tensors) of a SPHERE_F16 case: F16Role records in the order forward, input gradient, weight gradient (compact only, polar
+  only, all); tensors x, w, gy, pos, maps by name."""
+  from oracle import sphere_conv_ref as R
+  ih, iw, B, ci, co, g = case.shape
+  assert B == 1
+  pos = sphere_table(ih, iw)
+  H, W = pos.shape[2:]
+  kind, s = case.kind, case.seed
+  cig, cog, N = ci // g, co // g, H * W
+  build = SPHERE_F16_ROLES[case.shape]
+  maps = sphere_f16_maps(pos)
+  x = data((B, ci, H, W), s + 1, kind)
+  w = _randn((co, cig, 3, 3), s + 2, (2.0 / (9 * cig))**0.5)
+  gy = plateau((B, co, H, W), s + 3) if kind == PLATEAU else data((B, co, H, W), s + 3, kind, gradient=True)
+  pos64, w64 = pos.double(), w.double()
+  tensors = {'x': x, 'w': w, 'gy': gy, 'pos': pos, 'maps': maps}
+  decades = kind == 'six decades along a row'
+  colmask = None
+  if decades:
+    colmask = (torch.arange(W) < contract_columns(W)).view(1, W).expand(H, W)
+  mx, mw = float(x.abs().max()), float(w.abs().max())
+  out = []
+
+  def fwd(c, w_):
+    return torch.einsum('gok,bgkn->bgon', w_.reshape(g, cog, cig * 9), c.reshape(B, g, cig * 9, N)).reshape(B, co, H, W)
+
+  def wgr(gy_, c):
+    return torch.einsum('bgon,bgkn->gok', gy_.reshape(B, g, cog, N), c.reshape(B, g, cig * 9, N)).reshape(co, cig, 3, 3)
+
+  def adjoint(g_):
+    return torch.stack([R.col2im_scatter(g_[:, :, None], pos64[:, 2 * k:2 * k + 2], H, W, 1, 1, 1, 1) for k in range(9)], 2)
+
+  def bwd(G_, w_):
+    return torch.einsum('gock,bgokn->bgcn', w_.reshape(g, cog, cig, 9), G_.reshape(B, g, cog, 9, N)).reshape(B, ci, H, W)
+
+  if 'forward' in build or 'weight gradient' in build:
+    col64 = R.im2col(x.double(), pos64, 3, 3, 1, 1, H, W)  # (B, ci, 9, H, W), unrounded
+    col = col64.float().contiguous()
+    col_abs = R.im2col(x.double().abs(), pos64, 3, 3, 1, 1, H, W)
+
+  if 'forward' in build and kind != 'gradient-sized':
+    assert not bool(maps.fwd_fp32.any()), 'a wrap-around tile on the fp32 kernel: the forward map needs a second part'
+    want, den = fwd(col64, w64), fwd(col_abs, w64.abs())
+    muts = _f16_mutants(kind, W, True)
+    emu = emulations(fwd, col, w, 'f16x3', muts, (mx, mw))
+    regions = {n: (maps.cls == c) for c, n in enumerate(('compact', 'mid', 'wrap')) if bool((maps.cls == c).any())}
+    T = _part_T(want, den, 'f16x3', colmask, regions, emu, muts)
+
+    def fwd_noise():
+      cw, cc = w64.reshape(g, cog, cig, 9), col.double().reshape(B, g, cig, 9, N)
+      terms = (cw[None, :, :, c, k, None] * cc[:, :, None, c, k] for c0 in range(0, cig, 16) for k in range(9) for c in range(c0, min(c0 + 16, cig)))
+      return _seq32(terms, torch.zeros(B, g, cog, N)).reshape(B, co, H, W) - fwd(col.double(), w64)
+
+    tall = maps.cls > 0 if bool((maps.cls > 0).any()) else maps.cls == 0
+    cl = col.reshape(B, g, cig, 9, H, W)
+    lc = torch.zeros_like(cl)
+    lc[:, :, cig - 8:] = cl[:, :, cig - 8:]  # (the tall-window tiles reduce 8 channels x 2 taps per step: their last chunk)
+    lost = fwd(lc.reshape(B, ci, 9, H, W).double(), w64) * tall
+    lost[:, 32:] = 0
+    faults = {'a lost 8-channel chunk in the tall-window tiles': (emu[None] - lost, 'fp16 pieces')}
+    out.append(F16Role('forward', None, want, den, [Part('fp16 pieces', 'f16x3', colmask, T, emu, muts, regions)], 1, fwd_noise, faults))
+
+  if 'input gradient' in build:
+    assert maps.good is not None and cog % 16 == 0
+    G64 = adjoint(gy.double())
+    G, G_abs = G64.float().contiguous(), adjoint(gy.double().abs())
+    want, den = bwd(G64, w64), bwd(G_abs, w64.abs())
+    mg = float(gy.abs().max())
+    muts = _f16_mutants(kind, W, True)
+    emu = emulations(bwd, G, w, 'f16x3', muts, (mg, mw))
+    good, bad = maps.good, ~maps.good
+    gmask = good if colmask is None else good & colmask
+    regions = {n: m_ for n, m_ in (('four-slot tiles', good & ~maps.six), ('six-slot tiles', good & maps.six)) if bool(m_.any())}
+    parts = []
+    if bool(gmask.any()):
+      parts.append(Part('fp16 tiles', 'f16x3', gmask, _part_T(want, den, 'f16x3', gmask, regions, emu, muts), emu, muts, regions))
+    if bool(bad.any()):
+      muts3 = list(DROPS['bf16x6'])
+      emu3 = emulations(bwd, G, w, 'bf16x6', muts3)
+      parts.append(Part('fp32 tiles', 'bf16x6', bad, _part_T(want, den, 'bf16x6', bad, None, emu3, muts3), emu3, muts3, None))
+
+    def bwd_noise():
+      cw, cG = w64.reshape(g, cog, cig, 9), G.double().reshape(B, g, cog, 9, N)
+      terms = (cw[None, :, o, :, k, None] * cG[:, :, o, None, k] for o0 in range(0, cog, 16) for k in range(9) for o in range(o0, o0 + 16))
+      return _seq32(terms, torch.zeros(B, g, cig, N)).reshape(B, ci, H, W) - bwd(G.double(), w64)
+
+    faults = {}
+    if 'six-slot tiles' in regions:
+      Gl = torch.zeros_like(G)
+      Gl[:, co - 16:] = G[:, co - 16:]
+      faults['a lost 16-channel chunk in the six-slot tiles'] = (emu[None] - bwd(Gl.double(), w64) * regions['six-slot tiles'], 'fp16 tiles')
+    if bool(bad.any()):
+      h0, w0 = (int(v[0]) for v in torch.nonzero(bad, as_tuple=True))
+      v = parts[-1].emu[None].clone()
+      v[:, :, h0:h0 + 64, w0:w0 + 4] = 0.0
+      faults['one bad tile left unwritten'] = (v, 'fp32 tiles')
+    tensors['G'] = G
+    out.append(F16Role('input gradient', gy, want, den, parts, 1, bwd_noise, faults))
+
+  if 'weight gradient' in build and kind != PLATEAU and (not decades or N <= SPHERE_WGRAD_DECADES_MAX_PIXELS):
+    compact = (maps.cls == 0).view(1, 1, H, W)
+    has_polar = not bool(compact.all())  # (16 x 32: four compact tiles and nothing else -- the whole gradient on fp16 pieces)
+    assert maps.plan.counts[0] > 0 and (maps.plan.polar is not None) == has_polar
+    gy_c, gy_p = (gy * compact).contiguous(), (gy * ~compact).contiguous()
+    den_of = lambda g_: wgr(g_.double().abs(), col_abs)
+    m16, m3 = list(DROPS['f16x3']), list(DROPS['bf16x6'])
+    # the pixels of a 64 x 4 tile in sequence, then the tiles in sequence: blocks of 256 pixels in tile order
+    tile_id = (torch.arange(H).view(H, 1) // 64) * ((W + 3) // 4) + torch.arange(W).view(1, W) // 4
+    order = torch.argsort(tile_id.reshape(-1), stable=True)
+
+    def wgr_noise_of(g_):
+      def noise():
+        nb = -(-N // 256)
+        pad = nb * 256 - N
+        gg = F.pad(g_.double().reshape(g, cog, N)[:, :, order], (0, pad)).reshape(g, cog, nb, 256)
+        cc = F.pad(col.double().reshape(g, cig * 9, N)[:, :, order], (0, pad)).reshape(g, cig * 9, nb, 256)
+        per = _seq32((torch.einsum('gob,gkb->bgok', gg[..., i], cc[..., i]) for i in range(256)), torch.zeros(nb, g, cog, cig * 9))
+        return _seq32(per, per[0]).reshape(co, cig, 3, 3) - wgr(g_.double(), col.double())
+      return noise
+
+    if not has_polar:
+      e16 = emulations(wgr, gy, col, 'f16x3', m16, (float(gy.abs().max()), mx))
+      want, den = wgr(gy.double(), col64), den_of(gy)
+      out.append(F16Role('weight gradient', gy, want, den,
+                         [Part('fp16 pieces', 'f16x3', None, _part_T(want, den, 'f16x3', None, None, e16, m16), e16, m16, None)], 0,
+                         wgr_noise_of(gy), {}))
+      return out, tensors
+    e16c = emulations(wgr, gy_c, col, 'f16x3', m16, (float(gy_c.abs().max()), mx))
+    want, den = wgr(gy_c.double(), col64), den_of(gy_c)
+    out.append(F16Role('weight gradient, compact pixels', gy_c, want, den,
+                       [Part('fp16 pieces', 'f16x3', None, _part_T(want, den, 'f16x3', None, None, e16c, m16), e16c, m16, None)], 0,
+                       wgr_noise_of(gy_c), {}))
+    e3p = emulations(wgr, gy_p, col, 'bf16x6', m3)
+    want, den = wgr(gy_p.double(), col64), den_of(gy_p)
+    out.append(F16Role('weight gradient, polar pixels', gy_p, want, den,
+                       [Part('bf16 pieces', 'bf16x6', None, _part_T(want, den, 'bf16x6', None, None, e3p, m3), e3p, m3, None)], 0,
+                       wgr_noise_of(gy_p), {'the polar items left out': (torch.zeros_like(want), 'bf16 pieces')}))
+    # unmasked: the fp16 part scaled by the WHOLE tensor's maximum plus the bf16 part; T from the fp16 part's mutants
+    e16 = emulations(wgr, gy_c, col, 'f16x3', m16, (float(gy.abs().max()), mx))
+    emu = {k: v + e3p[None] for k, v in e16.items()}
+    want, den = wgr(gy.double(), col64), den_of(gy)
+    out.append(F16Role('weight gradient', gy, want, den,
+                       [Part('both', 'f16x3', None, _part_T(want, den, 'f16x3', None, None, emu, m16), emu, m16, None)], 0,
+                       wgr_noise_of(gy), {'the polar items left out': (e16[None], 'both')}))
+  return out, tensors
+
+
+def f16_role_id(case, role):
+  return '%s | %s' % (case_id(case), role.name)

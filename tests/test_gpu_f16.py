@@ -369,8 +369,8 @@ def test_classifier_backward_leaves_its_gradients_maximum(f16_switch, shape):
 @pytest.mark.parametrize('ih,iw,B,ci,co,groups', [(128, 256, 2, 128, 128, 1), (128, 256, 2, 64, 128, 1), (128, 256, 1, 32, 48, 2), (128, 256, 2, 16, 40, 1)])
 @pytest.mark.parametrize('case', ['unit variance', 'gradient-sized', 'one outlier'])
 def test_sphere_forward_on_two_fp16_pieces_against_float64(ih, iw, B, ci, co, groups, case, f16_switch):
-  """mode_sphere_conv_fwd_win_split_f16: the small-window tiles of the windowed spherical forward on two fp16 pieces and three MFMAs per
-  product (the tall-window tiles next to the poles keep three bf16 pieces), against the float64 oracle (oracle/sphere_conv_ref.py) on a
+  """mode_sphere_conv_fwd_win_split_f16: the windowed spherical forward on two fp16 pieces and three MFMAs per product (the tall-window
+  tiles next to the poles too: one launch over all window classes, their weights packed in fp16 pieces as well), against the float64 oracle (oracle/sphere_conv_ref.py) on a
   Cassini grid -- held to the bound of the three-piece path (2^-22 sqrt(terms) 8 of the largest output) and to twice that path's own
   error plus a tenth of the bound; the same bits in every call; an inference call (f16 = False) keeps the three-piece bits."""
   from oracle import mode_ref, sphere_conv_ref

@@ -19,8 +19,8 @@ its six-decades kind at 16 x 32 only; the windowed input gradient at 128 -> 128 
 an adjoint plan.  Two of these rows are recorded findings (KNOWN below): expected failures, not passes.
 
 Three bf16 pieces: CONV_ARITH = 'bf16x6' with CONV3D_S1_F16, CONV2D_F16, SPHERE_FWD_F16 and SPHERE_BWD_F16 off -- the 24-bit opt-out of
-inference and of `--no-conv3d-f16`.  Two fp16 pieces: the default switches; stride-1 3-D and 3 x 3 layers (the spherical fp16 setting mixes
-both arithmetics tile by tile and stays out).
+inference and of `--no-conv3d-f16`.  Two fp16 pieces: the default switches; stride-1 3-D and 3 x 3 layers (the spherical fp16 entries, whose weight and input
+gradients mix arithmetics tile by tile, are judged part by part in tests/test_gpu_sphere_f16_precision.py).
 
 MEASURED on an MI355X (one run of this file; T is computed, rms and worst slice are measured; for each family, role, arithmetic and kind of
 data the case with the least room, i.e. the largest worst slice / T, and over how many shapes):
