@@ -34,7 +34,9 @@ EXTENSIONS = (('SELFSUP', 'mode_hip_selfsup.h', 'MODE_SELFSUP_VERSION', 'mode_se
 # EXTENSIONS is pinned to those three rows by the fourth header's tests; the rows since stand in a second tuple that the same two
 # loops walk after the first.  The next header is one more row here.
 EXTENSIONS_2 = (('MVVIS', 'mode_hip_mvvis.h', 'MODE_MVVIS_VERSION', 'mode_mvvis_version'),)
-for _name, _file, _const, _ in EXTENSIONS + EXTENSIONS_2:
+# EXTENSIONS_2 is pinned to that row by the fifth header's tests in its turn: a third tuple, the same two loops.
+EXTENSIONS_3 = (('MVRENDER', 'mode_hip_mvrender.h', 'MODE_MVRENDER_VERSION', 'mode_mvrender_version'),)
+for _name, _file, _const, _ in EXTENSIONS + EXTENSIONS_2 + EXTENSIONS_3:
   _h = _header.load(os.path.join(os.path.dirname(_header.PATH), _file))
   globals().update({_name: _h, _name + '_VERSION': _h.constants[_const], _name + '_LAUNCHING': frozenset(
       n for n, (_, params) in _h.prototypes.items() if any(t == _header.STREAM for t, _ in params))})
@@ -60,7 +62,7 @@ def lib():
         if have != ABI_VERSION:
           raise RuntimeError('libmode_hip.so has ABI version %d, this binding needs %d: rebuild it (python '
                              'mode-2022_amd/mode_hip/build.py)' % (have, ABI_VERSION))
-        for ext, file, _, version_fn in EXTENSIONS + EXTENSIONS_2:
+        for ext, file, _, version_fn in EXTENSIONS + EXTENSIONS_2 + EXTENSIONS_3:
           have = getattr(handle, version_fn)() if hasattr(handle, version_fn) else None
           want = globals()[ext + '_VERSION']  # read now, not at import
           if have != want:
@@ -96,6 +98,10 @@ LrParams = _header.structure(SELFSUP, 'mode_lr_params', 'LrParams', 'struct mode
 # multi-view reprojection loss: the statistics as mode_mvphoto_loss_fwd leaves them
 MVP_MAX_SOURCES, MVP_STATS, MVP_NO_WINNER = (MVPHOTO.constants['MODE_MVP_' + k] for k in 'MAX_SOURCES STATS NO_WINNER'.split())
 (MVP_N, MVP_SUM_MIN, MVP_SUM_SMOOTH_X, MVP_SUM_SMOOTH_Y, MVP_WINS) = (MVPHOTO.constants['MODE_MVP_' + k] for k in 'N SUM_MIN SUM_SMOOTH_X SUM_SMOOTH_Y WINS'.split())
+
+# novel-view rendering: the colour modes, and the classes of a target pixel as mode_mv_render leaves them in hit
+MVR_SPLAT, MVR_RESAMPLE, MVR_MAX_CHANNELS = (MVRENDER.constants['MODE_MVR_' + k] for k in 'SPLAT RESAMPLE MAX_CHANNELS'.split())
+(MVR_HIT_NONE, MVR_HIT_DIRECT, MVR_HIT_FILLED, MVR_HIT_RESAMPLED) = (MVRENDER.constants['MODE_MVR_HIT_' + k] for k in 'NONE DIRECT FILLED RESAMPLED'.split())
 
 
 def check(rc, what):

@@ -6,7 +6,8 @@ import threading
 
 import torch
 
-from . import (CONSTANTS, LR_STATS, METRICS_COUNT, METRICS_MAX_THRESHOLDS, MVP_MAX_SOURCES, MVP_STATS, MVP_WINS, PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS,
+from . import (CONSTANTS, LR_STATS, METRICS_COUNT, METRICS_MAX_THRESHOLDS, MVP_MAX_SOURCES, MVP_STATS, MVP_WINS, MVR_MAX_CHANNELS, MVR_RESAMPLE, MVR_SPLAT,
+               PHOTOMETRIC_MAX_MAPS, PHOTOMETRIC_STATS,
                BnEpilogue, LrParams, MetricsParams, PhotometricParams, check, lib, profiling, ptr, require_f32c, require_gpu, stream_of)
 
 
@@ -2417,6 +2418,77 @@ def mv_visibility(depth, poses, tol=0.05, radius=0, return_zbuf=False):
     _call('mode_mv_visibility', ptr(d), poses.ctypes.data_as(ctypes.c_void_p), S, F, H, W, tol, int(radius), ptr(ws), ws.numel() * 8, ptr(vis),
           _optr(zbuf), stream_of(d))
   return (vis, zbuf) if return_zbuf else vis
+
+
+# ------------------------------------------------------------------------------------ novel-view rendering
+# What the fused depth map means, shown: the reference panorama lifted by it and splatted into other views.  The z-buffer is the
+# visibility's; every target pixel names the reference pixel it shows, and takes its colour or the bilinear value around the point
+# where its own ray at that range falls back into the reference.  Four launches for any F, T <= 8 and C.
+_MVR_MODES = {'splat': MVR_SPLAT, 'resample': MVR_RESAMPLE}
+
+
+def mv_render(image, depth, poses, tol=0.05, fill=1, mode='resample', return_range=False, return_hit=False, return_index=False):
+  """A panorama seen from T other poses through its depth map (include/mode_hip_mvrender.h has the definition): image
+  (F, C, H, W) fp32 on the device with C = 1 .. 4, taken as it is (normalised or not: values are copied or interpolated); depth
+  (F, 1, H, W) or (F, H, W) and poses in every form HF.mv_visibility takes, (T, 12) or (T, 3, 4) [A | o] with X_t = A X + o
+  (utils.rig.view_pose(centre, rotation) builds one).  Every pixel is lifted by its depth and lands in each target view; the nearest
+  one owns a target pixel.  fill = 1 closes holes from the 3 x 3 neighbourhood and replaces a surface that is more than (1 + tol)
+  times farther than the nearest neighbour's (seen through the cracks of a magnified near surface); fill = 0 leaves holes.
+  mode = 'splat' copies the owning pixel's colour; 'resample' samples the image bilinearly where the target pixel's own ray, at the
+  range found, falls back into the reference (sharper; the pixels beyond the reference's poles take the splat's value).  Returns out
+  (F, T, C, H, W) fp32, 0 where nothing is seen; the extras follow in the order range (F, T, H, W) fp32, +inf where nothing is seen;
+  hit (F, T, H, W) uint8: 0 nothing, 1 direct, 2 filled, plus 4 where resampled; index (F, T, H, W) int32: the reference pixel
+  h W + w shown, -1 for none.  T > 8 runs in chunks of 8.  No autograd (the inputs are detached), no host synchronisation."""
+  import math
+
+  import numpy as np
+  require_gpu(image, depth)
+  if image.dim() != 4 or not 1 <= image.shape[1] <= MVR_MAX_CHANNELS:
+    raise ValueError('mv_render: image must be (F, C, H, W) with C = 1 .. %d, got %s' % (MVR_MAX_CHANNELS, tuple(image.shape)))
+  F, C, H, W = image.shape
+  if tuple(depth.shape) not in ((F, 1, H, W), (F, H, W)):
+    raise ValueError('mv_render: a depth map of shape %s for an image %s' % (tuple(depth.shape), tuple(image.shape)))
+  if isinstance(poses, torch.Tensor):
+    poses = poses.detach().cpu().numpy()
+  poses = np.asarray(poses, dtype=np.float64)
+  if poses.ndim not in (2, 3) or poses.size % 12 or tuple(poses.shape[1:]) not in ((12,), (3, 4)):
+    raise ValueError('mv_render: poses must be (T, 12) or (T, 3, 4), got %s' % (tuple(poses.shape),))
+  poses = np.ascontiguousarray(poses.reshape(-1, 12))
+  T = poses.shape[0]
+  if T < 1:
+    raise ValueError('mv_render: no target view')
+  tol = float(tol)
+  if not (math.isfinite(tol) and tol >= 0):
+    raise ValueError('mv_render: tol = %r must be finite and >= 0' % (tol,))
+  if fill not in (0, 1):
+    raise ValueError('mv_render: fill = %r (0 or 1)' % (fill,))
+  if mode not in _MVR_MODES:
+    raise ValueError("mv_render: mode = %r ('splat' or 'resample')" % (mode,))
+  img = image.detach().contiguous()
+  d = depth.detach().reshape(F, H, W).contiguous()
+  require_f32c(img, d)
+  dev = d.device
+  out = torch.empty((F, T, C, H, W), dtype=torch.float32, device=dev)
+  hit = torch.empty((F, T, H, W), dtype=torch.uint8, device=dev)
+  rng = torch.empty((F, T, H, W), dtype=torch.float32, device=dev) if return_range else None
+  index = torch.empty((F, T, H, W), dtype=torch.int32, device=dev) if return_index else None
+  per_pair = 2 * 20 + 2 * 12 + 8 + 1 + 8 * C + (4 if return_range else 0) + (4 if return_index else 0)
+  with torch.cuda.device_of(d), profiling.region('mv_render', 4 * d.numel() + per_pair * hit.numel(), 0, dev):
+    for t0 in range(0, T, MVP_MAX_SOURCES):  # a call takes up to 8 views
+      n = min(MVP_MAX_SOURCES, T - t0)
+      whole = n == T
+      o, h = (out, hit) if whole else (out.new_empty((F, n, C, H, W)), hit.new_empty((F, n, H, W)))
+      r = rng if whole or rng is None else rng.new_empty((F, n, H, W))
+      i = index if whole or index is None else index.new_empty((F, n, H, W))
+      ws = torch.empty(max(lib().mode_mvrender_workspace_bytes(n, F, H, W) // 8, 1), dtype=torch.float64, device=dev)
+      _call('mode_mv_render', ptr(img), ptr(d), poses[t0:t0 + n].ctypes.data_as(ctypes.c_void_p), n, F, C, H, W, tol, int(fill), _MVR_MODES[mode],
+            ptr(ws), ws.numel() * 8, ptr(o), ptr(h), _optr(r), _optr(i), stream_of(d))
+      if not whole:
+        for whole_t, part_t in ((out, o), (hit, h), (rng, r), (index, i)):
+          if whole_t is not None:
+            whole_t[:, t0:t0 + n] = part_t
+  extras = tuple(x for x, want in ((rng, return_range), (hit, return_hit), (index, return_index)) if want)
+  return (out,) + extras if extras else out
 
 
 # ------------------------------------------------------------------------------------ scoring in the ERP domain

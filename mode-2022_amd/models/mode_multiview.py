@@ -271,6 +271,17 @@ class ModeMultiView(nn.Module):
       return self.fusion.feature_extraction(fusion_input, rgb)
     return self.fusion.feature_extraction(fusion_input)
 
+  def _posed_rig(self, who):
+    """The rig whose panorama poses fusion_selfsup_loss and render_views use: self.rig, or Deep360's for dbname='Deep360'."""
+    from utils.rig import CameraRig
+    if self.rig is not None:
+      return self.rig
+    if self.dbname != 'Deep360':
+      raise ValueError("ModeMultiView(dbname=%r).%s: that setting takes the baselines 0.6 sqrt(2) and 1.2 but keeps the "
+                       'unit square\'s translations, so its camera centres are not one rig and the panoramas have no consistent poses; '
+                       'build the module with rig=CameraRig.square(0.6 * sqrt(2))' % (self.dbname, who))
+    return CameraRig.deep360()
+
   def fusion_selfsup_loss(self, frames, sources=None, poses=None, visibility=None, **loss_kw):
     """fusion_loss without ground truth: frames exactly as fusion_loss takes them -> (loss, depth.detach()).  The chain is
     fusion_loss's with the SILog term replaced by HF.mv_photometric_loss: the fused depth lives in the common view's Cassini frame, and
@@ -289,17 +300,10 @@ class ModeMultiView(nn.Module):
     visibility: True, or a dict with tol and / or radius (HF.mv_visibility's; defaults 0.05 and 0): the loss counts a pixel
     for a source only where that source sees it -- the masks are HF.mv_visibility of the detached fused depth of this call with the
     same poses (the detached values of learned ones), constants of every gradient."""
-    from utils.rig import CameraRig
     if self.resize:
       raise ValueError('ModeMultiView(resize=True).fusion_selfsup_loss: the reprojection loss compares the panoramas at their own size, '
                        'and the fusion network runs at half size here; build the module with resize=False')
-    rig = self.rig
-    if rig is None:
-      if self.dbname != 'Deep360':
-        raise ValueError("ModeMultiView(dbname=%r).fusion_selfsup_loss: that setting takes the baselines 0.6 sqrt(2) and 1.2 but keeps the "
-                         'unit square\'s translations, so its camera centres are not one rig and the panoramas have no consistent poses; '
-                         'build the module with rig=CameraRig.square(0.6 * sqrt(2))' % (self.dbname,))
-      rig = CameraRig.deep360()
+    rig = self._posed_rig('fusion_selfsup_loss')
     for k in loss_kw:
       if k not in ('alpha', 'lam', 'beta', 'mean', 'std'):
         raise ValueError('fusion_selfsup_loss returns (loss, depth); %r is not a parameter of the loss (alpha, lam, beta, mean, std); call '
@@ -340,6 +344,41 @@ class ModeMultiView(nn.Module):
     else:
       loss = HF.mv_photometric_loss(ref, src, output, poses, masks=HF.mv_visibility(output.detach(), poses, **vis_kw), **loss_kw)
     return loss, output.detach()
+
+  def render_views(self, frames, poses, erp=False, **render_kw):
+    """What the fused depth map means, shown: frames as forward() takes them, poses (T, 12) or (T, 3, 4) [A | o] of the views
+    to render (utils.rig.view_pose(centre, rotation); any T) -> (rendered (F, T, 3, H, W), range (F, T, H, W), hit (F, T, H, W) uint8):
+    the frame's own panorama rig.reference_panorama() -- the image the fused depth map is a depth map of, normalised as the frames are
+    -- seen from each pose through forward()'s depth, by HF.mv_render.  render_kw: tol, fill, mode.  Runs under no_grad with every
+    module in eval mode, whatever mode they are in, and leaves their modes as they were.  erp=True: rendered and range go through
+    utils.geometry.cassini2Equirec, (F, T, 3, W, H) and (F, T, W, H); hit stays in the Cassini frame.  Refused: resize=True and
+    dbname='other', as fusion_selfsup_loss refuses them."""
+    if self.resize:
+      raise ValueError('ModeMultiView(resize=True).render_views: the depth map is rendered with the panorama at its own size; build the '
+                       'module with resize=False')
+    rig = self._posed_rig('render_views')
+    for k in render_kw:
+      if k not in ('tol', 'fill', 'mode'):
+        raise ValueError('render_views returns (rendered, range, hit); %r is not a parameter of the render (tol, fill, mode); call '
+                         'HF.mv_render for the index' % (k,))
+    ref_index = rig.reference_panorama()
+    modes = [(m, m.training) for m in self.modules()]
+    self.eval()
+    try:
+      with torch.no_grad():
+        depth = self.forward(frames)
+        left, right, _, _ = self._ingest(frames)
+        H, W = left.shape[-2:]
+        ref = (left, right)[ref_index % 2].reshape(-1, self.pairs, 3, H, W)[:, ref_index // 2]
+        rendered, rng, hit = HF.mv_render(ref, depth, poses, return_range=True, return_hit=True, **render_kw)
+        if erp:
+          F, T = hit.shape[:2]
+          rendered = geometry.cassini2Equirec(rendered.reshape(F * T, 3, H, W)).reshape(F, T, 3, W, H)
+          rng = geometry.cassini2Equirec(rng.reshape(F * T, 1, H, W)).reshape(F, T, W, H)
+    finally:
+      for m, was in modes:
+        m.training = was
+    return rendered, rng, hit
 
   def photometric_loss(self, frames, **loss_kw):
     """Adapt stage 1 to a rig's own images, which come without depth or disparity ground truth: frames exactly as

@@ -41,6 +41,20 @@ def _euler(R):
   return pitch, yaw, roll
 
 
+def view_pose(centre, rotation=None):
+  """(3, 4) float64 [A | o] of a camera that stands at `centre` (in the common view's axes) with orientation R = `rotation` (3 x 3,
+  orthonormal to 1e-9; None: the common view's own): A = R^T, o = -A centre, so that X_t = A X + o and the camera stands at -A^T o.
+  The inverse of CameraRig.camera_centres(); a target view of HF.mv_render / ModeMultiView.render_views."""
+  c = np.asarray(centre, dtype=np.float64)
+  if c.shape != (3,) or not np.isfinite(c).all():
+    raise ValueError('view_pose: centre must be 3 finite numbers, got %r' % (centre,))
+  R = np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64)
+  if R.shape != (3, 3) or not np.isfinite(R).all() or np.abs(R @ R.T - np.eye(3)).max() > 1e-9:
+    raise ValueError('view_pose: rotation must be a 3 x 3 matrix, orthonormal to 1e-9, got %r' % (rotation,))
+  A = R.T
+  return np.concatenate([A, -(A @ c)[:, None]], 1)
+
+
 class PairPose(object):
   """One stereo pair of a rig: PairPose(name, baseline, kind, pose=()).
 

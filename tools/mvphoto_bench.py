@@ -6,6 +6,7 @@ sources (Deep360's panoramas 1, 3, 5), F = 1 and F = 2.
 
     python tools/mvphoto_bench.py [--windows 4] [--min-window 0.3] [--out profiles/mvphoto_bench_mi355x.json]
     python tools/mvphoto_bench.py --visibility [--out profiles/mvvis_bench_mi355x.json]   (main_visibility below)
+    python tools/mvphoto_bench.py --render [--out profiles/mvrender_bench_mi355x.json]      (main_render below)
 
 First the two sides' outputs are compared, by the bound of tests/test_gpu_mvphoto.py: the composition is also run in float64, the
 yardstick of the loss and of the gradient is A's own fp32 error against that run (never below 2^-23 of the largest element), and B may
@@ -354,6 +355,181 @@ def main_visibility(args):
   return 0
 
 
+RENDER_TWISTS = ((0.01, 0.02, -0.015, 0.10, 0.02, -0.03), (0.05, -0.12, 0.08, -0.04, 0.07, 0.05), (-0.3, 0.2, 0.15, 0.15, -0.1, 0.2))
+
+
+def render_poses(torch):
+  """(3, 3, 4) float64: [I | 0] twisted by RENDER_TWISTS, A = Exp(omega), o = tau (the target poses of the tests of DESIGN 29)."""
+  tw = torch.tensor(RENDER_TWISTS, dtype=torch.float64)
+  w, z = tw[:, :3], torch.zeros(3, dtype=torch.float64)
+  K = torch.stack([torch.stack([z, -w[:, 2], w[:, 1]], -1), torch.stack([w[:, 2], z, -w[:, 0]], -1), torch.stack([-w[:, 1], w[:, 0], z], -1)], -2)
+  return torch.cat([torch.linalg.matrix_exp(K), tw[:, 3:].unsqueeze(-1)], -1).contiguous()
+
+
+def composed_render(torch, image, depth, poses, tol=0.05, fill=1, resample=True):
+  """The render of include/mode_hip_mvrender.h composed from torch operators on the GPU, from the definition: the projection in
+  float64, two scatter_reduce passes with amin (z, then the owners among the pairs whose rho is z), the 3 x 3 scan in the definition's
+  order, gathers, and a hand-written bilinear in fp32.  image (F, C, H, W) fp32, depth (F, H, W), poses (T, 3, 4) float64 on the device
+  -> (out (F, T, C, H, W) fp32, hit (F, T, H, W) uint8, index (F, T, H, W) int32)."""
+  F, C, H, W = image.shape
+  dev = depth.device
+  theta = (math.pi - (torch.arange(H, dtype=torch.float64, device=dev) + 0.5) * 2.0 * math.pi / H).view(H, 1)
+  phi = (math.pi / 2 - (torch.arange(W, dtype=torch.float64, device=dev) + 0.5) * math.pi / W).view(1, W)
+  n = torch.stack([torch.sin(phi).expand(H, W), torch.cos(phi) * torch.sin(theta), torch.cos(phi) * torch.cos(theta)], -1)
+  good = torch.isfinite(depth) & (depth > 0)
+  D = torch.where(good, depth, torch.ones_like(depth)).double()
+  inf = torch.full((F, H, W), float('inf'), dtype=torch.float64, device=dev)
+  big = 1 << 40
+  pixel = torch.arange(H * W, device=dev).expand(F, -1)
+  flat = image.reshape(F, C, H * W)
+
+  def angles(X, ok):
+    r = X.norm(dim=-1)
+    ok = ok & (r > 0)
+    u = (math.pi / 2 - torch.asin((X[..., 0] / torch.where(ok, r, torch.ones_like(r))).clamp(-1, 1))) * W / math.pi - 0.5
+    v = (math.pi - torch.atan2(X[..., 1], X[..., 2])) * H / (2.0 * math.pi) - 0.5
+    return r, u, v, ok & (u >= 0) & (u <= W - 1)
+
+  def shift(a, dy, dx, pad):
+    b = torch.roll(a, -dy, -2)
+    if dx == 0:
+      return b
+    edge = torch.full_like(b[..., :1], pad)
+    return torch.cat([b[..., 1:], edge], -1) if dx > 0 else torch.cat([edge, b[..., :-1]], -1)
+
+  def gather(idx):
+    return flat.gather(2, idx.reshape(F, 1, -1).expand(F, C, -1)).reshape(F, C, H, W)
+
+  outs, hits, indices = [], [], []
+  for t in range(poses.shape[0]):
+    A, o = poses[t, :, :3], poses[t, :, 3]
+    rho, u, v, valid = angles(D.unsqueeze(-1) * (n @ A.T) + o, good)
+    at = torch.where(valid, torch.remainder(torch.floor(v + 0.5).long(), H) * W + torch.floor(u + 0.5).long().clamp(0, W - 1),
+                     torch.zeros_like(u, dtype=torch.long)).reshape(F, -1)
+    key = torch.where(valid, rho, inf).reshape(F, -1)
+    z = inf.reshape(F, -1).scatter_reduce(1, at, key, 'amin')
+    mine = valid.reshape(F, -1) & (key == z.gather(1, at))
+    owner = torch.full_like(pixel, big).scatter_reduce(1, at, torch.where(mine, pixel, torch.full_like(pixel, big)), 'amin')
+    z, owner = z.reshape(F, H, W), torch.where(owner == big, torch.full_like(owner, -1), owner).reshape(F, H, W)
+    if fill:
+      zn, first = inf, torch.full_like(owner, -1)
+      for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+          zz, oo = shift(z, dy, dx, float('inf')), shift(owner, dy, dx, -1)
+          better = zz < zn
+          zn, first = torch.where(better, zz, zn), torch.where(better, oo, first)
+      direct = torch.isfinite(z) & (z <= (1.0 + tol) * zn)
+      filled = ~direct & torch.isfinite(zn)
+      zc, src = torch.where(direct, z, zn), torch.where(direct, owner, first)
+    else:
+      direct, filled, zc, src = torch.isfinite(z), torch.zeros_like(good), z, owner
+    seen = direct | filled
+    out = torch.where(seen.unsqueeze(1), gather(src.clamp(min=0)), torch.zeros((), device=dev))
+    hit = direct.to(torch.uint8) + 2 * filled.to(torch.uint8)
+    if resample:
+      _, ur, vr, ok = angles((torch.where(seen, zc, torch.ones_like(zc)).unsqueeze(-1) * n - o) @ A, seen)
+      us, vs = torch.where(ok, ur, torch.zeros_like(ur)), torch.where(ok, vr, torch.zeros_like(vr))
+      x0, y0 = us.floor().clamp(max=W - 2), vs.floor()
+      tt, q = (us - x0).float().unsqueeze(1), (vs - y0).float().unsqueeze(1)
+      x0 = x0.long()
+      ya, yb = torch.remainder(y0.long(), H), torch.remainder(y0.long() + 1, H)
+      top = (1 - tt) * gather(ya * W + x0) + tt * gather(ya * W + x0 + 1)
+      bot = (1 - tt) * gather(yb * W + x0) + tt * gather(yb * W + x0 + 1)
+      out = torch.where(ok.unsqueeze(1), (1 - q) * top + q * bot, out)
+      hit = hit + 4 * ok.to(torch.uint8)
+    outs.append(out)
+    hits.append(hit)
+    indices.append(torch.where(seen, src, torch.full_like(src, -1)).to(torch.int32))
+  return torch.stack(outs, 1), torch.stack(hits, 1), torch.stack(indices, 1)
+
+
+def main_render(args):
+  """--render: novel-view rendering at 1024 x 512 with T = 3 (RENDER_TWISTS), C = 3, fill = 1, tol = 0.05, both colour
+  modes.  A: composed_render.  B: HF.mv_render (csrc/mv_render.hip) with hit and index returned.  Before timing, B's hit and index
+  must equal A's in every element, and the colours are compared (the splat's exactly; the resampled ones' largest difference is
+  recorded: both sides are fp32 after the geometry).  The windows alternate A B per mode; no ratio is fixed in advance, the medians
+  and the window ranges are the result.  For B also the algorithmic bytes -- per pixel a depth read; per pixel and view a key and an
+  owner set, an atomic on a key, rho and the landing index written and read, a key read and an atomic on an owner, a key and an owner
+  read, hit, range and index written, and per channel a colour read and written -- over its device time."""
+  import torch
+  from mode_hip import functional as HF
+  assert torch.cuda.is_available(), 'mvphoto_bench needs a GPU'
+  dev = torch.device('cuda:0')
+  H, W, T, C = 1024, 512, 3, 3
+  poses = render_poses(torch)
+  poses_host, poses_dev = poses.numpy(), poses.to(dev)
+  out = {'tool': 'mvphoto_bench --render', 'H': H, 'W': W, 'T': T, 'C': C, 'tol': 0.05, 'fill': 1, 'min_window_s': args.min_window,
+         'windows': args.windows, 'frames': {}}
+  for F in args.frames:
+    image, _, depth = inputs(torch, F, H, W, 1, dev, 100 + F)
+    row = {'pixel_view_pairs': F * T * H * W}
+
+    def step(side, mode):
+      if side == 'A':
+        return composed_render(torch, image, depth, poses_dev, resample=mode == 'resample')
+      return HF.mv_render(image, depth, poses_host, mode=mode, return_hit=True, return_index=True)
+
+    for mode in ('splat', 'resample'):
+      oa, ha, ia = step('A', mode)
+      ob, hb, ib = step('B', mode)
+      torch.cuda.synchronize()
+      check = {'hit_that_differ': int((ha != hb).sum()), 'index_that_differ': int((ia != ib).sum()),
+               'share_none_direct_filled': [round(float((hb & 3 == k).float().mean()), 4) for k in range(3)],
+               'share_resampled': round(float((hb & 4 != 0).float().mean()), 4), 'max_abs_colour_difference': float((oa - ob).abs().max())}
+      row[mode] = check
+      print('F=%d %s: %s' % (F, mode, json.dumps(check)), flush=True)
+      assert check['hit_that_differ'] == 0 and check['index_that_differ'] == 0, check
+      assert check['max_abs_colour_difference'] == 0 if mode == 'splat' else check['max_abs_colour_difference'] < 1e-5, check
+      del oa, ha, ia, ob, hb, ib
+    torch.cuda.empty_cache()
+
+    def window(side, mode, n):
+      torch.cuda.synchronize()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(n):
+        step(side, mode)
+      e1.record()
+      torch.cuda.synchronize()
+      return 1e-3 * e0.elapsed_time(e1)
+
+    sides = [(side, mode) for mode in ('splat', 'resample') for side in ('A', 'B')]
+    iters = {}
+    for key in sides:
+      window(key[0], key[1], 3)  # warm-up: allocator, kernels loaded
+      per = window(key[0], key[1], 5) / 5
+      iters[key] = max(5, int(math.ceil(1.2 * args.min_window / per)))
+    times = {key: [] for key in sides}
+    for w in range(args.windows):
+      for key in sides:
+        sec = window(key[0], key[1], iters[key])
+        while sec < args.min_window:  # the calibration ran slow: a longer window, and this one is not counted
+          iters[key] = int(math.ceil(1.3 * iters[key] * args.min_window / sec))
+          sec = window(key[0], key[1], iters[key])
+        times[key].append(1e6 * sec / iters[key])
+        print('F=%d window %d %s %s: %.1f us (%d in %.3f s)' % (F, w, key[0], key[1], times[key][-1], iters[key], sec), flush=True)
+    nbytes = 4 * F * H * W + ((8 + 4) + 8 + 2 * (8 + 4) + (8 + 4) + (8 + 4) + (1 + 4) + 2 * 4 * C) * F * T * H * W
+    for mode in ('splat', 'resample'):
+      med = {}
+      for side in ('A', 'B'):
+        v = sorted(times[(side, mode)])
+        med[side] = 0.5 * (v[(len(v) - 1) // 2] + v[len(v) // 2])
+        row[mode]['%s_us' % side] = [round(x, 1) for x in times[(side, mode)]]
+        row[mode]['%s_us_median_min_max' % side] = [round(med[side], 1), round(v[0], 1), round(v[-1], 1)]
+      row[mode]['B_algorithmic_bytes'] = nbytes
+      row[mode]['B_effective_GBps'] = [round(nbytes / (us * 1e-6) / 1e9, 1) for us in times[('B', mode)]]
+      row[mode]['B_ns_per_pixel_and_view'] = [round(1e3 * us / (F * H * W * T), 3) for us in times[('B', mode)]]
+      row[mode]['A_over_B_median'] = round(med['A'] / med['B'], 2)
+    out['frames'][str(F)] = row
+  line = json.dumps(out)
+  print(line)
+  if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+      f.write(line + '\n')
+  return 0
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--windows', type=int, default=4, help='windows per side and number of frames')
@@ -364,7 +540,10 @@ def main():
                   '--out profiles/mvpose_bench_mi355x.json)')
   ap.add_argument('--visibility', action='store_true', help='the z-buffer visibility masks and the masked loss (DESIGN 28; '
                   '--out profiles/mvvis_bench_mi355x.json)')
+  ap.add_argument('--render', action='store_true', help='novel-view rendering (DESIGN 29; --out profiles/mvrender_bench_mi355x.json)')
   args = ap.parse_args()
+  if args.render:
+    return main_render(args)
   if args.poses:
     return main_poses(args)
   if args.visibility:
