@@ -176,32 +176,53 @@ def test_gpu_maxpool2x2_is_torchs(shape):
   assert HF.maxpool2x2_supported(xd, pool) and not HF.maxpool2x2_supported(xd, torch.nn.MaxPool2d(3, stride=2))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize('B,Ci,Co,H,W', [(2, 16, 8, 6, 8), (1, 64, 32, 16, 12), (1, 256, 128, 8, 4)])
-def test_gpu_deconv2x2_against_float64(B, Ci, Co, H, W):
-  """ConvTranspose2d(Ci, Co, 2, 2) as the 1x1 GEMM of csrc/conv1x1.hip + the rearrangement of csrc/fusion_ops.hip: forward, input
-  gradient, weight gradient, bias gradient against torch's float64 on the CPU; the eval form with the BatchNorm folded in."""
+def _deconv2x2_against_float64(B, Ci, Co, H, W, bias=True, x_grad=True):
+  """-> (convd, xd, the float64 output, the forward's tolerance) after one forward and backward on the device, every result checked
+  against torch's float64 on the CPU."""
   from mode_hip import functional as HF
   torch.manual_seed(5)
-  conv = torch.nn.ConvTranspose2d(Ci, Co, 2, 2)
+  conv = torch.nn.ConvTranspose2d(Ci, Co, 2, 2, bias=bias)
   x = torch.randn(B, Ci, H, W)
   go = torch.randn(B, Co, 2 * H, 2 * W)
-  c64 = torch.nn.ConvTranspose2d(Ci, Co, 2, 2).double()
+  c64 = torch.nn.ConvTranspose2d(Ci, Co, 2, 2, bias=bias).double()
   c64.load_state_dict({k: v.double() for k, v in conv.state_dict().items()})
   x64 = x.double().requires_grad_(True)
   y64 = c64(x64)
   y64.backward(go.double())
   convd = conv.to('cuda:0')
-  xd = x.to('cuda:0').requires_grad_(True)
+  xd = x.to('cuda:0').requires_grad_(x_grad)
   assert HF.deconv2x2_supported(xd, convd)
   y = HF.deconv2x2(xd, convd)
   y.backward(go.to('cuda:0'))
   tol = 2e-6 * Ci ** 0.5
   assert float((y.detach().cpu().double() - y64.detach()).abs().max()) <= tol * max(1.0, float(y64.abs().max()))
-  assert float((xd.grad.cpu().double() - x64.grad).abs().max()) <= 4 * tol * max(1.0, float(x64.grad.abs().max()))
-  gw64, gb64 = c64.weight.grad, c64.bias.grad
+  if x_grad:
+    assert float((xd.grad.cpu().double() - x64.grad).abs().max()) <= 4 * tol * max(1.0, float(x64.grad.abs().max()))
+  else:
+    assert xd.grad is None
+  gw64 = c64.weight.grad
   assert float((convd.weight.grad.cpu().double() - gw64).abs().max()) <= 2e-6 * (B * H * W) ** 0.5 * max(1.0, float(gw64.abs().max()))
-  assert float((convd.bias.grad.cpu().double() - gb64).abs().max()) <= 1e-5 * max(1.0, float(gb64.abs().max()))
+  if bias:
+    gb64 = c64.bias.grad
+    assert float((convd.bias.grad.cpu().double() - gb64).abs().max()) <= 1e-5 * max(1.0, float(gb64.abs().max()))
+  return convd, xd, y64, tol
+
+
+# (the last three: channel counts off the GEMM's 8 / 32 blocks, a single row, odd H)
+DECONV_SHAPES = [(2, 16, 8, 6, 8), (1, 64, 32, 16, 12), (1, 256, 128, 8, 4), (1, 12, 2, 1, 4), (2, 20, 6, 3, 4), (1, 3, 1, 5, 8)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('bias,x_grad', [(False, True), (True, False)])
+@pytest.mark.parametrize('B,Ci,Co,H,W', DECONV_SHAPES[3:])
+def test_gpu_deconv2x2_without_bias_or_input_gradient(B, Ci, Co, H, W, bias, x_grad):
+  """bias=None, and an input that needs no gradient (the input-gradient GEMM is not launched): the other results as before; with the
+  BatchNorm folded in, a missing bias is a zero bias."""
+  from mode_hip import functional as HF
+  convd, xd, y64, tol = _deconv2x2_against_float64(B, Ci, Co, H, W, bias, x_grad)
+  if not x_grad:  # the weight and bias gradients are, bit for bit, those of the run that also forms the input gradient
+    other = _deconv2x2_against_float64(B, Ci, Co, H, W, bias, True)[0]
+    assert torch.equal(convd.weight.grad, other.weight.grad) and torch.equal(convd.bias.grad, other.bias.grad)
   bn = torch.nn.BatchNorm2d(Co)
   with torch.no_grad():
     bn.running_mean.normal_()
@@ -217,13 +238,58 @@ def test_gpu_deconv2x2_against_float64(B, Ci, Co, H, W):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('B,C,H,W', [(2, 32, 8, 12), (1, 8, 6, 10), (1, 32, 64, 32)])
-def test_gpu_conv1x1_sigmoid_against_float64(B, C, H, W):
-  """Conv2d(C, 1, 1, bias=True) + Sigmoid in one pass (mode_conv1x1_sigmoid_fwd / _bwd) against torch's float64 on the CPU."""
+def test_gpu_deconv2x2_gradient_sink_and_support():
+  """The weight with a `_mode_grad_sink` (the GEMM's accumulate = 1): two backward passes leave exactly the sum of the two, and autograd
+  is handed nothing for the weight.  deconv2x2_supported says no where the GEMM's weight gradient cannot load 16-byte row pieces."""
+  from mode_hip import functional as HF
+  B, Ci, Co, H, W = 2, 20, 6, 3, 4
+  torch.manual_seed(8)
+  conv = torch.nn.ConvTranspose2d(Ci, Co, 2, 2).to('cuda:0')
+  xs = [torch.randn(B, Ci, H, W).to('cuda:0') for _ in range(2)]
+  gos = [torch.randn(B, Co, 2 * H, 2 * W).to('cuda:0') for _ in range(2)]
+  single = []
+  for x, go in zip(xs, gos):
+    conv.weight.grad = None
+    HF.deconv2x2(x, conv).backward(go)
+    single.append(conv.weight.grad.clone())
+  conv.weight.grad = torch.zeros_like(conv.weight)
+  conv.weight._mode_grad_sink = conv.weight.grad
+  for x, go in zip(xs, gos):
+    HF.deconv2x2(x, conv).backward(go)
+  assert conv.weight.grad is conv.weight._mode_grad_sink
+  assert torch.equal(conv.weight.grad, single[0] + single[1])
+  assert not HF.deconv2x2_supported(torch.zeros(1, Ci, 3, 6, device='cuda:0'), conv)
+  assert not HF.deconv2x2_supported(torch.zeros(1, Ci, 3, 5, device='cuda:0'), conv)
+  assert HF.deconv2x2_supported(torch.zeros(1, Ci, 3, 8, device='cuda:0'), conv)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('B,Ci,Co,H,W', DECONV_SHAPES)
+def test_gpu_deconv2x2_against_float64(B, Ci, Co, H, W):
+  """ConvTranspose2d(Ci, Co, 2, 2) as the 1x1 GEMM of csrc/conv1x1.hip + the rearrangement of csrc/fusion_ops.hip: forward, input
+  gradient, weight gradient, bias gradient against torch's float64 on the CPU; the eval form with the BatchNorm folded in."""
+  from mode_hip import functional as HF
+  convd, xd, y64, tol = _deconv2x2_against_float64(B, Ci, Co, H, W)
+  bn = torch.nn.BatchNorm2d(Co)
+  with torch.no_grad():
+    bn.running_mean.normal_()
+    bn.running_var.uniform_(0.5, 2.0)
+    bn.weight.uniform_(0.5, 1.5)
+    bn.bias.normal_()
+  bn.eval()
+  ref = torch.relu(bn.double()(y64.detach()))
+  bn = bn.float().to('cuda:0')
+  with torch.no_grad():
+    got = HF.deconv2x2_bn_eval(xd.detach(), convd, bn, True)
+  assert float((got.cpu().double() - ref).abs().max()) <= 4 * tol * max(1.0, float(ref.abs().max()))
+
+
+def _conv1x1_sigmoid_against_float64(B, C, H, W, x_grad=True, conv=None, x=None):
+  """-> (convd, xd, s) after one forward and backward on the device, every result checked against torch's float64 on the CPU."""
   from mode_hip import functional as HF
   torch.manual_seed(6)
-  conv = torch.nn.Conv2d(C, 1, 1, bias=True)
-  x = torch.randn(B, C, H, W)
+  conv = torch.nn.Conv2d(C, 1, 1, bias=True) if conv is None else conv
+  x = torch.randn(B, C, H, W) if x is None else x
   go = torch.randn(B, 1, H, W)
   c64 = torch.nn.Conv2d(C, 1, 1, bias=True).double()
   c64.load_state_dict({k: v.double() for k, v in conv.state_dict().items()})
@@ -231,11 +297,92 @@ def test_gpu_conv1x1_sigmoid_against_float64(B, C, H, W):
   s64 = torch.sigmoid(c64(x64))
   s64.backward(go.double())
   convd = conv.to('cuda:0')
-  xd = x.to('cuda:0').requires_grad_(True)
+  xd = x.to('cuda:0').requires_grad_(x_grad)
   assert HF.conv1x1_sigmoid_supported(xd, convd)
   s = HF.conv1x1_sigmoid(xd, convd)
   s.backward(go.to('cuda:0'))
+  assert bool(torch.isfinite(s).all())
   assert float((s.detach().cpu().double() - s64.detach()).abs().max()) <= 2e-6
-  assert float((xd.grad.cpu().double() - x64.grad).abs().max()) <= 2e-6 * max(1.0, float(x64.grad.abs().max()))
+  if x_grad:
+    assert bool(torch.isfinite(xd.grad).all())
+    assert float((xd.grad.cpu().double() - x64.grad).abs().max()) <= 2e-6 * max(1.0, float(x64.grad.abs().max()))
+  else:
+    assert xd.grad is None
   assert float((convd.weight.grad.cpu().double() - c64.weight.grad).abs().max()) <= 1e-5 * max(1.0, float(c64.weight.grad.abs().max()))
   assert float((convd.bias.grad.cpu().double() - c64.bias.grad).abs().max()) <= 1e-5 * max(1.0, float(c64.bias.grad.abs().max()))
+  return convd, xd, s
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('B,C,H,W', [(2, 32, 8, 12), (1, 8, 6, 10), (1, 32, 64, 32)])
+def test_gpu_conv1x1_sigmoid_against_float64(B, C, H, W):
+  """Conv2d(C, 1, 1, bias=True) + Sigmoid in one pass (mode_conv1x1_sigmoid_fwd / _bwd) against torch's float64 on the CPU."""
+  _conv1x1_sigmoid_against_float64(B, C, H, W)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('C', [1, 16, 48, 64])
+def test_gpu_conv1x1_sigmoid_channel_sweeps(C):
+  """head1_bwd_kernel sums 16 channels per sweep, the bias sum in the slot behind the last channel: at C = 16 and 48 that slot stands
+  alone at the head of a later sweep, C = 64 = HEAD_MAXC is the fifth sweep and the full LDS row.  And an input that needs no gradient
+  (gx NULL): the weight and bias gradients are those of the run that forms it, bit for bit."""
+  from mode_hip import functional as HF
+  convd, _, s = _conv1x1_sigmoid_against_float64(2, C, 4, 6)
+  convd2, _, s2 = _conv1x1_sigmoid_against_float64(2, C, 4, 6, x_grad=False)
+  assert torch.equal(s, s2) and torch.equal(convd.weight.grad, convd2.weight.grad) and torch.equal(convd.bias.grad, convd2.bias.grad)
+  assert not HF.conv1x1_sigmoid_supported(torch.zeros(1, 65, 4, 6, device='cuda:0'), torch.nn.Conv2d(65, 1, 1))
+  assert not HF.conv1x1_sigmoid_supported(torch.zeros(1, C, 3, 6, device='cuda:0'), torch.nn.Conv2d(C, 1, 1))
+  assert HF.conv1x1_sigmoid_supported(torch.zeros(1, C, 2, 6, device='cuda:0'), torch.nn.Conv2d(C, 1, 1))
+
+
+@pytest.mark.gpu
+def test_gpu_conv1x1_sigmoid_beyond_the_capped_grid():
+  """B H W > 2^20: the backward's grid is capped at 4 x CUs blocks of 256 threads x 4 pixels, so a thread sums more than one group."""
+  B, C, H, W = 3, 3, 512, 704
+  assert B * H * W > 2**20
+  _conv1x1_sigmoid_against_float64(B, C, H, W)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('logit', [30.0, 100.0])
+def test_gpu_conv1x1_sigmoid_saturated(logit):
+  """Logits at +-logit through a scaled weight: s and the gradients are what torch.sigmoid gives in float64, and nothing is NaN."""
+  conv = torch.nn.Conv2d(2, 1, 1, bias=True)
+  with torch.no_grad():
+    conv.weight.copy_(torch.tensor([logit, -logit]).view(1, 2, 1, 1))
+    conv.bias.zero_()
+  x = torch.zeros(1, 2, 4, 6)
+  x[0, 0, :2] = 1.0  # + logit
+  x[0, 1, 2:] = 1.0  # - logit
+  x[0, :, 0, 0] = 0.0  # and one at zero
+  _, xd, s = _conv1x1_sigmoid_against_float64(1, 2, 4, 6, conv=conv, x=x)
+  s = s.detach().cpu()
+  assert float(s[0, 0, 0, 0]) == 0.5 and float(s[0, 0, 1].min()) > 1 - 1e-6 and float(s[0, 0, 2:].max()) < 1e-6
+
+
+@pytest.mark.gpu
+def test_gpu_maxpool2x2_misaligned_view():
+  """A contiguous view 4 bytes past a 16-byte boundary with W % 4 == 0: the kernel's 16-byte row loads do not apply, it must take its
+  scalar path -- same bits as on an aligned copy, and as torch's on the CPU."""
+  from mode_hip import functional as HF
+  import torch.nn.functional as F
+  shape = (2, 3, 6, 8)
+  n = 2 * 3 * 6 * 8
+  g = torch.Generator().manual_seed(4)
+  flat = torch.randn(n + 4, generator=g)
+  go = torch.randn(2, 3, 3, 4, generator=g)
+  base = flat.to('cuda:0')
+  xv = base[1:n + 1].view(shape).requires_grad_(True)
+  assert xv.is_contiguous() and xv.data_ptr() % 16 == 4
+  xa = flat[1:n + 1].view(shape).clone().to('cuda:0').requires_grad_(True)
+  assert xa.data_ptr() % 16 == 0
+  res = []
+  for x in (xv, xa):
+    y = HF.maxpool2x2(x)
+    y.backward(go.to('cuda:0'))
+    res.append((y.detach().cpu(), x.grad.cpu()))
+  xr = flat[1:n + 1].view(shape).clone().requires_grad_(True)
+  yr = F.max_pool2d(xr, 2, 2)
+  yr.backward(go)
+  for y, gx in res:
+    assert torch.equal(y, yr.detach()) and torch.equal(gx, xr.grad)
